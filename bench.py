@@ -30,9 +30,15 @@ Two more workloads ride along as extra blocks of the same line (and can be made 
                     timed region, every rank decodes its contiguous 1/N; no collective (output offsets are
                     frame x 2048 x channels x 2).
 
-K steps are timed, bracketed by barrier + torch.cuda.synchronize(), MAX over ranks; that measurement is
-repeated until at least ~0.5 s has been timed and `value` is the median repetition (min / max reported; the
-first repetition, which runs while the clocks still settle, is reported separately).
+After W untimed warm-up steps (and, for W > 0, more until 0.2 s of them have run right before the timed
+region, while the clocks settle), exactly K steps are timed back to back, bracketed by barrier +
+torch.cuda.synchronize(), MAX over ranks: `ms_per_step` is that time / K and `value` follows from it.  (The
+one-lane leg of the `lanes` block times K more steps of its own; the extra blocks time theirs.)
+
+--dump-outputs DIR writes what the headline's last timed step computed -- the arrays a caller of the path
+receives -- as DIR/<name>.npy (float32 / float64, under 64 MB in all): every frame offset of the rank's
+stream, and the frame bytes and decoded PCM of a fixed, seeded sample of its frames.  The inputs are
+synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 
 WHAT IS TIMED IS WHAT IS CHECKED: the timed steps run as two independent encode->decode chains in flight on two
 HIP streams (`lanes`).  Every timed call leaves its status words in a slot of its own, all of them are OR-ed
@@ -78,6 +84,9 @@ DECODE_RESIDENT_WAVES = 7 * 1024  # k_decode_frames: seven waves per SIMD (72 VG
 DECODE10K_FRAMES, DECODE10K_TRACK = 10000, 2
 ENCODE_TARGET_MSPS = 1000.0  # BASELINE.json north_star: >= 1 G stereo samples/s encode on one MI355X
 METRIC = "Msamples/s encode+decode, 16-bit stereo 44.1kHz, 1/2/4/8 GPU; bit-exact vs CPU"  # BASELINE.json "metric"
+WARMUP_SETTLE_S, SETTLE_BLOCK_S = 0.2, 0.05  # untimed steps right before a timed region (with --warmup W > 0), and their blocks
+DUMP_FRAMES, DUMP_SEED = 1024, 20251015  # --dump-outputs: how many frames' bytes and PCM are written, and the seed that picks them
+DUMP_BUDGET_BYTES = 64_000_000
 
 
 # ---- N > 1 without a launcher: start one ----------------------------------------------------------------------
@@ -319,49 +328,31 @@ class Bench:
         self.exchange = torch.cuda.Stream() if self.dist is not None else None
         self.lanes_forced = args.lanes is not None  # (also --lanes=N and abbreviations: argparse's own answer)
         self.n_lanes = max(1, args.lanes if self.lanes_forced else 2)
+        # --dump-outputs: the first chain run (the headline's) keeps a sample of its outputs; rank 0's are written
+        self.outputs_pending = getattr(args, "dump_outputs", None) is not None and self.rank == 0
 
     def barrier(self):
         if self.dist is not None:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def timed_repetitions(self, step, steps, after=None, min_total_s=0.5, max_reps=40):
-        """Seconds per K-step measurement, each bracketed by barrier + synchronize, MAX over ranks.  `after` runs
-        between two measurements (outside the timed region)."""
+    def timed_steps(self, step, steps, after=None):
+        """Seconds for exactly `steps` steps run back to back, bracketed by barrier + synchronize, MAX over ranks.  `after`
+        runs behind the timed region."""
         torch, dist = self.torch, self.dist
-        out = []
-        total = 0.0
-        while len(out) < max_reps and (not out or total < min_total_s):
-            self.barrier()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                step()
-            self.barrier()
-            elapsed = time.perf_counter() - t0
-            if dist is not None:
-                t = torch.tensor([elapsed, total + elapsed], dtype=torch.float64, device=self.coll_device)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)  # the same numbers -- and the same loop exit -- on every rank
-                elapsed, agreed_total = float(t[0].item()), float(t[1].item())
-            else:
-                agreed_total = total + elapsed
-            out.append(elapsed)
-            total = agreed_total
-            if after is not None:
-                after()
-        return out
-
-    @staticmethod
-    def summarise(reps, steps):
-        """The first K-step measurement runs a few % slow while the clocks settle behind the W warm-up steps: with four
-        measurements or more it is reported (ms_per_step_first) but kept out of median / min / max."""
-        settled = reps[1:] if len(reps) >= 4 else reps
-        per_step = sorted(r / steps for r in settled)
-        median_s = per_step[len(per_step) // 2]
-        return median_s, {
-            "count": len(reps), "timed_s": sum(reps), "ms_per_step_first": reps[0] / steps * 1e3, "ms_per_step_min": per_step[0] * 1e3,
-            "ms_per_step_median": median_s * 1e3, "ms_per_step_max": per_step[-1] * 1e3, "spread_frac": (per_step[-1] - per_step[0]) / median_s,
-            "spread_frac_p10_p90": (per_step[(9 * len(per_step)) // 10 - (1 if len(per_step) >= 10 else 0)] - per_step[len(per_step) // 10]) / median_s,
-        }
+        self.barrier()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step()
+        self.barrier()
+        elapsed = time.perf_counter() - t0
+        if dist is not None:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=self.coll_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)  # the same number on every rank
+            elapsed = float(t[0].item())
+        if after is not None:
+            after()
+        return elapsed
 
 
 class ChainJob:
@@ -393,6 +384,7 @@ class ChainJob:
             self.lanes.append(lane)
         self.next_lane = 0
         self.steps_done = 0
+        self.outputs = None  # (--dump-outputs: set by run_chain on the headline's job)
         self.exchange = exchange and bench.dist is not None
         if self.exchange:
             ranges = bench.sharding.partition(n_total, bench.world)
@@ -522,7 +514,28 @@ class ChainJob:
         return snaps
 
 
-def run_chain(bench: Bench, job: ChainJob, steps: int, warmup: int, min_total_s=0.5):
+def output_sample(np, n_frames: int):
+    """The frames --dump-outputs writes the bytes and PCM of: a fixed, seeded draw, the same for every run of the same job."""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_frames, size=min(DUMP_FRAMES, n_frames), replace=False))
+
+
+def keep_outputs(bench: Bench, kept, sample, at: int, nb: int, frames, offsets, back, encoded: bool):
+    """Add one batch of a step's outputs to `kept` (host arrays): its frame offsets, continued across batches into offsets of
+    the rank's whole stream, and the frame bytes and decoded PCM of the sampled frames among its frames [at, at + nb)."""
+    torch, np = bench.torch, bench.np
+    sel = torch.as_tensor(sample[(sample >= at) & (sample < at + nb)] - at, dtype=torch.int64, device=back.device)
+    kept["pcm"].append(back[sel].cpu().numpy().astype(np.float32))
+    if not encoded:  # (decode only: frame bytes and offsets are the job's input, not its output)
+        return
+    o = offsets[: nb + 1].to(torch.int64)
+    kept["offsets"].append(o[1:].cpu().numpy() + kept["stream_bytes"])
+    kept["stream_bytes"] += int(o[nb].item())
+    starts, lens = o[sel], o[sel + 1] - o[sel]
+    pos = torch.arange(int(lens.sum().item()), dtype=torch.int64, device=back.device) + torch.repeat_interleave(starts - (torch.cumsum(lens, 0) - lens), lens)
+    kept["bytes"].append(frames[pos].cpu().numpy().astype(np.float32))
+
+
+def run_chain(bench: Bench, job: ChainJob, steps: int, warmup: int):
     """Warm up, time (all lanes, then one lane), then verify what was timed.  Returns the measurement record."""
     torch, np = bench.torch, bench.np
     job.size_rings(max(steps, warmup, 1))
@@ -548,22 +561,36 @@ def run_chain(bench: Bench, job: ChainJob, steps: int, warmup: int, min_total_s=
         torch.cuda.synchronize()
         job.fold_status()
     job.stream_renewals = renewals
-    reps = bench.timed_repetitions(job.step, steps, after=job.fold_status, min_total_s=min_total_s)
+    # The first steps after a pause run slow while the clocks settle (a first K-step block of the track ran ~2-3 ms long, at
+    # any K): right before the timed region, more untimed steps until WARMUP_SETTLE_S of them have run, in blocks that grow
+    # from W to the timed block's K steps (at most SETTLE_BLOCK_S long), so that the device runs as it will when timed.  The
+    # block times are agreed over ranks, so that every rank runs as many steps (and collectives).
+    settled, settle_steps, block = 0.0, 0, warmup
+    while warmup and settled < WARMUP_SETTLE_S:
+        t = bench.timed_steps(job.step, block, after=job.fold_status)
+        settled += t
+        settle_steps += block
+        block = max(warmup, min(steps, int(block * SETTLE_BLOCK_S / max(t, 1e-6))))
+    timed_s = bench.timed_steps(job.step, steps, after=job.fold_status)
     snaps = job.snapshot_lanes()
     timed_sizes = None
     if job.exchange and job.last_set is not None:  # the layout the LAST TIMED step gathered
         timed_sizes = job.last_set["all"].clone()
-    serial = bench.timed_repetitions(lambda: job.step(serial=True), steps, after=job.fold_status, min_total_s=0.15) if len(job.lanes) > 1 else reps
-    median_s, rep_stats = Bench.summarise(reps, steps)
-    serial_s, _ = Bench.summarise(serial, steps)
+    serial_timed_s = bench.timed_steps(lambda: job.step(serial=True), steps, after=job.fold_status) if len(job.lanes) > 1 else timed_s
 
     # ---- correctness of what was timed -------------------------------------------------------------------------------
     # One more step, serial and synchronised after every batch: its status words, its round trip, and -- batch by batch --
     # equality with what the lanes' last timed calls left behind.  The reference codec is not lossless on every frame
     # (its encoder rounds the prediction half-up, its decoder half-down: a frame whose Q35 sum hits 2^34 mod 2^35 comes
     # back off by one), and parity means reproducing that -- so the round trip may differ from the
-    # input in a handful of frames, never in many.
-    state = {"lossy": 0, "bytes": 0, "same": True, "compared": 0, "sizes": []}
+    # input in a handful of frames, never in many.  With --dump-outputs, the headline's chain keeps a sample of this step's
+    # outputs: those of the last timed step, which they are asserted to equal.
+    state = {"lossy": 0, "bytes": 0, "same": True, "compared": 0, "sizes": [], "at": 0}
+    n_local = sum(int(x.shape[0]) for x in job.batches)
+    kept, sample = None, None
+    if bench.outputs_pending:
+        bench.outputs_pending = False
+        kept, sample = {"pcm": [], "bytes": [], "offsets": [np.zeros(1, np.int64)], "stream_bytes": 0}, output_sample(np, n_local)
 
     def check(i, nb, pcm, frames, offsets, back, lane, slot):
         dec_st = lane["st_dec"][slot].cpu().numpy().view(np.uint32)
@@ -581,6 +608,9 @@ def run_chain(bench: Bench, job: ChainJob, steps: int, warmup: int, min_total_s=
                 same = same and torch.equal(s["offsets"], offsets) and torch.equal(s["frames"], frames[:total])
             state["same"] = state["same"] and bool(same)
             state["compared"] += 1
+        if kept is not None:
+            keep_outputs(bench, kept, sample, state["at"], nb, frames, offsets, back, encoded=job.pre is None)
+        state["at"] += nb
 
     last = job.step(serial=True, check=check)
     torch.cuda.synchronize()
@@ -593,14 +623,20 @@ def run_chain(bench: Bench, job: ChainJob, steps: int, warmup: int, min_total_s=
     acc = job.flag_acc.cpu().numpy().view(np.uint32)
     enc_bad = int(acc[0]) & (bench.capi.FLAG_WORDS_CAP | bench.capi.FLAG_RICE_RANGE | bench.capi.FLAG_COEF_OVERFLOW)
     dec_bad = int(acc[1]) & (bench.capi.FLAG_BAD_FRAME | bench.capi.FLAG_RICE_OVERRUN)
-    n_local = sum(int(x.shape[0]) for x in job.batches)
     assert enc_bad == 0 and int(acc[2]) == 0, f"an encode inside the timed region raised flags 0x{int(acc[0]):x} / {int(acc[2])} frames over capacity"
     assert dec_bad == 0 and int(acc[3]) == 0, f"a decode inside the timed region raised flags 0x{int(acc[1]):x} / {int(acc[3])} bad frames"
     assert state["same"] and state["compared"] == len(snaps), "the outputs of the timed (two-lane) steps differ from a serial step's"
     assert state["lossy"] <= max(1, n_local // 500), f"decode(encode(x)) differs from x in {state['lossy']} frames"
+    if kept is not None:
+        arrays = {}
+        if job.pre is None:
+            arrays["frame_offsets"] = np.concatenate(kept["offsets"]).astype(np.float64)
+            arrays["frame_bytes"] = np.concatenate(kept["bytes"])
+        arrays["decoded_pcm"] = np.concatenate(kept["pcm"])
+        job.outputs = {"arrays": arrays, "sampled_frames": sample}
     return {
-        "median_s": median_s, "serial_s": serial_s, "rep_stats": rep_stats, "reps": reps, "last": last, "lossy": state["lossy"], "bytes": state["bytes"],
-        "timed_sizes": timed_sizes,
+        "step_s": timed_s / steps, "serial_s": serial_timed_s / steps, "timed": {"steps": steps, "timed_s": timed_s, "warmup_steps": warmup, "settle_steps": settle_steps},
+        "last": last, "lossy": state["lossy"], "bytes": state["bytes"], "timed_sizes": timed_sizes,
         "timed_outputs": {"status_or_encode": int(acc[0]), "status_or_decode": int(acc[1]), "lanes_compared_with_serial_step": state["compared"],
                           "equal_to_serial_step": bool(state["same"]),
                           "what": "every timed call reports into a status slot of its own, all OR-ed; each lane's last timed outputs (frame bytes, offsets, "
@@ -668,7 +704,7 @@ def workload_track(bench: Bench, steps: int, warmup: int):
         bench.dist.all_reduce(t)
     samples = n_total * 2048
     rec = {
-        "value": samples / m["median_s"] / 1e6, "ms_per_step": m["median_s"] * 1e3, "scaling": "weak",
+        "value": samples / m["step_s"] / 1e6, "ms_per_step": m["step_s"] * 1e3, "scaling": "weak",
         "config": {
             "workload": ("BASELINE.json configs[1]: one 3-min 16-bit stereo 44.1 kHz track (3875 frames x 2048 stereo samples) PER GPU, "
                          "encode to .sela frames then decode, bit-exact" + ("; RCCL all-gather of the frame sizes every step" if job.exchange else "")),
@@ -676,7 +712,7 @@ def workload_track(bench: Bench, steps: int, warmup: int):
             "sharding": "single track" if bench.world == 1 else f"one track per GPU x{bench.world} (album tracks 0, 3, 6, ...)",
             "batch_frames": frames, "sela_bytes_total": int(t[1].item()), "pcm_bytes_total": n_total * 2048 * CHANNELS * 2,
         },
-        "lanes": lanes_block(job, m, samples, steps), "repetitions": m["rep_stats"], "roundtrip_lossy_frames": int(t[0].item()),
+        "lanes": lanes_block(job, m, samples, steps), "timed": m["timed"], "roundtrip_lossy_frames": int(t[0].item()),
         "layout_matches_reference": layout_ok, "digests_match_reference": digest_ok, "timed_outputs": m["timed_outputs"],
     }
     return rec, job, pcm, (blob, out_offsets.cpu().numpy().view(np.uint64), back.cpu().numpy())
@@ -700,7 +736,7 @@ def workload_album(bench: Bench, steps: int, warmup: int):
     per_batch = max(1, -(-int(local.shape[0]) // n_batches))
     batches = [local[i: i + per_batch] for i in range(0, local.shape[0], per_batch)] or [local]
     job = ChainJob(bench, batches, n_total, exchange=True)
-    m = run_chain(bench, job, steps, warmup, min_total_s=0.3)
+    m = run_chain(bench, job, steps, warmup)
     layout_ok = None
     if job.exchange:
         # the layout gathered by the last TIMED step must be the one-GPU layout: its digest was computed with the unmodified reference
@@ -717,7 +753,7 @@ def workload_album(bench: Bench, steps: int, warmup: int):
         bench.dist.all_reduce(t)
     samples = n_total * 2048
     rec = {
-        "value": samples / m["median_s"] / 1e6, "ms_per_step": m["median_s"] * 1e3, "scaling": "strong", "steps": steps, "warmup": warmup,
+        "value": samples / m["step_s"] / 1e6, "ms_per_step": m["step_s"] * 1e3, "scaling": "strong", "steps": steps, "warmup": warmup,
         "config": {
             "workload": ("BASELINE.json configs[3]: 100-track synthetic album (34/33/33 tracks at 44.1/48/96 kHz, 549,365 frames x 2048 "
                          f"stereo samples) sharded over {bench.world} GPU(s) in contiguous frame ranges, encode + "
@@ -726,7 +762,7 @@ def workload_album(bench: Bench, steps: int, warmup: int):
             "frames_total": n_total, "frames_rank0": my_end - my_begin, "channels": CHANNELS, "sharding": f"contiguous frame ranges x{bench.world}",
             "batch_frames": job.max_batch, "sela_bytes_total": int(t[1].item()), "pcm_bytes_total": n_total * 2048 * CHANNELS * 2,
         },
-        "lanes": lanes_block(job, m, samples, steps), "repetitions": m["rep_stats"], "roundtrip_lossy_frames": int(t[0].item()),
+        "lanes": lanes_block(job, m, samples, steps), "timed": m["timed"], "roundtrip_lossy_frames": int(t[0].item()),
         "layout_matches_reference": layout_ok, "timed_outputs": m["timed_outputs"],
         "one_gpu_anchor": "the `album` block (or, with --workload album, the headline) of the --gpus 1 line: same job, one GPU",
     }
@@ -745,7 +781,7 @@ def workload_decode10k(bench: Bench, steps: int, warmup: int):
     out.check()
     frames, offsets = out.frames, out.offsets
     job = ChainJob(bench, [pcm], n_total, exchange=False, pre_encoded=[(frames, offsets)])
-    m = run_chain(bench, job, steps, warmup, min_total_s=0.3)
+    m = run_chain(bench, job, steps, warmup)
     exact = None
     if bench.rank == 0 and not bench.args.no_cpu_baseline:  # the decode of rank 0's share against the CPU decoder
         impl, kind = cpu_reference()
@@ -769,18 +805,18 @@ def workload_decode10k(bench: Bench, steps: int, warmup: int):
         torch.cuda.synchronize()
         out8.check()
         job8 = ChainJob(bench, [pcm8], e8 - b8, exchange=False, pre_encoded=[(out8.frames, out8.offsets)])
-        m8 = run_chain(bench, job8, steps, warmup, min_total_s=0.2)
+        m8 = run_chain(bench, job8, steps, warmup)
         assert torch.equal(m8["last"][2], m["last"][2][: e8 - b8]), "decode10k: a rank's share decodes differently on its own"
         share8 = {
-            "frames": e8 - b8, "ms_per_step": m8["median_s"] * 1e3, "value": (e8 - b8) * 2048 / m8["median_s"] / 1e6,
+            "frames": e8 - b8, "ms_per_step": m8["step_s"] * 1e3, "value": (e8 - b8) * 2048 / m8["step_s"] / 1e6,
             "unit": "Msamples/s decode only, ONE GPU on one rank's share of an 8-GPU job",
-            "predicted_value_8_gpus": samples / m8["median_s"] / 1e6,
-            "predicted_strong_scaling_efficiency_8": m["median_s"] / (8 * m8["median_s"]),
+            "predicted_value_8_gpus": samples / m8["step_s"] / 1e6,
+            "predicted_strong_scaling_efficiency_8": m["step_s"] / (8 * m8["step_s"]),
             "what": "rank 0's contiguous 1/8 of the 10,000 frames, timed on this GPU like the full workload; a prediction, not an 8-GPU measurement",
         }
         del job8, enc8, out8
     rec = {
-        "value": samples / m["median_s"] / 1e6, "unit": "Msamples/s decode only", "ms_per_step": m["median_s"] * 1e3, "scaling": "strong",
+        "value": samples / m["step_s"] / 1e6, "unit": "Msamples/s decode only", "ms_per_step": m["step_s"] * 1e3, "scaling": "strong",
         "per_rank_share_8": share8,
         "steps": steps, "warmup": warmup,
         "config": {
@@ -788,7 +824,7 @@ def workload_decode10k(bench: Bench, steps: int, warmup: int):
                          f"every rank decodes its contiguous 1/{bench.world}; no collective"),
             "frames_total": n_total, "frames_rank0": e0 - b0, "channels": CHANNELS, "sharding": f"contiguous frame ranges x{bench.world}",
         },
-        "lanes": lanes_block(job, m, samples, steps), "repetitions": m["rep_stats"], "roundtrip_lossy_frames": int(t[0].item()),
+        "lanes": lanes_block(job, m, samples, steps), "timed": m["timed"], "roundtrip_lossy_frames": int(t[0].item()),
         "bit_exact_vs_cpu_decode": exact, "timed_outputs": m["timed_outputs"],
     }
     return rec, job, pcm, None
@@ -929,6 +965,23 @@ def any_length_leg(np):
     return out
 
 
+def write_outputs(path: str, outputs, np):
+    """--dump-outputs: DIR/<name>.npy for every kept array, float32 / float64 (exact for the bytes, samples and offsets)."""
+    arrays = outputs["arrays"]
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes, over the {DUMP_BUDGET_BYTES} allowed"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {
+        "dir": os.path.abspath(path), "bytes": total, "arrays": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()},
+        "sampled_frames": int(len(outputs["sampled_frames"])), "seed": DUMP_SEED,
+        "what": "rank 0's outputs of the headline's last timed step: frame_offsets = every frame's offset in the rank's frame stream (+ its end), "
+                "frame_bytes = the bytes of the sampled frames back to back, decoded_pcm = their decoded samples [frame, sample, channel]; the frames "
+                "are a seeded draw of the rank's frames, in order (decode-only workloads: decoded_pcm alone)",
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -949,7 +1002,11 @@ def main():
                     help="experiments only: 1..999 cuts every encode launch of teams of 16 in two (that share per mille to the first half); 0 (default): never")
     ap.add_argument("--encode-fused", action="store_true",
                     help="experiments only: the encoder's one-launch form (the host pipeline's) on device pointers, no plan / assemble kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed to DIR/<name>.npy (rank 0; a seeded sample of the frames)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus, sys.argv[1:]))
 
@@ -959,6 +1016,7 @@ def main():
     runners = {"track": workload_track, "album": workload_album, "decode10k": workload_decode10k}
 
     rec, job, pcm0, host_out = runners[headline](bench, args.steps, args.warmup)
+    dumped = write_outputs(args.dump_outputs, job.outputs, np) if job.outputs is not None else None
     kern = None
     if headline != "decode10k":
         k_enc, k_dec, n0, sela0 = kernel_leg(bench, job, pcm0, args.steps)
@@ -975,6 +1033,8 @@ def main():
         if kern is not None:
             result.update(kern)
             result["profiles_stale"] = kern["profiles"]["profiles_stale"]
+        if dumped is not None:
+            result["dump_outputs"] = dumped
     pcm_host = None
     if headline == "track" and bench.rank == 0:
         pcm_host = pcm0.cpu().numpy()

@@ -366,6 +366,17 @@ def test_bench_with_more_than_one_gpu_and_no_launcher_starts_its_own():
     assert not [t for t in r.stdout.splitlines() if t.startswith("{")]
 
 
+def test_bench_refuses_to_time_no_steps():
+    """--steps is the number of timed steps, and ms_per_step divides by it: fewer than one is refused before anything runs."""
+    import subprocess
+    import sys
+
+    for args in (["--steps", "0"], ["--steps", "2", "--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (args, r.stderr[-500:])
+        assert not r.stdout.strip()
+
+
 def test_reference_binding_is_built_and_fails_loudly_without_a_gpu(tmp_path):
     """oracle/_ref/sela_ref_bound (oracle/binding/bound.cpp: the reference's sela::Encoder / Decoder declarations with
     processFrames() bound to libsela_hip.so, built where /root/reference exists) links, and -- no GPU here -- reports the
