@@ -141,7 +141,8 @@ int sela_hip_decode_device(const uint8_t* d_frames, const uint64_t* d_frame_offs
  * Calls of at most 32 frames made from several threads at once -- a binding that keeps the reference's per-frame thread
  * loop (src/sela/encoder.cpp:58-73) -- are coalesced: calls that arrive while another one is on the device go there
  * together, as one job, when it returns.  Every call still gets exactly its own result and its own error (a buffer that
- * is too small, a malformed frame); a lone caller is not delayed. */
+ * is too small, a malformed frame, a coefficient outside the tables); a lone caller is not delayed.  The same holds for
+ * sela_hip_encode_i32 / sela_hip_decode_i32 below. */
 int sela_hip_encode(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
     uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames+1] */);
 int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels,
@@ -188,7 +189,10 @@ uint32_t sela_hip_index_samples(const uint8_t* frames, const uint64_t* frame_off
  *                SELA_HIP_ECAPACITY.  The calls run on a stream of the calling thread's own (leased, not the default stream)
  *                and return when the result is in host memory; after an error the outputs' contents are not defined.
  * Errors as above; values whose int32 zig-zag overflows in the reference (|residue| >= 2^30) and Rice streams beyond the u16
- * word count of a subframe are SELA_HIP_ERANGE. */
+ * word count of a subframe are SELA_HIP_ERANGE.
+ * These calls, sela_hip_encode_ragged_i32 and the any-length route of sela_hip_encode / sela_hip_decode also work while the
+ * calling thread has a streaming job open (below) and leave that job alone; the one-shot calls on 2048-sample frames refuse
+ * with SELA_HIP_EINVAL then. */
 int sela_hip_encode_i32(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
     uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames+1] */);
 int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels,

@@ -68,6 +68,11 @@ void sela_hip_debug_decode_recurrence(int form);
 /* Debug hook: how many per-thread contexts (streams, events, staging buffers) this process has CREATED so far -- threads
  * that take over a parked one (sela_hip.h, sela_hip_thread_release) do not count. */
 int sela_hip_debug_contexts_created(void);
+/* Debug hook (tests; process-wide, every device): the call coalescer of the host-pointer one-shot calls (sela_coalescer.h), by
+ * kind -- 0: sela_hip_decode, 1: sela_hip_encode, 2: sela_hip_decode_i32, 3: sela_hip_encode_i32 on frames of any shape.
+ * *batches: how many batches so far held more than one call; *retried: how many of those failed for what one of their calls
+ * brought and were run again call by call.  Zeros for any other kind. */
+void sela_hip_debug_coalesced(int kind, long long* batches, long long* retried);
 
 /* Debug hook (tests; process-wide): while on, a device-pointer encode with a d_trace pointer runs the PRODUCT kernels plus a few
  * instructions (their kMode 3 instantiations, not the trace builds) and leaves, instead of traces, two 64-bit words per block at

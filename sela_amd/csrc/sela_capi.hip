@@ -1624,13 +1624,14 @@ typedef sela::CallCoalescer<HipBackend> Coalescer;
 
 // One coalescer per device and direction: calls for different GPUs (one thread per GPU, each coding frame by frame) can never
 // share a batch, so they do not wait for each other's leaders either.
+std::mutex g_coalescers_mu;
+Coalescer* g_coalescers[4][64] = {};
+
 Coalescer* coalescer(Coalescer::Kind kind, int device)
 {
-    static std::mutex mu;
-    static Coalescer* table[4][64] = {};
     const int d = device >= 0 && device < 64 ? device : 0;
-    std::lock_guard<std::mutex> lock(mu);
-    Coalescer*& c = table[(int)kind][d];
+    std::lock_guard<std::mutex> lock(g_coalescers_mu);
+    Coalescer*& c = g_coalescers[(int)kind][d];
     if (!c)
         c = new Coalescer(kind, kind == Coalescer::kDecode || kind == Coalescer::kDecode32 ? sela::kCoalesceLeadersDecode : sela::kCoalesceLeaders); // (never destroyed: calls may outlive the statics)
     return c;
@@ -1642,6 +1643,24 @@ int submit_small(Coalescer::Kind kind, SmallCall& call)
     return rc == SELA_HIP_OK ? SELA_HIP_OK : fail(rc, call.error);
 }
 } // namespace
+
+void sela_hip_debug_coalesced(int kind, long long* batches, long long* retried)
+{
+    long long b = 0, r = 0;
+    if (kind >= 0 && kind < 4) {
+        std::lock_guard<std::mutex> lock(g_coalescers_mu);
+        for (Coalescer* c : g_coalescers[kind]) {
+            long long cb = 0, cr = 0;
+            if (c)
+                c->counts(&cb, &cr);
+            b += cb, r += cr;
+        }
+    }
+    if (batches)
+        *batches = b;
+    if (retried)
+        *retried = r;
+}
 
 int sela_hip_encode(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
     size_t frames_cap, uint64_t* frame_offsets_out)
@@ -1706,7 +1725,7 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     const std::string first_error = first_is_standard ? std::string(sela_hip_last_error()) : std::string("malformed frame stream");
     for (uint32_t f = 0; f < n_frames; f++)
         if (frame_offsets[f + 1] < frame_offsets[f])
-            return rc;
+            return fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
     bool standard = true;
     std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
     const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), &standard);
@@ -1745,9 +1764,12 @@ int sela_hip_encode_i32(const int32_t* samples, uint32_t n_frames, uint32_t chan
         return fail(SELA_HIP_EINVAL, "bad argument");
     // Small calls from many threads -- the reference's thread loop over frame::FrameEncoder (src/sela/encoder.cpp:58-73) on frames
     // that are not the CLI's shape -- go to the device together, like the one-shot calls of the fast path (sela_coalescer.h):
-    // calls of one shape (channels, samples per channel) share a job, every call gets its own bytes and its own error.
+    // calls of one shape (channels, samples per channel) share a job, every call gets its own bytes and its own error.  Not for a
+    // thread with a job open: a batch's leader gives its contexts back when the batch is through (HipBackend::after_batch), the
+    // job's with them; the any-length route leases a context of its own, so the call itself goes straight there.
     SmallCall call;
-    if (n_frames == 0 || n_frames > kCoalesceFrames || (size_t)n_frames * channels * samples_per_channel > ((size_t)1 << 20) || hipGetDevice(&call.device) != hipSuccess)
+    if (n_frames == 0 || n_frames > kCoalesceFrames || (size_t)n_frames * channels * samples_per_channel > ((size_t)1 << 20) || (g_lease.held && g_lease.held->job_open)
+        || hipGetDevice(&call.device) != hipSuccess)
         return sela::generic_encode(samples, false, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
     call.channels = channels, call.n_frames = n_frames, call.shape = samples_per_channel;
     call.samples = samples, call.frames_out = frames_out, call.frames_cap = frames_cap, call.offsets_out = frame_offsets_out;
@@ -1834,7 +1856,7 @@ int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
     // Small calls from many threads -- the reference's thread loop over frame::FrameDecoder -- go to the device together, like
     // the one-shot calls of the fast path (sela_coalescer.h): every call its own rows, its own error.
     SmallCall call;
-    if (n_frames > kCoalesceFrames || hipGetDevice(&call.device) != hipSuccess)
+    if (n_frames > kCoalesceFrames || (g_lease.held && g_lease.held->job_open) || hipGetDevice(&call.device) != hipSuccess) // (a thread with a job open: as in sela_hip_encode_i32)
         return sela::generic_decode(frames, frame_offsets, n_frames, channels, samples_out, stride, counts_out, nullptr, nullptr);
     call.channels = channels, call.n_frames = n_frames;
     call.frames = frames, call.offsets_in = frame_offsets, call.samples_out = samples_out, call.stride = stride, call.counts_out = counts_out;

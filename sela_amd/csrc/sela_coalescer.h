@@ -44,7 +44,8 @@ namespace sela {
 // it returns ONE of them takes everything that is waiting for the same device and channel count to the device as a
 // single job, hands every call its part of the result, and parks the streams it used for the next leader.  A lone caller
 // pays nothing; T busy threads end up in batches of about T / kCoalesceLeaders calls.  A call's own failure (output buffer
-// too small, a malformed frame) stays its own.
+// too small, a malformed frame, a coefficient outside the tables) stays its own: a batch that fails for what one call brought
+// is run again call by call.
 //
 // Up to kCoalesceLeaders batches are on the device at a time (round 6; one until then): a batch of a few dozen frames is a
 // trip of ~0.2 ms that leaves the device and the link nearly idle, and with one batch in flight a call waits out the batch
@@ -134,6 +135,8 @@ private:
     int leaders = 0;    // batches between "a call was told to lead" and "its callers have their results"
     int designated = 0; // of those, the ones still in the queue (lingering for company): arrivals join them instead of leading
     size_t last_batch = 0;
+    // (tests: batches of more than one call so far, and how many of those were retried call by call -- sela_hip_debug_coalesced)
+    std::atomic<long long> shared_batches{0}, retried_batches{0};
 
     // a free seat and calls nobody leads: the oldest of them leads (mu held; the caller notifies)
     bool promote_locked()
@@ -167,6 +170,7 @@ private:
     {
         if (batch.size() == 1)
             return run_one(*batch[0]);
+        shared_batches.fetch_add(1, std::memory_order_relaxed);
         const uint32_t channels = batch[0]->channels;
         const size_t frame_pcm = (size_t)SELA_HIP_SAMPLES_PER_FRAME * channels * sizeof(int16_t);
         size_t total = 0;
@@ -240,6 +244,7 @@ private:
                 rc = Backend::encode_i32_now(static_cast<const int32_t*>(in.p), (uint32_t)total, channels, n, static_cast<uint8_t*>(out.p), cap, offsets.data());
             }
             if (rc == SELA_HIP_ERANGE || rc == SELA_HIP_ECAPACITY) {
+                retried_batches.fetch_add(1, std::memory_order_relaxed);
                 for (SmallCall* c : batch) // a block the reference cannot answer must not fail its neighbours' calls: everyone on their own
                     run_one(*c);
             } else {
@@ -306,6 +311,7 @@ private:
                 }
             }
             if (rc == SELA_HIP_EFORMAT || rc == SELA_HIP_ERANGE || rc == SELA_HIP_ECAPACITY) {
+                retried_batches.fetch_add(1, std::memory_order_relaxed);
                 for (SmallCall* c : batch) // somebody's frame must not fail its neighbours' calls: everyone on their own
                     run_one(*c);
             } else if (rc != SELA_HIP_OK) {
@@ -334,8 +340,10 @@ private:
                 }
                 rc = Backend::decode_now(static_cast<const uint8_t*>(in.p), offsets.data(), (uint32_t)total, channels, static_cast<int16_t*>(shared_out.get()));
             }
-            if (rc == SELA_HIP_EFORMAT) {
-                // somebody's malformed frame must not fail its neighbours' calls: everyone on their own
+            if (rc == SELA_HIP_EFORMAT || rc == SELA_HIP_ERANGE || rc == SELA_HIP_ECAPACITY) {
+                // somebody's malformed frame -- or one with a coefficient outside the tables, which the job reports as SELA_HIP_ERANGE --
+                // must not fail its neighbours' calls: everyone on their own
+                retried_batches.fetch_add(1, std::memory_order_relaxed);
                 for (SmallCall* c : batch)
                     run_one(*c);
             } else {
@@ -355,6 +363,12 @@ private:
 public:
     explicit CallCoalescer(bool enc, int seats = kCoalesceLeaders) : kind(enc ? kEncode : kDecode), encode(enc), max_leaders(seats < 1 ? 1 : seats) {}
     explicit CallCoalescer(Kind k, int seats = kCoalesceLeaders) : kind(k), encode(k == kEncode), max_leaders(seats < 1 ? 1 : seats) {}
+
+    void counts(long long* batches, long long* retried) const
+    {
+        *batches = shared_batches.load(std::memory_order_relaxed);
+        *retried = retried_batches.load(std::memory_order_relaxed);
+    }
 
     int submit(SmallCall& call)
     {

@@ -1,8 +1,9 @@
 // tests/c/coalescer_stress.cpp -- the call coalescer of libsela_hip.so (sela_amd/csrc/sela_coalescer.h) on a CPU stub
 // backend, built with -fsanitize=thread by tests/test_sanitizers.py: many threads submit one- to four-frame calls of two
-// channel counts, every call must get back ITS OWN result and error (a too-small output buffer, a "malformed" frame that
-// fails a whole batch and is then retried call by call), and the thread sanitizer must see no race in the hand-overs
-// (queue, leader election, results written by the leader and read by the callers).
+// channel counts, every call must get back ITS OWN result and error (a too-small output buffer, a "malformed" frame or
+// one with a coefficient "out of range" that fails a whole batch and is then retried call by call), the coalescer's own
+// counters must show such retried batches, and the thread sanitizer must see no race in the hand-overs (queue, leader
+// election, results written by the leader and read by the callers).
 //
 // TEST INFRASTRUCTURE: the stub stands in for the device; nothing here is compiled into the library.
 #include <atomic>
@@ -19,7 +20,8 @@ std::atomic<int> g_jobs{ 0 }, g_frames{ 0 }, g_leaders_done{ 0 };
 thread_local std::string t_error;
 
 // "encoding" = 8 bytes per frame: the frame's first sample and a checksum of the rest; "decoding" = the inverse filling
-// the frame with the first sample.  A frame whose first sample is -32768 is "malformed" (decode only).
+// the frame with the first sample.  A frame whose first sample is -32768 is "malformed", one whose first sample is -32767 holds a
+// "coefficient out of range" (decode only: SELA_HIP_EFORMAT / SELA_HIP_ERANGE, as the device's decoders report them).
 struct StubBackend {
     static size_t encode_bound_bytes(uint32_t n_frames, uint32_t) { return (size_t)n_frames * 8; }
     static int encode_now(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint8_t* out, size_t cap, uint64_t* offsets)
@@ -53,6 +55,10 @@ struct StubBackend {
                 t_error = "malformed frame";
                 return SELA_HIP_EFORMAT;
             }
+            if ((int16_t)(uint16_t)first == -32767) {
+                t_error = "coefficient out of range";
+                return SELA_HIP_ERANGE;
+            }
             for (size_t i = 0; i < (size_t)kFrame * channels; i++)
                 pcm[(size_t)f * kFrame * channels + i] = (int16_t)(uint16_t)first;
         }
@@ -70,6 +76,10 @@ struct StubBackend {
             if ((int16_t)(uint16_t)first == -32768) {
                 t_error = "malformed frame";
                 return SELA_HIP_EFORMAT;
+            }
+            if ((int16_t)(uint16_t)first == -32767) {
+                t_error = "coefficient out of range";
+                return SELA_HIP_ERANGE;
             }
             for (uint32_t c = 0; c < channels; c++) {
                 const uint32_t cnt = 100 + 10 * c;
@@ -154,21 +164,23 @@ int worker(Coalescer& enc, Coalescer& dec, Coalescer& dec32, Coalescer& enc32, i
             if ((int16_t)(uint16_t)first != pcm[(size_t)f * kFrame * channels] || (first >> 16) != channels)
                 failures++, std::fprintf(stderr, "thread %d round %d: frame %u came back as somebody else's\n", id, r, f);
         }
-        // decode; every 13th call carries a "malformed" frame: the batch fails, is retried call by call, only this caller hears of it
-        const bool bad = r % 13 == 7;
-        if (bad) {
-            const uint32_t poison = 0x8000u | (channels << 16);
+        // decode; every 13th call carries a "malformed" frame, every 23rd one with a coefficient "out of range": the batch fails, is
+        // retried call by call, only this caller hears of it
+        const bool bad = r % 13 == 7, range = !bad && r % 23 == 11;
+        if (bad || range) {
+            const uint32_t poison = (bad ? 0x8000u : 0x8001u) | (channels << 16);
             std::memcpy(bytes.data() + offsets[n - 1], &poison, 4);
         }
+        const int want = bad ? SELA_HIP_EFORMAT : range ? SELA_HIP_ERANGE : SELA_HIP_OK;
         std::vector<int16_t> back(pcm.size(), 12345);
         sela::SmallCall d;
         d.device = e.device, d.channels = channels, d.n_frames = n;
         d.frames = bytes.data(), d.offsets_in = offsets.data(), d.pcm_out = back.data();
         const int rd = dec.submit(d);
-        if (bad ? rd != SELA_HIP_EFORMAT : (rd != SELA_HIP_OK || back != pcm))
-            failures++, std::fprintf(stderr, "thread %d round %d: decode rc %d (bad frame: %d)\n", id, r, rd, (int)bad);
+        if (rd != want || (want == SELA_HIP_OK && back != pcm) || (want != SELA_HIP_OK && d.error != (bad ? "malformed frame" : "coefficient out of range")))
+            failures++, std::fprintf(stderr, "thread %d round %d: decode rc %d (bad frame: %d, out of range: %d)\n", id, r, rd, (int)bad, (int)range);
         // the same frames to 32-bit channels, every caller with a stride of its own; every 17th call with one that is too small
-        const bool narrow = !bad && r % 17 == 3;
+        const bool narrow = want == SELA_HIP_OK && r % 17 == 3;
         const uint32_t stride = narrow ? 50u : 128u + (uint32_t)(id % 5) * 7u;
         std::vector<int32_t> wide((size_t)n * channels * stride, -7);
         std::vector<uint32_t> counts((size_t)n * channels, 999);
@@ -176,9 +188,9 @@ int worker(Coalescer& enc, Coalescer& dec, Coalescer& dec32, Coalescer& enc32, i
         w.device = e.device, w.channels = channels, w.n_frames = n;
         w.frames = bytes.data(), w.offsets_in = offsets.data(), w.samples_out = wide.data(), w.stride = stride, w.counts_out = counts.data();
         const int rw = dec32.submit(w);
-        if (bad ? rw != SELA_HIP_EFORMAT : (narrow ? rw != SELA_HIP_ECAPACITY : rw != SELA_HIP_OK)) {
-            failures++, std::fprintf(stderr, "thread %d round %d: decode32 rc %d (bad %d narrow %d)\n", id, r, rw, (int)bad, (int)narrow);
-        } else if (!bad && !narrow) {
+        if (narrow ? rw != SELA_HIP_ECAPACITY : rw != want) {
+            failures++, std::fprintf(stderr, "thread %d round %d: decode32 rc %d (bad %d out of range %d narrow %d)\n", id, r, rw, (int)bad, (int)range, (int)narrow);
+        } else if (want == SELA_HIP_OK && !narrow) {
             for (uint32_t f = 0; f < n; f++)
                 for (uint32_t c = 0; c < channels; c++) {
                     const size_t row = (size_t)f * channels + c;
@@ -230,6 +242,17 @@ int main(int argc, char** argv)
             pool.emplace_back(worker, std::ref(enc), std::ref(dec), std::ref(dec32), std::ref(enc32), t, rounds, std::ref(failures));
         for (std::thread& t : pool)
             t.join();
+        // the poisoned calls above really shared batches with others, and those batches were retried call by call (the 16-bit
+        // encoder's poisoned calls -- too-small buffers -- are answered from the batch's result without a retry)
+        const char* names[] = { "decode", "encode", "decode32", "encode32" };
+        Coalescer* kinds[] = { &dec, &enc, &dec32, &enc32 };
+        for (int k = 0; k < 4; k++) {
+            long long batches = 0, retried = 0;
+            kinds[k]->counts(&batches, &retried);
+            const bool poisoned = k != Coalescer::kEncode;
+            if (batches < 1 || retried > batches || (poisoned && retried < 1))
+                failures++, std::fprintf(stderr, "%d seats, %s: %lld batches of several calls, %lld of them retried call by call\n", seats, names[k], batches, retried);
+        }
         std::printf("%d seats: %d threads x %d rounds: %d device jobs for %d frames so far, %d batches led, %d failures\n", seats, threads, rounds, g_jobs.load(),
             g_frames.load(), g_leaders_done.load(), failures.load());
     }
