@@ -132,6 +132,36 @@ int sela_hip_decode_device(const uint8_t* d_frames, const uint64_t* d_frame_offs
     uint32_t channels, int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, size_t workspace_bytes,
     void* stream);
 
+/*
+ * Find the frames of a payload -- the byte stream that follows the 15-byte .sela file header -- on the device: the
+ * device-side sela_hip_index_frames().  d_frame_offsets (uint64 [max_frames + 1]) and *d_n_frames (uint32) receive exactly
+ * what sela_hip_index_frames(payload, payload_bytes, max_frames, channels, ...) returns for the same bytes, for every input:
+ * entries [0 .. *d_n_frames], the last of them where the walk stopped (a bad sync word, a header or stream running past
+ * payload_bytes, or the max_frames cap); entries beyond are not written.  d_payload must be 4-byte aligned.
+ * Asynchronous on `stream`, no allocation, no host synchronisation (a stream being captured into a graph may take it):
+ * 4 kernel launches up to max_frames = 4096, 5 + ceil(log2(max_frames)) above.
+ * d_workspace: sela_hip_index_workspace_bytes(payload_bytes, max_frames) bytes, no initialisation: 6 bytes per payload
+ * byte (six uint32 per 4-byte word: every word may start a frame), 1 byte per 4 KiB and at most 2.5 KiB more; the same for
+ * every max_frames.
+ * SELA_HIP_EINVAL: channels outside 1..255, a null pointer, a misaligned d_payload, a payload of 16 GiB or more;
+ * SELA_HIP_ECAPACITY: a smaller workspace.
+ */
+size_t sela_hip_index_workspace_bytes(size_t payload_bytes, uint32_t max_frames);
+int sela_hip_index_frames_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    uint64_t* d_frame_offsets /* [max_frames + 1] */, uint32_t* d_n_frames /* [1] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+/*
+ * sela_hip_index_frames_device() and then sela_hip_decode_device() on the frames it found, on one stream: the frame count
+ * never leaves the device.  d_pcm_out: int16 [max_frames][2048][channels], frames from *d_n_frames on are not decoded and
+ * their PCM is not written.  d_status as sela_hip_decode_device()'s (frames that do not say 2048 samples are
+ * SELA_HIP_FLAG_BAD_FRAME there too).  d_workspace: sela_hip_index_workspace_bytes(payload_bytes, max_frames) +
+ * sela_hip_decode_workspace_bytes(max_frames, channels) bytes.  channels <= sela_hip_decode_max_channels(); errors as the
+ * two calls'.  Returns immediately.
+ */
+int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    int16_t* d_pcm_out, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+
 /* ---- host-pointer API (synchronous) -------------------------------------------------------------- */
 /* frames_out must hold sela_hip_encode_bound_bytes() or the call may return SELA_HIP_ECAPACITY.
  * These are begin + feed(everything) + end of the streaming jobs below, on library-owned streams: an encode is ONE

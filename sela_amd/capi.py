@@ -30,6 +30,7 @@ EXPORTS = [
     "sela_hip_decode_begin", "sela_hip_decode_feed", "sela_hip_decode_end",
     "sela_hip_encode_bound_bytes_n", "sela_hip_index_samples", "sela_hip_encode_i32", "sela_hip_decode_i32", "sela_hip_encode_ragged_i32",
     "sela_hip_lpc_encode_n", "sela_hip_lpc_decode_n",
+    "sela_hip_index_workspace_bytes", "sela_hip_index_frames_device", "sela_hip_decode_payload_device",
 ]
 
 
@@ -100,6 +101,12 @@ def lib() -> C.CDLL:
     L.sela_hip_decode.restype = C.c_int
     L.sela_hip_index_frames.argtypes = [vp, sz, u32, u32, vp]
     L.sela_hip_index_frames.restype = u32
+    L.sela_hip_index_workspace_bytes.argtypes = [sz, u32]
+    L.sela_hip_index_workspace_bytes.restype = sz
+    L.sela_hip_index_frames_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, sz, vp]
+    L.sela_hip_index_frames_device.restype = C.c_int
+    L.sela_hip_decode_payload_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_payload_device.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]
     L.sela_hip_enable_kernel_timing.restype = None
     L.sela_hip_kernel_times.argtypes = [C.POINTER(C.c_float), C.c_int]

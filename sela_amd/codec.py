@@ -108,6 +108,31 @@ class Decoder:
             self.workspace.data_ptr(), self.workspace.numel(), stream))
         return self.pcm[:n_frames]
 
+    def decode_payload(self, payload, max_frames=None, status=None):
+        """Index and decode a .sela payload (the bytes after the file header: uint8 cuda tensor, 4-byte aligned) in one
+        asynchronous call: the frame count never leaves the device, so the call can be captured into a graph.
+        -> (pcm int16 [max_frames, 2048, channels], offsets int64 [max_frames + 1], count int32 [1]); frames from count[0] on
+        are not decoded.  All three are the decoder's own buffers, overwritten by the next call; so is its workspace, which
+        grows to the largest payload seen (make one call before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        status = self.status if status is None else status
+        assert status.dtype == torch.int32 and status.numel() == 4 and status.is_cuda and status.is_contiguous()
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_decode_workspace_bytes(max_frames, self.channels))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if getattr(self, "payload_offsets", None) is None:
+                self.payload_offsets = torch.empty(self.max_frames + 1, dtype=torch.int64, device=self.device)
+                self.payload_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.pcm.data_ptr(), self.payload_offsets.data_ptr(),
+            self.payload_count.data_ptr(), status.data_ptr(), self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.pcm[:max_frames], self.payload_offsets[: max_frames + 1], self.payload_count
+
     def check(self) -> None:
         st = self.status.cpu().numpy().view(np.uint32)
         if int(st[0]) & capi.FLAG_BAD_FRAME:
@@ -201,6 +226,57 @@ def index_frames(frames: np.ndarray, n_frames: int, channels: int) -> np.ndarray
     offs = np.zeros(n_frames + 1, np.uint64)
     found = lib.sela_hip_index_frames(fr.ctypes.data, fr.nbytes, n_frames, channels, offs.ctypes.data)
     return offs[: found + 1]
+
+
+def index_frames_device(payload, max_frames: int, channels: int, workspace=None):
+    """sela_hip_index_frames_device: the frames of a payload (uint8 cuda tensor, 4-byte aligned) found on the device,
+    asynchronously on the current stream -> (offsets int64 [max_frames + 1], count int32 [1]), both on the device; entries
+    [0 .. count] are what index_frames() returns for the same bytes.  workspace: uint8 cuda tensor of at least
+    index_workspace_bytes() bytes (default: a new one)."""
+    import torch
+
+    assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous()
+    lib = capi.lib()
+    device = payload.device
+    if workspace is None:
+        workspace = torch.empty(int(lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)), dtype=torch.uint8, device=device)
+    offsets = torch.empty(max_frames + 1, dtype=torch.int64, device=device)
+    count = torch.empty(1, dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    capi.check(lib.sela_hip_index_frames_device(payload.data_ptr(), payload.numel(), max_frames, channels, offsets.data_ptr(),
+                                                count.data_ptr(), workspace.data_ptr(), workspace.numel(), stream))
+    return offsets, count
+
+
+def index_workspace_bytes(payload_bytes: int, max_frames: int) -> int:
+    return int(capi.lib().sela_hip_index_workspace_bytes(payload_bytes, max_frames))
+
+
+@dataclass
+class SelaPayload:
+    """A .sela file's payload on the device, and what its 15-byte header says."""
+    payload: "torch.Tensor"  # uint8 [payload bytes], 4-byte aligned
+    channels: int
+    max_frames: int          # numFrames of the header
+    sample_rate: int
+    bits_per_sample: int
+
+
+def read_sela_payload(path, device) -> SelaPayload:
+    """Parse the 15-byte .sela header on the host ('SeLa', u32 rate, u16 bits, u8 channels, u32 frames: src/file/sela_file.cpp:
+    28-47) and upload the bytes after it into a new device tensor (device allocations are aligned far beyond 4 bytes)."""
+    import struct
+
+    import torch
+
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 15 or data[:4] != b"SeLa":
+        raise ValueError(f"{path}: not a .sela file")
+    rate, bits, channels, frames = struct.unpack_from("<IHBI", data, 4)
+    body = np.frombuffer(data, np.uint8, offset=15)
+    payload = torch.from_numpy(body.copy()).to(device)
+    return SelaPayload(payload, channels, frames, rate, bits)
 
 
 # ---- the stages on their own (sela_hip_lpc_* / sela_hip_rice_*: the reference's L1 classes, batched) -----------------------

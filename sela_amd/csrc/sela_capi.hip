@@ -42,8 +42,11 @@ hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_w
     uint32_t n_streams, int32_t* d_values, uint32_t* d_status, hipStream_t stream);
 hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles,
-    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0);
+    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0, const uint32_t* d_n_found = nullptr);
 int decode_waves(uint32_t channels);
+size_t index_workspace_bytes(uint64_t payload_bytes);
+hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
 // the any-length / 32-bit route (sela_capi_generic.hip)
 void generic_release();
 void generic_shutdown();
@@ -1419,6 +1422,49 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
     return SELA_HIP_OK;
 }
 
+namespace {
+// sela_hip_decode_device's launch, arguments checked; d_n_found (or null): the device's own count of frames to decode
+int decode_device_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
+    int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, void* stream, const uint32_t* d_n_found)
+{
+    hipEvent_t* ev = n_frames ? g_timing.events() : nullptr;
+    g_timing.recorded = ev ? 1 : 0;
+    // (the decoder's counterpart of the encoder's schedule: a launch that has the device to itself raises its heavy subframes)
+    int dev = -1;
+    uint32_t synth_priorities = 0;
+    if (n_frames && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+        const int64_t forced = g_forced_priorities.load(std::memory_order_relaxed);
+        synth_priorities = forced >= 0 ? (forced ? kHeavySubframesFirst : 0u)
+                                       : (stream_is_capturing(static_cast<hipStream_t>(stream)) || flights().others_pending(dev, static_cast<hipStream_t>(stream)) ? 0u : kHeavySubframesFirst);
+    } else {
+        dev = -1;
+    }
+    hipError_t e = sela::launch_decode(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace,
+        static_cast<hipStream_t>(stream), ev, g_phase_cycles, nullptr, g_recurrence_form, synth_priorities, d_n_found);
+    if (e != hipSuccess)
+        return fail_hip(e, "decode launch");
+    if (dev >= 0)
+        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
+            flights().note(dev, static_cast<hipStream_t>(stream));
+    return SELA_HIP_OK;
+}
+
+// the index's own checks (sela_hip_index_frames_device); SELA_HIP_OK or the failure, reported
+int check_index_args(const uint8_t* d_payload, size_t payload_bytes, uint32_t channels, const uint64_t* d_frame_offsets, const uint32_t* d_n_frames,
+    const void* d_workspace)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (!d_frame_offsets || !d_n_frames || !d_workspace || (payload_bytes && !d_payload))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_payload & 3)
+        return fail(SELA_HIP_EINVAL, "d_payload must be 4-byte aligned");
+    if (payload_bytes / 4 >= 0xFFFFFFFFull)
+        return fail(SELA_HIP_EINVAL, "payloads of 16 GiB and more are not indexed on the device (32-bit word indices)");
+    return SELA_HIP_OK;
+}
+} // namespace
+
 int sela_hip_decode_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
@@ -1432,25 +1478,48 @@ int sela_hip_decode_device(const uint8_t* d_frames, const uint64_t* d_frame_offs
         return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
     if (workspace_bytes < sela::decode_workspace_bytes(n_frames, channels))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_decode_workspace_bytes()");
-    hipEvent_t* ev = n_frames ? g_timing.events() : nullptr;
-    g_timing.recorded = ev ? 1 : 0;
-    // (the decoder's counterpart of the encoder's schedule: a launch that has the device to itself raises its heavy subframes)
-    int dev = -1;
-    uint32_t synth_priorities = 0;
-    if (n_frames && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        const int64_t forced = g_forced_priorities.load(std::memory_order_relaxed);
-        synth_priorities = forced >= 0 ? (forced ? kHeavySubframesFirst : 0u) : (flights().others_pending(dev, static_cast<hipStream_t>(stream)) ? 0u : kHeavySubframesFirst);
-    } else {
-        dev = -1;
-    }
-    hipError_t e = sela::launch_decode(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace,
-        static_cast<hipStream_t>(stream), ev, g_phase_cycles, nullptr, g_recurrence_form, synth_priorities);
+    return decode_device_launch(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace, stream, nullptr);
+}
+
+size_t sela_hip_index_workspace_bytes(size_t payload_bytes, uint32_t max_frames)
+{
+    (void)max_frames; // (every word of the payload may be a candidate, whatever the cap)
+    return sela::index_workspace_bytes(payload_bytes);
+}
+
+int sela_hip_index_frames_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    uint64_t* d_frame_offsets, uint32_t* d_n_frames, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (workspace_bytes < sela::index_workspace_bytes(payload_bytes))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes()");
+    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace,
+        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "index launch");
+}
+
+int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    int16_t* d_pcm_out, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes,
+    void* stream)
+{
+    const int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (channels > sela::decode_max_channels())
+        return fail(SELA_HIP_EINVAL, "too many channels for the on-chip decoder (sela_hip_decode_max_channels)");
+    if (!d_status || (max_frames && !d_pcm_out))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes);
+    if (workspace_bytes < index_bytes + sela::decode_workspace_bytes(max_frames, channels))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_workspace_bytes()");
+    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace,
+        static_cast<hipStream_t>(stream));
     if (e != hipSuccess)
-        return fail_hip(e, "decode launch");
-    if (dev >= 0)
-        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
-            flights().note(dev, static_cast<hipStream_t>(stream));
-    return SELA_HIP_OK;
+        return fail_hip(e, "index launch");
+    return decode_device_launch(d_payload, d_frame_offsets, max_frames, channels, d_pcm_out, d_status,
+        static_cast<unsigned char*>(d_workspace) + index_bytes, stream, d_n_frames);
 }
 
 // ---- streaming jobs (host pointers) ----------------------------------------------------------------------------

@@ -71,7 +71,8 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
     uint32_t* __restrict__ status, int32_t* __restrict__ ws_residues, uint64_t* __restrict__ phase_cycles,
     uint8_t* __restrict__ frame_flags /* or null: one byte per (frame, wave), written only when not zero */,
     uint32_t vec_shift_from /* frames from this one on run the synthesis with the shift on the vector side (synth_steps) */,
-    uint32_t synth_priorities /* s_setprio through the synthesis by the subframe's order class: byte 0 orders <= 48, 1 <= 60, 2 above; 0: none */)
+    uint32_t synth_priorities /* s_setprio through the synthesis by the subframe's order class: byte 0 orders <= 48, 1 <= 60, 2 above; 0: none */,
+    const uint32_t* __restrict__ n_frames_found /* or null: frames from *n_frames_found on are not decoded (sela_hip_decode_payload_device) */)
 {
     long long stamp[10];
     for (int i = 0; i < 10; i++)
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
     uint32_t* const too_big = sub_info + channels; // [n_waves]: this wave's subframe does not fit the fast plan
 
     const uint32_t f = blockIdx.x;
-    if (f >= n_frames)
+    if (f >= n_frames || (n_frames_found && f >= *n_frames_found))
         return;
     const bool vec_shift = f >= vec_shift_from;
     const uint8_t* const fb = frames + frame_offsets[f];
@@ -309,7 +310,8 @@ constexpr uint32_t kNoSubframe = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const uint8_t* __restrict__ frames,
     const uint64_t* __restrict__ frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* __restrict__ pcm_out,
-    uint32_t* __restrict__ status, int32_t* __restrict__ ws_residues, uint8_t* __restrict__ frame_flags, uint32_t vec_shift_from)
+    uint32_t* __restrict__ status, int32_t* __restrict__ ws_residues, uint8_t* __restrict__ frame_flags, uint32_t vec_shift_from,
+    const uint32_t* __restrict__ n_frames_found /* or null, as in k_decode_frames */)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64)), lane = threadIdx.x % 64;
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
     DecWaveScratch* const scratch = reinterpret_cast<DecWaveScratch*>(dyn + (size_t)kDecMaxWaves * sizeof(DecSubframeLds)) + wave;
     uint32_t* const sub_info = reinterpret_cast<uint32_t*>(dyn + (size_t)kDecMaxWaves * (sizeof(DecSubframeLds) + sizeof(DecWaveScratch)));
     const uint32_t f = blockIdx.x;
-    if (f >= n_frames)
+    if (f >= n_frames || (n_frames_found && f >= *n_frames_found))
         return;
     const bool vec_shift = f >= vec_shift_from;
     const uint8_t* const fb = frames + frame_offsets[f];
@@ -554,7 +556,9 @@ hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offset
                                  device to itself raises the subframes of orders above 60 -- two registers per lane, 1.6 x the
                                  synthesis work, 31 % of the bench track's subframes -- so that they do not finish last:
                                  k_decode_frames 0.247 -> 0.240 ms at 3875 frames, one lane +1.1 %; beside another stream's
-                                 kernels the same costs 0.4 %, so the caller passes 0 there */)
+                                 kernels the same costs 0.4 %, so the caller passes 0 there */,
+    const uint32_t* d_n_found /* or null: the device's own count of frames to decode, at most n_frames (the grid and the
+                                 choices above are made for n_frames) */)
 {
     hipError_t err = frame_flags ? hipSuccess : hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream);
     if (err != hipSuccess || n_frames == 0)
@@ -572,7 +576,7 @@ hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offset
         const uint32_t from = recurrence_form >= 0 ? (recurrence_form ? 0u : n_frames)
                                                    : vec_shift_from_for(n_frames, kDecMaxWaves, resident_frames(reinterpret_cast<const void*>(k_decode_frames_wide), kDecMaxWaves, lds));
         hipLaunchKernelGGL(k_decode_frames_wide, dim3(n_frames), dim3(kDecMaxWaves * 64), lds, stream, d_frames, d_frame_offsets, n_frames, channels,
-            d_pcm_out, d_status, ws, frame_flags, from);
+            d_pcm_out, d_status, ws, frame_flags, from, d_n_found);
         if (ev)
             (void)hipEventRecord(ev[1], stream);
         return hipGetLastError();
@@ -595,13 +599,16 @@ hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offset
         (void)hipEventRecord(ev[0], stream);
     if (d_phase_cycles)
         hipLaunchKernelGGL(k_decode_frames<true>, dim3(n_frames), dim3(n_waves * 64), lds, stream, d_frames, d_frame_offsets, n_frames, channels,
-            d_pcm_out, d_status, ws, d_phase_cycles, frame_flags, from, synth_prio);
+            d_pcm_out, d_status, ws, d_phase_cycles, frame_flags, from, synth_prio, d_n_found);
     else
         hipLaunchKernelGGL(k_decode_frames<false>, dim3(n_frames), dim3(n_waves * 64), lds, stream, d_frames, d_frame_offsets, n_frames, channels,
-            d_pcm_out, d_status, ws, d_phase_cycles, frame_flags, from, synth_prio);
+            d_pcm_out, d_status, ws, d_phase_cycles, frame_flags, from, synth_prio, d_n_found);
     if (ev)
         (void)hipEventRecord(ev[1], stream);
     return hipGetLastError();
 }
+
+// ---- the frames of a payload found on the device ------------------------------------------------------------------------
+#include "sela_index.inc"
 
 } // namespace sela
