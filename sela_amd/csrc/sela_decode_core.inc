@@ -443,12 +443,15 @@ __device__ inline uint32_t parse_stream_serial(const uint32_t* __restrict__ word
 // kFold: the residue is folded into its sum at the start of its block of 64,
 //     N' = N - r * 2^35  (one subtract on the high word per 64 samples)   ==>   s = -(N' >> 35),
 // which drops the per-sample v_readlane of r, and the high product is one v_mad_i32_i24.  Both need
-// small operands: the shift keeps 29 bits and the multiplier 24, so this equals the reference's 32-bit
-// r - (int32)((2^34 - P) >> 35) exactly while |s| < 2^23 and |a| < 2^55; the coefficients are checked
-// when the table is built and every 64 samples against 2^23.  A block that fails the check has stored
-// nothing: the caller puts the sums back as they were at the block's start and runs it -- and the rest of
-// the subframe -- in the exact form (v_readlane of r, v_mul_lo_u32 + v_add_u32).  16-bit audio never gets
-// there; crafted streams do (tests).
+// small operands: the high word keeps r only mod 2^29, so the folded s is (r - pred) reduced to 29 signed
+// bits, and the multiplier takes 24.  With |a| < 2^55 (checked when the table is built), |r| < 2^23 (checked
+// on the block's residues before it starts) and |pred| < 2^28 (a 29-bit value), the true |s| is below
+// 2^28 + 2^23: where it is below 2^28 the reduction is s itself, elsewhere the reduced value exceeds 2^23 in
+// size.  So with the check of every 64 samples against 2^23 the folded form equals the reference's 32-bit
+// r - (int32)((2^34 - P) >> 35) exactly, or gives up.  A block whose residues fail their check runs, with the
+// rest of the subframe, in the exact form (v_readlane of r, v_mul_lo_u32 + v_add_u32); one whose samples fail
+// theirs has stored nothing: the caller puts the sums back as they were at the block's start and does the
+// same.  16-bit audio never gets there; wide audio and crafted streams do (tests).
 // kShift: also hand back (new high word) >> 3, the next step's multiplier if the next step's sum is in this register
 // (kVecShift, see synth_steps).
 template <bool kFold, bool kShift>
@@ -633,6 +636,8 @@ __device__ __attribute__((noinline)) void synthesize( // (a real call: six of th
             issue(blk + 1); // in flight during this block's 64 steps
         int32_t s;
         bool done = false;
+        // (a residue the folded subtraction cannot carry whole: see synth_mac)
+        fold = fold && !__any((uint32_t)(r_block + (1 << 23) - 1) >= (1u << 24) - 1u);
         if (fold) {
             const uint32_t s0 = cl, s1 = ch, s2 = ol, s3 = oh;
             done = synth_block<R, true, G, kVecShift>(r_block, s, cl, ch, ol, oh, tab_lane, four, zero);

@@ -162,7 +162,7 @@ class Oracle:
         """planar: int32 [channels, n] (data::WavFrame.samples) -> bytes of the on-disk frame."""
         p = np.ascontiguousarray(planar, dtype=np.int32)
         ch, n = p.shape
-        out = np.zeros(4 + ch * (12 + 4 * 128 + 16 * n + 256), np.uint8)
+        out = np.zeros(4 + ch * (12 + 4 * 128 + 16 * n + 4 * 65536 + 256), np.uint8)  # (wide audio: up to 65535 Rice words per subframe)
         used = self._fenc32(p, ch, n, out, *self._fl())
         return out[:used].tobytes()
 
@@ -171,7 +171,7 @@ class Oracle:
         chans = [np.ascontiguousarray(c, dtype=np.int32).ravel() for c in channels]
         flat = np.concatenate(chans) if chans else np.zeros(0, np.int32)
         lengths = np.array([len(c) for c in chans], np.uint32)
-        out = np.zeros(4 + sum(12 + 4 * 128 + 16 * len(c) + 256 for c in chans), np.uint8)
+        out = np.zeros(4 + sum(12 + 4 * 128 + 16 * len(c) + 4 * 65536 + 256 for c in chans), np.uint8)
         used = self._fencr(flat, lengths, len(chans), out, *self._fl())
         return out[:used].tobytes()
 
