@@ -194,8 +194,9 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
  *     2048-sample frames pays nothing for the other kind) -- unless the stream's FIRST frame already says another length --
  *     and they may write up to [n_frames][2048][channels] before they find an odd frame further on: pcm_out must hold
  *     max(n_frames * 2048, sample_offsets[n_frames]) * channels samples.
- * The streaming jobs and the device-pointer calls below stay what they are: the fast path for what the reference's CLI writes
- * (2048 everywhere); a stream with another length gets SELA_HIP_EFORMAT from them, and the caller comes here. */
+ * The streaming jobs and the int16 device-pointer calls (sela_hip_decode_device, sela_hip_decode_payload_device) stay what they
+ * are: the fast path for what the reference's CLI writes (2048 everywhere); a stream with another length gets SELA_HIP_EFORMAT
+ * from them, and the caller comes here -- or, with the stream in device memory, to sela_hip_decode_i32_device below. */
 size_t sela_hip_encode_bound_bytes_n(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel);
 /* sample_offsets[f] = samples per channel before frame f (its first subframe's samplesPerChannel counts for the frame),
  * [n_frames + 1] entries; returns the largest samplesPerChannel any subframe of the stream names (0 for a stream the walk
@@ -241,6 +242,45 @@ int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
  * Errors as sela_hip_encode_i32. */
 int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap,
     size_t* frame_bytes);
+/* sela_hip_decode_i32 on DEVICE pointers -- the whole domain the reference decodes (any samplesPerChannel in 0 .. 65535, 32-bit
+ * samples, channels of different lengths), asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of
+ * device data, so a stream being captured into a HIP graph may take either call.
+ *   d_samples_out [n_frames][channels][stride] and d_counts_out [n_frames * channels]: exactly the layouts of sela_hip_decode_i32;
+ *                 what lies behind a channel's count is not defined.
+ *   d_sample_offsets [n_frames + 1] (or NULL): what sela_hip_index_samples() returns for the same frames (for decreasing
+ *                 offsets, where that function writes none, their contents are not defined).
+ *   d_status uint32[4], written by the call (needs no initialisation):
+ *     [0] the OR of the flag bits, [1] the number of malformed frames,
+ *     [2] the largest samplesPerChannel any subframe names, or 0 where sela_hip_index_samples() returns 0 (a caller whose
+ *         stride was too small can resize from it without walking the stream on the host),
+ *     [3] reserved, zeroed.
+ *   SELA_HIP_FLAG_STRIDE is set exactly where sela_hip_decode_i32 returns SELA_HIP_ECAPACITY: the offsets never decrease, the
+ *     whole header walk succeeds and [2] > stride.  Decreasing frame offsets are malformed frames here.
+ *   sela_hip_decode_status_error() turns a host copy of the status words into the code sela_hip_decode_i32 returns for the same
+ *     input (for a stream the host call decodes in one chunk of frames -- its chunks hold 768 MiB of device scratch -- since that
+ *     call stops at the first chunk in trouble).
+ * d_frames: 4-byte aligned, holding every frame the offsets name.  d_workspace: sela_hip_decode_i32_workspace_bytes(n_frames,
+ * channels, stride) bytes, no initialisation (the payload call: sela_hip_index_workspace_bytes(payload_bytes, max_frames) more);
+ * one call at a time may use it.  channels * n_frames below 2^31.
+ * sela_hip_debug_standard_first (include/sela_hip_debug.h) routes these calls as it routes the host call (0: the serial kernel
+ * alone, 2: every subframe by segments).
+ * SELA_HIP_EINVAL: a null pointer (d_sample_offsets may be NULL), channels outside 1..255, stride 0, a misaligned d_frames /
+ * d_payload; SELA_HIP_ECAPACITY: a smaller workspace. */
+size_t sela_hip_decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out /* [n_frames][channels][stride] */, uint32_t* d_counts_out /* [n_frames * channels] */,
+    uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count never leaves the device.
+ * Frames from *d_n_frames on are not decoded: their samples and counts are not written; d_sample_offsets[0 .. *d_n_frames] is. */
+int sela_hip_decode_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host only, no GPU: the code sela_hip_decode_i32 returns for the input whose device status words (a host copy) these are,
+ * in the host call's order -- SELA_HIP_FLAG_STRIDE: SELA_HIP_ECAPACITY; a malformed frame (decreasing offsets among them) or a
+ * Rice stream that runs dry: SELA_HIP_EFORMAT; a coefficient beyond int64 or outside the tables, a subframe not longer than its
+ * order: SELA_HIP_ERANGE; SELA_HIP_FLAG_INTERNAL: SELA_HIP_ENODEV; else 0.  A null pointer: SELA_HIP_EINVAL. */
+int sela_hip_decode_status_error(const uint32_t* status /* [4], host copy */);
 
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
@@ -331,6 +371,8 @@ int sela_hip_kernel_times(float* ms_out, int capacity);
 #define SELA_HIP_FLAG_INTERNAL 64u     /* a bounded wait inside a kernel ran out (never expected; reported as SELA_HIP_ENODEV) */
 #define SELA_HIP_FLAG_SHORT_BLOCK 128u /* a block no longer than its own predictor order: the reference's warm-up loop reads past
                                         * its vector there (src/lpc/residue_generator.cpp:104-110); reported as SELA_HIP_ERANGE */
+#define SELA_HIP_FLAG_STRIDE 256u     /* a subframe is longer than the caller's stride (sela_hip_decode_i32_device: what the host call reports
+                                        * as SELA_HIP_ECAPACITY; nothing is written past [n_frames][channels][stride] all the same) */
 
 #ifdef __cplusplus
 }

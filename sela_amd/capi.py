@@ -16,6 +16,7 @@ ERRORS = {-1: "ENODEV", -2: "EINVAL", -3: "ENOMEM", -4: "ECAPACITY", -5: "EFORMA
 SAMPLES_PER_FRAME = 2048
 
 FLAG_Q_RANGE, FLAG_COEF_OVERFLOW, FLAG_RICE_RANGE, FLAG_RICE_OVERRUN, FLAG_WORDS_CAP, FLAG_BAD_FRAME, FLAG_INTERNAL, FLAG_SHORT_BLOCK = 1, 2, 4, 8, 16, 32, 64, 128
+FLAG_STRIDE = 256
 
 # every symbol include/sela_hip.h declares
 EXPORTS = [
@@ -31,6 +32,7 @@ EXPORTS = [
     "sela_hip_encode_bound_bytes_n", "sela_hip_index_samples", "sela_hip_encode_i32", "sela_hip_decode_i32", "sela_hip_encode_ragged_i32",
     "sela_hip_lpc_encode_n", "sela_hip_lpc_decode_n",
     "sela_hip_index_workspace_bytes", "sela_hip_index_frames_device", "sela_hip_decode_payload_device",
+    "sela_hip_decode_i32_workspace_bytes", "sela_hip_decode_i32_device", "sela_hip_decode_payload_i32_device", "sela_hip_decode_status_error",
 ]
 
 
@@ -107,6 +109,14 @@ def lib() -> C.CDLL:
     L.sela_hip_index_frames_device.restype = C.c_int
     L.sela_hip_decode_payload_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, vp, vp, sz, vp]
     L.sela_hip_decode_payload_device.restype = C.c_int
+    L.sela_hip_decode_i32_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_i32_workspace_bytes.restype = sz
+    L.sela_hip_decode_i32_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_i32_device.restype = C.c_int
+    L.sela_hip_decode_payload_i32_device.argtypes = [vp, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_payload_i32_device.restype = C.c_int
+    L.sela_hip_decode_status_error.argtypes = [vp]
+    L.sela_hip_decode_status_error.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]
     L.sela_hip_enable_kernel_timing.restype = None
     L.sela_hip_kernel_times.argtypes = [C.POINTER(C.c_float), C.c_int]

@@ -59,6 +59,10 @@ int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, in
 int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);
 size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels);
 uint32_t decode_max_channels();
+int generic_standard_first_mode();
+size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 } // namespace sela
 
 namespace {
@@ -1520,6 +1524,89 @@ int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_byte
         return fail_hip(e, "index launch");
     return decode_device_launch(d_payload, d_frame_offsets, max_frames, channels, d_pcm_out, d_status,
         static_cast<unsigned char*>(d_workspace) + index_bytes, stream, d_n_frames);
+}
+
+// ---- the 32-bit decode on device pointers --------------------------------------------------------
+namespace {
+// what sela_hip_decode_i32_device and the payload call check alike; SELA_HIP_OK or the failure, reported
+int check_decode_i32_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* d_samples_out, const uint32_t* d_counts_out,
+    const uint32_t* d_status, const void* d_workspace)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (stride == 0)
+        return fail(SELA_HIP_EINVAL, "stride must not be 0");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!d_status || !d_workspace || (n_frames && (!d_samples_out || !d_counts_out)))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    return SELA_HIP_OK;
+}
+} // namespace
+
+size_t sela_hip_decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::decode_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = check_decode_i32_args(n_frames, channels, stride, d_samples_out, d_counts_out, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!d_frame_offsets || (n_frames && !d_frames))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_frames & 3)
+        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
+    if (workspace_bytes < sela::decode_i32_workspace_bytes(n_frames, channels, stride))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_decode_i32_workspace_bytes()");
+    const hipError_t e = sela::launch_decode_i32_device(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_samples_out, d_counts_out,
+        d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "decode_i32 launch");
+}
+
+int sela_hip_decode_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc == SELA_HIP_OK)
+        rc = check_decode_i32_args(max_frames, channels, stride, d_samples_out, d_counts_out, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), decode_bytes = sela::decode_i32_workspace_bytes(max_frames, channels, stride);
+    if (decode_bytes == SIZE_MAX || workspace_bytes < index_bytes + decode_bytes)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_i32_workspace_bytes()");
+    hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "index launch");
+    e = sela::launch_decode_i32_device(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_samples_out, d_counts_out, d_sample_offsets,
+        d_status, static_cast<unsigned char*>(d_workspace) + index_bytes, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "decode_i32 launch");
+}
+
+// sela_hip_decode_i32's checks after its walk, in its order (sela_hip_decode_i32 above, generic_decode in sela_capi_generic.hip)
+int sela_hip_decode_status_error(const uint32_t* status)
+{
+    if (!status)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    const uint32_t flags = status[0];
+    if (flags & SELA_HIP_FLAG_STRIDE)
+        return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (status[2])");
+    if ((flags & SELA_HIP_FLAG_BAD_FRAME) || status[1])
+        return fail(SELA_HIP_EFORMAT, "malformed frame (decreasing offsets, sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, or channels of different lengths)");
+    if (flags & SELA_HIP_FLAG_RICE_OVERRUN)
+        return fail(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
+    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
+        return fail(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
+    if (flags & SELA_HIP_FLAG_Q_RANGE)
+        return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
+    if (flags & SELA_HIP_FLAG_SHORT_BLOCK)
+        return fail(SELA_HIP_ERANGE, "decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)");
+    if (flags & SELA_HIP_FLAG_INTERNAL)
+        return fail(SELA_HIP_ENODEV, "decode: a bounded wait inside a kernel ran out");
+    return SELA_HIP_OK;
 }
 
 // ---- streaming jobs (host pointers) ----------------------------------------------------------------------------

@@ -242,6 +242,7 @@ int flags_error(uint32_t flags, const char* who)
 namespace sela {
 
 void generic_release() { g_lease.give_back(); }
+int generic_standard_first_mode() { return g_standard_first_mode.load(std::memory_order_relaxed); }
 void generic_shutdown()
 {
     g_lease.give_back();

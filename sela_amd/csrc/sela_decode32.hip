@@ -312,7 +312,8 @@ template <bool kVecShift>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_decode_subframes32(const uint8_t* __restrict__ frames,
     const uint64_t* __restrict__ frame_offsets, uint64_t base_bytes, uint32_t n_frames, uint32_t channels, uint32_t stride,
     int32_t* __restrict__ dec_ws /* [n_frames][channels][stride] by subframe position */, GenericSubInfo* __restrict__ info, uint32_t* __restrict__ status,
-    uint32_t standard_path /* 0: every subframe by segments (tests) */)
+    uint32_t standard_path /* 0: every subframe by segments (tests) */,
+    const uint32_t* __restrict__ n_frames_found /* or null: frames from *n_frames_found on are not decoded (sela_hip_decode_payload_i32_device) */)
 {
     __shared__ __attribute__((aligned(16))) DecSubframeLds sl;
     __shared__ DecWaveScratch scratch;
@@ -321,6 +322,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         return;
     const int lane = threadIdx.x;
     const uint32_t f = sub / channels, c = sub % channels;
+    if (n_frames_found && f >= *n_frames_found)
+        return;
     const uint64_t at = frame_offsets[f] - base_bytes;
     const uint8_t* const fb = frames + at;
     const uint64_t fbytes = frame_offsets[f + 1] - frame_offsets[f];
@@ -429,17 +432,17 @@ __global__ __launch_bounds__(64) void k_lpc_decode_any(const int32_t* __restrict
 }
 
 hipError_t launch_decode_subframes32(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint64_t base_bytes, uint32_t n_frames, uint32_t channels,
-    uint32_t stride, int32_t* d_dec, GenericSubInfo* d_info, uint32_t* d_status, bool standard_path, hipStream_t stream)
+    uint32_t stride, int32_t* d_dec, GenericSubInfo* d_info, uint32_t* d_status, bool standard_path, hipStream_t stream, const uint32_t* d_n_found)
 {
     const uint64_t subs = (uint64_t)n_frames * channels;
     if (subs == 0)
         return hipSuccess;
     if (subs <= kLonelyWaves) // (the recurrence's form for waves that have their SIMD nearly to themselves, vec_shift_from_for)
         hipLaunchKernelGGL(k_decode_subframes32<true>, dim3((uint32_t)subs), dim3(64), 0, stream, d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec,
-            d_info, d_status, standard_path ? 1u : 0u);
+            d_info, d_status, standard_path ? 1u : 0u, d_n_found);
     else
         hipLaunchKernelGGL(k_decode_subframes32<false>, dim3((uint32_t)subs), dim3(64), 0, stream, d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec,
-            d_info, d_status, standard_path ? 1u : 0u);
+            d_info, d_status, standard_path ? 1u : 0u, d_n_found);
     return hipGetLastError();
 }
 

@@ -32,8 +32,14 @@ hipError_t launch_generic_emit(const GenericMeta* d_meta, uint32_t n_frames, uin
 hipError_t launch_generic_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint64_t base_bytes, uint32_t n_frames, uint32_t channels, uint32_t stride,
     int32_t* d_dec, GenericSubInfo* d_info, int32_t* d_all, uint32_t* d_counts, const uint64_t* d_sample_offsets, int16_t* d_pcm_out, uint32_t* d_status,
     bool fast_first, bool standard_path, hipStream_t stream);
+// d_n_found (or null): the device's own count of frames; frames from *d_n_found on are left alone (sela_hip_decode_payload_i32_device)
 hipError_t launch_decode_subframes32(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint64_t base_bytes, uint32_t n_frames, uint32_t channels,
-    uint32_t stride, int32_t* d_dec, GenericSubInfo* d_info, uint32_t* d_status, bool standard_path, hipStream_t stream);
+    uint32_t stride, int32_t* d_dec, GenericSubInfo* d_info, uint32_t* d_status, bool standard_path, hipStream_t stream, const uint32_t* d_n_found = nullptr);
+// sela_hip_decode_i32_device / sela_hip_decode_payload_i32_device: the sample index, the fast kernel, the judge
+// and the combine, all on `stream`, nothing waited for.  Arguments checked by the caller; mode as sela_hip_debug_standard_first.
+size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 hipError_t launch_lpc_decode_any(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, uint32_t n, int32_t* d_samples,
     int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
 

@@ -17,6 +17,7 @@
 // -> k_generic_combine (independent subframes first, then dependent ones in subframe order: src/frame/frame_decoder.cpp:17-69).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "sela_device.h"
@@ -1005,15 +1006,21 @@ __device__ inline int32_t rice_chunk(RiceScan& sc, const uint8_t* base, uint32_t
 
 __global__ __launch_bounds__(64) void k_generic_decode(const uint8_t* __restrict__ frames, const uint64_t* __restrict__ frame_offsets, uint64_t base_bytes,
     uint32_t n_frames, uint32_t channels, uint32_t stride, int32_t* __restrict__ dec_ws /* [n_frames][channels][stride] by subframe position */,
-    GenericSubInfo* __restrict__ info /* [n_frames][channels] */, uint32_t* __restrict__ status)
+    GenericSubInfo* __restrict__ info /* [n_frames][channels] */, uint32_t* __restrict__ status,
+    const uint32_t* __restrict__ n_frames_found /* or null: frames from *n_frames_found on are not decoded */,
+    const uint32_t* __restrict__ left_alone /* or null: the workgroup returns at once while *left_alone is 0 (the judge's decision on the device) */)
 {
     __shared__ int64_t a_lds[kMaxOrder + 1];
     __shared__ int32_t q_lds[256];
     const uint32_t sub = blockIdx.x;
     if (sub >= n_frames * channels)
         return;
+    if (left_alone && *left_alone == 0)
+        return;
     const int lane = threadIdx.x;
     const uint32_t f = sub / channels, c = sub % channels;
+    if (n_frames_found && f >= *n_frames_found)
+        return;
     const uint8_t* const fb = frames + (frame_offsets[f] - base_bytes);
     const uint64_t fbytes = frame_offsets[f + 1] - frame_offsets[f];
     GenericSubInfo si;
@@ -1136,11 +1143,12 @@ constexpr uint32_t kCombineSlice = 4096;
 template <bool kOut16>
 __global__ __launch_bounds__(kCombineThreads) void k_generic_combine(const int32_t* __restrict__ dec_ws, const GenericSubInfo* __restrict__ info, uint32_t n_frames,
     uint32_t channels, uint32_t stride, int32_t* __restrict__ all /* [n_frames][channels][stride] by channel */, uint32_t* __restrict__ counts,
-    const uint64_t* __restrict__ sample_offsets, int16_t* __restrict__ pcm_out, uint32_t* __restrict__ status)
+    const uint64_t* __restrict__ sample_offsets, int16_t* __restrict__ pcm_out, uint32_t* __restrict__ status,
+    const uint32_t* __restrict__ n_frames_found /* or null, as in k_generic_decode */)
 {
     __shared__ uint32_t cnt[256];
     const uint32_t f = blockIdx.x;
-    if (f >= n_frames)
+    if (f >= n_frames || (n_frames_found && f >= *n_frames_found))
         return;
     const uint32_t t = threadIdx.x;
     const uint32_t lo = blockIdx.y * kCombineSlice, hi = lo + kCombineSlice; // this workgroup's samples
@@ -1215,6 +1223,192 @@ __global__ __launch_bounds__(kCombineThreads) void k_generic_combine(const int32
     }
 }
 
+// ---- the sample index on the device (sela_hip_decode_i32_device) --------------------------------------------
+// generic_index_samples (sela_capi_generic.hip) taken apart: every frame's header walk is independent of the others, only the
+// running total is not.  A thread walks kSampleFramesPerThread frames with that function's own byte reads and bounds, and a
+// workgroup scans its kSampleTileFrames frames' first samplesPerChannel.  Up to one tile (a track: 4096 frames) that is the
+// whole index, in one launch; above, every tile scans its own frames (k_index_samples<false>), one workgroup scans the tiles'
+// totals (k_sample_tiles) and every tile adds its base (k_sample_spread).  The launch that finishes also writes the caller's
+// status words ([2] = what sela_hip_index_samples would return, SELA_HIP_FLAG_STRIDE where sela_hip_decode_i32 would refuse
+// the stride) and zeroes the fast kernel's counters in the workspace: nothing else on the stream initialises them.
+constexpr uint32_t kSampleThreads = 1024, kSampleFramesPerThread = 4, kSampleTileFrames = kSampleThreads * kSampleFramesPerThread;
+constexpr uint32_t kSampleBroken = 1, kSampleDecreasing = 2;
+struct SampleTile {
+    uint64_t total; // this tile's samples per channel; k_sample_tiles replaces it by the samples before the tile
+    uint32_t largest, bad;
+};
+
+// one frame of generic_index_samples: its first subframe's samplesPerChannel; largest / bad accumulate
+__device__ inline uint32_t sample_head(const uint8_t* __restrict__ frames, const uint64_t* __restrict__ frame_offsets, uint32_t f, uint32_t channels,
+    uint32_t& largest, uint32_t& bad)
+{
+    const uint64_t o0 = frame_offsets[f], o1 = frame_offsets[f + 1];
+    if (o1 < o0)
+        bad |= kSampleDecreasing;
+    const uint8_t* const fb = frames + o0;
+    const uint64_t fbytes = o1 >= o0 ? o1 - o0 : 0;
+    uint64_t p = 4;
+    uint32_t first = 0;
+    for (uint32_t c = 0; c < channels; c++) {
+        if (p + 12 > fbytes) {
+            bad |= kSampleBroken;
+            break;
+        }
+        const uint64_t cw = (uint64_t)fb[p + 4] | ((uint64_t)fb[p + 5] << 8);
+        const uint64_t p2 = p + 7 + 4 * cw;
+        if (p2 + 5 > fbytes) {
+            bad |= kSampleBroken;
+            break;
+        }
+        const uint64_t rw = (uint64_t)fb[p2 + 1] | ((uint64_t)fb[p2 + 2] << 8);
+        const uint32_t n = (uint32_t)fb[p2 + 3] | ((uint32_t)fb[p2 + 4] << 8);
+        if (c == 0)
+            first = n;
+        largest = max(largest, n);
+        p = p2 + 5 + 4 * rw;
+        if (p > fbytes) {
+            bad |= kSampleBroken;
+            break;
+        }
+    }
+    return first;
+}
+
+// exclusive scan of one value per thread over the workgroup (blockDim.x a multiple of 64, at most 1024); *total: the sum
+__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t* part /* LDS [17] */, uint64_t& total)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    uint64_t inc = v;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(inc, d, 64);
+        if (lane >= d)
+            inc += o;
+    }
+    if (lane == 63)
+        part[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t run = 0;
+        for (uint32_t w = 0; w < waves; w++) {
+            const uint64_t t = part[w];
+            part[w] = run;
+            run += t;
+        }
+        part[16] = run;
+    }
+    __syncthreads();
+    const uint64_t excl = part[wave] + inc - v;
+    total = part[16];
+    __syncthreads();
+    return excl;
+}
+
+// the status words as the host call would leave them after its walk, and the fast kernel's counters zeroed
+__device__ inline void finish_sample_index(uint32_t largest, uint32_t bad, uint32_t stride, uint32_t* __restrict__ status, uint32_t* __restrict__ counters)
+{
+    const uint32_t walked = (bad & kSampleBroken) ? 0u : largest; // sela_hip_index_samples: 0 for a stream the walk cannot follow
+    status[0] = !(bad & kSampleDecreasing) && walked > stride ? (uint32_t)SELA_HIP_FLAG_STRIDE : 0u;
+    status[1] = 0;
+    status[2] = walked;
+    status[3] = 0;
+    for (int i = 0; i < 4; i++)
+        counters[i] = 0;
+}
+
+template <bool kOneTile>
+__global__ __launch_bounds__(kSampleThreads) void k_index_samples(const uint8_t* __restrict__ frames, const uint64_t* __restrict__ frame_offsets, uint32_t max_frames,
+    const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t channels, uint32_t stride, uint64_t* __restrict__ sample_offsets /* or null */,
+    uint32_t* __restrict__ status, uint32_t* __restrict__ counters, SampleTile* __restrict__ tiles)
+{
+    __shared__ uint64_t part[17];
+    __shared__ uint32_t s_largest, s_bad;
+    const uint32_t n = n_frames_found ? min(*n_frames_found, max_frames) : max_frames;
+    const uint32_t t = threadIdx.x;
+    if (t == 0)
+        s_largest = 0, s_bad = 0;
+    const uint64_t f0 = (uint64_t)blockIdx.x * kSampleTileFrames + (uint64_t)t * kSampleFramesPerThread;
+    uint32_t first[kSampleFramesPerThread];
+    uint32_t largest = 0, bad = 0;
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kSampleFramesPerThread; j++) {
+        first[j] = f0 + j < n ? sample_head(frames, frame_offsets, (uint32_t)(f0 + j), channels, largest, bad) : 0u;
+        sum += first[j];
+    }
+    __syncthreads();
+    if (largest)
+        atomicMax(&s_largest, largest);
+    if (bad)
+        atomicOr(&s_bad, bad);
+    uint64_t total;
+    uint64_t run = block_exclusive_scan(sum, part, total); // (its barriers also close the atomics above)
+    if (sample_offsets) {
+#pragma unroll
+        for (uint32_t j = 0; j < kSampleFramesPerThread; j++) {
+            if (f0 + j < n)
+                sample_offsets[f0 + j] = run;
+            run += first[j];
+        }
+    }
+    if (t != 0)
+        return;
+    if (kOneTile) {
+        if (sample_offsets)
+            sample_offsets[n] = total;
+        finish_sample_index(s_largest, s_bad, stride, status, counters);
+    } else {
+        SampleTile st;
+        st.total = total, st.largest = s_largest, st.bad = s_bad;
+        tiles[blockIdx.x] = st;
+    }
+}
+
+__global__ __launch_bounds__(kSampleThreads) void k_sample_tiles(SampleTile* __restrict__ tiles, uint32_t n_tiles, uint32_t max_frames,
+    const uint32_t* __restrict__ n_frames_found, uint32_t stride, uint64_t* __restrict__ sample_offsets, uint32_t* __restrict__ status,
+    uint32_t* __restrict__ counters)
+{
+    __shared__ uint64_t part[17];
+    __shared__ uint32_t s_largest, s_bad;
+    const uint32_t t = threadIdx.x;
+    if (t == 0)
+        s_largest = 0, s_bad = 0;
+    __syncthreads();
+    uint64_t carry = 0;
+    for (uint32_t i0 = 0; i0 < n_tiles; i0 += kSampleThreads) {
+        const uint32_t i = i0 + t;
+        SampleTile st;
+        st.total = 0, st.largest = 0, st.bad = 0;
+        if (i < n_tiles)
+            st = tiles[i];
+        if (st.largest)
+            atomicMax(&s_largest, st.largest);
+        if (st.bad)
+            atomicOr(&s_bad, st.bad);
+        uint64_t sum;
+        const uint64_t excl = block_exclusive_scan(st.total, part, sum);
+        if (i < n_tiles)
+            tiles[i].total = carry + excl;
+        carry += sum;
+    }
+    if (t != 0)
+        return;
+    const uint32_t n = n_frames_found ? min(*n_frames_found, max_frames) : max_frames;
+    if (sample_offsets)
+        sample_offsets[n] = carry;
+    finish_sample_index(s_largest, s_bad, stride, status, counters);
+}
+
+__global__ __launch_bounds__(kSampleThreads) void k_sample_spread(const SampleTile* __restrict__ tiles, uint32_t max_frames,
+    const uint32_t* __restrict__ n_frames_found, uint64_t* __restrict__ sample_offsets)
+{
+    const uint32_t n = n_frames_found ? min(*n_frames_found, max_frames) : max_frames;
+    const uint64_t base = tiles[blockIdx.x].total;
+    const uint64_t f0 = (uint64_t)blockIdx.x * kSampleTileFrames;
+    for (uint32_t j = threadIdx.x; j < kSampleTileFrames; j += kSampleThreads)
+        if (f0 + j < n)
+            sample_offsets[f0 + j] += base;
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------------
 size_t generic_encode_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
 {
@@ -1272,15 +1466,83 @@ hipError_t launch_generic_decode(const uint8_t* d_frames, const uint64_t* d_fram
         if (e != hipSuccess)
             return e;
     } else
-        hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec, d_info, d_status);
+        hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec, d_info, d_status,
+            nullptr, nullptr);
     const dim3 grid(n_frames, (stride + kCombineSlice - 1) / kCombineSlice);
     if (d_pcm_out)
         hipLaunchKernelGGL(k_generic_combine<true>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all, d_counts,
-            d_sample_offsets, d_pcm_out, d_status);
+            d_sample_offsets, d_pcm_out, d_status, nullptr);
     else
         hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all, d_counts,
-            d_sample_offsets, d_pcm_out, d_status);
+            d_sample_offsets, d_pcm_out, d_status, nullptr);
+    return hipGetLastError();
+}
+
+// Workspace of the device-pointer 32-bit decode: subframes as decoded, by position | one GenericSubInfo per subframe | the fast
+// kernel's four counters | one SampleTile per 4096 frames; every piece 256-byte aligned, the base too.
+struct DecodeI32Layout {
+    uint64_t dec, info, counters, tiles, bytes;
+};
+static DecodeI32Layout decode_i32_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t subs = (uint64_t)max_frames * channels, n_tiles = ((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames;
+    DecodeI32Layout l;
+    l.dec = 0;
+    l.info = l.dec + up(subs * stride * sizeof(int32_t));
+    l.counters = l.info + up(subs * sizeof(GenericSubInfo));
+    l.tiles = l.counters + up(4 * sizeof(uint32_t));
+    l.bytes = l.tiles + up(std::max<uint64_t>(n_tiles, 1) * sizeof(SampleTile)) + 256; // (+ the base's alignment)
+    return l;
+}
+
+size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    if ((uint64_t)max_frames * channels * stride >= (1ull << 60))
+        return SIZE_MAX;
+    return (size_t)decode_i32_layout(max_frames, channels, stride).bytes;
+}
+
+// The host route (generic_decode) on one chunk, with its decisions taken on the device: the sample index and the stride check
+// (the host's header walk), k_decode_subframes32 counting what it leaves alone in the workspace (attempt 0), k_generic_decode over
+// every subframe, each workgroup returning at once unless that count is non-zero (attempt 1: then it decodes every subframe
+// again, as the host's second attempt does), and one combine.  mode 0: the serial kernel alone; 2: the fast kernel by segments.
+hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+{
+    const DecodeI32Layout l = decode_i32_layout(max_frames, channels, stride);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.dec);
+    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.info);
+    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.counters);
+    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.tiles);
+    if (max_frames <= kSampleTileFrames) {
+        hipLaunchKernelGGL(k_index_samples<true>, dim3(1), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
+            d_sample_offsets, d_status, d_counters, d_tiles);
+    } else {
+        const uint32_t n_tiles = (uint32_t)(((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames);
+        hipLaunchKernelGGL(k_index_samples<false>, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
+            d_sample_offsets, d_status, d_counters, d_tiles);
+        hipLaunchKernelGGL(k_sample_tiles, dim3(1), dim3(kSampleThreads), 0, stream, d_tiles, n_tiles, max_frames, d_n_found, stride, d_sample_offsets, d_status,
+            d_counters);
+        if (d_sample_offsets)
+            hipLaunchKernelGGL(k_sample_spread, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_tiles, max_frames, d_n_found, d_sample_offsets);
+    }
+    const uint32_t subs = max_frames * channels;
+    if (subs == 0)
+        return hipGetLastError();
+    if (mode != 0) {
+        const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, d_n_found);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
+        d_n_found, mode != 0 ? d_counters + 2 : nullptr);
+    const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
+    hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_samples_out, d_counts_out,
+        nullptr, nullptr, d_status, d_n_found);
     return hipGetLastError();
 }
 
 } // namespace sela
+
