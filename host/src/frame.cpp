@@ -7,11 +7,11 @@
 #include <string>
 #include <vector>
 
+#include "sela_format.h"
 #include "sela_hip.h"
 
 namespace {
 
-constexpr uint32_t kSyncWord = 0xAA55FF00u;
 constexpr size_t kBlock = SELA_HIP_SAMPLES_PER_FRAME;
 
 uint16_t load16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
@@ -34,7 +34,7 @@ namespace frame {
 
 size_t parseFrame(const uint8_t* bytes, size_t available, uint8_t channels, uint8_t bitsPerSample, data::SelaFrame& out)
 {
-    if (available < 4 || load32(bytes) != kSyncWord)
+    if (available < 4 || load32(bytes) != SELA_SYNC_WORD)
         throw data::Exception("frame does not start with the sync word");
     size_t pos = 4;
     out = data::SelaFrame(bitsPerSample);

@@ -1868,12 +1868,11 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     // the fast kernels at all -- they would write 2048-sample frames of silence into a pcm_out its caller sized from
     // sela_hip_index_samples().  A stream that turns odd LATER still needs the room the header asks for.)
     bool first_is_standard = true;
-    if (n_frames && frame_offsets[1] >= frame_offsets[0] + 16) {
-        const uint8_t* fb = frames + frame_offsets[0];
-        const uint64_t fbytes = frame_offsets[1] - frame_offsets[0];
-        const uint64_t cw = (uint64_t)fb[8] | ((uint64_t)fb[9] << 8), p2 = 4 + 7 + 4 * cw;
-        if (p2 + 5 <= fbytes)
-            first_is_standard = ((uint32_t)fb[p2 + 3] | ((uint32_t)fb[p2 + 4] << 8)) == SELA_HIP_SAMPLES_PER_FRAME;
+    if (n_frames && frame_offsets[1] >= frame_offsets[0]) {
+        SelaSubframeHeader h;
+        h.n = SELA_HIP_SAMPLES_PER_FRAME; // (stays so when the header itself is not in the frame)
+        sela_subframe_read_bytes(frames + frame_offsets[0], frame_offsets[1] - frame_offsets[0], 4, &h);
+        first_is_standard = h.n == SELA_HIP_SAMPLES_PER_FRAME;
     }
     const int rc = first_is_standard ? decode_standard(frames, frame_offsets, n_frames, channels, pcm_out) : SELA_HIP_EFORMAT;
     if (rc != SELA_HIP_EFORMAT || n_frames == 0)
@@ -2237,25 +2236,12 @@ uint32_t sela_hip_index_frames(const uint8_t* frames, size_t frames_bytes, uint3
         std::memcpy(&sync, frames + off, 4);
         if (sync != SELA_SYNC_WORD) // src/file/sela_file.cpp:54-56: stop silently
             break;
-        size_t p = off + 4;
-        bool ok = true;
-        for (uint32_t c = 0; c < channels && ok; c++) {
-            if (p + 7 > frames_bytes) {
-                ok = false;
-                break;
-            }
-            const size_t cw = (size_t)frames[p + 4] | ((size_t)frames[p + 5] << 8);
-            p += 7 + 4 * cw;
-            if (p + 5 > frames_bytes) {
-                ok = false;
-                break;
-            }
-            const size_t rw = (size_t)frames[p + 1] | ((size_t)frames[p + 2] << 8);
-            p += 5 + 4 * rw;
-            if (p > frames_bytes)
-                ok = false;
+        uint64_t p = off + 4;
+        for (uint32_t c = 0; c < channels && p; c++) {
+            SelaSubframeHeader h;
+            p = sela_subframe_read_bytes(frames, frames_bytes, p, &h);
         }
-        if (!ok)
+        if (!p)
             break;
         off = p;
     }

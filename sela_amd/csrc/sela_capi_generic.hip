@@ -404,24 +404,13 @@ uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offs
         uint64_t p = 4;
         uint32_t first = 0;
         for (uint32_t c = 0; c < channels; c++) {
-            if (p + 12 > fbytes) {
-                broken = true;
-                break;
-            }
-            const uint64_t cw = (uint64_t)fb[p + 4] | ((uint64_t)fb[p + 5] << 8);
-            const uint64_t p2 = p + 7 + 4 * cw;
-            if (p2 + 5 > fbytes) {
-                broken = true;
-                break;
-            }
-            const uint64_t rw = (uint64_t)fb[p2 + 1] | ((uint64_t)fb[p2 + 2] << 8);
-            const uint32_t n = (uint32_t)fb[p2 + 3] | ((uint32_t)fb[p2 + 4] << 8);
+            SelaSubframeHeader h = {}; // (n is read, and counts, even when only the residue words run past the frame)
+            p = sela_subframe_read_bytes(fb, fbytes, p, &h);
             if (c == 0)
-                first = n;
-            largest = std::max(largest, n);
-            standard = standard && n == SELA_HIP_SAMPLES_PER_FRAME;
-            p = p2 + 5 + 4 * rw;
-            if (p > fbytes) {
+                first = h.n;
+            largest = std::max(largest, h.n);
+            standard = standard && h.n == SELA_HIP_SAMPLES_PER_FRAME;
+            if (p == 0) {
                 broken = true;
                 break;
             }

@@ -100,9 +100,10 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
 
     // ---- mode: every subframe of the frame must fit the fast plan ----------------------------------------------
     const bool fast_plan = channels <= (uint32_t)kDecMaxWaves;
-    SubHeader hd = walk_headers(fb, fbytes, (uint32_t)wave < channels ? (uint32_t)wave : 0u, channels);
+    SubHeader hd = walk_headers(fb, fbytes, (uint32_t)wave < channels ? (uint32_t)wave : 0u);
+    bool ok = block_header_ok(hd, channels);
     if (lane == 0)
-        too_big[wave] = (fast_plan && (!hd.ok || (hd.cw + 2 + hd.rw <= (uint32_t)kStreamCap && hd.order <= 2 * (uint32_t)kWave))) ? 0u : 1u;
+        too_big[wave] = (fast_plan && (!ok || (hd.cw + 2 + hd.rw <= (uint32_t)kStreamCap && hd.order <= 2 * (uint32_t)kWave))) ? 0u : 1u;
     __syncthreads();
     bool fast = fast_plan;
     for (int w = 0; w < n_waves; w++)
@@ -111,9 +112,11 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
         stamp[1] = clock64();
 
     for (uint32_t c = wave; c < channels; c += n_waves) {
-        if (c != (uint32_t)wave)
-            hd = walk_headers(fb, fbytes, c, channels);
-        if (!hd.ok) {
+        if (c != (uint32_t)wave) {
+            hd = walk_headers(fb, fbytes, c);
+            ok = block_header_ok(hd, channels);
+        }
+        if (!ok) {
             flags |= SELA_HIP_FLAG_BAD_FRAME;
             continue;
         }
@@ -260,52 +263,6 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
 // difference, where the parent's samples are the raw ones an independent subframe left there.  The reference's encoder
 // writes difference subframes for exactly-stereo input only (src/frame/frame_encoder.cpp:18), so for these frames the
 // pass has nothing to do -- but files are input, not promises.
-struct HeaderCursor {
-    uint32_t index; // subframe the cursor stands in front of
-    uint64_t p;     // its byte offset in the frame
-    bool ok;
-};
-
-__device__ inline SubHeader walk_on(const uint8_t* fb, uint64_t fbytes, HeaderCursor& cur, uint32_t c, uint32_t channels)
-{
-    SubHeader h;
-    h.ok = cur.ok;
-    h.channel = h.type = h.parent = h.ck = h.cw = h.order = h.rk = h.rw = 0;
-    uint32_t n = 0;
-    uint64_t p = cur.p;
-    while (h.ok && cur.index <= c) { // over the headers up to and including subframe c
-        p = cur.p;
-        if (p + 12 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h0 = *reinterpret_cast<const uint32_t*>(fb + p);
-        const uint32_t h1 = *reinterpret_cast<const uint32_t*>(fb + p + 4);
-        h.channel = h0 & 0xFF, h.type = (h0 >> 8) & 0xFF, h.parent = (h0 >> 16) & 0xFF, h.ck = h0 >> 24;
-        h.cw = h1 & 0xFFFF, h.order = (h1 >> 16) & 0xFF;
-        const uint64_t p2 = p + 4 + 4 * (uint64_t)h.cw;
-        if (p2 + 8 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h2 = *reinterpret_cast<const uint32_t*>(fb + p2);
-        const uint32_t h3 = *reinterpret_cast<const uint32_t*>(fb + p2 + 4);
-        h.rk = h2 >> 24, h.rw = h3 & 0xFFFF, n = h3 >> 16;
-        const uint64_t next = p + 12 + 4 * ((uint64_t)h.cw + h.rw);
-        if (next > fbytes) {
-            h.ok = false;
-            break;
-        }
-        cur.p = next;
-        cur.index++;
-    }
-    cur.ok = h.ok; // (a frame is walked front to back: behind a broken header there is nothing to find)
-    h.ok = h.ok && h.channel < channels && h.order <= (uint32_t)kMaxOrder && n == (uint32_t)kBlock && h.ck < 32 && h.rk < 32 && h.type <= 1
-        && (h.type == 0 || h.parent < channels);
-    h.p = (uint32_t)p;
-    return h;
-}
-
 constexpr uint32_t kNoSubframe = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const uint8_t* __restrict__ frames,
@@ -328,14 +285,11 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
     for (uint32_t c = threadIdx.x; c < channels; c += blockDim.x)
         sub_info[c] = kNoSubframe; // "no subframe delivered this channel"
     __syncthreads();
-    HeaderCursor cur;
-    cur.index = 0;
-    cur.p = 4;
-    cur.ok = fbytes >= 4 && fbytes < 0x7FFFFFFFull && (fbytes & 3) == 0 && reinterpret_cast<const uint32_t*>(fb)[0] == SELA_SYNC_WORD;
+    HeaderCursor cur = frame_cursor(fb, fbytes);
     int16_t* const out_frame = pcm_out + (size_t)f * kBlock * channels;
     for (uint32_t c = wave; c < channels; c += kDecMaxWaves) {
-        const SubHeader hd = walk_on(fb, fbytes, cur, c, channels);
-        if (!hd.ok) {
+        const SubHeader hd = walk_to(fb, fbytes, cur, c);
+        if (!block_header_ok(hd, channels)) {
             flags |= SELA_HIP_FLAG_BAD_FRAME;
             continue;
         }
@@ -343,7 +297,7 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
         const uint32_t* const gw = reinterpret_cast<const uint32_t*>(fb + hd.p + 4); // the subframe's aligned words
         const int32_t* ws_c = nullptr;
         ParseProfile pp;
-        if (nw <= (uint32_t)kStreamCap) { // (hd.order <= 100 <= 2 waves' worth: checked by walk_on)
+        if (nw <= (uint32_t)kStreamCap) { // (hd.order <= 100 <= 2 waves' worth: checked by block_header_ok)
             for (uint32_t w = lane; w < nw + kStreamMargin; w += kWave) // the start bitmap
                 sl->marks[w] = 0;
             wave_sync();

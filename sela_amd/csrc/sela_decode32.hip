@@ -254,48 +254,6 @@ __device__ __forceinline__ uint32_t parse_stream_segments(const uint32_t* gw, ui
     return overrun ? (uint32_t)SELA_HIP_FLAG_RICE_OVERRUN : 0u;
 }
 
-// ---- subframe header walk for any length (layout of src/file/sela_file.cpp:58-91): what k_generic_decode accepts, of a frame
-// of whole words at a word-aligned place --------------------------------------------------------------------------------------
-struct AnyHeader {
-    bool ok;
-    uint32_t p, channel, type, parent, ck, cw, order, rk, rw, n;
-};
-__device__ inline AnyHeader walk_headers_any(const uint8_t* fb, uint64_t fbytes, uint32_t c)
-{
-    AnyHeader h;
-    h.ok = fbytes >= 4 && fbytes < 0x7FFFFFFFull && (fbytes & 3) == 0 && reinterpret_cast<const uint32_t*>(fb)[0] == SELA_SYNC_WORD;
-    uint64_t p = 4;
-    h.channel = h.type = h.parent = h.ck = h.cw = h.order = h.rk = h.rw = h.n = 0;
-    for (uint32_t i = 0; h.ok && i <= c; i++) {
-        if (p + 12 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h0 = *reinterpret_cast<const uint32_t*>(fb + p);
-        const uint32_t h1 = *reinterpret_cast<const uint32_t*>(fb + p + 4);
-        h.channel = h0 & 0xFF, h.type = (h0 >> 8) & 0xFF, h.parent = (h0 >> 16) & 0xFF, h.ck = h0 >> 24;
-        h.cw = h1 & 0xFFFF, h.order = (h1 >> 16) & 0xFF;
-        const uint64_t p2 = p + 4 + 4 * (uint64_t)h.cw;
-        if (p2 + 8 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h2 = *reinterpret_cast<const uint32_t*>(fb + p2);
-        const uint32_t h3 = *reinterpret_cast<const uint32_t*>(fb + p2 + 4);
-        h.rk = h2 >> 24, h.rw = h3 & 0xFFFF, h.n = h3 >> 16;
-        const uint64_t next = p + 12 + 4 * ((uint64_t)h.cw + h.rw);
-        if (next > fbytes) {
-            h.ok = false;
-            break;
-        }
-        if (i < c)
-            p = next;
-    }
-    h.ok = h.ok && h.order <= (uint32_t)kMaxOrder && h.ck < 32 && h.rk < 32;
-    h.p = (uint32_t)p;
-    return h;
-}
-
 // ---- subframes of any length, 32-bit samples out ---------------------------------------------------------------------------------
 // frame::FrameDecoder returns what the synthesis produces, untruncated (src/frame/frame_decoder.cpp:24-25,64-71), at each
 // subframe's own samplesPerChannel, so the class -- and sela_hip_decode_i32 behind it -- cannot use k_decode_frames, whose
@@ -327,12 +285,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     const uint64_t at = frame_offsets[f] - base_bytes;
     const uint8_t* const fb = frames + at;
     const uint64_t fbytes = frame_offsets[f + 1] - frame_offsets[f];
-    AnyHeader hd;
-    hd.ok = false;
-    hd.channel = hd.type = hd.parent = hd.n = 0;
-    if ((at & 3) == 0)
-        hd = walk_headers_any(fb, fbytes, c);
-    const bool mine = hd.ok && hd.n <= stride && hd.n != 0 && hd.n > hd.order; // (a subframe not longer than its order: the reference writes past its vector -- the judge's)
+    const SubHeader hd = walk_headers(fb, (at & 3) == 0 ? fbytes : 0 /* a frame at a place that is not word-aligned: not walked */, c);
+    const bool mine = hd.ok && sela_subframe_decodable(&hd) && hd.n <= stride && hd.n != 0 && hd.n > hd.order; // (a subframe not longer than its order: the reference writes past its vector -- the judge's)
     uint32_t flags = 0;
     if (mine) {
         const uint32_t nw = hd.cw + 2 + hd.rw;

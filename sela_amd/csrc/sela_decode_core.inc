@@ -709,49 +709,57 @@ __device__ inline bool build_synth_table(const int64_t* a, uint64_t* tab, int or
     return !__any(!fits);
 }
 
-// ---- subframe header walk (layout of src/file/sela_file.cpp:58-91) ------------------------------------------
-struct SubHeader {
-    bool ok;
-    uint32_t p;  // byte offset of the subframe in the frame
-    uint32_t channel, type, parent, ck, cw, order, rk, rw;
+// ---- subframe header walk (the layout and its bounds: sela_format.h) ---------------------------------------------------------
+// The decoders take frames of whole words at word-aligned places and read each header with two pairs of 32-bit loads
+// (sela_subframe_read_words).  The walk stops on the header asked for; what a decoder accepts there is its own test
+// (block_header_ok for the 2048-sample kernels, k_decode_subframes32 its own).
+struct SubHeader : SelaSubframeHeader {
+    bool ok;    // the walk got here: this header and the subframe's words lie inside the frame
+    uint32_t p; // byte offset of the subframe in the frame
+};
+struct HeaderCursor {
+    uint32_t index; // subframe the cursor stands in front of
+    uint64_t p;     // its byte offset in the frame
+    bool ok;        // (a frame is walked front to back: behind a broken header there is nothing to find)
 };
 
-__device__ inline SubHeader walk_headers(const uint8_t* fb, uint64_t fbytes, uint32_t c, uint32_t channels)
+__device__ inline HeaderCursor frame_cursor(const uint8_t* fb, uint64_t fbytes)
+{
+    HeaderCursor cur;
+    cur.index = 0;
+    cur.p = 4;
+    cur.ok = fbytes >= 4 && fbytes < 0x7FFFFFFFull && (fbytes & 3) == 0 && reinterpret_cast<const uint32_t*>(fb)[0] == SELA_SYNC_WORD;
+    return cur;
+}
+
+// On from the cursor over the headers up to and including subframe c; the cursor is left behind it.
+__device__ inline SubHeader walk_to(const uint8_t* fb, uint64_t fbytes, HeaderCursor& cur, uint32_t c)
 {
     SubHeader h;
-    h.ok = fbytes >= 4 && fbytes < 0x7FFFFFFFull && (fbytes & 3) == 0 && reinterpret_cast<const uint32_t*>(fb)[0] == SELA_SYNC_WORD;
-    uint64_t p = 4;
-    uint32_t n = 0;
-    h.channel = h.type = h.parent = h.ck = h.cw = h.order = h.rk = h.rw = 0;
-    for (uint32_t i = 0; h.ok && i <= c; i++) { // walk the headers up to this subframe
-        if (p + 12 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h0 = *reinterpret_cast<const uint32_t*>(fb + p);     // channel, type, parent, coefficient k
-        const uint32_t h1 = *reinterpret_cast<const uint32_t*>(fb + p + 4); // word count (u16), order (u8), first coefficient byte
-        h.channel = h0 & 0xFF, h.type = (h0 >> 8) & 0xFF, h.parent = (h0 >> 16) & 0xFF, h.ck = h0 >> 24;
-        h.cw = h1 & 0xFFFF, h.order = (h1 >> 16) & 0xFF;
-        const uint64_t p2 = p + 4 + 4 * (uint64_t)h.cw; // aligned word: last 3 coefficient bytes + residue k
-        if (p2 + 8 > fbytes) {
-            h.ok = false;
-            break;
-        }
-        const uint32_t h2 = *reinterpret_cast<const uint32_t*>(fb + p2);
-        const uint32_t h3 = *reinterpret_cast<const uint32_t*>(fb + p2 + 4);
-        h.rk = h2 >> 24, h.rw = h3 & 0xFFFF, n = h3 >> 16;
-        const uint64_t next = p + 12 + 4 * ((uint64_t)h.cw + h.rw);
-        if (next > fbytes) {
-            h.ok = false;
-            break;
-        }
-        if (i < c)
-            p = next;
+    h.channel = h.type = h.parent = h.ck = h.cw = h.order = h.rk = h.rw = h.n = 0;
+    h.ok = cur.ok;
+    h.p = (uint32_t)cur.p;
+    while (h.ok && cur.index <= c) {
+        h.p = (uint32_t)cur.p;
+        cur.p = sela_subframe_read_words(fb, fbytes, cur.p, &h);
+        h.ok = cur.p != 0;
+        cur.index++;
     }
-    h.ok = h.ok && h.channel < channels && h.order <= (uint32_t)kMaxOrder && n == (uint32_t)kBlock && h.ck < 32 && h.rk < 32 && h.type <= 1
-        && (h.type == 0 || h.parent < channels);
-    h.p = (uint32_t)p;
+    cur.ok = h.ok;
     return h;
+}
+
+__device__ inline SubHeader walk_headers(const uint8_t* fb, uint64_t fbytes, uint32_t c)
+{
+    HeaderCursor cur = frame_cursor(fb, fbytes);
+    return walk_to(fb, fbytes, cur, c);
+}
+
+// What k_decode_frames and k_decode_frames_wide decode: a 2048-sample subframe of a channel the frame has, independent or
+// difference-coded against one.
+__device__ inline bool block_header_ok(const SubHeader& h, uint32_t channels)
+{
+    return h.ok && sela_subframe_decodable(&h) && h.n == (uint32_t)kBlock && h.channel < channels && h.type <= 1 && (h.type == 0 || h.parent < channels);
 }
 
 // Launches of at most this many waves run their recurrence in the form for a wave that has its SIMD (nearly) to itself

@@ -1026,32 +1026,19 @@ __global__ __launch_bounds__(64) void k_generic_decode(const uint8_t* __restrict
     GenericSubInfo si;
     si.channel = si.type = si.parent = 0, si.n = 0, si.ok = 0;
     uint32_t flags = 0;
-    // ---- the headers up to this subframe (src/file/sela_file.cpp:58-91) ----
+    // ---- the headers up to this subframe (sela_format.h), byte by byte: a frame here may lie anywhere ----
     bool ok = fbytes >= 4 && fbytes < (1ull << 31) && fb[0] == 0x00 && fb[1] == 0xFF && fb[2] == 0x55 && fb[3] == 0xAA;
     uint64_t p = 4;
-    uint32_t ck = 0, cw = 0, order = 0, rk = 0, rw = 0, n = 0;
+    SelaSubframeHeader h = {};
     for (uint32_t i = 0; ok && i <= c; i++) {
-        if (p + 12 > fbytes) {
-            ok = false;
-            break;
-        }
-        si.channel = fb[p], si.type = fb[p + 1], si.parent = fb[p + 2];
-        ck = fb[p + 3], cw = fb[p + 4] | ((uint32_t)fb[p + 5] << 8), order = fb[p + 6];
-        const uint64_t p2 = p + 7 + 4 * (uint64_t)cw;
-        if (p2 + 5 > fbytes) {
-            ok = false;
-            break;
-        }
-        rk = fb[p2], rw = fb[p2 + 1] | ((uint32_t)fb[p2 + 2] << 8), n = fb[p2 + 3] | ((uint32_t)fb[p2 + 4] << 8);
-        const uint64_t next = p2 + 5 + 4 * (uint64_t)rw;
-        if (next > fbytes) {
-            ok = false;
-            break;
-        }
+        const uint64_t next = sela_subframe_read_bytes(fb, fbytes, p, &h);
+        ok = next != 0;
         if (i < c)
             p = next;
     }
-    ok = ok && order <= (uint32_t)kMaxOrder && ck < 32 && rk < 32 && n <= stride;
+    si.channel = (uint8_t)h.channel, si.type = (uint8_t)h.type, si.parent = (uint8_t)h.parent;
+    const uint32_t cw = h.cw, order = h.order, rw = h.rw, n = h.n, ck = h.ck, rk = h.rk;
+    ok = ok && sela_subframe_decodable(&h) && n <= stride;
     if (!ok) {
         if (lane == 0) {
             info[sub] = si;
@@ -1225,9 +1212,9 @@ __global__ __launch_bounds__(kCombineThreads) void k_generic_combine(const int32
 
 // ---- the sample index on the device (sela_hip_decode_i32_device) --------------------------------------------
 // generic_index_samples (sela_capi_generic.hip) taken apart: every frame's header walk is independent of the others, only the
-// running total is not.  A thread walks kSampleFramesPerThread frames with that function's own byte reads and bounds, and a
-// workgroup scans its kSampleTileFrames frames' first samplesPerChannel.  Up to one tile (a track: 4096 frames) that is the
-// whole index, in one launch; above, every tile scans its own frames (k_index_samples<false>), one workgroup scans the tiles'
+// running total is not.  A thread walks kSampleFramesPerThread frames as that function does (sela_subframe_read_bytes, its stop
+// rule and counts), and a workgroup scans its kSampleTileFrames frames' first samplesPerChannel.  Up to one tile (a track:
+// 4096 frames) that is the whole index, in one launch; above, every tile scans its own frames (k_index_samples<false>), one workgroup scans the tiles'
 // totals (k_sample_tiles) and every tile adds its base (k_sample_spread).  The launch that finishes also writes the caller's
 // status words ([2] = what sela_hip_index_samples would return, SELA_HIP_FLAG_STRIDE where sela_hip_decode_i32 would refuse
 // the stride) and zeroes the fast kernel's counters in the workspace: nothing else on the stream initialises them.
@@ -1250,23 +1237,12 @@ __device__ inline uint32_t sample_head(const uint8_t* __restrict__ frames, const
     uint64_t p = 4;
     uint32_t first = 0;
     for (uint32_t c = 0; c < channels; c++) {
-        if (p + 12 > fbytes) {
-            bad |= kSampleBroken;
-            break;
-        }
-        const uint64_t cw = (uint64_t)fb[p + 4] | ((uint64_t)fb[p + 5] << 8);
-        const uint64_t p2 = p + 7 + 4 * cw;
-        if (p2 + 5 > fbytes) {
-            bad |= kSampleBroken;
-            break;
-        }
-        const uint64_t rw = (uint64_t)fb[p2 + 1] | ((uint64_t)fb[p2 + 2] << 8);
-        const uint32_t n = (uint32_t)fb[p2 + 3] | ((uint32_t)fb[p2 + 4] << 8);
+        SelaSubframeHeader h = {}; // (n is read, and counts, even when only the residue words run past the frame)
+        p = sela_subframe_read_bytes(fb, fbytes, p, &h);
         if (c == 0)
-            first = n;
-        largest = max(largest, n);
-        p = p2 + 5 + 4 * rw;
-        if (p > fbytes) {
+            first = h.n;
+        largest = max(largest, h.n);
+        if (p == 0) {
             bad |= kSampleBroken;
             break;
         }

@@ -4,9 +4,10 @@
 // The host walk (sela_hip_index_frames) follows the chain offset 0 -> end of frame 0 -> end of frame 1 -> ...; a frame's size
 // is known only from its `channels` subframe headers, so the chain is sequential.  Here it is taken apart:
 //
-//   k_index_candidates  every payload word that holds the sync word and whose header walk succeeds (the host walk's own
-//                       bounds checks) is a CANDIDATE; its `next` is the end of the frame it would be.  Frames are 4-byte
-//                       aligned relative to the payload (4 + 12 per subframe + 4 per word), so only words are looked at.
+//   k_index_candidates  every payload word that holds the sync word and whose header walk succeeds (the host walk's
+//                       reader and bounds, sela_format.h) is a CANDIDATE; its `next` is the end of the frame it would be.
+//                       Frames are 4-byte aligned relative to the payload (4 + 12 per subframe + 4 per word), so only
+//                       words are looked at.
 //                       Each workgroup lists its candidates in position order in its own stretch of the workspace and
 //                       counts them;
 //   k_index_scan        one workgroup: exclusive scan of the counts (and the outputs' initial state: no frame found);
@@ -62,21 +63,16 @@ struct IndexWs {
 };
 
 // The host walk's test of one position (sela_hip_index_frames): the frame's end in words, or kIndexNone.  `off` is a word
-// boundary that holds the sync word; every read stays below `bytes` (the same checks come first).
+// boundary that holds the sync word, so every subframe of the frame is one too: the word form of the header reader, whose
+// bounds are the host walk's (only the word counts are used: the other loads fold away).
 __device__ __forceinline__ uint32_t index_frame_end(const uint8_t* __restrict__ payload, uint64_t bytes, uint64_t off, uint32_t channels)
 {
     uint64_t p = off + 4;
-    for (uint32_t c = 0; c < channels; c++) {
-        if (p + 7 > bytes)
-            return kIndexNone;
-        p += 7 + 4 * (uint64_t)*reinterpret_cast<const uint16_t*>(payload + p + 4); // coefficient words (p is a word boundary)
-        if (p + 5 > bytes)
-            return kIndexNone;
-        p += 5 + 4 * (uint64_t)*reinterpret_cast<const uint16_t*>(payload + p + 1); // residue words (p + 1 is a word boundary)
-        if (p > bytes)
-            return kIndexNone;
+    for (uint32_t c = 0; c < channels && p; c++) {
+        SelaSubframeHeader h;
+        p = sela_subframe_read_words(payload, bytes, p, &h);
     }
-    return (uint32_t)(p >> 2);
+    return p ? (uint32_t)(p >> 2) : kIndexNone;
 }
 
 // Exclusive scan of one value per thread over the workgroup (totals fit 32 bits).  sh: 17 words of LDS.

@@ -110,6 +110,28 @@ def test_scale_division_is_exact(tmp_path):
     assert subprocess.check_output([str(exe)]).decode().strip() == "0"
 
 
+def test_the_two_header_reader_forms_agree(tmp_path):
+    """include/sela_format.h reads a subframe header byte by byte (any alignment) or as 32-bit words (an aligned frame: the
+    decoders and the device frame index).  tests/c/header_forms.c feeds both the same inputs -- every golden frame cut at every
+    length and read at every word-aligned place, then a seeded fuzz of frames with random headers -- and counts the inputs
+    where their `next` or fields differ, or where either looked past the frame."""
+    import subprocess
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = tmp_path / "header_forms"
+    subprocess.check_call(["gcc", "-O2", "-std=c11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(here, "..", "include"), "-o", str(exe),
+                           os.path.join(here, "c", "header_forms.c")])
+    k = np.load(os.path.join(here, "golden", "kats.npz"))
+    args = []
+    for name in k["frame_names"]:
+        path = tmp_path / f"{name}.bin"
+        path.write_bytes(k[f"frame/{name}/bytes"].tobytes())
+        args += [str(path), str(k[f"frame/{name}/pcm"].shape[1])]
+    assert len(args) == 16
+    checks, mismatches = map(int, subprocess.check_output([str(exe)] + args).decode().split())
+    assert mismatches == 0 and checks > 10_000_000, (checks, mismatches)
+
+
 def test_residue_filter_in_fp64_is_exact_under_its_bounds():
     """What sela_encode_tail.inc relies on (round 4).  One pass: while 2^34 + sum |a[j]| x max |s| < 2^53 every partial sum of
     2^34 + sum a[j] s[i-j] is an integer below 2^53, so float64 arithmetic carries it exactly and floor(sum / 2^35) is the
