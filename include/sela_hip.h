@@ -281,6 +281,33 @@ int sela_hip_decode_payload_i32_device(const uint8_t* d_payload, size_t payload_
  * Rice stream that runs dry: SELA_HIP_EFORMAT; a coefficient beyond int64 or outside the tables, a subframe not longer than its
  * order: SELA_HIP_ERANGE; SELA_HIP_FLAG_INTERNAL: SELA_HIP_ENODEV; else 0.  A null pointer: SELA_HIP_EINVAL. */
 int sela_hip_decode_status_error(const uint32_t* status /* [4], host copy */);
+/* sela_hip_encode_i32 -- and sela_hip_encode of any samples_per_channel -- on DEVICE pointers, asynchronous on `stream`: no
+ * allocation, no host synchronisation, no host-side read of device data, so a stream being captured into a HIP graph may take
+ * either call.  Neither touches the calling thread's scratch or an open streaming job.
+ *   d_samples int32 [n_frames][channels][samples_per_channel] (planar, as sela_hip_encode_i32), 4-byte aligned;
+ *   d_pcm int16 [n_frames][samples_per_channel][channels] (interleaved, as sela_hip_encode), 2-byte aligned.
+ *   samples_per_channel: 1 .. 65535 (2048 included).
+ *   d_frames (4-byte aligned) receives exactly the bytes of the host call on the same input, d_frame_offsets[0 .. n_frames] its
+ *     offsets -- always written in full, also when frames do not fit: a caller whose buffer was too small resizes from
+ *     d_frame_offsets[n_frames].  A frame that ends beyond frames_cap is not written; nothing at or past frames_cap is.
+ *   d_status uint32[4], written by the call (needs no initialisation): [0] the OR of the flag bits (both stereo candidates'),
+ *     [1] the number of frames not written for capacity, [2] and [3] zero.
+ * d_workspace: sela_hip_encode_i32_workspace_bytes(n_frames, channels, samples_per_channel) bytes (it does not depend on the
+ * data), no initialisation; one call at a time may use it.  sela_hip_debug_generic_wrap_taps applies as to the host call.
+ * n_frames = 0 writes d_frame_offsets[0] = 0 and zero status words.
+ * SELA_HIP_EINVAL: a null pointer, channels outside 1..255, samples_per_channel outside 1..65535, n_frames x signals per frame
+ * at 2^31 or more, a misaligned d_frames or input; SELA_HIP_ECAPACITY: a smaller workspace.  Nothing is enqueued then. */
+size_t sela_hip_encode_i32_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel);
+int sela_hip_encode_i32_device(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_encode_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host only, no GPU: the code the host call returns for the input whose device status words (a host copy) these are, in its
+ * order -- SELA_HIP_FLAG_SHORT_BLOCK, _RICE_RANGE, _COEF_OVERFLOW or _WORDS_CAP: SELA_HIP_ERANGE; then [1] > 0:
+ * SELA_HIP_ECAPACITY; else 0 (SELA_HIP_FLAG_Q_RANGE alone included).  A null pointer: SELA_HIP_EINVAL. */
+int sela_hip_encode_status_error(const uint32_t* status /* [4], host copy */);
 
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and

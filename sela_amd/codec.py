@@ -210,6 +210,73 @@ def decode_status_error(status) -> int:
     return int(capi.lib().sela_hip_decode_status_error(st.ctypes.data))
 
 
+class Encoder32:
+    """sela_hip_encode_i32 -- and sela_hip_encode of any length -- on the device: frames of any samples_per_channel (1 .. 65535),
+    32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
+    asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the host route's
+    estimate -- 4.5 bytes per sample, which holds noise of up to 20 bits -- not the certain bound; a call that did not fit says
+    so in check(), and needed_bytes() is what it needs."""
+
+    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, capacity=None, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.n = max_frames, channels, samples_per_channel
+        if capacity is None:
+            capacity = max_frames * ((samples_per_channel * channels * 9) // 2 + channels * 192 + 64)
+        self.capacity = max(int(capacity), 4)
+        ws = int(self.lib.sela_hip_encode_i32_workspace_bytes(max_frames, channels, samples_per_channel))
+        with torch.cuda.device(self.device):
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+            self.offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.n_frames = 0
+
+    def encode(self, samples):
+        """samples: int32 cuda tensor [n_frames, channels, n] (planar) or int16 [n_frames, n, channels] (interleaved), contiguous
+        -> (frames uint8 [capacity], offsets int64 [n_frames + 1], status int32 [4]): the encoder's own buffers, the first
+        offsets[n_frames] bytes of frames the stream's when check() passes."""
+        torch = self.torch
+        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 3
+        n_frames = samples.shape[0]
+        if samples.dtype == torch.int32:
+            assert tuple(samples.shape[1:]) == (self.channels, self.n)
+            call = self.lib.sela_hip_encode_i32_device
+        else:
+            assert samples.dtype == torch.int16 and tuple(samples.shape[1:]) == (self.n, self.channels)
+            call = self.lib.sela_hip_encode_n_device
+        assert n_frames <= self.max_frames
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(call(samples.data_ptr(), n_frames, self.channels, self.n, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+                        self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        self.n_frames = n_frames
+        return self.frames, self.offsets[: n_frames + 1], self.status
+
+    def needed_bytes(self) -> int:
+        """Waits for the last call: the bytes its frames take (offsets[n_frames])."""
+        return int(self.offsets[self.n_frames].item())
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code the host call gives for the same input."""
+        capi.check(encode_status_error(self.status.cpu().numpy()))
+
+    def to_host(self):
+        """check(), then -> (frames uint8 [...], offsets uint64 [n_frames + 1]) on the host."""
+        self.check()
+        offs = self.offsets[: self.n_frames + 1].cpu().numpy().view(np.uint64)
+        return self.frames[: int(offs[-1])].cpu().numpy(), offs
+
+
+def encode_status_error(status) -> int:
+    """sela_hip_encode_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_encode_status_error(st.ctypes.data))
+
+
 # ---- host-pointer API on numpy arrays (what the C++ host calls) --------------------------------------
 def encode_host(pcm: np.ndarray):
     """pcm: int16 [n_frames, n, channels] (n = 2048: the fast kernels; anything else in 1..65535: the any-length route)

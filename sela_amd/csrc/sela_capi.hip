@@ -63,6 +63,9 @@ int generic_standard_first_mode();
 size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
 hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
+hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
 } // namespace sela
 
 namespace {
@@ -1606,6 +1609,68 @@ int sela_hip_decode_status_error(const uint32_t* status)
         return fail(SELA_HIP_ERANGE, "decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)");
     if (flags & SELA_HIP_FLAG_INTERNAL)
         return fail(SELA_HIP_ENODEV, "decode: a bounded wait inside a kernel ran out");
+    return SELA_HIP_OK;
+}
+
+// ---- the any-length / 32-bit encode on device pointers ------------------------------------------
+namespace {
+// what sela_hip_encode_i32_device and sela_hip_encode_n_device check alike, then the launch; no lease, no coalescer, no wait
+int encode_i32_device_call(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (n == 0 || n > 65535)
+        return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
+    if ((uint64_t)n_frames * sela_hip_signals_per_frame(channels) >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * signals per frame must stay below 2^31");
+    if (!d_frame_offsets || !d_status || !d_workspace || (n_frames && (!d_input || !d_frames)))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if (((uintptr_t)d_frames & 3) || ((uintptr_t)d_input & (in16 ? 1 : 3)))
+        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned, the samples aligned to their type");
+    if (workspace_bytes < sela::encode_i32_device_workspace_bytes(n_frames, channels, n))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_i32_workspace_bytes()");
+    const hipError_t e = sela::launch_encode_i32_device(d_input, in16, n_frames, channels, n, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "encode_i32 launch");
+}
+} // namespace
+
+size_t sela_hip_encode_i32_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel)
+{
+    return sela::encode_i32_device_workspace_bytes(n_frames, channels, samples_per_channel);
+}
+
+int sela_hip_encode_i32_device(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return encode_i32_device_call(d_samples, false, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+        workspace_bytes, stream);
+}
+
+int sela_hip_encode_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+        workspace_bytes, stream);
+}
+
+// the any-length route's checks after its plan, in its order (flags_error, then the capacity: generic_encode in sela_capi_generic.hip)
+int sela_hip_encode_status_error(const uint32_t* status)
+{
+    if (!status)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    const uint32_t flags = status[0];
+    if (flags & SELA_HIP_FLAG_SHORT_BLOCK)
+        return fail(SELA_HIP_ERANGE, "encode: a block is not longer than its predictor order (the reference reads past its vector there, src/lpc/residue_generator.cpp:104-110)");
+    if (flags & SELA_HIP_FLAG_RICE_RANGE)
+        return fail(SELA_HIP_ERANGE, "encode: a residue is beyond the reference's int32 zig-zag (|value| >= 2^30)");
+    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
+        return fail(SELA_HIP_ERANGE, "encode: a predictor coefficient left the int64 range");
+    if (flags & SELA_HIP_FLAG_WORDS_CAP)
+        return fail(SELA_HIP_ERANGE, "encode: a Rice stream needs more words than a subframe's 16-bit count can say");
+    if (status[1])
+        return fail(SELA_HIP_ECAPACITY, "d_frames too small: status[1] frames were not written (d_frame_offsets[n_frames] bytes are needed)");
     return SELA_HIP_OK;
 }
 

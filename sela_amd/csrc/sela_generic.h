@@ -40,6 +40,11 @@ hipError_t launch_decode_subframes32(const uint8_t* d_frames, const uint64_t* d_
 size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
 hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
+// k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
+hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
 hipError_t launch_lpc_decode_any(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, uint32_t n, int32_t* d_samples,
     int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
 

@@ -701,22 +701,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
 // 46 us at 3875 frames; the first version's single thread walking 256 partial sums: 60) -- its subframes' word counts go to LDS;
 // then every thread sums a contiguous run of the tile's frames, the runs are scanned across the workgroup (shuffles within a
 // wave, the sixteen waves' totals through LDS), and the offsets and the subframes' word bases are written frame by frame again.
+// kDevice (sela_hip_encode_i32_device): base_bytes is 0; the frames that end beyond frames_cap are counted, and the status words are
+// written whole (plain stores: the caller's words need no initialisation) -- [0] the flags, [1] that count, [2] and [3] zero.
 constexpr int kPlanThreads = 1024, kPlanTile = 4096;
+template <bool kDevice>
 __global__ __launch_bounds__(kPlanThreads) void k_generic_plan(const GenericMeta* __restrict__ meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig,
     uint64_t base_bytes, uint64_t* __restrict__ frame_offsets /* [n_frames + 1], absolute */, uint64_t* __restrict__ word_base /* [n_frames * channels + 1] */,
-    uint32_t* __restrict__ chosen /* [n_frames * channels]: signal index */, uint32_t* __restrict__ status, uint64_t* __restrict__ total_words_out)
+    uint32_t* __restrict__ chosen /* [n_frames * channels]: signal index */, uint32_t* __restrict__ status, uint64_t* __restrict__ total_words_out, uint64_t frames_cap)
 {
     constexpr int kWaves = kPlanThreads / 64;
     __shared__ uint64_t wave_bytes[kWaves], wave_words[kWaves];
     __shared__ uint32_t frame_words[kPlanTile]; // words of the frames of one tile (their bytes follow: 4 + 12 channels + 4 words)
     __shared__ uint32_t frame_first_hi[kPlanTile];
-    __shared__ uint32_t all_flags;
+    __shared__ uint32_t all_flags, all_over;
     const uint32_t t = threadIdx.x;
     const int lane = t % 64, wave = t / 64;
     if (t == 0)
-        all_flags = 0;
+        all_flags = 0, all_over = 0;
     uint64_t base_b = 0, base_w = 0; // bytes / words of the tiles before this one (the same in every thread)
-    uint32_t my_flags = 0;
+    uint32_t my_flags = 0, my_over = 0;
     for (uint32_t tile0 = 0; tile0 < n_frames; tile0 += kPlanTile) {
         const uint32_t tile_n = min((uint32_t)kPlanTile, n_frames - tile0);
         __syncthreads(); // (the tile before has been read)
@@ -801,17 +804,27 @@ __global__ __launch_bounds__(kPlanThreads) void k_generic_plan(const GenericMeta
             }
             // bytes before frame f = (frames before it) x (4 + 12 channels) + 4 x (words before it)
             frame_offsets[f] = base_bytes + (uint64_t)f * (4 + (uint64_t)channels * SELA_SUBFRAME_HEADER_BYTES) + 4 * first;
+            if constexpr (kDevice) { // (the frame's end: the next frame's first word, from the scan)
+                const uint64_t next = i + 1 < tile_n ? base_w + (((uint64_t)frame_first_hi[i + 1] << 32) | frame_words[i + 1]) : base_w + tile_w;
+                my_over += (uint64_t)(f + 1) * (4 + (uint64_t)channels * SELA_SUBFRAME_HEADER_BYTES) + 4 * next > frames_cap;
+            }
         }
         base_b += tile_b, base_w += tile_w;
     }
     if (my_flags)
         atomicOr(&all_flags, my_flags);
+    if (kDevice && my_over)
+        atomicAdd(&all_over, my_over);
     __syncthreads();
     if (t == 0) {
         frame_offsets[n_frames] = base_bytes + base_b;
         word_base[(size_t)n_frames * channels] = base_w;
         *total_words_out = base_w;
-        atomicOr(&status[0], all_flags);
+        if constexpr (kDevice) {
+            status[0] = all_flags, status[1] = all_over, status[2] = 0, status[3] = 0;
+        } else {
+            atomicOr(&status[0], all_flags);
+        }
     }
 }
 
@@ -883,6 +896,71 @@ __global__ __launch_bounds__(kAsmThreads) void k_generic_assemble(const GenericM
     uint8_t* const rdst = dst + 12 + 4 * (size_t)cw;
     for (size_t i = t; i < 4 * (size_t)rw; i += kAsmThreads)
         rdst[i] = (uint8_t)(src[cw + (i >> 2)] >> (8 * (i & 3)));
+}
+
+// ---- write: the on-disk bytes at their final place, one wave per subframe (sela_hip_encode_i32_device) -----------------------
+// pack + assemble in one pass, with no Rice words in between.  A frame is 4-aligned and so is every subframe (12 header bytes and
+// whole words), at byte 4 (f + 1) + 12 sub + 4 word_base[sub] of the stream.  Its first 3 + cw words -- the 7 header bytes, the
+// coefficient words 3 bytes off alignment, the residue header's 5 bytes -- are put together from the coefficient stream packed
+// in LDS, one aligned word per lane by a funnel shift, and stored once; the residue words follow aligned, packed by
+// rice_pack_stream straight into the frame.  That packer ORs into zeroed words and leaves words that come out zero alone: the
+// wave zeroes its residue words first and waits for those stores.  A frame that ends beyond frames_cap is not written at all;
+// nothing is written outside a subframe's own words (the sync word: by the frame's first subframe).
+__global__ __launch_bounds__(64) void k_generic_write(const GenericMeta* __restrict__ meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n,
+    const int32_t* __restrict__ res_ws, const int32_t* __restrict__ q_ws, const uint32_t* __restrict__ chosen, const uint64_t* __restrict__ word_base,
+    const uint64_t* __restrict__ frame_offsets, uint8_t* __restrict__ frames /* 4-byte aligned */, uint64_t frames_cap)
+{
+    const uint32_t sub = blockIdx.x;
+    if (sub >= n_frames * channels)
+        return;
+    const int lane = threadIdx.x;
+    const uint32_t f = sub / channels, c = sub % channels;
+    const uint32_t sgn = chosen[sub];
+    const size_t b = (size_t)f * n_sig + sgn;
+    // (as k_generic_pack: the record, the coefficients and the first stretch of residues asked for together)
+    int32_t first[kPackPerLane], coefs[kPackPerLane];
+    pack_fetch(res_ws + b * n, n, 0, lane, first);
+    pack_fetch(q_ws + b * kMaxOrder, kMaxOrder, 0, lane, coefs);
+    const GenericMeta m = meta[b];
+    const uint64_t wb = word_base[sub];
+    if (frame_offsets[f + 1] > frames_cap)
+        return;
+    const bool broken = (m.flags & (SELA_HIP_FLAG_WORDS_CAP | SELA_HIP_FLAG_RICE_RANGE)) != 0; // (as k_generic_assemble: an empty header)
+    const uint32_t cw = broken ? 0 : m.coef_words, rw = broken ? 0 : m.res_words;
+    uint32_t* const dst = reinterpret_cast<uint32_t*>(frames) + (f + 1) + 3 * (uint64_t)sub + wb;
+    __shared__ uint32_t win[kPackWindow];
+    __shared__ uint32_t coef[kCoefWordsCap];
+    static_assert(kCoefWordsCap <= 64 - 3, "a subframe's header words: one lane each");
+    if (lane < kCoefWordsCap)
+        coef[lane] = 0;
+    wave_sync();
+    if (cw)
+        rice_pack_stream<true>(q_ws + b * kMaxOrder, m.order, m.coef_k, coef, lane, win, coefs);
+    if (rw) { // zero the residue words; the stores are done before the packer's first OR
+        for (uint32_t w = lane; w < rw; w += 64)
+            dst[3 + cw + w] = 0;
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wave_sync();
+    // the header words: the byte stream [pad] c type parent coef_k cw(2) order | coefficient words | res_k rw(2) n(2) [pad x 3] as
+    // words x(0 .. cw + 3); aligned word j is x(j) >> 8 | x(j + 1) << 24
+    auto x = [&](uint32_t i) -> uint32_t {
+        if (i == 0)
+            return (c << 8) | ((sgn >= channels ? 1u : 0u) << 16) | ((sgn >= channels ? c - 1 : c) << 24);
+        if (i == 1)
+            return m.coef_k | (cw << 8) | (m.order << 24);
+        if (i < cw + 2)
+            return coef[i - 2];
+        if (i == cw + 2)
+            return m.res_k | (rw << 8) | ((n & 0xFFu) << 24);
+        return n >> 8;
+    };
+    if ((uint32_t)lane < 3 + cw)
+        dst[lane] = __builtin_amdgcn_alignbit(x((uint32_t)lane + 1), x((uint32_t)lane), 8);
+    if (c == 0 && lane == 63)
+        dst[-1] = SELA_SYNC_WORD;
+    if (rw)
+        rice_pack_stream<true>(res_ws + b * n, n, m.res_k, dst + 3 + cw, lane, win, first);
 }
 
 // ---- decode: one wave per subframe -------------------------------------------------------------------------------------------
@@ -1412,8 +1490,8 @@ hipError_t launch_generic_analyse(const void* d_input, bool in16, uint32_t n_fra
 hipError_t launch_generic_plan(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint64_t base_bytes, uint64_t* d_frame_offsets,
     uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_generic_plan, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, base_bytes, d_frame_offsets, d_word_base, d_chosen,
-        d_status, d_total_words);
+    hipLaunchKernelGGL(k_generic_plan<false>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, base_bytes, d_frame_offsets, d_word_base,
+        d_chosen, d_status, d_total_words, (uint64_t)0);
     return hipGetLastError();
 }
 
@@ -1517,6 +1595,61 @@ hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
     hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_samples_out, d_counts_out,
         nullptr, nullptr, d_status, d_n_found);
+    return hipGetLastError();
+}
+
+// Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total; every
+// piece 256-byte aligned, the base too.  No Rice words: k_generic_write packs into the frames.
+struct EncodeI32Layout {
+    uint64_t sig, res, q, meta, word_base, chosen, total, bytes;
+};
+static EncodeI32Layout encode_i32_layout(uint32_t n_frames, uint32_t channels, uint32_t n)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t blocks = (uint64_t)n_frames * (channels == 2 ? 3 : channels), subs = (uint64_t)n_frames * channels;
+    EncodeI32Layout l;
+    l.sig = 0;
+    l.res = l.sig + up(blocks * n * sizeof(int32_t));
+    l.q = l.res + up(blocks * n * sizeof(int32_t));
+    l.meta = l.q + up(blocks * kMaxOrder * sizeof(int32_t));
+    l.word_base = l.meta + up(blocks * sizeof(GenericMeta));
+    l.chosen = l.word_base + up((subs + 1) * sizeof(uint64_t));
+    l.total = l.chosen + up(subs * sizeof(uint32_t));
+    l.bytes = l.total + up(sizeof(uint64_t)) + 256; // (+ the base's alignment)
+    return l;
+}
+
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
+{
+    if (channels == 0 || channels > 255 || n == 0 || n > 65535 || (uint64_t)n_frames * (channels == 2 ? 3 : channels) >= (1ull << 31))
+        return SIZE_MAX;
+    return (size_t)encode_i32_layout(n_frames, channels, n).bytes;
+}
+
+// sela_hip_encode_i32_device / sela_hip_encode_n_device: analyse, plan (base 0, the offsets straight into the
+// caller's, the status words written whole) and write, all on `stream`, nothing waited for.  Arguments checked by the caller.
+hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream)
+{
+    const EncodeI32Layout l = encode_i32_layout(n_frames, channels, n);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    int32_t* const d_sig = reinterpret_cast<int32_t*>(base + l.sig);
+    int32_t* const d_res = reinterpret_cast<int32_t*>(base + l.res);
+    int32_t* const d_q = reinterpret_cast<int32_t*>(base + l.q);
+    GenericMeta* const d_meta = reinterpret_cast<GenericMeta*>(base + l.meta);
+    uint64_t* const d_word_base = reinterpret_cast<uint64_t*>(base + l.word_base);
+    uint32_t* const d_chosen = reinterpret_cast<uint32_t*>(base + l.chosen);
+    uint64_t* const d_total = reinterpret_cast<uint64_t*>(base + l.total);
+    const uint32_t n_sig = channels == 2 ? 3u : channels;
+    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets, d_word_base,
+        d_chosen, d_status, d_total, frames_cap);
+    const uint32_t subs = n_frames * channels;
+    if (subs)
+        hipLaunchKernelGGL(k_generic_write, dim3(subs), dim3(64), 0, stream, d_meta, n_frames, channels, n_sig, n, d_res, d_q, d_chosen, d_word_base,
+            d_frame_offsets, d_frames, frames_cap);
     return hipGetLastError();
 }
 
