@@ -1561,6 +1561,40 @@ __device__ __forceinline__ void team_load_raw(const int16_t* __restrict__ fp, ui
     }
 }
 
+// team_fetch + team_unpack are team_load_raw in two halves (kStereo: channels == 2), for a caller that holds the loaded words
+// until it needs the samples: the unpack waits for the loads.
+template <int kPer, int kStep, bool kStereo>
+__device__ __forceinline__ void team_fetch(const int16_t* __restrict__ fp, uint32_t channels, uint32_t sig, int first, uint32_t (&w)[kPer])
+{
+    if constexpr (kStereo) { // both channels' samples of a frame: the signal is taken apart in team_unpack
+        const uint32_t* pw = reinterpret_cast<const uint32_t*>(fp) + first;
+#pragma unroll
+        for (int u = 0; u < kPer; u++)
+            w[u] = pw[u * kStep];
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPer; i++)
+            w[i] = (uint32_t)(int32_t)fp[(size_t)(first + i * kStep) * channels + sig];
+    }
+}
+template <int kPer, bool kStereo>
+__device__ __forceinline__ void team_unpack(uint32_t sig, const uint32_t (&w)[kPer], int32_t (&raw)[kPer])
+{
+    if constexpr (kStereo) {
+        const uint32_t first_shift = sig == 1 ? 16u : 0u; // as team_load_raw
+        const uint32_t second_mask = sig == 2 ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+        for (int i = 0; i < kPer; i++) {
+            const int32_t a = (int32_t)(w[i] << (16 - first_shift)) >> 16, b = ((int32_t)w[i] >> 16) & (int32_t)second_mask;
+            raw[i] = a - b;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPer; i++)
+            raw[i] = (int32_t)w[i];
+    }
+}
+
 // x = s / 32767 (kCentre: minus the block's mean) of a lane's kPer samples to ring positions pos, pos + kStep, ..; kMirror: the
 // ring's first entries also behind its end
 template <int kPer, int kStep, bool kCentre, bool kMirror, int kRing>
@@ -1606,6 +1640,69 @@ __device__ __forceinline__ double team_chain(const double* x, double sum)
 #pragma unroll
         for (int i = 0; i < kBatch; i++)
             sum += v[i];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return sum;
+}
+
+// The same chain for teams of 16, which are DPP rows: lane p of a row holds x[i] = sample 16 i + p of the chunk, and
+// sum += x[i] of row lane 0, 1, .., 15 in turn is one v_fmac_f64 with a row_newbcast source each (x * 1.0 is exact, so the
+// fused step rounds exactly as the add does; the sum starts at +0, so signed zeros come out the same).  Every lane of a row
+// walks the row's chain; nothing goes through LDS.  (64-bit DPP takes no other row control than row_newbcast, and the
+// assembler has no v_add_f64_dpp.)
+template <int kN>
+__device__ __forceinline__ double row_chain(const double (&x)[kN], double sum)
+{
+#define SELA_ROW_FMAC(j) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #j "\n\t"
+#pragma unroll
+    for (int i = 0; i < kN; i++) // (s_nop 1: a DPP source written by the VALU wants two wait states first)
+        asm("s_nop 1\n\t" SELA_ROW_FMAC(0) SELA_ROW_FMAC(1) SELA_ROW_FMAC(2) SELA_ROW_FMAC(3) SELA_ROW_FMAC(4) SELA_ROW_FMAC(5)
+            SELA_ROW_FMAC(6) SELA_ROW_FMAC(7) SELA_ROW_FMAC(8) SELA_ROW_FMAC(9) SELA_ROW_FMAC(10) SELA_ROW_FMAC(11) SELA_ROW_FMAC(12)
+            SELA_ROW_FMAC(13) SELA_ROW_FMAC(14) SELA_ROW_FMAC(15)
+            : "+v"(sum) : "v"(x[i]), "v"(1.0));
+#undef SELA_ROW_FMAC
+    return sum;
+}
+
+// The mean's sum of one block for teams of 16 (P = 16, kStep = 16): lane p of a row converts samples p, p + 16, p + 32, p + 48 of
+// each chunk of 64, and the row's chain runs through them in sample order (row_chain).  The PCM of a chunk is fetched two chunks
+// ahead and held as loaded words; two chunks per trip, so that the two sets of words take turns without a copy (a copy waits for
+// the newest load).
+template <int kPer, bool kStereo>
+__device__ __forceinline__ double team_row_mean_sum(const int16_t* __restrict__ fp, uint32_t channels, uint32_t sig, int p)
+{
+    constexpr int kStep = 16, kChunks = kBlock / kTeamMeanChunk;
+    static_assert(kPer * kStep == kTeamMeanChunk && kChunks % 2 == 0, "lane p holds samples p, p + 16, .. of a chunk; two chunks per trip");
+    uint32_t w_a[kPer], w_b[kPer];
+    double x[kPer];
+    int32_t raw[kPer];
+    team_fetch<kPer, kStep, kStereo>(fp, channels, sig, p, w_a);
+    team_unpack<kPer, kStereo>(sig, w_a, raw);
+#pragma unroll
+    for (int i = 0; i < kPer; i++)
+        x[i] = scale_sample(raw[i]);
+    team_fetch<kPer, kStep, kStereo>(fp, channels, sig, kTeamMeanChunk + p, w_a);
+    team_fetch<kPer, kStep, kStereo>(fp, channels, sig, 2 * kTeamMeanChunk + p, w_b);
+    double sum = 0.0;
+    // (the fetches behind the last chunk take the last chunk again, and the last trip converts one chunk for nothing: a fetch
+    // or a conversion under a condition makes the compiler copy the words, and a copy waits for the newest load)
+#pragma unroll 1
+    for (int c = 0; c < kChunks; c += 2) {
+        sum = row_chain<kPer>(x, sum); // chunk c
+        __builtin_amdgcn_sched_barrier(0);
+        team_unpack<kPer, kStereo>(sig, w_a, raw); // chunk c + 1
+#pragma unroll
+        for (int i = 0; i < kPer; i++)
+            x[i] = scale_sample(raw[i]);
+        team_fetch<kPer, kStep, kStereo>(fp, channels, sig, min(c + 3, kChunks - 1) * kTeamMeanChunk + p, w_a);
+        __builtin_amdgcn_sched_barrier(0);
+        sum = row_chain<kPer>(x, sum); // chunk c + 1
+        __builtin_amdgcn_sched_barrier(0);
+        team_unpack<kPer, kStereo>(sig, w_b, raw); // chunk c + 2
+#pragma unroll
+        for (int i = 0; i < kPer; i++)
+            x[i] = scale_sample(raw[i]);
+        team_fetch<kPer, kStep, kStereo>(fp, channels, sig, min(c + 4, kChunks - 1) * kTeamMeanChunk + p, w_b);
         __builtin_amdgcn_sched_barrier(0);
     }
     return sum;
@@ -1695,9 +1792,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         wave_stamp[0] = clock64();
 
     // ---- the mean (src/lpc/residue_generator.cpp:27-30): x = s / 32767 summed in order, the B chains side by side ----
-    // Chunks of 64 samples alternate between two places in the ring; the PCM of a chunk is fetched two chunks ahead.
+    // Teams of 8: chunks of 64 samples alternate between two places in the ring; the PCM of a chunk is fetched two chunks ahead.
     double mean;
-    {
+    if constexpr (P == 16) { // teams are DPP rows: the chain without LDS (team_row_mean_sum)
+        static_assert(kStep == P, "lane p holds samples p, p + 16, .. of a chunk");
+        set_wave_priority((int)(team_priorities & 0xFF)); // (see the note on priorities at the autocorrelation's loop)
+        const double sum = channels == 2 ? team_row_mean_sum<kMeanPer, true>(fp, channels, sig, p) : team_row_mean_sum<kMeanPer, false>(fp, channels, sig, p);
+        mean = sum / (double)kBlock;
+    } else {
         constexpr int kChunks = kBlock / kTeamMeanChunk;
         const int mine = kStep == 1 ? p * kMeanPer : p; // this lane's samples of a chunk: mine + kStep i
         int32_t raw_a[kMeanPer], raw_b[kMeanPer];
