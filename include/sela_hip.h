@@ -194,9 +194,10 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
  *     2048-sample frames pays nothing for the other kind) -- unless the stream's FIRST frame already says another length --
  *     and they may write up to [n_frames][2048][channels] before they find an odd frame further on: pcm_out must hold
  *     max(n_frames * 2048, sample_offsets[n_frames]) * channels samples.
- * The streaming jobs and the int16 device-pointer calls (sela_hip_decode_device, sela_hip_decode_payload_device) stay what they
- * are: the fast path for what the reference's CLI writes (2048 everywhere); a stream with another length gets SELA_HIP_EFORMAT
- * from them, and the caller comes here -- or, with the stream in device memory, to sela_hip_decode_i32_device below. */
+ * The streaming jobs and the 2048-sample int16 device-pointer calls (sela_hip_decode_device, sela_hip_decode_payload_device)
+ * stay what they are: the fast path for what the reference's CLI writes (2048 everywhere); a stream with another length gets
+ * SELA_HIP_EFORMAT from them, and the caller comes here -- or, with the stream in device memory, to sela_hip_decode_n_device
+ * (this call's output on device pointers) or sela_hip_decode_i32_device below. */
 size_t sela_hip_encode_bound_bytes_n(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel);
 /* sample_offsets[f] = samples per channel before frame f (its first subframe's samplesPerChannel counts for the frame),
  * [n_frames + 1] entries; returns the largest samplesPerChannel any subframe of the stream names (0 for a stream the walk
@@ -308,6 +309,49 @@ int sela_hip_encode_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t c
  * order -- SELA_HIP_FLAG_SHORT_BLOCK, _RICE_RANGE, _COEF_OVERFLOW or _WORDS_CAP: SELA_HIP_ERANGE; then [1] > 0:
  * SELA_HIP_ECAPACITY; else 0 (SELA_HIP_FLAG_Q_RANGE alone included).  A null pointer: SELA_HIP_EINVAL. */
 int sela_hip_encode_status_error(const uint32_t* status /* [4], host copy */);
+
+/* sela_hip_decode on DEVICE pointers -- any samplesPerChannel in 0 .. 65535, samples wider than 16 bits narrowed as that call
+ * narrows them -- asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of device data, so a
+ * stream being captured into a HIP graph may take either call.  Neither touches the calling thread's scratch, its open streaming
+ * job or the coalescer.  The route the host call takes is taken on the device, before anything is decoded: the 2048-sample
+ * decoder (k_decode_frames / _wide) where every subframe says 2048, the header walk is whole and stride >= 2048; else the
+ * any-length kernels where the walk gives a largest samplesPerChannel that fits stride and the offsets never decrease; else none.
+ *   d_pcm_out int16, room for n_frames * stride * channels samples: where sela_hip_decode on the same frames returns 0, exactly
+ *                 the bytes it writes (frame f at d_pcm_out + sample_offsets[f] * channels).  Nothing at or past
+ *                 n_frames * stride * channels is written, on any input; on success nothing at or past
+ *                 sample_offsets[n_frames] * channels either.
+ *   d_sample_offsets [n_frames + 1] (or NULL): what sela_hip_index_samples() returns for the same frames (for decreasing
+ *                 offsets their contents are not defined).
+ *   d_status uint32[4], written by the call (needs no initialisation):
+ *     [0] the OR of the flag bits, [1] the number of malformed frames, [2] the largest samplesPerChannel (as the i32 call),
+ *     [3] the route taken: 0 nothing decoded, 1 the 2048-sample decoder, 2 the any-length kernels.
+ *   SELA_HIP_FLAG_STRIDE: the offsets never decrease, the walk is whole and [2] > stride (a 2048 stream with stride < 2048
+ *     included); nothing is decoded then.
+ *   sela_hip_decode_n_status_error() turns a host copy of the status words into the code sela_hip_decode returns for the same
+ *     input, SELA_HIP_FLAG_STRIDE aside (SELA_HIP_ECAPACITY, which that call never needs).
+ * d_frames: 4-byte aligned, holding every frame the offsets name.  d_workspace: sela_hip_decode_n_workspace_bytes(n_frames,
+ * channels, stride) bytes, no initialisation (the payload call: sela_hip_index_workspace_bytes(payload_bytes, max_frames) more);
+ * one call at a time may use it.  channels * n_frames below 2^31.  sela_hip_debug_standard_first routes the any-length kernels
+ * as it routes the i32 call.
+ * SELA_HIP_EINVAL: a null pointer (d_sample_offsets may be NULL), channels outside 1..255, stride 0, a misaligned d_frames /
+ * d_payload; SELA_HIP_ECAPACITY: a smaller workspace.  Nothing is enqueued then. */
+size_t sela_hip_decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    int16_t* d_pcm_out /* [n_frames * stride][channels] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count never leaves the device.
+ * Frames from *d_n_frames on are not decoded; d_sample_offsets[0 .. *d_n_frames] is written. */
+int sela_hip_decode_payload_n_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* Host only, no GPU: the code sela_hip_decode returns for the input whose device status words (a host copy) these are --
+ * SELA_HIP_FLAG_STRIDE: SELA_HIP_ECAPACITY; then by the route ([3]):
+ *   1 (the streaming job's mapping): a malformed frame or a Rice stream that runs dry: SELA_HIP_EFORMAT; a coefficient beyond
+ *     int64 or outside the tables: SELA_HIP_ERANGE; else 0;
+ *   2: sela_hip_decode_status_error()'s order (generic_decode's);
+ *   0: SELA_HIP_FLAG_BAD_FRAME (the walk breaks, offsets decrease, or the largest length is 0): SELA_HIP_EFORMAT; else 0 (no frames).
+ * A null pointer: SELA_HIP_EINVAL. */
+int sela_hip_decode_n_status_error(const uint32_t* status /* [4], host copy */);
 
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and

@@ -33,6 +33,7 @@ EXPORTS = [
     "sela_hip_lpc_encode_n", "sela_hip_lpc_decode_n",
     "sela_hip_index_workspace_bytes", "sela_hip_index_frames_device", "sela_hip_decode_payload_device",
     "sela_hip_decode_i32_workspace_bytes", "sela_hip_decode_i32_device", "sela_hip_decode_payload_i32_device", "sela_hip_decode_status_error",
+    "sela_hip_decode_n_workspace_bytes", "sela_hip_decode_n_device", "sela_hip_decode_payload_n_device", "sela_hip_decode_n_status_error",
     "sela_hip_encode_i32_workspace_bytes", "sela_hip_encode_i32_device", "sela_hip_encode_n_device", "sela_hip_encode_status_error",
 ]
 
@@ -118,6 +119,14 @@ def lib() -> C.CDLL:
     L.sela_hip_decode_payload_i32_device.restype = C.c_int
     L.sela_hip_decode_status_error.argtypes = [vp]
     L.sela_hip_decode_status_error.restype = C.c_int
+    L.sela_hip_decode_n_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_n_workspace_bytes.restype = sz
+    L.sela_hip_decode_n_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_n_device.restype = C.c_int
+    L.sela_hip_decode_payload_n_device.argtypes = [vp, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_payload_n_device.restype = C.c_int
+    L.sela_hip_decode_n_status_error.argtypes = [vp]
+    L.sela_hip_decode_n_status_error.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]

@@ -210,6 +210,78 @@ def decode_status_error(status) -> int:
     return int(capi.lib().sela_hip_decode_status_error(st.ctypes.data))
 
 
+class DecoderN:
+    """sela_hip_decode on the device: int16 interleaved PCM of streams of any samplesPerChannel (0 .. 65535), samples wider
+    than 16 bits narrowed as the host call narrows them, the route (2048-sample decoder or any-length kernels) chosen on the
+    device.  Owns its outputs and its workspace on the current device (or `device`); every call is asynchronous on the current
+    stream and overwrites them."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        with torch.cuda.device(self.device):
+            self.pcm = torch.empty((max_frames * stride, channels), dtype=torch.int16, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_decode_n_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def decode(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1]
+        -> (pcm int16 [max_frames * stride, channels], sample_offsets int64 [n + 1]), views of the decoder's own buffers: frame f
+        at pcm[sample_offsets[f]], sample_offsets[n] samples in all (the library's uint64 bit patterns)."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_n_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.pcm.data_ptr(), self.sample_offsets.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.pcm, self.sample_offsets[: n_frames + 1]
+
+    def decode_payload(self, payload, max_frames=None):
+        """Index and decode a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (pcm int16 [max_frames * stride, channels],
+        sample_offsets [max_frames + 1], frame_offsets int64 [max_frames + 1], count int32 [1]): offsets up to count[0] are the
+        stream's, pcm up to sample_offsets[count[0]].  The workspace grows to the largest payload seen (make one call before
+        capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_decode_n_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_payload_n_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.pcm.data_ptr(), self.sample_offsets.data_ptr(),
+            self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
+            self.payload_workspace.numel(), stream))
+        return self.pcm[: max_frames * self.stride], self.sample_offsets[: max_frames + 1], self.frame_offsets[: max_frames + 1], self.count
+
+    def route(self) -> int:
+        """Waits for the last call -> the route it took: 0 nothing decoded, 1 the 2048-sample decoder, 2 the any-length kernels."""
+        return int(self.status[3].item())
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same input."""
+        capi.check(decode_n_status_error(self.status.cpu().numpy()))
+
+
+def decode_n_status_error(status) -> int:
+    """sela_hip_decode_n_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_decode_n_status_error(st.ctypes.data))
+
+
 class Encoder32:
     """sela_hip_encode_i32 -- and sela_hip_encode of any length -- on the device: frames of any samples_per_channel (1 .. 65535),
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is

@@ -42,7 +42,7 @@ hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_w
     uint32_t n_streams, int32_t* d_values, uint32_t* d_status, hipStream_t stream);
 hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles,
-    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0, const uint32_t* d_n_found = nullptr);
+    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0, const uint32_t* d_n_found = nullptr, bool zero_status = true);
 int decode_waves(uint32_t channels);
 size_t index_workspace_bytes(uint64_t payload_bytes);
 hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
@@ -63,6 +63,10 @@ int generic_standard_first_mode();
 size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
 hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
+    hipStream_t stream);
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
@@ -1430,22 +1434,29 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
 }
 
 namespace {
+// The decoder's counterpart of the encoder's schedule: a launch that has the device to itself raises its heavy subframes.
+// *dev: the current device, or -1 (then nothing is to be noted in flights() after the launch).
+uint32_t decode_synth_priorities(uint32_t n_frames, void* stream, int* dev)
+{
+    uint32_t synth_priorities = 0;
+    if (n_frames && hipGetDevice(dev) == hipSuccess && *dev >= 0 && *dev < 64) {
+        const int64_t forced = g_forced_priorities.load(std::memory_order_relaxed);
+        synth_priorities = forced >= 0 ? (forced ? kHeavySubframesFirst : 0u)
+                                       : (stream_is_capturing(static_cast<hipStream_t>(stream)) || flights().others_pending(*dev, static_cast<hipStream_t>(stream)) ? 0u : kHeavySubframesFirst);
+    } else {
+        *dev = -1;
+    }
+    return synth_priorities;
+}
+
 // sela_hip_decode_device's launch, arguments checked; d_n_found (or null): the device's own count of frames to decode
 int decode_device_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, void* stream, const uint32_t* d_n_found)
 {
     hipEvent_t* ev = n_frames ? g_timing.events() : nullptr;
     g_timing.recorded = ev ? 1 : 0;
-    // (the decoder's counterpart of the encoder's schedule: a launch that has the device to itself raises its heavy subframes)
     int dev = -1;
-    uint32_t synth_priorities = 0;
-    if (n_frames && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        const int64_t forced = g_forced_priorities.load(std::memory_order_relaxed);
-        synth_priorities = forced >= 0 ? (forced ? kHeavySubframesFirst : 0u)
-                                       : (stream_is_capturing(static_cast<hipStream_t>(stream)) || flights().others_pending(dev, static_cast<hipStream_t>(stream)) ? 0u : kHeavySubframesFirst);
-    } else {
-        dev = -1;
-    }
+    const uint32_t synth_priorities = decode_synth_priorities(n_frames, stream, &dev);
     hipError_t e = sela::launch_decode(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace,
         static_cast<hipStream_t>(stream), ev, g_phase_cycles, nullptr, g_recurrence_form, synth_priorities, d_n_found);
     if (e != hipSuccess)
@@ -1671,6 +1682,103 @@ int sela_hip_encode_status_error(const uint32_t* status)
         return fail(SELA_HIP_ERANGE, "encode: a Rice stream needs more words than a subframe's 16-bit count can say");
     if (status[1])
         return fail(SELA_HIP_ECAPACITY, "d_frames too small: status[1] frames were not written (d_frame_offsets[n_frames] bytes are needed)");
+    return SELA_HIP_OK;
+}
+
+// ---- the int16 decode of any length on device pointers ----------------------------------------------------
+namespace {
+// what sela_hip_decode_n_device and the payload call check alike; SELA_HIP_OK or the failure, reported
+int check_decode_n_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm_out, const uint32_t* d_status, const void* d_workspace)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (stride == 0)
+        return fail(SELA_HIP_EINVAL, "stride must not be 0");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!d_status || !d_workspace || (n_frames && !d_pcm_out))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    return SELA_HIP_OK;
+}
+
+int decode_n_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
+    int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
+{
+    int dev = -1;
+    const uint32_t synth_priorities = decode_synth_priorities(max_frames, stream, &dev);
+    const hipError_t e = sela::launch_decode_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm_out, d_sample_offsets, d_status,
+        d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "decode_n launch");
+    if (dev >= 0)
+        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
+            flights().note(dev, static_cast<hipStream_t>(stream));
+    return SELA_HIP_OK;
+}
+} // namespace
+
+size_t sela_hip_decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::decode_n_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = check_decode_n_args(n_frames, channels, stride, d_pcm_out, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!d_frame_offsets || (n_frames && !d_frames))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_frames & 3)
+        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
+    const size_t need = sela::decode_n_workspace_bytes(n_frames, channels, stride);
+    if (need == SIZE_MAX || workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_decode_n_workspace_bytes()");
+    return decode_n_launch(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_workspace, stream);
+}
+
+int sela_hip_decode_payload_n_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc == SELA_HIP_OK)
+        rc = check_decode_n_args(max_frames, channels, stride, d_pcm_out, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), decode_bytes = sela::decode_n_workspace_bytes(max_frames, channels, stride);
+    if (decode_bytes == SIZE_MAX || workspace_bytes < index_bytes + decode_bytes)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_n_workspace_bytes()");
+    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "index launch");
+    return decode_n_launch(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_pcm_out, d_sample_offsets, d_status,
+        static_cast<unsigned char*>(d_workspace) + index_bytes, stream);
+}
+
+// sela_hip_decode's code, by the route the device took (status[3]): the streaming job's mapping behind the fast kernels
+// (job_end), generic_decode's order behind the any-length route, EFORMAT where the host call's walk refuses the stream
+int sela_hip_decode_n_status_error(const uint32_t* status)
+{
+    if (!status)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    const uint32_t flags = status[0];
+    if (flags & SELA_HIP_FLAG_STRIDE)
+        return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (status[2])");
+    if (status[3] == 2)
+        return sela_hip_decode_status_error(status);
+    if ((flags & SELA_HIP_FLAG_BAD_FRAME) || status[1])
+        return fail(SELA_HIP_EFORMAT, status[3] == 1 ? "malformed frame stream (bad sync word or subframe header)"
+                                                     : "malformed frame stream (the header walk breaks, frame offsets decrease, or no subframe says a length)");
+    if (status[3] != 1)
+        return SELA_HIP_OK;
+    if (flags & SELA_HIP_FLAG_RICE_OVERRUN)
+        return fail(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
+    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
+        return fail(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
+    if (flags & SELA_HIP_FLAG_Q_RANGE)
+        return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
     return SELA_HIP_OK;
 }
 

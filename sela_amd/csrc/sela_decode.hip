@@ -512,9 +512,11 @@ hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offset
                                  k_decode_frames 0.247 -> 0.240 ms at 3875 frames, one lane +1.1 %; beside another stream's
                                  kernels the same costs 0.4 %, so the caller passes 0 there */,
     const uint32_t* d_n_found /* or null: the device's own count of frames to decode, at most n_frames (the grid and the
-                                 choices above are made for n_frames) */)
+                                 choices above are made for n_frames) */,
+    bool zero_status /* false: d_status keeps what it holds and the kernels add to it (sela_hip_decode_n_device: the sample index
+                        wrote it) */)
 {
-    hipError_t err = frame_flags ? hipSuccess : hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream);
+    hipError_t err = frame_flags || !zero_status ? hipSuccess : hipMemsetAsync(d_status, 0, 4 * sizeof(uint32_t), stream);
     if (err != hipSuccess || n_frames == 0)
         return err;
     const int n_waves = decode_waves(channels);

@@ -38,6 +38,12 @@ hipError_t launch_decode_subframes32(const uint8_t* d_frames, const uint64_t* d_
 // sela_hip_decode_i32_device / sela_hip_decode_payload_i32_device: the sample index, the fast kernel, the judge
 // and the combine, all on `stream`, nothing waited for.  Arguments checked by the caller; mode as sela_hip_debug_standard_first.
 size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+// sela_hip_decode_n_device / sela_hip_decode_payload_n_device: the sample index, the route taken on the device,
+// both routes' kernels gated by it, the int16 writer.  Arguments checked by the caller.
+size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
+    hipStream_t stream);
 hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and

@@ -25,6 +25,11 @@
 
 namespace sela {
 
+// the 2048-sample decoder (sela_decode.hip): route 1 of sela_hip_decode_n_device
+hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* d_pcm_out, uint32_t* d_status,
+    void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles, uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities,
+    const uint32_t* d_n_found, bool zero_status);
+
 namespace {
 
 __device__ __forceinline__ uint64_t wave_sum_wrap(uint64_t v) // sum over the 64 lanes mod 2^64 (wave-uniform result)
@@ -1298,6 +1303,7 @@ __global__ __launch_bounds__(kCombineThreads) void k_generic_combine(const int32
 // the stride) and zeroes the fast kernel's counters in the workspace: nothing else on the stream initialises them.
 constexpr uint32_t kSampleThreads = 1024, kSampleFramesPerThread = 4, kSampleTileFrames = kSampleThreads * kSampleFramesPerThread;
 constexpr uint32_t kSampleBroken = 1, kSampleDecreasing = 2;
+constexpr uint32_t kSampleOdd = 4, kSampleMisaligned = 8; // (k_route_n: a subframe that does not say 2048, a frame offset not a multiple of 4)
 struct SampleTile {
     uint64_t total; // this tile's samples per channel; k_sample_tiles replaces it by the samples before the tile
     uint32_t largest, bad;
@@ -1310,6 +1316,8 @@ __device__ inline uint32_t sample_head(const uint8_t* __restrict__ frames, const
     const uint64_t o0 = frame_offsets[f], o1 = frame_offsets[f + 1];
     if (o1 < o0)
         bad |= kSampleDecreasing;
+    if (o0 & 3)
+        bad |= kSampleMisaligned;
     const uint8_t* const fb = frames + o0;
     const uint64_t fbytes = o1 >= o0 ? o1 - o0 : 0;
     uint64_t p = 4;
@@ -1320,6 +1328,8 @@ __device__ inline uint32_t sample_head(const uint8_t* __restrict__ frames, const
         if (c == 0)
             first = h.n;
         largest = max(largest, h.n);
+        if (h.n != (uint32_t)kBlock)
+            bad |= kSampleOdd;
         if (p == 0) {
             bad |= kSampleBroken;
             break;
@@ -1357,7 +1367,8 @@ __device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t* part /* LD
     return excl;
 }
 
-// the status words as the host call would leave them after its walk, and the fast kernel's counters zeroed
+// the status words as the host call would leave them after its walk, the fast kernel's counters zeroed, and the walk's verdict
+// bits in counters[4] (k_route_n reads them: sela_hip_decode's "2048 everywhere")
 __device__ inline void finish_sample_index(uint32_t largest, uint32_t bad, uint32_t stride, uint32_t* __restrict__ status, uint32_t* __restrict__ counters)
 {
     const uint32_t walked = (bad & kSampleBroken) ? 0u : largest; // sela_hip_index_samples: 0 for a stream the walk cannot follow
@@ -1367,6 +1378,7 @@ __device__ inline void finish_sample_index(uint32_t largest, uint32_t bad, uint3
     status[3] = 0;
     for (int i = 0; i < 4; i++)
         counters[i] = 0;
+    counters[4] = bad;
 }
 
 template <bool kOneTile>
@@ -1463,6 +1475,123 @@ __global__ __launch_bounds__(kSampleThreads) void k_sample_spread(const SampleTi
             sample_offsets[f0 + j] += base;
 }
 
+// ---- the int16 decode of any length on the device (sela_hip_decode_n_device) --------------------------------
+// sela_hip_decode picks its route on the host: the fast kernels for a stream of 2048 everywhere, the any-length route for the
+// rest.  Here the sample index has walked every header already; k_route_n takes the same decision from what it left and hands
+// each route a frame count of its own in the workspace -- n for the route taken, 0 for the other -- which the kernels of both
+// routes, launched on their largest grids, read as their device-side frame count (a route not taken returns at once).
+//   counters[4] the walk's verdict bits (finish_sample_index), [5] the fast decoder's count, [6] the any-length route's;
+//   status[3] the route: 0 nothing decoded, 1 the 2048-sample decoder, 2 the any-length route.
+// A stream that takes no route and is not refused for its stride is a malformed one (the walk breaks, offsets decrease, no
+// subframe says a length, or a 2048 stream has a frame offset that is not a multiple of 4): SELA_HIP_FLAG_BAD_FRAME, as the host
+// call's EFORMAT.
+__global__ __launch_bounds__(64) void k_route_n(uint32_t max_frames, const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t stride,
+    uint32_t* __restrict__ status, uint32_t* __restrict__ counters)
+{
+    if (threadIdx.x != 0)
+        return;
+    const uint32_t n = n_frames_found ? min(*n_frames_found, max_frames) : max_frames;
+    const uint32_t bad = counters[4], largest = status[2];
+    uint32_t route = 0;
+    if (n != 0 && !(bad & kSampleOdd)) // 2048 everywhere: the fast kernels, or nothing (their job refuses offsets that are not
+        route = bad == 0 && stride >= (uint32_t)kBlock ? 1u : 0u; // multiples of 4, and the host's walk then refuses the stream)
+    else if (n != 0 && largest != 0 && largest <= stride && !(bad & kSampleDecreasing))
+        route = 2;
+    if (n != 0 && route == 0 && !(status[0] & SELA_HIP_FLAG_STRIDE))
+        status[0] |= SELA_HIP_FLAG_BAD_FRAME;
+    status[3] = route;
+    counters[5] = route == 1 ? n : 0u;
+    counters[6] = route == 2 ? n : 0u;
+}
+
+// k_generic_combine<true> without its channel-major copy: one workgroup per (frame, slice of kInterleaveSlice samples), a thread
+// per sample.  Thread 0 turns the frame's subframe records into the reference's order of writes (src/frame/frame_decoder.cpp:
+// 17-69: independent subframes first, then dependent ones in subframe order, a later subframe of a channel overwriting an earlier
+// one, an unknown type skipped) under the combine's rules (the channel and the parent exist, the parent is long enough, every
+// channel ends at the first one's length); then every thread runs those writes for its own sample in a channel table of its own
+// in LDS -- each decoded sample read once -- and the table goes out as interleaved int16 (src/file/wav_file.cpp:244-266), one
+// store per sample.  Frames of more than kInterleaveChannels channels take k_generic_combine<true>.
+constexpr uint32_t kInterleaveThreads = 256, kInterleaveChannels = 8, kInterleaveSlice = 4096, kNoParent = 0xFFu;
+__global__ __launch_bounds__(kInterleaveThreads) void k_interleave16(const int32_t* __restrict__ dec_ws /* [frames][channels][stride] by position */,
+    const GenericSubInfo* __restrict__ info, uint32_t max_frames, uint32_t channels /* <= kInterleaveChannels */, uint32_t stride,
+    const uint64_t* __restrict__ sample_offsets, int16_t* __restrict__ pcm_out, uint32_t* __restrict__ status,
+    const uint32_t* __restrict__ n_frames_found /* or null, as in k_generic_decode */)
+{
+    __shared__ int32_t tab[kInterleaveChannels][kInterleaveThreads];
+    __shared__ uint32_t op_sub[kInterleaveChannels], op_n[kInterleaveChannels], op_dst[kInterleaveChannels], op_parent[kInterleaveChannels];
+    __shared__ uint32_t cnt[kInterleaveChannels];
+    __shared__ uint32_t s_ops, s_n, s_ok;
+    const uint32_t f = blockIdx.x;
+    if (f >= max_frames || (n_frames_found && f >= *n_frames_found))
+        return;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) {
+        const GenericSubInfo* const inf = info + (size_t)f * channels;
+        for (uint32_t c = 0; c < channels; c++)
+            cnt[c] = 0;
+        bool bad = false;
+        uint32_t k = 0;
+        for (uint32_t type = 0; type < 2; type++) { // :17-37, then :40-69
+            for (uint32_t c = 0; c < channels; c++) {
+                const GenericSubInfo si = inf[c];
+                if (!si.ok || si.type != type)
+                    continue;
+                if (si.channel >= channels || (type == 1 && (si.parent >= channels || cnt[si.parent] < si.n))) {
+                    bad = true;
+                    continue;
+                }
+                op_sub[k] = c, op_n[k] = si.n, op_dst[k] = si.channel, op_parent[k] = type == 1 ? si.parent : kNoParent;
+                k++;
+                cnt[si.channel] = si.n;
+            }
+        }
+        const uint32_t n = (uint32_t)(sample_offsets[f + 1] - sample_offsets[f]);
+        for (uint32_t c = 0; c < channels; c++)
+            bad |= cnt[c] != n;
+        s_ops = k, s_n = n, s_ok = bad ? 0u : 1u;
+        if (bad && blockIdx.y == 0) {
+            atomicOr(&status[0], (uint32_t)SELA_HIP_FLAG_BAD_FRAME);
+            atomicAdd(&status[1], 1u);
+        }
+    }
+    __syncthreads();
+    const uint32_t n = s_n, ops = s_ops, lo = blockIdx.y * kInterleaveSlice;
+    if (!s_ok || lo >= n)
+        return;
+    const uint32_t hi = min(n, lo + kInterleaveSlice);
+    const int32_t* const fd = dec_ws + (size_t)f * channels * stride;
+    int16_t* const o = pcm_out + sample_offsets[f] * channels;
+    const bool pairs = channels == 2 && ((uintptr_t)o & 3) == 0;
+    for (uint32_t base = lo; base < hi; base += kInterleaveThreads) {
+        const uint32_t i = base + t;
+        if (i < hi) {
+            for (uint32_t k = 0; k < ops; k++) {
+                if (i >= op_n[k])
+                    continue;
+                int32_t v = fd[(size_t)op_sub[k] * stride + i];
+                const uint32_t p = op_parent[k];
+                if (p != kNoParent)
+                    v = (int32_t)((uint32_t)tab[p][t] - (uint32_t)v);
+                tab[op_dst[k]][t] = v;
+            }
+            if (channels == 1)
+                o[i] = (int16_t)(uint16_t)tab[0][t];
+            else if (pairs) // (a sample pair per thread: one 32-bit store)
+                reinterpret_cast<uint32_t*>(o)[i] = ((uint32_t)tab[0][t] & 0xFFFFu) | ((uint32_t)tab[1][t] << 16);
+        }
+        if (channels != 1 && !pairs) { // through the table: consecutive threads store consecutive int16
+            __syncthreads();
+            const uint32_t m = min(kInterleaveThreads, hi - base) * channels;
+            int16_t* const ob = o + (size_t)base * channels;
+            for (uint32_t j = t; j < m; j += kInterleaveThreads) {
+                const uint32_t s = j / channels, c = j - s * channels;
+                ob[j] = (int16_t)(uint16_t)tab[c][s];
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------------
 size_t generic_encode_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
 {
@@ -1557,6 +1686,24 @@ size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32
     return (size_t)decode_i32_layout(max_frames, channels, stride).bytes;
 }
 
+// The sample index (the host's header walk) on `stream`: one launch up to a tile of frames, three above.
+static void launch_sample_index(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint64_t* d_sample_offsets, uint32_t* d_status, uint32_t* d_counters, SampleTile* d_tiles, hipStream_t stream)
+{
+    if (max_frames <= kSampleTileFrames) {
+        hipLaunchKernelGGL(k_index_samples<true>, dim3(1), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
+            d_sample_offsets, d_status, d_counters, d_tiles);
+    } else {
+        const uint32_t n_tiles = (uint32_t)(((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames);
+        hipLaunchKernelGGL(k_index_samples<false>, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
+            d_sample_offsets, d_status, d_counters, d_tiles);
+        hipLaunchKernelGGL(k_sample_tiles, dim3(1), dim3(kSampleThreads), 0, stream, d_tiles, n_tiles, max_frames, d_n_found, stride, d_sample_offsets, d_status,
+            d_counters);
+        if (d_sample_offsets)
+            hipLaunchKernelGGL(k_sample_spread, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_tiles, max_frames, d_n_found, d_sample_offsets);
+    }
+}
+
 // The host route (generic_decode) on one chunk, with its decisions taken on the device: the sample index and the stride check
 // (the host's header walk), k_decode_subframes32 counting what it leaves alone in the workspace (attempt 0), k_generic_decode over
 // every subframe, each workgroup returning at once unless that count is non-zero (attempt 1: then it decodes every subframe
@@ -1570,18 +1717,7 @@ hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.info);
     uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.counters);
     SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.tiles);
-    if (max_frames <= kSampleTileFrames) {
-        hipLaunchKernelGGL(k_index_samples<true>, dim3(1), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
-            d_sample_offsets, d_status, d_counters, d_tiles);
-    } else {
-        const uint32_t n_tiles = (uint32_t)(((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames);
-        hipLaunchKernelGGL(k_index_samples<false>, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride,
-            d_sample_offsets, d_status, d_counters, d_tiles);
-        hipLaunchKernelGGL(k_sample_tiles, dim3(1), dim3(kSampleThreads), 0, stream, d_tiles, n_tiles, max_frames, d_n_found, stride, d_sample_offsets, d_status,
-            d_counters);
-        if (d_sample_offsets)
-            hipLaunchKernelGGL(k_sample_spread, dim3(n_tiles), dim3(kSampleThreads), 0, stream, d_tiles, max_frames, d_n_found, d_sample_offsets);
-    }
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, d_counters, d_tiles, stream);
     const uint32_t subs = max_frames * channels;
     if (subs == 0)
         return hipGetLastError();
@@ -1595,6 +1731,81 @@ hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
     hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_samples_out, d_counts_out,
         nullptr, nullptr, d_status, d_n_found);
+    return hipGetLastError();
+}
+
+// Workspace of the device-pointer int16 decode: subframes as decoded, by position (the fast decoder parks its residues there too:
+// the routes never run together) | one GenericSubInfo per subframe | the counters | one SampleTile per 4096 frames | the sample
+// offsets | above kInterleaveChannels channels, k_generic_combine's channel-major copy; every piece 256-byte aligned, the base too.
+struct DecodeNLayout {
+    uint64_t dec, info, counters, tiles, offsets, all, bytes;
+};
+static DecodeNLayout decode_n_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t subs = (uint64_t)max_frames * channels, n_tiles = ((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames;
+    DecodeNLayout l;
+    l.dec = 0;
+    l.info = l.dec + up(subs * stride * sizeof(int32_t));
+    l.counters = l.info + up(subs * sizeof(GenericSubInfo));
+    l.tiles = l.counters + up(8 * sizeof(uint32_t));
+    l.offsets = l.tiles + up(std::max<uint64_t>(n_tiles, 1) * sizeof(SampleTile));
+    l.all = l.offsets + up(((uint64_t)max_frames + 1) * sizeof(uint64_t));
+    l.bytes = l.all + (channels > kInterleaveChannels ? up(subs * stride * sizeof(int32_t)) : 0) + 256; // (+ the base's alignment)
+    return l;
+}
+
+size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    if ((uint64_t)max_frames * channels * stride >= (1ull << 60))
+        return SIZE_MAX;
+    return (size_t)decode_n_layout(max_frames, channels, stride).bytes;
+}
+
+// sela_hip_decode on one chunk with its decisions taken on the device: the sample index, k_route_n, the 2048-sample decoder
+// (k_decode_frames / _wide, sela_decode.hip) on its count, the any-length route on its own (k_decode_subframes32 and
+// k_generic_decode as in launch_decode_i32_device) and the int16 writer.  mode as sela_hip_debug_standard_first (the any-length
+// route only); recurrence_form and synth_priorities go to the fast decoder (launch_decode).
+hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
+    hipStream_t stream)
+{
+    const DecodeNLayout l = decode_n_layout(max_frames, channels, stride);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.dec);
+    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.info);
+    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.counters);
+    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.tiles);
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : reinterpret_cast<uint64_t*>(base + l.offsets);
+    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.all);
+    const uint32_t* const n_fast = d_counters + 5;
+    const uint32_t* const n_any = d_counters + 6;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, d_counters, d_tiles, stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, d_counters);
+    const uint32_t subs = max_frames * channels;
+    if (subs == 0)
+        return hipGetLastError();
+    // route 1: frame f at f * 2048 * channels (= sample_offsets[f] * channels there); flags and malformed frames into d_status
+    // as the route's kernels leave them, the words the index wrote kept (no zeroing); its workspace: d_dec, big enough whenever
+    // stride >= 2048, the only case in which the route runs
+    hipError_t e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, d_dec, stream, nullptr, nullptr, nullptr, recurrence_form,
+        synth_priorities, n_fast, false);
+    if (e != hipSuccess)
+        return e;
+    // route 2
+    if (mode != 0) {
+        e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, n_any);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
+        n_any, mode != 0 ? d_counters + 2 : nullptr);
+    if (channels <= kInterleaveChannels)
+        hipLaunchKernelGGL(k_interleave16, dim3(max_frames, (stride + kInterleaveSlice - 1) / kInterleaveSlice), dim3(kInterleaveThreads), 0, stream, d_dec, d_info,
+            max_frames, channels, stride, d_so, d_pcm_out, d_status, n_any);
+    else
+        hipLaunchKernelGGL(k_generic_combine<true>, dim3(max_frames, (stride + kCombineSlice - 1) / kCombineSlice), dim3(kCombineThreads), 0, stream, d_dec, d_info,
+            max_frames, channels, stride, d_all, nullptr, d_so, d_pcm_out, d_status, n_any);
     return hipGetLastError();
 }
 
