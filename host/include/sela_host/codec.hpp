@@ -8,6 +8,7 @@
 // is unavailable process() throws data::Exception.
 #pragma once
 
+#include <cstdint>
 #include <fstream>
 #include <string>
 #include <vector>
@@ -62,6 +63,34 @@ public:
 size_t decodeFileTo(const std::string& inPath, DecodedStream& to, sela_host::PinnedBuffer<int16_t>& into);
 // Threads of that pool (before its first use; 0 = default: min(6, hardware threads / 2)).
 void setIoThreads(unsigned n);
+
+// ---- verification: does this .sela give this WAV back? ---------------------------------------------------------------
+// The codec reproduces the reference bit for bit, and the reference is not lossless on every frame;
+// the encoder also drops the WAV's samples beyond the last whole 2048-sample frame.  verifyFile() says which frames of a
+// .sela come back different from the WAV (sela_hip_verify: compared on the GPU, nothing decoded into host memory) and what
+// of the WAV the .sela never held.  A .sela whose frames say other lengths is compared at the positions decodeFile writes them.
+struct VerifyReport {
+    struct Frame {
+        uint64_t frame;
+        uint32_t differing, first; // values that differ; the first of them, i * channels + c from the frame's start
+    };
+    size_t framesCompared = 0;
+    std::vector<Frame> lossy;
+    uint64_t tailSamplesPerChannel = 0; // WAV samples beyond what the .sela's frames hold
+    // Samples the .sela's frames hold beyond the WAV's end.  They are compared against silence, so the frames they lie in are
+    // listed in `lossy` as well (unless they decode to silence): one cause, reported by its own line and by those frames.
+    uint64_t missingSamplesPerChannel = 0;
+    uint32_t channels = 0;
+    bool rateDiffers = false, channelsDiffer = false, frameCountDiffers = false;
+    uint32_t wavRate = 0, selaRate = 0, wavChannels = 0, selaChannels = 0;
+    uint64_t wavFrames = 0, selaFrames = 0, selaHeaderFrames = 0;
+    bool headersDisagree() const { return rateDiffers || channelsDiffer || frameCountDiffers; }
+};
+VerifyReport verifyFile(const std::string& wavPath, const std::string& selaPath);
+// One line per lossy frame, one per header disagreement, one for the tail, one summary; no GPU needed.
+std::string formatVerifyReport(const VerifyReport& report);
+// 0: everything in the WAV comes back exactly; 3: a frame differs or the headers disagree; 4: only tail samples are missing.
+int verifyExitCode(const VerifyReport& report);
 
 // ---- many files, all GPUs of the node ------------------------------------------------------------------
 // BASELINE.json configs[3]: an album's tracks are one index space of frames, cut into contiguous balanced

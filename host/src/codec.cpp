@@ -772,6 +772,86 @@ size_t decodeFileTo(const std::string& inPath, DecodedStream& to, sela_host::Pin
     return sela.frameCount();
 }
 
+// ---- verification ------------------------------------------------------------------------------------------------------
+VerifyReport verifyFile(const std::string& wavPath, const std::string& selaPath)
+{
+    const WavInfo wav = probeWav(wavPath);
+    const SelaInfo info = probeSela(selaPath);
+    VerifyReport r;
+    r.channels = info.header.channels;
+    r.wavRate = wav.rate, r.selaRate = info.header.sampleRate;
+    r.wavChannels = wav.channels, r.selaChannels = info.header.channels;
+    r.rateDiffers = r.wavRate != r.selaRate;
+    r.channelsDiffer = r.wavChannels != r.selaChannels;
+    r.selaHeaderFrames = info.header.numFrames;
+    const uint32_t channels = info.header.channels;
+    // the frames the file really holds, and where their samples lie (as decodeFile / decodeOddStream place them)
+    std::vector<uint8_t> payload(info.payload + 8);
+    if (info.payload)
+        sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
+    std::vector<uint64_t> offsets(info.announced + 1, 0);
+    const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
+    offsets.resize((size_t)found + 1);
+    std::vector<uint64_t> sampleOffsets((size_t)found + 1, 0);
+    const uint32_t largest = sela_hip_index_samples(payload.data(), offsets.data(), found, channels, sampleOffsets.data());
+    if (found && largest == 0)
+        throw data::Exception("Verify: malformed frame stream");
+    const uint64_t selaSamples = sampleOffsets[found];
+    bool ordinary = true;
+    for (uint32_t f = 0; ordinary && f <= found; f++)
+        ordinary = sampleOffsets[f] == (uint64_t)f * kBlock;
+    r.selaFrames = found;
+    r.wavFrames = wav.frames;
+    r.frameCountDiffers = r.selaHeaderFrames != found || (ordinary && !r.channelsDiffer && found != wav.frames);
+    if (r.channelsDiffer)
+        return r; // (nothing to hold against each other)
+    const uint64_t wavSamples = wav.dataBytes / 2 / channels;
+    r.tailSamplesPerChannel = wavSamples > selaSamples ? wavSamples - selaSamples : 0;
+    r.missingSamplesPerChannel = selaSamples > wavSamples ? selaSamples - wavSamples : 0;
+    std::vector<int16_t> pcm((size_t)selaSamples * channels + 8, 0);
+    const size_t have = (size_t)std::min(wavSamples, selaSamples) * channels * 2;
+    if (have)
+        sela_host::PosixFile::openForRead(wavPath).readAt(pcm.data(), have, wav.dataOffset);
+    std::vector<uint32_t> counts((size_t)found + 1), first((size_t)found + 1);
+    uint32_t lossy = 0;
+    if (sela_hip_verify(payload.data(), offsets.data(), found, channels, pcm.data(), counts.data(), first.data(), &lossy) != SELA_HIP_OK)
+        gpuFailure("Verify");
+    r.framesCompared = found;
+    for (uint32_t f = 0; f < found; f++)
+        if (counts[f])
+            r.lossy.push_back({ f, counts[f], first[f] });
+    return r;
+}
+
+std::string formatVerifyReport(const VerifyReport& r)
+{
+    std::string out;
+    if (r.rateDiffers)
+        out += "header: sample rate " + std::to_string(r.wavRate) + " in the .wav, " + std::to_string(r.selaRate) + " in the .sela\n";
+    if (r.channelsDiffer)
+        out += "header: " + std::to_string(r.wavChannels) + " channels in the .wav, " + std::to_string(r.selaChannels) + " in the .sela\n";
+    if (r.frameCountDiffers)
+        out += "header: the .sela announces " + std::to_string(r.selaHeaderFrames) + " frames and holds " + std::to_string(r.selaFrames) + ", the .wav has "
+            + std::to_string(r.wavFrames) + " whole frames\n";
+    const uint32_t ch = r.channels ? r.channels : 1;
+    for (const VerifyReport::Frame& f : r.lossy)
+        out += "frame " + std::to_string(f.frame) + ": " + std::to_string(f.differing) + " values differ, first at index " + std::to_string(f.first) + " (sample "
+            + std::to_string(f.first / ch) + ", channel " + std::to_string(f.first % ch) + ")\n";
+    if (r.missingSamplesPerChannel)
+        out += "end: the .sela holds " + std::to_string(r.missingSamplesPerChannel) + " samples per channel beyond the end of the .wav\n";
+    if (r.tailSamplesPerChannel)
+        out += "tail: " + std::to_string(r.tailSamplesPerChannel) + " samples per channel beyond the last whole frame are not in the .sela\n";
+    out += "verified " + std::to_string(r.framesCompared) + " frames: " + std::to_string(r.lossy.size()) + " differ\n";
+    return out;
+}
+
+int verifyExitCode(const VerifyReport& r)
+{
+    if (!r.lossy.empty() || r.headersDisagree() || r.missingSamplesPerChannel)
+        return 3;
+    return r.tailSamplesPerChannel ? 4 : 0;
+}
+
 // ---- many files by path: every GPU worker reads, codes and writes its own pieces ----------------------------------
 namespace {
 

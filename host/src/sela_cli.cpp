@@ -1,6 +1,9 @@
 // sela_cli.cpp -- command line front end of the MI355X SELA host:
 //   sela_mi355x -e in.wav out.sela     encode
 //   sela_mi355x -d in.sela out.wav     decode
+//   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
+//                                      what of in.wav it never held; exit 0: all of it comes back exactly, 3: a frame differs or
+//                                      the headers disagree, 4: only tail samples are missing, 1: an error
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -30,6 +33,7 @@ int usage(const std::string& program)
     std::cout << "Usage:\n\n"
               << "Encoding a file:\n" << program << " -e path/to/input.wav path/to/output.sela\n\n"
               << "Decoding a file:\n" << program << " -d path/to/input.sela path/to/output.wav\n\n"
+              << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -121,6 +125,12 @@ int run(int argc, char** argv)
             (void)::close(fd);
         std::cerr << frames << " frames, first packet after " << player.firstPacketSeconds * 1e3 << " ms" << std::endl;
         return 0;
+    }
+    if (verb == "-v" && argc == 4) {
+        std::cout << "Verifying: " << argv[3] << " against " << argv[2] << std::endl;
+        const sela::VerifyReport report = sela::verifyFile(std::string(argv[2]), std::string(argv[3]));
+        std::cout << sela::formatVerifyReport(report) << std::flush;
+        return sela::verifyExitCode(report);
     }
     if (argc != 4 || (verb != "-e" && verb != "-d"))
         return usage(program);

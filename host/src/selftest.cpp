@@ -250,6 +250,47 @@ int main(int argc, char** argv)
         }
         CHECK(threw && sink.opened == 1);
     }
+    // ---- the verification report: its lines and the CLI's exit codes (sela_mi355x -v) ---------------------------------
+    {
+        sela::VerifyReport clean;
+        clean.framesCompared = 70, clean.channels = 2;
+        CHECK(sela::verifyExitCode(clean) == 0 && sela::formatVerifyReport(clean) == "verified 70 frames: 0 differ\n");
+        sela::VerifyReport tail = clean;
+        tail.tailSamplesPerChannel = 777;
+        CHECK(sela::verifyExitCode(tail) == 4);
+        CHECK(sela::formatVerifyReport(tail) == "tail: 777 samples per channel beyond the last whole frame are not in the .sela\nverified 70 frames: 0 differ\n");
+        sela::VerifyReport lossy = tail;
+        lossy.lossy.push_back({ 41, 377, 2967 });
+        lossy.lossy.push_back({ 69, 1, 0 });
+        CHECK(sela::verifyExitCode(lossy) == 3); // (a difference outweighs the tail)
+        CHECK(sela::formatVerifyReport(lossy)
+            == "frame 41: 377 values differ, first at index 2967 (sample 1483, channel 1)\n"
+               "frame 69: 1 values differ, first at index 0 (sample 0, channel 0)\n"
+               "tail: 777 samples per channel beyond the last whole frame are not in the .sela\nverified 70 frames: 2 differ\n");
+        sela::VerifyReport headers = clean;
+        headers.rateDiffers = true, headers.wavRate = 48000, headers.selaRate = 44100;
+        CHECK(sela::verifyExitCode(headers) == 3 && headers.headersDisagree());
+        CHECK(sela::formatVerifyReport(headers) == "header: sample rate 48000 in the .wav, 44100 in the .sela\nverified 70 frames: 0 differ\n");
+        headers = clean;
+        headers.channelsDiffer = true, headers.wavChannels = 1, headers.selaChannels = 2, headers.framesCompared = 0;
+        CHECK(sela::verifyExitCode(headers) == 3);
+        CHECK(sela::formatVerifyReport(headers) == "header: 1 channels in the .wav, 2 in the .sela\nverified 0 frames: 0 differ\n");
+        headers = clean;
+        headers.frameCountDiffers = true, headers.selaHeaderFrames = 71, headers.selaFrames = 70, headers.wavFrames = 70;
+        CHECK(sela::verifyExitCode(headers) == 3);
+        CHECK(sela::formatVerifyReport(headers) == "header: the .sela announces 71 frames and holds 70, the .wav has 70 whole frames\nverified 70 frames: 0 differ\n");
+        sela::VerifyReport longer = clean;
+        longer.missingSamplesPerChannel = 5;
+        CHECK(sela::verifyExitCode(longer) == 3);
+        // a file that is not there is an error (the CLI's exit 1), not a report
+        bool threw = false;
+        try {
+            sela::verifyFile(dir + "/no_such_file.wav", dir + "/no_such_file.sela");
+        } catch (const data::Exception&) {
+            threw = true;
+        }
+        CHECK(threw);
+    }
     // ---- GPU mode: the reference's own frame tests (test/frametests.cpp:8-70) through the host classes --
     if (argc > 2 && std::string(argv[2]) == "gpu") {
         try {

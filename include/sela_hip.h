@@ -353,6 +353,38 @@ int sela_hip_decode_payload_n_device(const uint8_t* d_payload, size_t payload_by
  * A null pointer: SELA_HIP_EINVAL. */
 int sela_hip_decode_n_status_error(const uint32_t* status /* [4], host copy */);
 
+/* ---- verification: a stream against its PCM, frame by frame ----------------------------------------------
+ * The codec reproduces the reference bit for bit, and the reference is not lossless on every frame.  These calls
+ * say which frames of a stream come back different from the PCM they were made from, and where: what sela_hip_decode_n_device
+ * does, with a compare where it stores -- on the 2048-sample route (up to eight channels) in one kernel that writes no PCM at all.
+ *   d_pcm          int16, the layout sela_hip_decode writes: frame f at d_pcm + sample_offsets[f] * channels.  Read only.
+ *   d_diff_counts  [n_frames]: the (sample, channel) values of frame f that sela_hip_decode_n_device would have written
+ *                  differently from d_pcm.
+ *   d_first_diff   [n_frames]: the smallest such index relative to the frame's start (i * channels + c), or 0xFFFFFFFF.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_n_device leaves them for the same frames;
+ *                  [2] the number of frames whose count is not 0 (the largest samplesPerChannel is not reported here:
+ *                  sela_hip_index_samples() or d_sample_offsets say it).
+ *   sela_hip_decode_n_status_error() applies to [0], [1] and [3] unchanged; where it gives non-zero, or SELA_HIP_FLAG_STRIDE is
+ *   set, the two arrays are not defined.  n_frames = 0 writes zero status words.
+ * Arguments, alignment (d_diff_counts and d_first_diff: 4 bytes), errors, capture and the one-call-at-a-time rule of the workspace
+ * (sela_hip_verify_workspace_bytes; the payload call: sela_hip_index_workspace_bytes more) are sela_hip_decode_n_device's.  Apart
+ * from the outputs named here and the workspace nothing is written.  sela_hip_debug_standard_first routes the any-length kernels
+ * as it does for the decode call. */
+size_t sela_hip_verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_verify_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    const int16_t* d_pcm, uint32_t* d_diff_counts /* [n_frames] */, uint32_t* d_first_diff /* [n_frames] */,
+    uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their entries in the two arrays are not written). */
+int sela_hip_verify_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames: returns what sela_hip_decode returns for the stream (0: the arrays are
+ * valid).  *lossy_frames (or NULL): the frames with a difference.  Runs on the calling thread's any-length context and its own
+ * stream, past the coalescer; an open streaming job of the thread is left alone. */
+int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm,
+    uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

@@ -6,6 +6,7 @@
 #ifndef SELA_HIP_DEBUG_H_
 #define SELA_HIP_DEBUG_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -73,6 +74,8 @@ int sela_hip_debug_contexts_created(void);
  * *batches: how many batches so far held more than one call; *retried: how many of those failed for what one of their calls
  * brought and were run again call by call.  Zeros for any other kind. */
 void sela_hip_debug_coalesced(int kind, long long* batches, long long* retried);
+/* The dynamic LDS, in bytes, that a launch of k_verify_frames asks for with this many channels (1 .. 8; else 0). */
+size_t sela_hip_debug_verify_lds_bytes(uint32_t channels);
 
 /* Debug hook (tests; process-wide): while on, a device-pointer encode with a d_trace pointer runs the PRODUCT kernels plus a few
  * instructions (their kMode 3 instantiations, not the trace builds) and leaves, instead of traces, two 64-bit words per block at

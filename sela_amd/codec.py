@@ -282,6 +282,99 @@ def decode_n_status_error(status) -> int:
     return int(capi.lib().sela_hip_decode_n_status_error(st.ctypes.data))
 
 
+class Verifier:
+    """sela_hip_verify_device: a stream held against the PCM it was made from, frame by frame, on the device -- which frames the
+    decoder returns differently (the reference's rounding ties), how many values, and the first of them.  Owns its
+    outputs and its workspace on the current device (or `device`); every call is asynchronous on the current stream and
+    overwrites them.  No PCM is written: on the 2048-sample route of up to eight channels not even into the workspace."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        with torch.cuda.device(self.device):
+            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_verify_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def _pcm_ok(self, pcm) -> bool:
+        return pcm.dtype == self.torch.int16 and pcm.is_cuda and pcm.is_contiguous()
+
+    def verify(self, frames, offsets, n_frames: int, pcm):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1], pcm: int16 cuda tensor in the
+        layout DecoderN.decode returns (frame f at sample_offsets[f]; [n_frames, 2048, channels] for a 2048 stream)
+        -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]; -1: nothing differs), views of the verifier's own buffers."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        assert self._pcm_ok(pcm)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, pcm.data_ptr(), self.diff_counts.data_ptr(),
+            self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+            stream))
+        return self.diff_counts[:n_frames], self.first_diff[:n_frames]
+
+    def verify_payload(self, payload, pcm, max_frames=None):
+        """Index and verify a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (diff_counts [max_frames], first_diff [max_frames],
+        count int32 [1]): entries up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call
+        before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        assert self._pcm_ok(pcm)
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_verify_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, pcm.data_ptr(), self.diff_counts.data_ptr(),
+            self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
+            self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
+
+    def lossy_frames(self) -> int:
+        """Waits for the last call -> the number of frames with a difference (status[2])."""
+        return int(self.status[2].item())
+
+    def route(self) -> int:
+        """Waits for the last call -> the route it took: 0 nothing verified, 1 the 2048-sample decoder, 2 the any-length kernels."""
+        return int(self.status[3].item())
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        st[2] = 0
+        capi.check(decode_n_status_error(st))
+
+
+def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.ndarray):
+    """sela_hip_verify on numpy arrays; pcm: int16 in the layout decode_host returns.  Returns three values:
+    diff_counts (uint32 [n_frames]), first_diff (uint32 [n_frames]; 0xFFFFFFFF where nothing differs) and the number of
+    frames with a difference (int)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    p = np.ascontiguousarray(pcm, dtype=np.int16)
+    n_frames = len(offs) - 1
+    counts = np.zeros(n_frames, np.uint32)
+    first = np.zeros(n_frames, np.uint32)
+    lossy = C.c_uint32(0)
+    capi.check(lib.sela_hip_verify(fr.ctypes.data, offs.ctypes.data, n_frames, channels, p.ctypes.data, counts.ctypes.data, first.ctypes.data, C.byref(lossy)))
+    return counts, first, int(lossy.value)
+
+
 class Encoder32:
     """sela_hip_encode_i32 -- and sela_hip_encode of any length -- on the device: frames of any samples_per_channel (1 .. 65535),
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is

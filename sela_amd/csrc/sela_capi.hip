@@ -67,6 +67,12 @@ size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t
 hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
     hipStream_t stream);
+size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
+int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
+    uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
@@ -1780,6 +1786,93 @@ int sela_hip_decode_n_status_error(const uint32_t* status)
     if (flags & SELA_HIP_FLAG_Q_RANGE)
         return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
     return SELA_HIP_OK;
+}
+
+// ---- verification: a stream against its PCM -----------------------------------------------------------------
+namespace {
+// what sela_hip_verify_device and the payload call check alike (check_decode_n_args with the two arrays); SELA_HIP_OK or the failure
+int check_verify_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm, const uint32_t* d_diff_counts, const uint32_t* d_first_diff,
+    const uint32_t* d_status, const void* d_workspace)
+{
+    const int rc = check_decode_n_args(n_frames, channels, stride, d_pcm, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (n_frames && (!d_diff_counts || !d_first_diff))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if (((uintptr_t)d_pcm & 1) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3))
+        return fail(SELA_HIP_EINVAL, "d_pcm must be 2-byte aligned, d_diff_counts and d_first_diff 4-byte aligned");
+    return SELA_HIP_OK;
+}
+
+int verify_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
+    const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
+{
+    int dev = -1;
+    const uint32_t synth_priorities = decode_synth_priorities(max_frames, stream, &dev);
+    const hipError_t e = sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff,
+        d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "verify launch");
+    if (dev >= 0)
+        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
+            flights().note(dev, static_cast<hipStream_t>(stream));
+    return SELA_HIP_OK;
+}
+} // namespace
+
+size_t sela_hip_verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::verify_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_verify_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm,
+    uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = check_verify_args(n_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!d_frame_offsets || (n_frames && !d_frames))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_frames & 3)
+        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
+    const size_t need = sela::verify_workspace_bytes(n_frames, channels, stride);
+    if (need == SIZE_MAX || workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_verify_workspace_bytes()");
+    return verify_launch(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets, d_status, d_workspace,
+        stream);
+}
+
+int sela_hip_verify_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm,
+    uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc == SELA_HIP_OK)
+        rc = check_verify_args(max_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), verify_bytes = sela::verify_workspace_bytes(max_frames, channels, stride);
+    if (verify_bytes == SIZE_MAX || workspace_bytes < index_bytes + verify_bytes)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_verify_workspace_bytes()");
+    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "index launch");
+    return verify_launch(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets, d_status,
+        static_cast<unsigned char*>(d_workspace) + index_bytes, stream);
+}
+
+// Host pointers, synchronous: on the any-length route's leased context and stream (generic_verify), past the coalescer; the
+// calling thread's open streaming job lives in the fast path's context and is left alone.
+int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
+    uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!frame_offsets || (n_frames && (!frames || !pcm || !diff_counts || !first_diff)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    return sela::generic_verify(frames, frame_offsets, n_frames, channels, pcm, diff_counts, first_diff, lossy_frames, g_recurrence_form);
 }
 
 // ---- streaming jobs (host pointers) ----------------------------------------------------------------------------

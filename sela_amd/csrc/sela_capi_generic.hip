@@ -562,6 +562,85 @@ int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     return SELA_HIP_OK;
 }
 
+// sela_hip_verify: launch_verify_n_device on chunks of frames, on the calling thread's context and stream.  The
+// stride is the stream's largest samplesPerChannel (the host's walk), a chunk's PCM lies where sela_hip_decode writes it
+// (sample_offsets, relative to the chunk's first frame), and every chunk's status words are judged as
+// sela_hip_decode_n_status_error judges them: the first chunk that fails ends the call with that code.
+int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
+    uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form)
+{
+    if (lossy_frames)
+        *lossy_frames = 0;
+    if (device_ready() != SELA_HIP_OK)
+        return SELA_HIP_ENODEV;
+    hipError_t ctx_err = hipSuccess;
+    GenericContext* const ctx = g_lease.get(ctx_err);
+    if (!ctx)
+        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
+    Arena& g_arena = ctx->arena;
+    for (uint32_t f = 0; f < n_frames; f++)
+        if (frame_offsets[f + 1] < frame_offsets[f])
+            return report_error(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
+    const uint32_t largest = generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), nullptr);
+    if (n_frames && largest == 0)
+        return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    const uint32_t stride = std::max(largest, 1u);
+    const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2 + 2) + (size_t)channels * sizeof(GenericSubInfo) + 64;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const hipStream_t st = ctx->stream;
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    uint32_t lossy = 0;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
+        const uint64_t s0 = sample_offsets[f0], chunk_values = (sample_offsets[f0 + cf] - s0) * channels;
+        const size_t ws_bytes = verify_workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, "verify: the chunk is too large");
+        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + (size_t)chunk_values * 2 + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
+        hipError_t e = g_arena.reserve(need);
+        if (e != hipSuccess)
+            return report_hip_error(e, "verify: scratch");
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
+        int16_t* d_pcm = g_arena.take<int16_t>((size_t)chunk_values);
+        // what the host reads back, in one piece: status (4 x u32) | diff_counts [cf] | first_diff [cf]
+        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "verify: internal scratch estimate too small");
+        std::vector<uint64_t> local((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && chunk_values)
+            e = hipMemcpyAsync(d_pcm, pcm + s0 * channels, (size_t)chunk_values * 2, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_verify_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode,
+                recurrence_form, 0, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "verify");
+        const uint32_t route_status[4] = { tail[0], tail[1], 0, tail[3] };
+        const int rc = sela_hip_decode_n_status_error(route_status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
+        std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
+        lossy += tail[2];
+    }
+    if (lossy_frames)
+        *lossy_frames = lossy;
+    return SELA_HIP_OK;
+}
+
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out)
 {
     if (device_ready() != SELA_HIP_OK)

@@ -393,26 +393,26 @@ size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels)
 // (synth_steps, kVecShift): all of them when the whole launch is at most kLonelyWaves waves, else those of the last, partial
 // round of resident workgroups if that round is as small -- they start when the rounds before them are done.
 struct DecodeResidency {
-    std::atomic<uint32_t> frames[64][kDecMaxWaves + 1]; // [device][waves per workgroup]: workgroups the device holds at once, 0 = not asked yet
+    std::atomic<uint32_t> frames[kResidencySlots][64][kDecMaxWaves + 1]; // [kernel slot][device][waves per workgroup]: workgroups the device holds at once, 0 = not asked yet
 };
-inline uint32_t resident_frames(const void* kernel, int n_waves, size_t lds)
+uint32_t resident_frames(const void* kernel, int n_waves, size_t lds, int slot)
 {
     static DecodeResidency cache;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || slot < 0 || slot >= kResidencySlots || n_waves < 0 || n_waves > kDecMaxWaves)
         return 0;
-    uint32_t have = cache.frames[dev][n_waves].load(std::memory_order_relaxed);
+    uint32_t have = cache.frames[slot][dev][n_waves].load(std::memory_order_relaxed);
     if (have == 0) {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, n_waves * 64, lds) != hipSuccess
             || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
             return 0;
         have = (uint32_t)per_cu * (uint32_t)cus;
-        cache.frames[dev][n_waves].store(have, std::memory_order_relaxed);
+        cache.frames[slot][dev][n_waves].store(have, std::memory_order_relaxed);
     }
     return have;
 }
-inline uint32_t vec_shift_from_for(uint32_t n_frames, int n_waves, uint32_t resident)
+uint32_t vec_shift_from_for(uint32_t n_frames, int n_waves, uint32_t resident)
 {
     if ((uint64_t)n_frames * (uint32_t)n_waves <= kLonelyWaves)
         return 0;

@@ -302,5 +302,14 @@ __device__ inline void step_up(const double* kd, int64_t* a, int order, int lane
     step_up_regs(k_lo, k_hi, a, order, lane, flags);
 }
 
+// ---- launch helpers of the 2048-sample decoder (sela_decode.hip), shared with sela_verify.hip -------------------------------
+// resident_frames: the workgroups of `kernel` the current device holds at once (0: the runtime would not say), asked once per
+// (kernel slot, device, waves per workgroup) -- the occupancy query is per kernel, so every kernel has a slot of its own.
+// vec_shift_from_for: which workgroups of a launch run their recurrence in the lonely-wave form (k_decode_frames).
+constexpr int kResidencyDecode = 0, kResidencyVerify = 1, kResidencySlots = 2;
+uint32_t resident_frames(const void* kernel, int n_waves, size_t lds, int slot = kResidencyDecode);
+uint32_t vec_shift_from_for(uint32_t n_frames, int n_waves, uint32_t resident);
+int decode_waves(uint32_t channels);
+
 } // namespace sela
 #endif // SELA_DEVICE_H_

@@ -46,6 +46,22 @@ hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     hipStream_t stream);
 hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_verify_device / sela_hip_verify_payload_device: launch_decode_n_device's shape with the decode's
+// stores turned into a compare against d_pcm.  Up to kVerifyFusedChannels channels the 2048-sample route is one kernel
+// (k_verify_frames, sela_verify.hip); every other route decodes into the workspace and k_verify_compare takes it from there.
+constexpr uint32_t kVerifyFusedChannels = 8;    // = kDecMaxWaves (sela_decode_core.inc)
+constexpr uint32_t kVerifySliceValues = 16384;  // interleaved int16 values one workgroup of k_verify_compare takes
+uint32_t verify_slices(uint32_t channels, uint32_t stride);
+hipError_t launch_verify_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* d_pcm,
+    uint32_t* d_diff_counts, uint32_t* d_first_diff, uint32_t* d_status, void* d_workspace, hipStream_t stream, int recurrence_form, uint32_t synth_priorities,
+    const uint32_t* d_n_found);
+hipError_t launch_verify_compare(const int16_t* d_decoded, const int16_t* d_pcm, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels,
+    uint32_t stride, const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, void* d_parts /* [max_frames][verify_slices()] x 8 bytes */,
+    uint32_t* d_diff_counts, uint32_t* d_first_diff, uint32_t* d_status, hipStream_t stream);
+size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);

@@ -1762,6 +1762,31 @@ size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t
     return (size_t)decode_n_layout(max_frames, channels, stride).bytes;
 }
 
+// Route 2 of the int16 calls on device pointers (launch_decode_n_device, launch_verify_n_device): k_decode_subframes32 and
+// k_generic_decode as in launch_decode_i32_device, gated by the any-length route's count (counters[6]), then the int16 writer
+// into d_pcm_out at the sample offsets.  (max_frames * channels is not 0.)
+static hipError_t launch_any_length_n(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    int32_t* d_dec, GenericSubInfo* d_info, int32_t* d_all, uint32_t* d_counters, const uint64_t* d_so, int16_t* d_pcm_out, uint32_t* d_status, int mode,
+    hipStream_t stream)
+{
+    const uint32_t subs = max_frames * channels;
+    const uint32_t* const n_any = d_counters + 6;
+    if (mode != 0) {
+        const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, n_any);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
+        n_any, mode != 0 ? d_counters + 2 : nullptr);
+    if (channels <= kInterleaveChannels)
+        hipLaunchKernelGGL(k_interleave16, dim3(max_frames, (stride + kInterleaveSlice - 1) / kInterleaveSlice), dim3(kInterleaveThreads), 0, stream, d_dec, d_info,
+            max_frames, channels, stride, d_so, d_pcm_out, d_status, n_any);
+    else
+        hipLaunchKernelGGL(k_generic_combine<true>, dim3(max_frames, (stride + kCombineSlice - 1) / kCombineSlice), dim3(kCombineThreads), 0, stream, d_dec, d_info,
+            max_frames, channels, stride, d_all, nullptr, d_so, d_pcm_out, d_status, n_any);
+    return hipGetLastError();
+}
+
 // sela_hip_decode on one chunk with its decisions taken on the device: the sample index, k_route_n, the 2048-sample decoder
 // (k_decode_frames / _wide, sela_decode.hip) on its count, the any-length route on its own (k_decode_subframes32 and
 // k_generic_decode as in launch_decode_i32_device) and the int16 writer.  mode as sela_hip_debug_standard_first (the any-length
@@ -1779,7 +1804,6 @@ hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : reinterpret_cast<uint64_t*>(base + l.offsets);
     int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.all);
     const uint32_t* const n_fast = d_counters + 5;
-    const uint32_t* const n_any = d_counters + 6;
     launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, d_counters, d_tiles, stream);
     hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, d_counters);
     const uint32_t subs = max_frames * channels;
@@ -1793,20 +1817,85 @@ hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     if (e != hipSuccess)
         return e;
     // route 2
-    if (mode != 0) {
-        e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, n_any);
-        if (e != hipSuccess)
-            return e;
-    }
-    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
-        n_any, mode != 0 ? d_counters + 2 : nullptr);
-    if (channels <= kInterleaveChannels)
-        hipLaunchKernelGGL(k_interleave16, dim3(max_frames, (stride + kInterleaveSlice - 1) / kInterleaveSlice), dim3(kInterleaveThreads), 0, stream, d_dec, d_info,
-            max_frames, channels, stride, d_so, d_pcm_out, d_status, n_any);
+    return launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, d_dec, d_info, d_all, d_counters, d_so, d_pcm_out, d_status, mode, stream);
+}
+
+// ---- verification on the device (sela_hip_verify_device) ----------------------------------------------------
+// Workspace: launch_decode_n_device's | the PCM of the routes that are not fused (as sela_hip_decode_n_device writes it) |
+// k_verify_compare's words per (frame, slice); every piece 256-byte aligned, the base too.
+struct VerifyLayout {
+    DecodeNLayout n;
+    uint64_t pcm, parts, bytes;
+};
+static VerifyLayout verify_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    VerifyLayout l;
+    l.n = decode_n_layout(max_frames, channels, stride);
+    l.pcm = l.n.bytes - 256;
+    l.parts = l.pcm + up((uint64_t)max_frames * channels * stride * sizeof(int16_t));
+    l.bytes = l.parts + up(std::max<uint64_t>((uint64_t)max_frames * verify_slices(channels, stride), 1) * 8) + 256; // (+ the base's alignment)
+    return l;
+}
+
+size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    // (frames x channels first: the product of all three can wrap 64 bits; the launch calls keep it below 2^31)
+    if ((uint64_t)max_frames * channels >= (1ull << 31) || (uint64_t)max_frames * channels * stride >= (1ull << 60))
+        return SIZE_MAX;
+    return (size_t)verify_layout(max_frames, channels, stride).bytes;
+}
+
+// launch_decode_n_device with a compare in place of the PCM: the sample index, k_route_n, then
+//   route 1, up to kVerifyFusedChannels channels: k_verify_frames on the fast decoder's count -- nothing decoded reaches memory;
+//   route 1 above (k_decode_frames_wide) and route 2 (the any-length kernels and the int16 writer): decoded into the workspace as
+//   sela_hip_decode_n_device decodes into d_pcm_out, then k_verify_compare / k_verify_combine on the count of the route that ran.
+// status[2], the largest samplesPerChannel while k_route_n reads it, is zeroed behind it by k_verify_begin (one thread): the
+// kernels count the frames with a difference there.
+__global__ __launch_bounds__(64) void k_verify_begin(uint32_t* __restrict__ status)
+{
+    if (threadIdx.x == 0)
+        status[2] = 0;
+}
+
+hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream)
+{
+    const VerifyLayout l = verify_layout(max_frames, channels, stride);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.n.dec);
+    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.n.info);
+    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.n.counters);
+    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.n.tiles);
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : reinterpret_cast<uint64_t*>(base + l.n.offsets);
+    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.n.all);
+    int16_t* const d_back = reinterpret_cast<int16_t*>(base + l.pcm);
+    const uint32_t* const n_fast = d_counters + 5;
+    const uint32_t* const n_any = d_counters + 6;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, d_counters, d_tiles, stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, d_counters);
+    hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, stream, d_status);
+    hipError_t e = hipGetLastError();
+    const uint32_t subs = max_frames * channels;
+    if (e != hipSuccess || subs == 0)
+        return e;
+    // route 1 (its workspace: d_dec, as in launch_decode_n_device)
+    const bool fused = channels <= kVerifyFusedChannels;
+    if (fused)
+        e = launch_verify_frames(d_frames, d_frame_offsets, max_frames, channels, d_pcm, d_diff_counts, d_first_diff, d_status, d_dec, stream, recurrence_form,
+            synth_priorities, n_fast);
     else
-        hipLaunchKernelGGL(k_generic_combine<true>, dim3(max_frames, (stride + kCombineSlice - 1) / kCombineSlice), dim3(kCombineThreads), 0, stream, d_dec, d_info,
-            max_frames, channels, stride, d_all, nullptr, d_so, d_pcm_out, d_status, n_any);
-    return hipGetLastError();
+        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_back, d_status, d_dec, stream, nullptr, nullptr, nullptr, recurrence_form,
+            synth_priorities, n_fast, false);
+    if (e != hipSuccess)
+        return e;
+    // route 2
+    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, d_dec, d_info, d_all, d_counters, d_so, d_back, d_status, mode, stream);
+    if (e != hipSuccess)
+        return e;
+    return launch_verify_compare(d_back, d_pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, base + l.parts, d_diff_counts, d_first_diff,
+        d_status, stream);
 }
 
 // Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total; every
