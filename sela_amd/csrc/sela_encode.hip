@@ -147,6 +147,9 @@ __device__ __forceinline__ uint64_t rice_shifted_sum(const uint32_t (&u)[V], uin
 #pragma unroll
         for (int t = 0; t < V; t++)
             part += u[t] >> k;
+        // (the sum is kept from the compiler's sight: it merged this loop with the 64-bit one below -- the low words agree --
+        // and every lane paid a 64-bit add and a copy per value for a high word that is zero)
+        asm volatile("" : "+v"(part));
         lane_part = part;
         return wave_sum_small(part);
     }
@@ -220,6 +223,27 @@ __device__ __forceinline__ double scale_sample(int32_t s)
     const double q0 = x * r;
     const double e = __builtin_fma(-SELA_SAMPLE_SCALE, q0, x);
     return __builtin_fma(e, r, q0);
+}
+
+// Signal `sig` of stereo PCM from the loaded words (left in the low half, right in the high half): 0: l, 1: r, 2: l - r
+// (src/frame/frame_encoder.cpp:22-24).  sig is the same for the whole wave, so the form is chosen by ONE branch for all the
+// words -- a bit-field extract, a shift, or a subtraction that sign-extends both halves itself -- not per sample by selects.
+template <int kN>
+__device__ __forceinline__ void unpack_stereo(uint32_t sig, const uint32_t (&w)[kN], int32_t (&raw)[kN])
+{
+    if (sig == 0) {
+#pragma unroll
+        for (int i = 0; i < kN; i++)
+            raw[i] = (int32_t)(int16_t)(w[i] & 0xFFFFu);
+    } else if (sig == 1) {
+#pragma unroll
+        for (int i = 0; i < kN; i++)
+            raw[i] = (int32_t)w[i] >> 16;
+    } else {
+#pragma unroll
+        for (int i = 0; i < kN; i++)
+            raw[i] = (int32_t)(int16_t)(w[i] & 0xFFFFu) - ((int32_t)w[i] >> 16);
+    }
 }
 
 // ---- mean chain operand fetch (see k_encode_blocks): E[m..m+7] and O[m..m+7] by broadcast reads ------
@@ -347,22 +371,41 @@ __device__ __forceinline__ void ac_steps_tail(const AcFetch& f, double& A, doubl
 // integers is EXACT while every partial sum stays below 2^53 -- which the caller has checked for the block, for the whole
 // coefficients (one pass) or for their halves (two passes).  coef[j] = the coefficient (or its half) as a double, the window
 // holds the samples as doubles, acc the exact sum.
+//
+// Addresses: the sample buffer keeps index i at word i + i / 32, and tap j reads index e = kPadS + 32 lane - j.  kPadS and j0
+// are multiples of 32, so over the 32 taps of a group e runs down through ONE aligned run of 32 indices, whose pad term is the
+// same: the group's words lie side by side, and the caller passes fir_group_window() -- the lowest of them, tap j0 + 32's --
+// so that every tap's word is a ds_read_b32 at a constant offset (which is unsigned: hence the lowest).  The coefficients of
+// the group likewise, from fir_group_coefs(): a_f + j0 in a VECTOR register.  Left as the uniform value it is, the address
+// was put together in scalar registers and copied to a vector register for every tap.
+// The coefficient itself stays in the vector register pair it was read into (every lane reads the same word: it used to be
+// moved to a scalar pair, two v_readfirstlane per tap).
 template <int JJ>
-__device__ __forceinline__ void fir_taps_f64(int j0, int order, int lane, const int32_t* sT, const double* a_f,
+__device__ __forceinline__ void fir_taps_f64(int j0, int order, const int32_t* s_grp, const double* a_grp,
     double (&win)[kPerLane], double (&acc)[kPerLane])
 {
     const int j = j0 + JJ + 1;
     if (j > order)
         return;
-    const double aj = read_first_lane(a_f[j]);
-    const int e = kPadS + 32 * lane - j;
-    win[(32 - JJ - 1) & 31] = (double)sT[e + (e >> 5)];
+    const double aj = a_grp[JJ + 1];
+    win[(32 - JJ - 1) & 31] = (double)s_grp[31 - JJ];
 #pragma unroll
     for (int t = 0; t < kPerLane; t++)
         acc[t] = __builtin_fma(aj, win[(t - JJ - 1) & 31], acc[t]); // s[32 lane + t - j]
     __builtin_amdgcn_sched_barrier(0); // (taps are not interleaved: the window and the sums already fill the register file)
     if constexpr (JJ < 31)
-        fir_taps_f64<JJ + 1>(j0, order, lane, sT, a_f, win, acc);
+        fir_taps_f64<JJ + 1>(j0, order, s_grp, a_grp, win, acc);
+}
+__device__ __forceinline__ const int32_t* fir_group_window(const int32_t* sT, int lane, int j0)
+{
+    const int e = kPadS + 32 * lane - j0 - 32; // tap j0 + 32's index: a multiple of 32
+    return sT + e + (e >> 5);
+}
+__device__ __forceinline__ const double* fir_group_coefs(const double* a_f, int j0)
+{
+    uint32_t at = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) double*)(a_f + j0);
+    asm volatile("" : "+v"(at));
+    return (const double*)(const __attribute__((address_space(3))) double*)(uintptr_t)at;
 }
 
 // The predictions for a predictor the FP64 taps cannot carry exactly (sela_encode_tail.inc): one multiply-add per (sample, tap) in
@@ -1137,18 +1180,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         const int16_t* fp = pcm_after_wait(pcm) + (size_t)frame * kBlock * channels;
         if (channels == 2) {
             const uint32_t* fp2 = reinterpret_cast<const uint32_t*>(fp);
+            uint32_t w[kPerLane];
 #pragma unroll
             for (int t = 0; t < kPerLane; t++) {
                 // (behind the stagers: past the L2 like await_frame's check -- an acquire fence here instead, one per block,
                 // cost the 3,875-frame call 0.24 ms)
-                const uint32_t w = (kFused && fa.pcm_ready) ? load_through(fp2 + lane + 64 * t) : fp2[lane + 64 * t];
-                const int32_t l = (int16_t)(w & 0xFFFFu), r = (int16_t)(w >> 16);
-                s[t] = sig == 0 ? l : (sig == 1 ? r : l - r); // src/frame/frame_encoder.cpp:22-24
+                w[t] = (kFused && fa.pcm_ready) ? load_through(fp2 + lane + 64 * t) : fp2[lane + 64 * t];
             }
+            unpack_stereo<kPerLane>(sig, w, s);
         } else {
+            const int16_t* const ps = fp + (size_t)lane * channels + sig; // (one 64-bit address; the strides are the wave's)
 #pragma unroll
             for (int t = 0; t < kPerLane; t++)
-                s[t] = fp[(size_t)(lane + 64 * t) * channels + sig];
+                s[t] = ps[(uint32_t)(64 * t) * channels];
         }
     }
 
@@ -1547,17 +1591,22 @@ __device__ __forceinline__ void team_load_raw(const int16_t* __restrict__ fp, ui
             for (int u = 0; u < kPer; u++)
                 w[u] = pw[u * kStep];
         }
-        const uint32_t first_shift = sig == 1 ? 16u : 0u;     // signal 0: l, 1: r, 2: l - r  as  a - (b & mask)
-        const uint32_t second_mask = sig == 2 ? 0xFFFFFFFFu : 0u;
+        if constexpr (kStep == 1) { // (teams of 8 keep the selects, signal 0: l, 1: r, 2: l - r  as  a - (b & mask): the branches cost k_encode_teams<., 8> an eleventh spilled register)
+            const uint32_t first_shift = sig == 1 ? 16u : 0u;
+            const uint32_t second_mask = sig == 2 ? 0xFFFFFFFFu : 0u;
 #pragma unroll
-        for (int i = 0; i < kPer; i++) {
-            const int32_t a = (int32_t)(w[i] << (16 - first_shift)) >> 16, b = ((int32_t)w[i] >> 16) & (int32_t)second_mask;
-            raw[i] = a - b;
+            for (int i = 0; i < kPer; i++) {
+                const int32_t a = (int32_t)(w[i] << (16 - first_shift)) >> 16, b = ((int32_t)w[i] >> 16) & (int32_t)second_mask;
+                raw[i] = a - b;
+            }
+        } else {
+            unpack_stereo<kPer>(sig, w, raw);
         }
     } else {
+        const int16_t* const ps = fp + (size_t)first * channels + sig; // (one 64-bit address; the strides are the wave's)
 #pragma unroll
         for (int i = 0; i < kPer; i++)
-            raw[i] = fp[(size_t)(first + i * kStep) * channels + sig];
+            raw[i] = ps[(uint32_t)(i * kStep) * channels];
     }
 }
 
@@ -1572,22 +1621,17 @@ __device__ __forceinline__ void team_fetch(const int16_t* __restrict__ fp, uint3
         for (int u = 0; u < kPer; u++)
             w[u] = pw[u * kStep];
     } else {
+        const int16_t* const ps = fp + (size_t)first * channels + sig; // (as team_load_raw)
 #pragma unroll
         for (int i = 0; i < kPer; i++)
-            w[i] = (uint32_t)(int32_t)fp[(size_t)(first + i * kStep) * channels + sig];
+            w[i] = (uint32_t)(int32_t)ps[(uint32_t)(i * kStep) * channels];
     }
 }
 template <int kPer, bool kStereo>
 __device__ __forceinline__ void team_unpack(uint32_t sig, const uint32_t (&w)[kPer], int32_t (&raw)[kPer])
 {
     if constexpr (kStereo) {
-        const uint32_t first_shift = sig == 1 ? 16u : 0u; // as team_load_raw
-        const uint32_t second_mask = sig == 2 ? 0xFFFFFFFFu : 0u;
-#pragma unroll
-        for (int i = 0; i < kPer; i++) {
-            const int32_t a = (int32_t)(w[i] << (16 - first_shift)) >> 16, b = ((int32_t)w[i] >> 16) & (int32_t)second_mask;
-            raw[i] = a - b;
-        }
+        unpack_stereo<kPer>(sig, w, raw); // as team_load_raw
     } else {
 #pragma unroll
         for (int i = 0; i < kPer; i++)
@@ -2076,16 +2120,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             const int16_t* fb = pcm + (size_t)frame * kBlock * channels;
             if (channels == 2) {
                 const uint32_t* fp2 = reinterpret_cast<const uint32_t*>(fb);
-#pragma unroll
-                for (int t = 0; t < kPerLane; t++) {
-                    const uint32_t w = fp2[lane + 64 * t];
-                    const int32_t l = (int16_t)(w & 0xFFFFu), r = (int16_t)(w >> 16);
-                    s[t] = sig == 0 ? l : (sig == 1 ? r : l - r); // src/frame/frame_encoder.cpp:22-24
-                }
-            } else {
+                uint32_t w[kPerLane];
 #pragma unroll
                 for (int t = 0; t < kPerLane; t++)
-                    s[t] = fb[(size_t)(lane + 64 * t) * channels + sig];
+                    w[t] = fp2[lane + 64 * t];
+                unpack_stereo<kPerLane>(sig, w, s);
+            } else {
+                const int16_t* const ps = fb + (size_t)lane * channels + sig; // (one 64-bit address; the strides are the wave's)
+#pragma unroll
+                for (int t = 0; t < kPerLane; t++)
+                    s[t] = ps[(uint32_t)(64 * t) * channels];
             }
         }
         uint32_t flags = 0;

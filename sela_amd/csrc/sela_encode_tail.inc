@@ -99,10 +99,10 @@
     for (int m = lane; m < kPadS; m += 64)
         sT[m + (m >> 5)] = 0;
     int32_t s_max = 0, s_min = 0; // (of this lane's samples: the FP64 form of the taps below needs the block's largest magnitude)
+    int32_t* const put_s = sT + (kPadS + lane) + ((kPadS + lane) >> 5); // index i = kPadS + lane + 64 t sits at i + i / 32: 66 words on per t
 #pragma unroll
     for (int t = 0; t < kPerLane; t++) {
-        const int i = kPadS + lane + 64 * t;
-        sT[i + (i >> 5)] = s[t];
+        put_s[66 * t] = s[t];
         s_max = max(s_max, s[t]);
         s_min = min(s_min, s[t]);
     }
@@ -154,8 +154,13 @@
             uint32_t* const plain_pred = slots + (size_t)block_id * kSlotWords; // 2048 words of the block's own slot
             fir_plain(order, lane, sT, sm->a, plain_pred);
 #pragma unroll
-            for (int t = 0; t < kPerLane; t++)
+            for (int t = 0; t < kPerLane; t++) {
                 pred_u[t] = plain_pred[t * 64 + lane];
+                // zig-zag would not fit 32 bits: only this form can get there -- the FP64 forms are taken with samples within
+                // 2^16 and leave predictions (floor(sum / 2^35), |sum| < 2^53) within 2^18
+                const int32_t rt = (int32_t)((uint32_t)mine_s[t] - pred_u[t]);
+                wide |= (rt >= (1 << 30)) || (rt < -(1 << 30));
+            }
         } else {
             // the coefficients as doubles: one pass -- (double)a[j] in place of a[j] (|a[j]| < 2^39: 2^20 x its high part + its
             // low 20 bits, both exact); two passes -- the low 20 bits in place, the high part (< 2^35: 2^16 x its high part +
@@ -176,16 +181,18 @@
             }
             wave_sync();
             double win_f[kPerLane], acc_f[kPerLane];
+            double half = (double)((int64_t)1 << (SELA_Q_SHIFT - 1));
+            asm volatile("" : "+s"(half)); // (in a scalar register pair: one 64-bit move per sum; as a literal it took two 32-bit ones)
 #pragma unroll
             for (int t = 0; t < kPerLane; t++)
-                acc_f[t] = (double)((int64_t)1 << (SELA_Q_SHIFT - 1));
+                acc_f[t] = half;
             if (single) { // (its own copy of the unrolled taps: with one loop over one or two passes k_encode_blocks spilled 40 registers)
 #pragma unroll
                 for (int t = 0; t < kPerLane; t++)
                     win_f[t] = (double)mine_s[t];
 #pragma unroll 1
                 for (int j0 = 0; j0 < order; j0 += 32)
-                    fir_taps_f64<0>(j0, order, lane, sT, c_first, win_f, acc_f);
+                    fir_taps_f64<0>(j0, order, fir_group_window(sT, lane, j0), fir_group_coefs(c_first, j0), win_f, acc_f);
 #pragma unroll
                 for (int t = 0; t < kPerLane; t++) // floor(sum / 2^35): |.| < 2^18
                     pred_u[t] = (uint32_t)(int32_t)__builtin_floor(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT)));
@@ -198,7 +205,7 @@
                         win_f[t] = (double)mine_s[t];
 #pragma unroll 1
                     for (int j0 = 0; j0 < order; j0 += 32)
-                        fir_taps_f64<0>(j0, order, lane, sT, coef, win_f, acc_f);
+                        fir_taps_f64<0>(j0, order, fir_group_window(sT, lane, j0), fir_group_coefs(coef, j0), win_f, acc_f);
                     const double down = pass ? 1.0 / (double)((int64_t)1 << (SELA_Q_SHIFT - 20)) : 1.0 / 1048576.0;
 #pragma unroll
                     for (int t = 0; t < kPerLane; t++) // floor(L / 2^20), then floor(sum / 2^15)
@@ -213,7 +220,6 @@
         for (int t = 0; t < kPerLane; t++) {
             const int32_t rt = (int32_t)((uint32_t)mine_s[t] - pred_u[t]);
             ru[t] = zigzag32(rt);
-            wide |= (rt >= (1 << 30)) || (rt < -(1 << 30)); // zig-zag would not fit 32 bits
 #ifdef SELA_TAIL_TRACE_RESIDUES
             if (kTrace && (SELA_TAIL_TRACE_RESIDUES)) // (the LPC stage on its own, sela_hip_lpc_encode: the trace build also leaves the residues)
                 (SELA_TAIL_TRACE_RESIDUES)[(size_t)block_id * kBlock + 32 * lane + t] = rt;
