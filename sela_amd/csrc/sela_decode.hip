@@ -230,7 +230,10 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
             else if ((info & 0xFF) == 1) {
                 const uint32_t pinfo = sub_info[(info >> 8) & 0xFF];
                 if (pinfo == 0xFFFFFFFFu || (pinfo & 0xFF) != 0)
-                    flags |= SELA_HIP_FLAG_BAD_FRAME; // a parent that is itself dependent is outside what the reference defines
+                    // a parent that is itself dependent is refused here by policy.  (The reference resolves its type-1 subframes in
+                    // stream order: a chain in that order is defined there, and the 32-bit decoders decode it; against that order it
+                    // subtracts from a vector that is still empty.)
+                    flags |= SELA_HIP_FLAG_BAD_FRAME;
             }
         }
     }
@@ -352,7 +355,9 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
         } else if ((info & 0xFF) == 1) {
             const uint32_t parent = (info >> 8) & 0xFF;
             const uint32_t pinfo = sub_info[parent];
-            // (a parent that is itself difference-coded is outside what the reference defines: flagged, and its raw samples taken)
+            // (a parent that is itself difference-coded is refused here by policy: flagged, and its raw samples taken.  The
+            // reference defines such a chain where it runs in stream order -- the 32-bit decoders decode it -- and reads an empty
+            // vector where it runs against it)
             if (threadIdx.x == 0 && (pinfo == kNoSubframe || (pinfo & 0xFF) != 0))
                 flags |= SELA_HIP_FLAG_BAD_FRAME;
             for (uint32_t i = threadIdx.x; i < (uint32_t)kBlock; i += blockDim.x) {

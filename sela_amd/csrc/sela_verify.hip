@@ -199,7 +199,9 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
             else if ((info & 0xFF) == 1) {
                 const uint32_t pinfo = sub_info[(info >> 8) & 0xFF];
                 if (pinfo == 0xFFFFFFFFu || (pinfo & 0xFF) != 0)
-                    flags |= SELA_HIP_FLAG_BAD_FRAME; // a parent that is itself dependent is outside what the reference defines
+                    // a parent that is itself dependent is refused by policy, as k_decode_frames refuses it.  (The reference defines a
+                    // chain in stream order, and the 32-bit decoders decode it; against that order it reads an empty vector.)
+                    flags |= SELA_HIP_FLAG_BAD_FRAME;
             }
         }
     }
