@@ -385,6 +385,60 @@ int sela_hip_verify_payload_device(const uint8_t* d_payload, size_t payload_byte
 int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm,
     uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
 
+/* ---- verification of 32-bit and ragged streams: a stream against its int32 samples ------------------------
+ * The calls above on the whole domain of sela_hip_decode_i32_device: samples of up to 32 bits, planar frames, channels of
+ * different lengths, every subframe layout that call takes.  What sela_hip_decode_i32_device does, with a compare where it
+ * stores: for every layout this library's encoders write (each channel named by one subframe, a difference subframe's parent an
+ * independent one at least as long) no decoded sample is written to the caller's memory or moved by channel at all.
+ *   d_samples      int32 [n_frames][channels][stride], the layout sela_hip_decode_i32_device writes (channel c of frame f at
+ *                  ((f * channels) + c) * stride; with stride == samples_per_channel also what sela_hip_encode_i32_device
+ *                  reads).  Read only.
+ *   d_lengths      [n_frames * channels], the original's length of every channel, or NULL: every channel is stride long.  No
+ *                  sample at or beyond stride is read; a length above stride counts as stride.
+ *   With m the count sela_hip_decode_i32_device would report for (f, c) and L the original's length:
+ *   d_diff_counts  [n_frames]: the sum over the channels of #{ i < min(m, L) : decoded[i] != original[i] } + |m - L| (a sample
+ *                  that is missing or extra is a difference).
+ *   d_first_diff   [n_frames]: the smallest c * stride + i over the channels, i the first differing index of channel c -- where
+ *                  no value differs but the lengths do, min(m, L) -- or 0xFFFFFFFF when nothing differs.
+ *   d_status uint32[4], written by the call (needs no initialisation): [0] and [1] exactly as sela_hip_decode_i32_device leaves
+ *                  them for the same frames (SELA_HIP_FLAG_STRIDE included: nothing is compared then); [2] the number of frames
+ *                  whose count is not 0; [3] zero.
+ *   sela_hip_decode_status_error() applies unchanged; where it gives non-zero the two arrays are not defined.  n_frames = 0
+ *   writes zero status words.
+ * Asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of device data, so a stream being captured
+ * into a HIP graph may take either device call.  Apart from the outputs named here and the workspace nothing is written; the two
+ * arrays need no initialisation; the results are deterministic.  sela_hip_debug_standard_first routes the decode kernels as it
+ * does for the decode call.
+ * d_workspace: sela_hip_verify_i32_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at a time may use it.  With up(b) = b rounded up to
+ * a multiple of 256 it is
+ *     sela_hip_decode_i32_workspace_bytes(max_frames, channels, stride)      the subframes as decoded, their records, the index
+ *   + up(max_frames * channels * stride * 4)                                 the samples by channel, for frames of any other layout
+ *   + up(max_frames * channels * 4)                                          ... and their counts
+ *   + up(max(max_frames, 1) * 4)                                             a mark per frame: which way it went
+ *   + up(max(max_frames * ceil(stride / 4096), 1) * 8)                       two words per (frame, slice of 4096 samples)
+ *   + 256                                                                    the two control words
+ * and SIZE_MAX where sela_hip_decode_i32_workspace_bytes() is, or where max_frames * channels reaches 2^31.
+ * Errors and alignment as sela_hip_decode_i32_device; also SELA_HIP_EINVAL for a null d_samples, d_diff_counts or d_first_diff
+ * (n_frames > 0) or one of them, or d_lengths, not 4-byte aligned.  Nothing is enqueued then; an argument error is found before a
+ * device is asked for. */
+size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    const int32_t* d_samples /* [n_frames][channels][stride] */, const uint32_t* d_lengths /* [n_frames * channels] or NULL */,
+    uint32_t* d_diff_counts /* [n_frames] */, uint32_t* d_first_diff /* [n_frames] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */,
+    uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their entries in the two arrays are not written). */
+int sela_hip_verify_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames: returns what sela_hip_decode_i32 returns for the stream and this stride (0: the
+ * arrays are valid).  *lossy_frames (or NULL): the frames with a difference.  Runs on the calling thread's any-length context and
+ * its own stream, past the coalescer; an open streaming job of the thread is left alone. */
+int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    const int32_t* samples /* [n_frames][channels][stride] */, const uint32_t* lengths /* [n_frames * channels] or NULL */,
+    uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

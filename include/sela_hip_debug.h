@@ -76,6 +76,12 @@ int sela_hip_debug_contexts_created(void);
 void sela_hip_debug_coalesced(int kind, long long* batches, long long* retried);
 /* The dynamic LDS, in bytes, that a launch of k_verify_frames asks for with this many channels (1 .. 8; else 0). */
 size_t sela_hip_debug_verify_lds_bytes(uint32_t channels);
+/* Debug hook (tests): how many frames of the LAST sela_hip_verify_i32_device call that used this workspace (same max_frames,
+ * channels and stride as that call) were not of a direct layout and went through the fallback (k_generic_combine<false> and
+ * k_verify32_rest) -- 0: k_verify32_direct compared every frame from the subframes as decoded.  For the payload
+ * call pass the workspace behind its index part (d_workspace + sela_hip_index_workspace_bytes()).  Synchronises the device.
+ * -1 on an error. */
+long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);
 
 /* Debug hook (tests; process-wide): while on, a device-pointer encode with a d_trace pointer runs the PRODUCT kernels plus a few
  * instructions (their kMode 3 instantiations, not the trace builds) and leaves, instead of traces, two 64-bit words per block at

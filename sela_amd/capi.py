@@ -36,6 +36,7 @@ EXPORTS = [
     "sela_hip_decode_n_workspace_bytes", "sela_hip_decode_n_device", "sela_hip_decode_payload_n_device", "sela_hip_decode_n_status_error",
     "sela_hip_encode_i32_workspace_bytes", "sela_hip_encode_i32_device", "sela_hip_encode_n_device", "sela_hip_encode_status_error",
     "sela_hip_verify_workspace_bytes", "sela_hip_verify_device", "sela_hip_verify_payload_device", "sela_hip_verify",
+    "sela_hip_verify_i32_workspace_bytes", "sela_hip_verify_i32_device", "sela_hip_verify_payload_i32_device", "sela_hip_verify_i32",
 ]
 
 
@@ -43,6 +44,7 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     "sela_hip_debug_phase_buffer", "sela_hip_debug_force_plain_fir", "sela_hip_debug_mean_workers", "sela_hip_debug_encode_teams", "sela_hip_debug_encode_kernel", "sela_hip_debug_encode_fused", "sela_hip_debug_priorities", "sela_hip_debug_priorities_adaptive", "sela_hip_debug_launches_alone", "sela_hip_debug_block_forms", "sela_hip_debug_encode_hashes", "sela_hip_debug_standard_first", "sela_hip_debug_standard_chunks", "sela_hip_debug_segment_subframes", "sela_hip_debug_generic_wrap_taps", "sela_hip_debug_encode_split", "sela_hip_debug_launches_split", "sela_hip_debug_keep_both_candidates", "sela_hip_debug_stage_wait",
     "sela_hip_debug_reissued_feeds", "sela_hip_debug_contexts_created", "sela_hip_debug_decode_recurrence", "sela_hip_debug_coalesced", "sela_hip_debug_verify_lds_bytes",
+    "sela_hip_debug_verify_i32_fallback_frames",
 ]
 
 
@@ -136,6 +138,14 @@ def lib() -> C.CDLL:
     L.sela_hip_verify_payload_device.restype = C.c_int
     L.sela_hip_verify.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.sela_hip_verify.restype = C.c_int
+    L.sela_hip_verify_i32_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_verify_i32_workspace_bytes.restype = sz
+    L.sela_hip_verify_i32_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_verify_i32_device.restype = C.c_int
+    L.sela_hip_verify_payload_i32_device.argtypes = [vp, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_verify_payload_i32_device.restype = C.c_int
+    L.sela_hip_verify_i32.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.sela_hip_verify_i32.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]
@@ -213,6 +223,8 @@ def lib() -> C.CDLL:
     L.sela_hip_debug_coalesced.restype = None
     L.sela_hip_debug_verify_lds_bytes.argtypes = [u32]
     L.sela_hip_debug_verify_lds_bytes.restype = sz
+    L.sela_hip_debug_verify_i32_fallback_frames.argtypes = [vp, u32, u32, u32]
+    L.sela_hip_debug_verify_i32_fallback_frames.restype = C.c_longlong
     L.sela_hip_host_alloc.argtypes = [sz]
     L.sela_hip_host_alloc.restype = C.c_void_p
     L.sela_hip_host_free.argtypes = [C.c_void_p]

@@ -375,6 +375,111 @@ def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.
     return counts, first, int(lossy.value)
 
 
+class Verifier32:
+    """sela_hip_verify_i32_device: a stream held against the int32 samples it was made from, frame by frame, on the device --
+    the whole domain of Decoder32 (samples of up to 32 bits, planar frames, channels of different lengths).  Owns its outputs and
+    its workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  For
+    the layouts the encoders write no decoded sample is stored anywhere beyond the subframes as decoded."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        with torch.cuda.device(self.device):
+            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_verify_i32_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def _inputs_ok(self, samples, lengths, n_frames: int) -> bool:
+        torch = self.torch
+        ok = samples.dtype == torch.int32 and samples.is_cuda and samples.is_contiguous() and samples.numel() >= n_frames * self.channels * self.stride
+        if lengths is not None:
+            ok = ok and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n_frames * self.channels
+        return ok
+
+    def verify(self, frames, offsets, n_frames: int, samples, lengths=None):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1], samples: int32 cuda tensor
+        [n_frames, channels, stride] (the layout Decoder32.decode returns), lengths: int32 cuda tensor [n_frames, channels] (the
+        original's length of every channel) or None: every channel is stride long
+        -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]; -1: nothing differs), views of the verifier's own buffers."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        assert self._inputs_ok(samples, lengths, n_frames)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_i32_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, samples.data_ptr(),
+            None if lengths is None else lengths.data_ptr(), self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.diff_counts[:n_frames], self.first_diff[:n_frames]
+
+    def verify_payload(self, payload, samples, lengths=None, max_frames=None):
+        """Index and verify a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (diff_counts [max_frames], first_diff [max_frames],
+        count int32 [1]): entries up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call
+        before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        assert self._inputs_ok(samples, lengths, max_frames)
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_verify_i32_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_payload_i32_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, samples.data_ptr(),
+            None if lengths is None else lengths.data_ptr(), self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(),
+            self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
+            self.payload_workspace.numel(), stream))
+        return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
+
+    def lossy_frames(self) -> int:
+        """Waits for the last call -> the number of frames with a difference (status[2])."""
+        return int(self.status[2].item())
+
+    def fallback_frames(self, n_frames=None) -> int:
+        """Waits for the last verify() call (not verify_payload) -> the frames whose layout was not direct (test hook)."""
+        return int(self.lib.sela_hip_debug_verify_i32_fallback_frames(
+            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        st[2] = 0
+        capi.check(decode_status_error(st))
+
+
+def verify_i32(frames: np.ndarray, offsets: np.ndarray, channels: int, samples: np.ndarray, lengths=None):
+    """sela_hip_verify_i32 on numpy arrays; samples: int32 [n_frames, channels, stride] (the layout decode_i32 fills), lengths:
+    [n_frames, channels] or None (every channel is stride long).  Returns three values: diff_counts (uint32 [n_frames]),
+    first_diff (uint32 [n_frames]; 0xFFFFFFFF where nothing differs) and the number of frames with a difference (int)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    smp = np.ascontiguousarray(samples, dtype=np.int32)
+    assert smp.ndim == 3 and smp.shape[:2] == (n_frames, channels)
+    stride = smp.shape[2]
+    ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint32)
+    assert ln is None or ln.size == n_frames * channels
+    counts = np.zeros(n_frames, np.uint32)
+    first = np.zeros(n_frames, np.uint32)
+    lossy = C.c_uint32(0)
+    capi.check(lib.sela_hip_verify_i32(fr.ctypes.data, offs.ctypes.data, n_frames, channels, stride, smp.ctypes.data, None if ln is None else ln.ctypes.data,
+                                       counts.ctypes.data, first.ctypes.data, C.byref(lossy)))
+    return counts, first, int(lossy.value)
+
+
 class Encoder32:
     """sela_hip_encode_i32 -- and sela_hip_encode of any length -- on the device: frames of any samples_per_channel (1 .. 65535),
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is

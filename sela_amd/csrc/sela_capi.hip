@@ -73,6 +73,13 @@ hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
 int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
     uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
+size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride);
+hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
+    const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
@@ -1873,6 +1880,105 @@ int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (!frame_offsets || (n_frames && (!frames || !pcm || !diff_counts || !first_diff)))
         return fail(SELA_HIP_EINVAL, "null pointer");
     return sela::generic_verify(frames, frame_offsets, n_frames, channels, pcm, diff_counts, first_diff, lossy_frames, g_recurrence_form);
+}
+
+// ---- verification of 32-bit and ragged streams: a stream against its int32 samples ---------------------------
+namespace {
+// what sela_hip_verify_i32_device and the payload call check alike (check_decode_i32_args with the compare's arrays)
+int check_verify_i32_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths,
+    const uint32_t* d_diff_counts, const uint32_t* d_first_diff, const uint32_t* d_status, const void* d_workspace)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (stride == 0)
+        return fail(SELA_HIP_EINVAL, "stride must not be 0");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!d_status || !d_workspace || (n_frames && (!d_samples || !d_diff_counts || !d_first_diff)))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if (((uintptr_t)d_samples & 3) || ((uintptr_t)d_lengths & 3) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3))
+        return fail(SELA_HIP_EINVAL, "d_samples, d_lengths, d_diff_counts and d_first_diff must be 4-byte aligned");
+    return SELA_HIP_OK;
+}
+} // namespace
+
+size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::verify_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const int rc = check_verify_i32_args(n_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!d_frame_offsets || (n_frames && !d_frames))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_frames & 3)
+        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
+    const size_t need = sela::verify_i32_workspace_bytes(n_frames, channels, stride);
+    if (need == SIZE_MAX || workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_verify_i32_workspace_bytes()");
+    const hipError_t e = sela::launch_verify_i32_device(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_samples, d_lengths, d_diff_counts,
+        d_first_diff, d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "verify_i32 launch");
+}
+
+int sela_hip_verify_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
+    if (rc == SELA_HIP_OK)
+        rc = check_verify_i32_args(max_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff, d_status, d_workspace);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), verify_bytes = sela::verify_i32_workspace_bytes(max_frames, channels, stride);
+    if (verify_bytes == SIZE_MAX || workspace_bytes < index_bytes + verify_bytes)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_verify_i32_workspace_bytes()");
+    hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+        return fail_hip(e, "index launch");
+    e = sela::launch_verify_i32_device(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff,
+        d_sample_offsets, d_status, static_cast<unsigned char*>(d_workspace) + index_bytes, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "verify_i32 launch");
+}
+
+// Host pointers, synchronous: sela_hip_decode_i32's checks in its order, then chunks of frames on the any-length route's leased
+// context and stream (generic_verify_i32), past the coalescer; an open streaming job of the thread is left alone.
+int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
+    const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    if (lossy_frames)
+        *lossy_frames = 0;
+    if (channels == 0 || channels > 255 || stride == 0 || (n_frames && (!frames || !frame_offsets || !samples || !diff_counts || !first_diff)))
+        return fail(SELA_HIP_EINVAL, "bad argument");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    for (uint32_t f = 0; f < n_frames; f++)
+        if (frame_offsets[f + 1] < frame_offsets[f])
+            return fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (largest > stride)
+        return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (see sela_hip_index_samples)");
+    return sela::generic_verify_i32(frames, frame_offsets, n_frames, channels, stride, samples, lengths, diff_counts, first_diff, lossy_frames);
+}
+
+// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
+long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    if (!d_workspace || sela::verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return -1;
+    const unsigned char* const base = reinterpret_cast<const unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    uint32_t left = 0;
+    if (hipDeviceSynchronize() != hipSuccess
+        || hipMemcpy(&left, base + sela::verify_i32_ctl_offset(max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return (long long)left;
 }
 
 // ---- streaming jobs (host pointers) ----------------------------------------------------------------------------

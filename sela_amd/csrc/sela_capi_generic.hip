@@ -641,6 +641,77 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     return SELA_HIP_OK;
 }
 
+// sela_hip_verify_i32: launch_verify_i32_device on chunks of frames, on the calling thread's context and stream.
+// The caller has walked the stream (the offsets never decrease, the largest samplesPerChannel fits the stride); every chunk's
+// status words are judged as sela_hip_decode_status_error judges them: the first chunk that fails ends the call with that code.
+int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
+    const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    if (device_ready() != SELA_HIP_OK)
+        return SELA_HIP_ENODEV;
+    hipError_t ctx_err = hipSuccess;
+    GenericContext* const ctx = g_lease.get(ctx_err);
+    if (!ctx)
+        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
+    Arena& g_arena = ctx->arena;
+    const size_t per_frame = (size_t)channels * stride * 12 + (size_t)channels * (sizeof(GenericSubInfo) + 8) + 64;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const hipStream_t st = ctx->stream;
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    uint32_t lossy = 0;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const size_t subs = (size_t)cf * channels;
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
+        const size_t ws_bytes = verify_i32_workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, "verify_i32: the chunk is too large");
+        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + subs * stride * 4 + subs * 4 + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
+        hipError_t e = g_arena.reserve(need);
+        if (e != hipSuccess)
+            return report_hip_error(e, "verify_i32: scratch");
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
+        int32_t* d_samples = g_arena.take<int32_t>(subs * stride);
+        uint32_t* d_lengths = lengths ? g_arena.take<uint32_t>(subs) : nullptr;
+        // what the host reads back, in one piece: status (4 x u32) | diff_counts [cf] | first_diff [cf]
+        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "verify_i32: internal scratch estimate too small");
+        std::vector<uint64_t> local((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_samples, samples + (size_t)f0 * channels * stride, subs * stride * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && lengths)
+            e = hipMemcpyAsync(d_lengths, lengths + (size_t)f0 * channels, subs * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_verify_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_samples, d_lengths, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws,
+                mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "verify_i32");
+        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
+        const int rc = sela_hip_decode_status_error(decode_status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
+        std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
+        lossy += tail[2];
+    }
+    if (lossy_frames)
+        *lossy_frames = lossy;
+    return SELA_HIP_OK;
+}
+
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out)
 {
     if (device_ready() != SELA_HIP_OK)

@@ -62,6 +62,24 @@ size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t s
 hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
+// sela_hip_verify_i32_device / sela_hip_verify_payload_i32_device: launch_decode_i32_device's shape with the
+// combine turned into a compare against d_samples ([frames][channels][stride] int32, d_lengths or null).  The kernels are
+// sela_verify32.hip's: frames of a direct layout are compared from the subframes as decoded, nothing stored; any other frame goes
+// through k_generic_combine<false> into the workspace first, the whole call's frames as soon as one frame needs it.
+constexpr uint32_t kVerify32Slice = 4096;       // samples of every channel one workgroup of k_verify32_direct takes (= kCombineSlice)
+uint32_t verify32_slices(uint32_t stride);
+hipError_t launch_verify32_begin(uint32_t* d_status, uint32_t* d_ctl /* [2] */, hipStream_t stream);
+hipError_t launch_verify32_direct(const int32_t* d_dec, const GenericSubInfo* d_info, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, const uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks /* [max_frames] */,
+    void* d_parts /* [max_frames][verify32_slices()] x 8 bytes */, hipStream_t stream);
+hipError_t launch_verify32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
+    const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, void* d_parts,
+    uint32_t* d_diff_counts, uint32_t* d_first_diff, hipStream_t stream);
+size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride); // of the two control words, from the aligned base
+hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);

@@ -1898,6 +1898,81 @@ hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_fra
         d_status, stream);
 }
 
+// ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
+// Workspace: launch_decode_i32_device's | the fallback's samples by channel, [frames][channels][stride] | its counts | a mark per
+// frame | k_verify32_direct's / _rest's words per (frame, slice) | the two control words; every piece 256-byte aligned, the base too.
+struct VerifyI32Layout {
+    DecodeI32Layout d;
+    uint64_t all, counts, marks, parts, ctl, bytes;
+};
+static VerifyI32Layout verify_i32_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t subs = (uint64_t)max_frames * channels;
+    VerifyI32Layout l;
+    l.d = decode_i32_layout(max_frames, channels, stride);
+    l.all = l.d.bytes - 256;
+    l.counts = l.all + up(subs * stride * sizeof(int32_t));
+    l.marks = l.counts + up(subs * sizeof(uint32_t));
+    l.parts = l.marks + up(std::max<uint64_t>(max_frames, 1) * sizeof(uint32_t));
+    l.ctl = l.parts + up(std::max<uint64_t>((uint64_t)max_frames * verify32_slices(stride), 1) * 8);
+    l.bytes = l.ctl + 256 + 256; // (+ the base's alignment)
+    return l;
+}
+
+size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    // (frames x channels first: the product of all three can wrap 64 bits; the launch calls keep it below 2^31)
+    if ((uint64_t)max_frames * channels >= (1ull << 31) || decode_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return (size_t)verify_i32_layout(max_frames, channels, stride).bytes;
+}
+
+size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride) { return (size_t)verify_i32_layout(max_frames, channels, stride).ctl; }
+
+// launch_decode_i32_device with a compare in place of the combine: the sample index, k_verify32_begin (status[2], the largest
+// samplesPerChannel, becomes the count of frames with a difference; nothing on this route reads it behind the index),
+// k_decode_subframes32 and the judge into the workspace by position, then k_verify32_direct on the subframes as decoded.  The
+// frames it leaves alone (any layout that is not direct) send the whole call through k_generic_combine<false> -- gated on the
+// device by k_verify32_gate's count, 0 when no frame was left: every workgroup returns at once -- and k_verify32_rest compares
+// those frames from the combine's output.  SELA_HIP_FLAG_BAD_FRAME and status[1] come from the combine as in the decode call:
+// a direct frame is never malformed there.
+hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+{
+    const VerifyI32Layout l = verify_i32_layout(max_frames, channels, stride);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.d.dec);
+    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.d.info);
+    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.d.counters);
+    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.d.tiles);
+    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.all);
+    uint32_t* const d_counts = reinterpret_cast<uint32_t*>(base + l.counts);
+    uint32_t* const d_marks = reinterpret_cast<uint32_t*>(base + l.marks);
+    uint32_t* const d_ctl = reinterpret_cast<uint32_t*>(base + l.ctl);
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, d_counters, d_tiles, stream);
+    hipError_t e = launch_verify32_begin(d_status, d_ctl, stream);
+    const uint32_t subs = max_frames * channels;
+    if (e != hipSuccess || subs == 0)
+        return e;
+    if (mode != 0) {
+        e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, d_n_found);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
+        d_n_found, mode != 0 ? d_counters + 2 : nullptr);
+    e = launch_verify32_direct(d_dec, d_info, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, d_ctl, d_marks, base + l.parts, stream);
+    if (e != hipSuccess)
+        return e;
+    const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
+    hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_all, d_counts, nullptr, nullptr,
+        d_status, d_ctl + 1);
+    return launch_verify32_rest(d_all, d_counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, d_ctl, d_marks, base + l.parts, d_diff_counts,
+        d_first_diff, stream);
+}
+
 // Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total; every
 // piece 256-byte aligned, the base too.  No Rice words: k_generic_write packs into the frames.
 struct EncodeI32Layout {
