@@ -1462,22 +1462,31 @@ uint32_t decode_synth_priorities(uint32_t n_frames, void* stream, int* dev)
     return synth_priorities;
 }
 
+// A launch of the 2048-sample decoder or of what runs it (decode, decode_n, verify): ask for the priorities, launch, and leave
+// the launch in flights() unless the stream is capturing.  launch: uint32_t synth_priorities -> hipError_t; what: fail_hip's text.
+extern "C++" template <typename Launch>
+int launch_with_priorities(uint32_t n_frames, void* stream, const char* what, Launch launch)
+{
+    int dev = -1;
+    const hipError_t e = launch(decode_synth_priorities(n_frames, stream, &dev));
+    if (e != hipSuccess)
+        return fail_hip(e, what);
+    if (dev >= 0)
+        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
+            flights().note(dev, static_cast<hipStream_t>(stream));
+    return SELA_HIP_OK;
+}
+
 // sela_hip_decode_device's launch, arguments checked; d_n_found (or null): the device's own count of frames to decode
 int decode_device_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, void* stream, const uint32_t* d_n_found)
 {
     hipEvent_t* ev = n_frames ? g_timing.events() : nullptr;
     g_timing.recorded = ev ? 1 : 0;
-    int dev = -1;
-    const uint32_t synth_priorities = decode_synth_priorities(n_frames, stream, &dev);
-    hipError_t e = sela::launch_decode(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace,
-        static_cast<hipStream_t>(stream), ev, g_phase_cycles, nullptr, g_recurrence_form, synth_priorities, d_n_found);
-    if (e != hipSuccess)
-        return fail_hip(e, "decode launch");
-    if (dev >= 0)
-        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
-            flights().note(dev, static_cast<hipStream_t>(stream));
-    return SELA_HIP_OK;
+    return launch_with_priorities(n_frames, stream, "decode launch", [&](uint32_t synth_priorities) {
+        return sela::launch_decode(d_frames, d_frame_offsets, n_frames, channels, d_pcm_out, d_status, d_workspace, static_cast<hipStream_t>(stream), ev,
+            g_phase_cycles, nullptr, g_recurrence_form, synth_priorities, d_n_found);
+    });
 }
 
 // the index's own checks (sela_hip_index_frames_device); SELA_HIP_OK or the failure, reported
@@ -1717,16 +1726,10 @@ int check_decode_n_args(uint32_t n_frames, uint32_t channels, uint32_t stride, c
 int decode_n_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
     int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
 {
-    int dev = -1;
-    const uint32_t synth_priorities = decode_synth_priorities(max_frames, stream, &dev);
-    const hipError_t e = sela::launch_decode_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm_out, d_sample_offsets, d_status,
-        d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "decode_n launch");
-    if (dev >= 0)
-        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
-            flights().note(dev, static_cast<hipStream_t>(stream));
-    return SELA_HIP_OK;
+    return launch_with_priorities(max_frames, stream, "decode_n launch", [&](uint32_t synth_priorities) {
+        return sela::launch_decode_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_workspace,
+            sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
+    });
 }
 } // namespace
 
@@ -1814,16 +1817,10 @@ int check_verify_args(uint32_t n_frames, uint32_t channels, uint32_t stride, con
 int verify_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
     const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
 {
-    int dev = -1;
-    const uint32_t synth_priorities = decode_synth_priorities(max_frames, stream, &dev);
-    const hipError_t e = sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff,
-        d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "verify launch");
-    if (dev >= 0)
-        if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
-            flights().note(dev, static_cast<hipStream_t>(stream));
-    return SELA_HIP_OK;
+    return launch_with_priorities(max_frames, stream, "verify launch", [&](uint32_t synth_priorities) {
+        return sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets,
+            d_status, d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
+    });
 }
 } // namespace
 

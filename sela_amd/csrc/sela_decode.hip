@@ -57,13 +57,6 @@ namespace sela {
 
 #include "sela_decode_core.inc" // the parser, the synthesis, the header walk: shared with sela_decode32.hip
 
-// LDS plan of k_decode_frames (dynamic): one DecSubframeLds per subframe POSITION | one DecWaveScratch per wave |
-// sub_info[channels] (channel -> type | parent << 8 | position << 16) | too_big[n_waves].
-__host__ __device__ inline size_t decode_lds_bytes_for(uint32_t channels, int n_waves)
-{
-    return (size_t)channels * sizeof(DecSubframeLds) + (size_t)n_waves * sizeof(DecWaveScratch) + (size_t)channels * 4 + (size_t)n_waves * 4;
-}
-
 // kProf: also write per-phase cycle counts (debug hook sela_hip_debug_phase_buffer; 16 uint64 per subframe).
 template <bool kProf>
 __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_decode_frames(const uint8_t* __restrict__ frames,
@@ -77,16 +70,13 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
     long long stamp[10];
     for (int i = 0; i < 10; i++)
         stamp[i] = 0;
-    uint32_t prof_sub = 0xFFFFFFFFu;
+    uint32_t prof_sub = kNoSubframe;
     if (kProf)
         stamp[0] = clock64();
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     const int n_waves = blockDim.x / 64;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64)), lane = threadIdx.x % 64;
-    DecSubframeLds* const sub = reinterpret_cast<DecSubframeLds*>(dyn);
-    DecWaveScratch* const scratch = reinterpret_cast<DecWaveScratch*>(dyn + (size_t)channels * sizeof(DecSubframeLds)) + wave;
-    uint32_t* const sub_info = reinterpret_cast<uint32_t*>(dyn + (size_t)channels * sizeof(DecSubframeLds) + (size_t)n_waves * sizeof(DecWaveScratch));
-    uint32_t* const too_big = sub_info + channels; // [n_waves]: this wave's subframe does not fit the fast plan
+    const DecFrameLds l = carve_frame_lds(dyn, channels, n_waves);
 
     const uint32_t f = blockIdx.x;
     if (f >= n_frames || (n_frames_found && f >= *n_frames_found))
@@ -95,19 +85,9 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
     const uint8_t* const fb = frames + frame_offsets[f];
     const uint64_t fbytes = frame_offsets[f + 1] - frame_offsets[f];
     uint32_t flags = 0;
-    for (uint32_t c = threadIdx.x; c < channels; c += blockDim.x)
-        sub_info[c] = 0xFFFFFFFFu; // "no subframe delivered this channel"
-
-    // ---- mode: every subframe of the frame must fit the fast plan ----------------------------------------------
-    const bool fast_plan = channels <= (uint32_t)kDecMaxWaves;
-    SubHeader hd = walk_headers(fb, fbytes, (uint32_t)wave < channels ? (uint32_t)wave : 0u);
-    bool ok = block_header_ok(hd, channels);
-    if (lane == 0)
-        too_big[wave] = (fast_plan && (!ok || (hd.cw + 2 + hd.rw <= (uint32_t)kStreamCap && hd.order <= 2 * (uint32_t)kWave))) ? 0u : 1u;
-    __syncthreads();
-    bool fast = fast_plan;
-    for (int w = 0; w < n_waves; w++)
-        fast = fast && too_big[w] == 0;
+    SubHeader hd;
+    bool ok;
+    const bool fast = frame_prologue(l, fb, fbytes, channels, n_waves, wave, lane, hd, ok);
     if (kProf)
         stamp[1] = clock64();
 
@@ -120,123 +100,28 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
             flags |= SELA_HIP_FLAG_BAD_FRAME;
             continue;
         }
-        DecSubframeLds* const sl = sub + c;
-        const uint32_t nw = hd.cw + 2 + hd.rw;
-        const uint32_t* const gw = reinterpret_cast<const uint32_t*>(fb + hd.p + 4); // the subframe's aligned words
-        const int32_t* ws_c = nullptr;
-        ParseProfile pp;
-        if (fast) {
-            for (uint32_t w = lane; w < nw + kStreamMargin; w += kWave) // the start bitmap
-                sl->marks[w] = 0;
-            wave_sync();
-            if (kProf)
-                stamp[2] = clock64(), prof_sub = c;
-            const StreamWords sw = { gw, nw };
-            flags |= parse_subframe<kProf>(sw, sl->marks, sl->pos, reinterpret_cast<uint16_t*>(&scratch->t), coef_values(scratch), hd.cw, hd.rw, hd.ck, hd.rk,
-                hd.order, lane, pp);
-        } else {
-            if (kProf)
-                stamp[2] = clock64(), prof_sub = c;
-            int32_t* const wres = ws_residues + ((size_t)f * channels + c) * kBlock;
-            const uint32_t n_frame_words = (uint32_t)((fbytes - hd.p - 4) / 4);
-            flags |= parse_stream_serial(gw, 24, 24 + 32 * hd.cw, n_frame_words, hd.ck, hd.order, coef_values(scratch), lane);
-            flags |= parse_stream_serial(gw, 32 * (hd.cw + 2), 32 * (hd.cw + 2 + hd.rw), n_frame_words, hd.rk, (uint32_t)kBlock, wres, lane);
-            __threadfence(); // lane 0's stores to the workspace are read back by every lane
-            ws_c = wres;
-            pp.t[0] = pp.t[1] = pp.t[2] = pp.t[3] = kProf ? clock64() : 0;
-        }
         if (kProf)
-            stamp[3] = pp.t[0], stamp[4] = pp.t[1], stamp[5] = pp.t[2], stamp[6] = pp.t[3];
-
-        // dequantise (src/lpc/linear_predictor.cpp:16-28) + step-up
-        SynthTables* const tables = &scratch->t;
-        const uint32_t order = hd.order;
-        const int32_t q_lo = (uint32_t)lane < order ? coef_values(scratch)[lane] : 0, q_hi = (uint32_t)lane + 64 < order ? coef_values(scratch)[lane + 64] : 0;
-        wave_sync();
-        const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-        const double k_hi = (uint32_t)lane + 64 < order ? dequant(lane + 64, q_hi, flags) : 0.0;
-        step_up_regs(k_lo, k_hi, tables->a, (int)order, lane, flags);
-        const bool fits24 = build_synth_table(tables->a, tables->tab, (int)order, lane);
-        if (kProf)
-            stamp[7] = clock64();
-        if (synth_priorities)
-            set_wave_priority((int)((synth_priorities >> (order <= 48 ? 0 : (order <= 60 ? 8 : 16))) & 0xFF));
-        if (vec_shift)
-            synthesize_by_order<true>(order, gw, nw, hd.rk, sl->pos, ws_c, tables->tab, fits24, lane);
-        else
-            synthesize_by_order<false>(order, gw, nw, hd.rk, sl->pos, ws_c, tables->tab, fits24, lane);
-        if (synth_priorities)
-            __builtin_amdgcn_s_setprio(0);
-        if (kProf)
-            stamp[8] = clock64();
+            prof_sub = c;
+        decode_subframe<kProf>(fb, fbytes, hd, fast, l.sub + c, l.scratch0 + wave, ws_residues, (size_t)f * channels + c, vec_shift, synth_priorities, lane, flags, stamp);
         if (lane == 0)
-            sub_info[hd.channel] = hd.type | (hd.parent << 8) | (c << 16);
+            l.sub_info[hd.channel] = sub_info_word(hd.type, hd.parent, c);
     }
     __syncthreads();
 
-    // ---- second pass of frame::FrameDecoder + interleave to int16 ------------------------------------
-    // dependent channels become parent - difference (parents are independent subframes); a channel
-    // that no valid subframe delivered decodes to silence and raises BAD_FRAME.  All of it mod 2^16: the
-    // reference truncates to int16 when it writes the WAV (src/file/wav_file.cpp:248-251).
+    // ---- second pass + interleave to int16, stored coalesced ------------------------------------------------------------
     if (channels == 2) {
-        // stereo: four samples of both channels per thread, one 16-byte store (wave-uniform case analysis)
-        const uint32_t i0 = sub_info[0], i1 = sub_info[1];
-        const bool have0 = i0 != 0xFFFFFFFFu, have1 = i1 != 0xFFFFFFFFu;
-        const bool dep0 = have0 && (i0 & 0xFF) == 1, dep1 = have1 && (i1 & 0xFF) == 1;
-        const uint32_t par0 = (i0 >> 8) & 0xFF, par1 = (i1 >> 8) & 0xFF; // parent channel of a dependent subframe (0 or 1, checked above)
-        const uint2* s0 = reinterpret_cast<const uint2*>(sub[have0 ? i0 >> 16 : 0].smp);
-        const uint2* s1 = reinterpret_cast<const uint2*>(sub[have1 ? i1 >> 16 : 0].smp);
+        // stereo: four samples of both channels per thread, one 16-byte store
+        const StereoPass sp = stereo_pass(l.sub, l.sub_info);
         uint4* out = reinterpret_cast<uint4*>(pcm_out + (size_t)f * kBlock * 2);
-        for (uint32_t i4 = threadIdx.x; i4 < (uint32_t)kBlock / 4; i4 += blockDim.x) {
-            const uint2 zero = make_uint2(0, 0);
-            const uint2 r0 = have0 ? s0[i4] : zero, r1 = have1 ? s1[i4] : zero; // raw subframe outputs, two samples per word
-            // per 16-bit half: parent - difference (the parent's own, independent samples)
-            auto sub16 = [](uint32_t a, uint32_t b) -> uint32_t { return ((a - (b & 0xFFFFu)) & 0xFFFFu) | ((a & 0xFFFF0000u) - (b & 0xFFFF0000u)); };
-            uint2 a = r0, b = r1;
-            if (dep0) {
-                const uint2 pv = par0 == 0 ? r0 : r1;
-                a = make_uint2(sub16(pv.x, r0.x), sub16(pv.y, r0.y));
-            }
-            if (dep1) {
-                const uint2 pv = par1 == 0 ? r0 : r1;
-                b = make_uint2(sub16(pv.x, r1.x), sub16(pv.y, r1.y));
-            }
-            uint4 w;
-            w.x = (a.x & 0xFFFFu) | (b.x << 16);
-            w.y = (a.x >> 16) | (b.x & 0xFFFF0000u);
-            w.z = (a.y & 0xFFFFu) | (b.y << 16);
-            w.w = (a.y >> 16) | (b.y & 0xFFFF0000u);
-            out[i4] = w;
-        }
+        for (uint32_t i4 = threadIdx.x; i4 < (uint32_t)kBlock / 4; i4 += blockDim.x)
+            out[i4] = stereo_words(sp, i4);
     } else {
-        for (uint32_t i = threadIdx.x; i < (uint32_t)kBlock; i += blockDim.x) {
-            for (uint32_t c = 0; c < channels; c++) {
-                const uint32_t info = sub_info[c];
-                uint32_t v = info == 0xFFFFFFFFu ? 0u : (uint32_t)(uint16_t)sub[info >> 16].smp[i];
-                if (info != 0xFFFFFFFFu && (info & 0xFF) == 1) {
-                    const uint32_t pinfo = sub_info[(info >> 8) & 0xFF];
-                    const uint32_t pv = pinfo == 0xFFFFFFFFu ? 0u : (uint32_t)(uint16_t)sub[pinfo >> 16].smp[i];
-                    v = pv - v;
-                }
-                pcm_out[((size_t)f * kBlock + i) * channels + c] = (int16_t)(uint16_t)v;
-            }
-        }
+        for (uint32_t i = threadIdx.x; i < (uint32_t)kBlock; i += blockDim.x)
+            for (uint32_t c = 0; c < channels; c++)
+                pcm_out[((size_t)f * kBlock + i) * channels + c] = (int16_t)(uint16_t)channel_value16(l.sub, l.sub_info, c, i);
     }
-    if (threadIdx.x == 0) {
-        for (uint32_t c = 0; c < channels; c++) {
-            const uint32_t info = sub_info[c];
-            if (info == 0xFFFFFFFFu)
-                flags |= SELA_HIP_FLAG_BAD_FRAME;
-            else if ((info & 0xFF) == 1) {
-                const uint32_t pinfo = sub_info[(info >> 8) & 0xFF];
-                if (pinfo == 0xFFFFFFFFu || (pinfo & 0xFF) != 0)
-                    // a parent that is itself dependent is refused here by policy.  (The reference resolves its type-1 subframes in
-                    // stream order: a chain in that order is defined there, and the 32-bit decoders decode it; against that order it
-                    // subtracts from a vector that is still empty.)
-                    flags |= SELA_HIP_FLAG_BAD_FRAME;
-            }
-        }
-    }
+    if (threadIdx.x == 0)
+        flags |= layout_flags(l.sub_info, channels);
     flags = wave_or(flags);
     if (lane == 0 && flags) {
         if (frame_flags) // (the host pipeline: page-locked host memory, zeroed by the host; a plain store, no atomics over the link)
@@ -247,7 +132,7 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
                 atomicAdd(&status[1], 1u);
         }
     }
-    if (kProf && lane == 0 && prof_sub != 0xFFFFFFFFu) { // (one subframe per wave is reported)
+    if (kProf && lane == 0 && prof_sub != kNoSubframe) { // (one subframe per wave is reported)
         stamp[9] = clock64();
         for (int i = 0; i < 9; i++)
             phase_cycles[((size_t)f * channels + prof_sub) * 16 + i] = (uint64_t)(stamp[i + 1] - stamp[i]);
@@ -259,15 +144,13 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
 // frame::FrameDecoder::process takes any channel count the header's 8-bit field carries (src/frame/frame_decoder.cpp:
 // 11-72).  k_decode_frames keeps every channel of a frame in LDS until the parent - difference pass, which bounds it
 // (one wave and one 4.5 KB record per channel).  Here the eight waves of a workgroup take the frame's subframes in
-// rounds, each wave with a record of its own: a subframe goes from the frame bytes to finished samples exactly as above
-// (the segment-parallel parse when it fits the plan, the serial parse into the workspace otherwise -- decided per
-// SUBFRAME: no other wave depends on this one's record) and leaves its raw samples in the output, strided.  The second
-// pass (src/frame/frame_decoder.cpp:40-69) then runs over the output: a difference-coded channel becomes parent -
+// rounds, each wave with a record of its own: a subframe goes from the frame bytes to finished samples through the same
+// decode_subframe (the segment-parallel parse when it fits the plan, the serial parse into the workspace otherwise --
+// decided per SUBFRAME: no other wave depends on this one's record) and leaves its raw samples in the output, strided.  The
+// second pass (src/frame/frame_decoder.cpp:40-69) then runs over the output: a difference-coded channel becomes parent -
 // difference, where the parent's samples are the raw ones an independent subframe left there.  The reference's encoder
 // writes difference subframes for exactly-stereo input only (src/frame/frame_encoder.cpp:18), so for these frames the
 // pass has nothing to do -- but files are input, not promises.
-constexpr uint32_t kNoSubframe = 0xFFFFFFFFu;
-
 __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const uint8_t* __restrict__ frames,
     const uint64_t* __restrict__ frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* __restrict__ pcm_out,
     uint32_t* __restrict__ status, int32_t* __restrict__ ws_residues, uint8_t* __restrict__ frame_flags, uint32_t vec_shift_from,
@@ -286,7 +169,7 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
     const uint64_t fbytes = frame_offsets[f + 1] - frame_offsets[f];
     uint32_t flags = 0;
     for (uint32_t c = threadIdx.x; c < channels; c += blockDim.x)
-        sub_info[c] = kNoSubframe; // "no subframe delivered this channel"
+        sub_info[c] = kNoSubframe;
     __syncthreads();
     HeaderCursor cur = frame_cursor(fb, fbytes);
     int16_t* const out_frame = pcm_out + (size_t)f * kBlock * channels;
@@ -296,46 +179,14 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
             flags |= SELA_HIP_FLAG_BAD_FRAME;
             continue;
         }
-        const uint32_t nw = hd.cw + 2 + hd.rw;
-        const uint32_t* const gw = reinterpret_cast<const uint32_t*>(fb + hd.p + 4); // the subframe's aligned words
-        const int32_t* ws_c = nullptr;
-        ParseProfile pp;
-        if (nw <= (uint32_t)kStreamCap) { // (hd.order <= 100 <= 2 waves' worth: checked by block_header_ok)
-            for (uint32_t w = lane; w < nw + kStreamMargin; w += kWave) // the start bitmap
-                sl->marks[w] = 0;
-            wave_sync();
-            const StreamWords sw = { gw, nw };
-            flags |= parse_subframe<false>(sw, sl->marks, sl->pos, reinterpret_cast<uint16_t*>(&scratch->t), coef_values(scratch), hd.cw, hd.rw, hd.ck, hd.rk,
-                hd.order, lane, pp);
-        } else {
-            int32_t* const wres = ws_residues + ((size_t)f * channels + c) * kBlock;
-            const uint32_t n_frame_words = (uint32_t)((fbytes - hd.p - 4) / 4);
-            flags |= parse_stream_serial(gw, 24, 24 + 32 * hd.cw, n_frame_words, hd.ck, hd.order, coef_values(scratch), lane);
-            flags |= parse_stream_serial(gw, 32 * (hd.cw + 2), 32 * (hd.cw + 2 + hd.rw), n_frame_words, hd.rk, (uint32_t)kBlock, wres, lane);
-            // lane 0's stores to the workspace are read back by every lane of this wave: they have left the CU, and nothing
-            // older is served from its vector cache (not __threadfence(): its release half writes back the whole L2)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            ws_c = wres;
-        }
-        SynthTables* const tables = &scratch->t;
-        const uint32_t order = hd.order;
-        const int32_t q_lo = (uint32_t)lane < order ? coef_values(scratch)[lane] : 0, q_hi = (uint32_t)lane + 64 < order ? coef_values(scratch)[lane + 64] : 0;
-        wave_sync();
-        const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-        const double k_hi = (uint32_t)lane + 64 < order ? dequant(lane + 64, q_hi, flags) : 0.0;
-        step_up_regs(k_lo, k_hi, tables->a, (int)order, lane, flags);
-        const bool fits24 = build_synth_table(tables->a, tables->tab, (int)order, lane);
-        if (vec_shift)
-            synthesize_by_order<true>(order, gw, nw, hd.rk, sl->pos, ws_c, tables->tab, fits24, lane);
-        else
-            synthesize_by_order<false>(order, gw, nw, hd.rk, sl->pos, ws_c, tables->tab, fits24, lane);
+        // (hd.order <= 100 <= 2 waves' worth: checked by block_header_ok)
+        decode_subframe<false>(fb, fbytes, hd, hd.cw + 2 + hd.rw <= (uint32_t)kStreamCap, sl, scratch, ws_residues, (size_t)f * channels + c, vec_shift, 0, lane, flags, nullptr);
         // the raw samples of this subframe, where its channel lies in the output (mod 2^16: src/file/wav_file.cpp:248-251)
         for (int i = lane; i < kBlock; i += kWave)
             out_frame[(size_t)i * channels + hd.channel] = sl->smp[i];
         wave_sync(); // (the record is reused by this wave's next subframe)
         if (lane == 0)
-            sub_info[hd.channel] = hd.type | (hd.parent << 8);
+            sub_info[hd.channel] = sub_info_word(hd.type, hd.parent, 0);
     }
     // ---- second pass of frame::FrameDecoder, over the output -----------------------------------------------------------
     // Writers and readers are waves of ONE workgroup, i.e. of one CU behind one L2: the stores only have to have left the
@@ -352,13 +203,10 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) void k_decode_frames_wide(const 
                 out_frame[(size_t)i * channels + c] = 0;
             if (threadIdx.x == 0)
                 flags |= SELA_HIP_FLAG_BAD_FRAME;
-        } else if ((info & 0xFF) == 1) {
-            const uint32_t parent = (info >> 8) & 0xFF;
+        } else if (sub_info_type(info) == 1) {
+            const uint32_t parent = sub_info_parent(info);
             const uint32_t pinfo = sub_info[parent];
-            // (a parent that is itself difference-coded is refused here by policy: flagged, and its raw samples taken.  The
-            // reference defines such a chain where it runs in stream order -- the 32-bit decoders decode it -- and reads an empty
-            // vector where it runs against it)
-            if (threadIdx.x == 0 && (pinfo == kNoSubframe || (pinfo & 0xFF) != 0))
+            if (threadIdx.x == 0 && parent_refused(pinfo)) // (flagged, and a dependent parent's raw samples taken)
                 flags |= SELA_HIP_FLAG_BAD_FRAME;
             for (uint32_t i = threadIdx.x; i < (uint32_t)kBlock; i += blockDim.x) {
                 const uint32_t pv = pinfo == kNoSubframe ? 0u : (uint32_t)(uint16_t)out_frame[(size_t)i * channels + parent];
@@ -451,10 +299,8 @@ __global__ __launch_bounds__(64) void k_stage_lpc_decode(const int32_t* __restri
     const uint32_t order = (uint32_t)o;
     const int32_t q_lo = (uint32_t)lane < order ? q_in[(size_t)b * kMaxOrder + lane] : 0;
     const int32_t q_hi = (uint32_t)lane + 64 < order ? q_in[(size_t)b * kMaxOrder + lane + 64] : 0;
-    const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-    const double k_hi = (uint32_t)lane + 64 < order ? dequant(lane + 64, q_hi, flags) : 0.0;
     SynthTables* const tables = &scratch.t;
-    step_up_regs(k_lo, k_hi, tables->a, (int)order, lane, flags);
+    step_up_from_q(order, q_lo, q_hi, tables->a, lane, flags);
     if (coefs_out) // lpc::LinearPredictor::linearPredictionCoefficients (src/lpc/linear_predictor.cpp:57-60)
         for (uint32_t i = lane; i <= order; i += kWave)
             coefs_out[(size_t)b * (kMaxOrder + 1) + i] = tables->a[i];

@@ -318,10 +318,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         }
         const int32_t q_lo = (uint32_t)lane < order ? coef_values(&scratch)[lane] : 0, q_hi = (uint32_t)lane + 64 < order ? coef_values(&scratch)[lane + 64] : 0;
         wave_sync();
-        const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-        const double k_hi = (uint32_t)lane + 64 < order ? dequant(lane + 64, q_hi, flags) : 0.0;
-        step_up_regs(k_lo, k_hi, tables->a, (int)order, lane, flags);
-        const bool fits24 = build_synth_table(tables->a, tables->tab, (int)order, lane);
+        const bool fits24 = predictor_table(order, q_lo, q_hi, tables, lane, flags);
         SynthOut<true> out32;
         out32.samples = samples;
         out32.n = hd.n;
@@ -366,10 +363,8 @@ __global__ __launch_bounds__(64) void k_lpc_decode_any(const int32_t* __restrict
         flags |= SELA_HIP_FLAG_SHORT_BLOCK;
     const int32_t q_lo = (uint32_t)lane < order ? q_in[(size_t)b * kMaxOrder + lane] : 0;
     const int32_t q_hi = (uint32_t)lane + 64 < order ? q_in[(size_t)b * kMaxOrder + lane + 64] : 0;
-    const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-    const double k_hi = (uint32_t)lane + 64 < order ? dequant(lane + 64, q_hi, flags) : 0.0;
     SynthTables* const tables = &scratch.t;
-    step_up_regs(k_lo, k_hi, tables->a, (int)order, lane, flags);
+    step_up_from_q(order, q_lo, q_hi, tables->a, lane, flags);
     if (coefs_out) // lpc::LinearPredictor::linearPredictionCoefficients (src/lpc/linear_predictor.cpp:57-60)
         for (uint32_t i = lane; i <= order; i += kWave)
             coefs_out[(size_t)b * (kMaxOrder + 1) + i] = tables->a[i];

@@ -1,9 +1,17 @@
-// sela_decode_core.inc -- the decoder's device code that more than one translation unit uses: the per-wave LDS records, the
-// segment-parallel Rice parser, the synthesis (transposed-form recurrence) and the header walk.  Included inside namespace
-// sela by sela_decode.hip (k_decode_frames, k_decode_frames_wide, the stage kernels) and by sela_decode32.hip
-// (k_decode_subframes32); the algorithms are described at the top of sela_decode.hip.  A file of its own so that the 32-bit
-// kernel is compiled apart: a further caller in sela_decode.hip's translation unit moved the inliner's decisions inside
-// k_decode_frames (2637 -> 2627 instructions), and the timed kernel is to stay, instruction for instruction, what was measured.
+// sela_decode_core.inc -- the decoder's device code, once, for every kernel that decodes a subframe.  Included inside namespace
+// sela by sela_decode.hip (k_decode_frames, k_decode_frames_wide, the stage kernels), sela_verify.hip (k_verify_frames) and
+// sela_decode32.hip (k_decode_subframes32, k_lpc_decode_any); the algorithms are described at the top of sela_decode.hip.
+//
+//   the per-wave LDS records, the segment-parallel Rice parser, the serial parser, the synthesis (transposed-form recurrence),
+//   the header walk                                                  -- every kernel above
+//   predictor_table: dequantise, step-up, synthesis table            -- the three frame kernels and k_decode_subframes32
+//   decode_subframe: one 2048-sample subframe, bytes -> int16 in LDS -- k_decode_frames, k_decode_frames_wide, k_verify_frames
+//   the sub_info word, decode_lds_bytes_for, frame_prologue          -- k_decode_frames, k_verify_frames (the word: the wide kernel too)
+//   the second pass: stereo_pass / stereo_words, channel_value16, layout_flags, parent_refused
+//                                                                    -- k_decode_frames stores what they give, k_verify_frames compares it
+//
+// Each translation unit compiles its own copy (the kernels live on their register budgets -- tests/test_isa_*.py -- and the
+// synthesis is a real call, see synthesize); profiles/decode_subframe/README.md has what the kernels cost.
 
 constexpr int kDecMaxWaves = 8;     // waves per workgroup; frames with more channels take k_decode_frames_wide
 constexpr int kDecMaxChannels = 255; // what the 8-bit channel field of the .sela header can say (src/file/sela_file.cpp:40)
@@ -760,6 +768,199 @@ __device__ inline SubHeader walk_headers(const uint8_t* fb, uint64_t fbytes, uin
 __device__ inline bool block_header_ok(const SubHeader& h, uint32_t channels)
 {
     return h.ok && sela_subframe_decodable(&h) && h.n == (uint32_t)kBlock && h.channel < channels && h.type <= 1 && (h.type == 0 || h.parent < channels);
+}
+
+// ---- quantised reflection coefficients -> synthesis table ------------------------------------------------------------------
+// dequantise (src/lpc/linear_predictor.cpp:16-28), step-up into t->a, the table over it.  Returns build_synth_table's answer
+// (every high word fits 24 bits: the synthesis may start in the folded form).
+__device__ __forceinline__ bool predictor_table(uint32_t order, int32_t q_lo, int32_t q_hi, SynthTables* t, int lane, uint32_t& flags)
+{
+    step_up_from_q(order, q_lo, q_hi, t->a, lane, flags);
+    return build_synth_table(t->a, t->tab, (int)order, lane);
+}
+
+// ---- one 2048-sample subframe, from the frame's bytes to int16 samples in its record ----------------------------------------
+// The body of a wave of k_decode_frames, k_decode_frames_wide and k_verify_frames.  fast: the segment-parallel parse into the
+// record (the caller has checked hd.cw + 2 + hd.rw <= kStreamCap); otherwise the serial parse, the residues parked in block
+// ws_block of the workspace (int32[kBlock] each, 256-byte aligned).  flags is a reference on purpose: a local that is returned
+// stays alive across the synthesis in a register of its own, which k_verify_frames does not have (two spilled VGPRs).
+// kProf: stamps 2 .. 8 of k_decode_frames' phase counts.
+template <bool kProf>
+__device__ __forceinline__ void decode_subframe(const uint8_t* fb, uint64_t fbytes, const SubHeader& hd, bool fast, DecSubframeLds* sl, DecWaveScratch* scratch,
+    int32_t* ws_residues, size_t ws_block, bool vec_shift, uint32_t synth_priorities /* as k_decode_frames takes them; 0: none */, int lane, uint32_t& flags,
+    long long* stamp /* kProf only */)
+{
+    const uint32_t nw = hd.cw + 2 + hd.rw;
+    const uint32_t* const gw = reinterpret_cast<const uint32_t*>(fb + hd.p + 4); // the subframe's aligned words
+    const int32_t* ws_c = nullptr;
+    ParseProfile pp;
+    if (fast) {
+        for (uint32_t w = lane; w < nw + kStreamMargin; w += kWave) // the start bitmap
+            sl->marks[w] = 0;
+        wave_sync();
+        if (kProf)
+            stamp[2] = clock64();
+        const StreamWords sw = { gw, nw };
+        flags |= parse_subframe<kProf>(sw, sl->marks, sl->pos, reinterpret_cast<uint16_t*>(&scratch->t), coef_values(scratch), hd.cw, hd.rw, hd.ck, hd.rk,
+            hd.order, lane, pp);
+    } else {
+        if (kProf)
+            stamp[2] = clock64();
+        int32_t* const wres = ws_residues + ws_block * kBlock;
+        const uint32_t n_frame_words = (uint32_t)((fbytes - hd.p - 4) / 4);
+        flags |= parse_stream_serial(gw, 24, 24 + 32 * hd.cw, n_frame_words, hd.ck, hd.order, coef_values(scratch), lane);
+        flags |= parse_stream_serial(gw, 32 * (hd.cw + 2), 32 * (hd.cw + 2 + hd.rw), n_frame_words, hd.rk, (uint32_t)kBlock, wres, lane);
+        // lane 0's stores to the workspace are read back by every lane of this wave: they have left the CU, and nothing older is
+        // served from its vector cache -- every block of the workspace is 8 KB at a 256-byte boundary, written before it is first
+        // read (not __threadfence(): its release half writes back the whole L2)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        ws_c = wres;
+        pp.t[0] = pp.t[1] = pp.t[2] = pp.t[3] = kProf ? clock64() : 0;
+    }
+    if (kProf)
+        stamp[3] = pp.t[0], stamp[4] = pp.t[1], stamp[5] = pp.t[2], stamp[6] = pp.t[3];
+
+    const uint32_t order = hd.order;
+    const int32_t q_lo = (uint32_t)lane < order ? coef_values(scratch)[lane] : 0, q_hi = (uint32_t)lane + 64 < order ? coef_values(scratch)[lane + 64] : 0;
+    wave_sync();
+    const bool fits24 = predictor_table(order, q_lo, q_hi, &scratch->t, lane, flags);
+    if (kProf)
+        stamp[7] = clock64();
+    if (synth_priorities)
+        set_wave_priority((int)((synth_priorities >> (order <= 48 ? 0 : (order <= 60 ? 8 : 16))) & 0xFF));
+    if (vec_shift)
+        synthesize_by_order<true>(order, gw, nw, hd.rk, sl->pos, ws_c, scratch->t.tab, fits24, lane);
+    else
+        synthesize_by_order<false>(order, gw, nw, hd.rk, sl->pos, ws_c, scratch->t.tab, fits24, lane);
+    if (synth_priorities)
+        __builtin_amdgcn_s_setprio(0);
+    if (kProf)
+        stamp[8] = clock64();
+}
+
+// ---- what a frame's subframes delivered: one word per CHANNEL ---------------------------------------------------------------
+constexpr uint32_t kNoSubframe = 0xFFFFFFFFu; // "no subframe delivered this channel"
+__device__ __forceinline__ uint32_t sub_info_word(uint32_t type, uint32_t parent, uint32_t position) { return type | (parent << 8) | (position << 16); }
+__device__ __forceinline__ uint32_t sub_info_type(uint32_t info) { return info & 0xFF; }
+__device__ __forceinline__ uint32_t sub_info_parent(uint32_t info) { return (info >> 8) & 0xFF; }
+__device__ __forceinline__ uint32_t sub_info_position(uint32_t info) { return info >> 16; }
+
+// LDS plan of k_decode_frames and k_verify_frames (dynamic): one DecSubframeLds per subframe POSITION | one DecWaveScratch per
+// wave | sub_info[channels] | too_big[n_waves].
+__host__ __device__ inline size_t decode_lds_bytes_for(uint32_t channels, int n_waves)
+{
+    return (size_t)channels * sizeof(DecSubframeLds) + (size_t)n_waves * sizeof(DecWaveScratch) + (size_t)channels * 4 + (size_t)n_waves * 4;
+}
+struct DecFrameLds {
+    DecSubframeLds* sub;       // [channels]
+    DecWaveScratch* scratch0;  // [n_waves]
+    uint32_t* sub_info;        // [channels]
+    uint32_t* too_big;         // [n_waves]: this wave's subframe does not fit the fast plan
+};
+__device__ __forceinline__ DecFrameLds carve_frame_lds(unsigned char* dyn, uint32_t channels, int n_waves)
+{
+    DecFrameLds l;
+    l.sub = reinterpret_cast<DecSubframeLds*>(dyn);
+    l.scratch0 = reinterpret_cast<DecWaveScratch*>(dyn + (size_t)channels * sizeof(DecSubframeLds));
+    l.sub_info = reinterpret_cast<uint32_t*>(dyn + (size_t)channels * sizeof(DecSubframeLds) + (size_t)n_waves * sizeof(DecWaveScratch));
+    l.too_big = l.sub_info + channels;
+    return l;
+}
+
+// The start of a frame's workgroup: nothing delivered yet, this wave's first header (hd, ok), and the vote on the mode -- every
+// subframe of the frame must fit the fast plan.  Returns the vote's result; ends in a workgroup barrier.
+__device__ __forceinline__ bool frame_prologue(const DecFrameLds& l, const uint8_t* fb, uint64_t fbytes, uint32_t channels, int n_waves, int wave, int lane,
+    SubHeader& hd, bool& ok)
+{
+    for (uint32_t c = threadIdx.x; c < channels; c += blockDim.x)
+        l.sub_info[c] = kNoSubframe;
+    const bool fast_plan = channels <= (uint32_t)kDecMaxWaves;
+    hd = walk_headers(fb, fbytes, (uint32_t)wave < channels ? (uint32_t)wave : 0u);
+    ok = block_header_ok(hd, channels);
+    if (lane == 0)
+        l.too_big[wave] = (fast_plan && (!ok || (hd.cw + 2 + hd.rw <= (uint32_t)kStreamCap && hd.order <= 2 * (uint32_t)kWave))) ? 0u : 1u;
+    __syncthreads();
+    bool fast = fast_plan;
+    for (int w = 0; w < n_waves; w++)
+        fast = fast && l.too_big[w] == 0;
+    return fast;
+}
+
+// ---- second pass of frame::FrameDecoder + interleave to int16 (src/frame/frame_decoder.cpp:40-69) ---------------------------
+// Dependent channels become parent - difference (parents are independent subframes); a channel that no valid subframe
+// delivered decodes to silence.  All of it mod 2^16: the reference truncates to int16 when it writes the WAV
+// (src/file/wav_file.cpp:248-251).  k_decode_frames stores what these give, k_verify_frames compares it.
+
+// A difference-coded subframe whose parent is missing or itself dependent is refused by policy.  (The reference resolves its
+// type-1 subframes in stream order: a chain in that order is defined there, and the 32-bit decoders decode it; against that
+// order it subtracts from a vector that is still empty.)
+__device__ __forceinline__ bool parent_refused(uint32_t pinfo) { return pinfo == kNoSubframe || sub_info_type(pinfo) != 0; }
+
+// SELA_HIP_FLAG_BAD_FRAME if a channel is missing or a parent refused, else 0.
+__device__ __forceinline__ uint32_t layout_flags(const uint32_t* sub_info, uint32_t channels)
+{
+    uint32_t flags = 0;
+    for (uint32_t c = 0; c < channels; c++) {
+        const uint32_t info = sub_info[c];
+        if (info == kNoSubframe || (sub_info_type(info) == 1 && parent_refused(sub_info[sub_info_parent(info)])))
+            flags |= SELA_HIP_FLAG_BAD_FRAME;
+    }
+    return flags;
+}
+
+// The 16-bit value of channel c at sample i.
+__device__ __forceinline__ uint32_t channel_value16(const DecSubframeLds* sub, const uint32_t* sub_info, uint32_t c, uint32_t i)
+{
+    const uint32_t info = sub_info[c];
+    uint32_t v = info == kNoSubframe ? 0u : (uint32_t)(uint16_t)sub[sub_info_position(info)].smp[i];
+    if (info != kNoSubframe && sub_info_type(info) == 1) {
+        const uint32_t pinfo = sub_info[sub_info_parent(info)];
+        const uint32_t pv = pinfo == kNoSubframe ? 0u : (uint32_t)(uint16_t)sub[sub_info_position(pinfo)].smp[i];
+        v = pv - v;
+    }
+    return v & 0xFFFFu;
+}
+
+// Stereo: four samples of both channels per thread.  The case analysis is wave-uniform and done once ...
+struct StereoPass {
+    bool have0, have1, dep0, dep1;
+    uint32_t par0, par1;  // parent channel of a dependent subframe (0 or 1: block_header_ok)
+    const uint2 *s0, *s1; // the channels' raw samples, two per word
+};
+__device__ __forceinline__ StereoPass stereo_pass(const DecSubframeLds* sub, const uint32_t* sub_info)
+{
+    const uint32_t i0 = sub_info[0], i1 = sub_info[1];
+    StereoPass sp;
+    sp.have0 = i0 != kNoSubframe, sp.have1 = i1 != kNoSubframe;
+    sp.dep0 = sp.have0 && sub_info_type(i0) == 1, sp.dep1 = sp.have1 && sub_info_type(i1) == 1;
+    sp.par0 = sub_info_parent(i0), sp.par1 = sub_info_parent(i1);
+    sp.s0 = reinterpret_cast<const uint2*>(sub[sp.have0 ? sub_info_position(i0) : 0].smp);
+    sp.s1 = reinterpret_cast<const uint2*>(sub[sp.have1 ? sub_info_position(i1) : 0].smp);
+    return sp;
+}
+// ... and these are the four output words of samples 4 i4 .. 4 i4 + 3 (sample i: channel 0 | channel 1 << 16).
+__device__ __forceinline__ uint4 stereo_words(const StereoPass& sp, uint32_t i4)
+{
+    const uint2 zero = make_uint2(0, 0);
+    const uint2 r0 = sp.have0 ? sp.s0[i4] : zero, r1 = sp.have1 ? sp.s1[i4] : zero; // raw subframe outputs
+    // per 16-bit half: parent - difference (the parent's own, independent samples)
+    auto sub16 = [](uint32_t a, uint32_t b) -> uint32_t { return ((a - (b & 0xFFFFu)) & 0xFFFFu) | ((a & 0xFFFF0000u) - (b & 0xFFFF0000u)); };
+    uint2 a = r0, b = r1;
+    if (sp.dep0) {
+        const uint2 pv = sp.par0 == 0 ? r0 : r1;
+        a = make_uint2(sub16(pv.x, r0.x), sub16(pv.y, r0.y));
+    }
+    if (sp.dep1) {
+        const uint2 pv = sp.par1 == 0 ? r0 : r1;
+        b = make_uint2(sub16(pv.x, r1.x), sub16(pv.y, r1.y));
+    }
+    uint4 w;
+    w.x = (a.x & 0xFFFFu) | (b.x << 16);
+    w.y = (a.x >> 16) | (b.x & 0xFFFF0000u);
+    w.z = (a.y & 0xFFFFu) | (b.y << 16);
+    w.w = (a.y >> 16) | (b.y & 0xFFFF0000u);
+    return w;
 }
 
 // Launches of at most this many waves run their recurrence in the form for a wave that has its SIMD (nearly) to itself

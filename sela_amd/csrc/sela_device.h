@@ -302,6 +302,21 @@ __device__ inline void step_up(const double* kd, int64_t* a, int order, int lane
     step_up_regs(k_lo, k_hi, a, order, lane, flags);
 }
 
+// The decoders' way to the predictor: quantised reflection coefficients `lane` (q_lo) and `lane + 64` (q_hi) -> a[0 .. order].
+// Dequantised into registers (src/lpc/linear_predictor.cpp:16-28): 0 beyond the order, and the only coefficient of an
+// order <= 1 predictor stays 0; then step_up_regs.
+// (The lane as dequant() sees it is opaque, in every decoder: the compiler otherwise selects the lane's table in front of
+// whatever parse precedes this and carries the pointer through it -- two spilled registers in k_verify_frames, two more
+// registers in k_decode_frames, which the budget of seven waves per SIMD does not have.)
+__device__ __forceinline__ void step_up_from_q(uint32_t order, int32_t q_lo, int32_t q_hi, int64_t* a, int lane, uint32_t& flags)
+{
+    int table_lane = lane;
+    asm volatile("" : "+v"(table_lane));
+    const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(table_lane, q_lo, flags)) : 0.0;
+    const double k_hi = (uint32_t)lane + 64 < order ? dequant(64, q_hi, flags) : 0.0; // (coefficients 2 and up share one table)
+    step_up_regs(k_lo, k_hi, a, (int)order, lane, flags);
+}
+
 // ---- launch helpers of the 2048-sample decoder (sela_decode.hip), shared with sela_verify.hip -------------------------------
 // resident_frames: the workgroups of `kernel` the current device holds at once (0: the runtime would not say), asked once per
 // (kernel slot, device, waves per workgroup) -- the occupancy query is per kernel, so every kernel has a slot of its own.

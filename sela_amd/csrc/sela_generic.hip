@@ -1152,9 +1152,7 @@ __global__ __launch_bounds__(64) void k_generic_decode(const uint8_t* __restrict
         const uint32_t o = order;
         const int32_t q_lo = (uint32_t)lane < o ? q_lds[lane] : 0;
         const int32_t q_hi = (uint32_t)lane + 64 < o ? q_lds[lane + 64] : 0;
-        const double k_lo = (uint32_t)lane < o ? (o <= 1 ? 0.0 : dequant(lane, q_lo, flags)) : 0.0;
-        const double k_hi = (uint32_t)lane + 64 < o ? dequant(lane + 64, q_hi, flags) : 0.0;
-        step_up_regs(k_lo, k_hi, a_lds, (int)o, lane, flags);
+        step_up_from_q(o, q_lo, q_hi, a_lds, lane, flags);
     }
     // lane l: a[l + 1], a[l + 65] (0 beyond the order)
     const uint64_t a_lo = (uint32_t)lane + 1 <= order ? (uint64_t)a_lds[lane + 1] : 0;

@@ -7,6 +7,8 @@ the other round of the eight waves, parent - difference beyond int16, a subframe
 All accepted cases of one channel count are one stream: one launch per call.  The expectation is always the CPU oracle's PCM
 (topology_cases.accepted_stream, pinned to the reference by test_oracle_topologies.py), never another GPU call; what the
 verify calls must report for planted differences is computed in numpy from (oracle PCM, planted PCM) alone."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -240,3 +242,75 @@ def test_refused_layouts_are_reported_and_their_neighbours_decoded(gpu, ch):  # 
     assert (int(st[0]), int(st[1]), int(st[3])) == (int(dst[0]), int(dst[1]), int(dst[3])), (st, dst)
     assert codec.decode_n_status_error(st) == EFORMAT
     assert (counts[good] == 0).all() and (first[good] == NO_DIFF).all(), [(cs[f][0], int(counts[f])) for f in good if counts[f]]
+
+
+# ---- f. the serial parse between two frames on the fast plan --------------------------------------------------------------------------
+# (layout of ACCEPTED_LAYOUTS / SERIAL_LAYOUTS, position of the long subframe): a parent with a dependant behind it; a dependant
+# in k_decode_frames' general pass; the parent that the wide kernel's second round decodes
+_SERIAL_BETWEEN = {2: (tc.SERIAL_LAYOUTS[2][0][1], 0), 8: (tc.ACCEPTED_LAYOUTS[8][0][1], 4), 9: (tc.ACCEPTED_LAYOUTS[9][0][1], 8)}
+
+
+@functools.lru_cache(maxsize=None)
+def _serial_between_fast(ch):
+    """Three frames of one layout, the middle one with a subframe beyond the 1072-word plan -> (blobs, stream, offsets, oracle PCM),
+    computed once per channel count and read-only."""
+    from oracle_lib import oracle
+
+    o = oracle()
+    layout, pos = _SERIAL_BETWEEN[ch]
+    blobs = []
+    for f in range(3):
+        scales = {pos: tc.LONG} if f == 1 else None
+        blob = tc.wc.frame_bytes(o, tc.subframes(layout, tc.ORDINARY, 7000 + 10 * ch + f, scales))
+        words = tc.subframe_words(blob, ch)
+        assert [p for p in range(ch) if words[p] > tc.PLAN_WORDS] == ([pos] if f == 1 else []), (ch, f, words)
+        blobs.append(blob)
+    stream = np.frombuffer(b"".join(blobs), np.uint8).copy()
+    offs = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
+    pcm = np.stack([o.frame_decode(b, ch)[0] for b in blobs])
+    for a in (stream, offs, pcm):
+        a.setflags(write=False)
+    return blobs, stream, offs, pcm
+
+
+@pytest.mark.parametrize("form", [0, 1])
+@pytest.mark.parametrize("ch", sorted(_SERIAL_BETWEEN))
+def test_a_serial_parse_between_two_fast_frames_in_one_launch(gpu, ch, form):  # noqa: F811
+    """The workspace hand-over behind the serial parse (lane 0 stores the residues, the wave reads them back) is one fence in
+    k_decode_frames, k_decode_frames_wide and k_verify_frames: one launch whose middle workgroup takes it while its
+    neighbours run the fast plan, in both recurrence forms, against the oracle's PCM."""
+    torch = gpu
+    _, stream, offs, want = _serial_between_fast(ch)
+    stream, offs = np.array(stream), np.array(offs)  # (copies of the test's own; the oracle's PCM stays the shared one)
+    n = 3
+    frames, o = _on_device(torch, stream, offs)
+    labels = [("fast",), ("serial",), ("fast",)]
+    # differences in every frame, the serial one's long channel and its relatives among them
+    changed = want.copy()
+    bits = changed.view(np.uint16)
+    for f, i, c, x in ((0, 5, 0, 1), (1, 0, ch - 1, 0x8000), (1, 777, 0, 3), (1, tc.N - 1, 1, 0xFFFF), (2, tc.N - 1, ch - 1, 0x10)):
+        bits[f, i, c] ^= np.uint16(x)
+    want_counts, want_first, lossy = _expected(want, changed)
+    assert want_counts.tolist() == [1, 3, 1] and lossy == 3
+    lib = capi.lib()
+    lib.sela_hip_debug_decode_recurrence(form)
+    try:
+        dec = codec.Decoder(n, ch)
+        back = dec.decode(frames, o, n)
+        torch.cuda.synchronize()
+        dec.check()
+        assert dec.status.cpu().numpy()[:2].tolist() == [0, 0]
+        _same_frames(back.cpu().numpy(), want, labels)
+        pcm, so, st = _decode_n(torch, stream, offs, ch, tc.N)
+        assert codec.decode_n_status_error(st) == 0 and int(st[0]) == 0 and int(st[1]) == 0 and int(st[3]) == FAST, st
+        assert np.array_equal(so, _standard_offsets(n))
+        _same_frames(pcm[: n * tc.N].cpu().numpy(), want, labels)
+        ver = codec.Verifier(n, ch, tc.N)
+        for p, counts_want, first_want, lossy_want in ((want, np.zeros(n, np.uint32), np.full(n, NO_DIFF, np.uint32), 0), (changed, want_counts, want_first, lossy)):
+            counts, first = ver.verify(frames, o, n, torch.from_numpy(np.array(p)).cuda())
+            ver.check()
+            assert ver.status.cpu().numpy().view(np.uint32).tolist() == [0, 0, lossy_want, FAST]
+            assert np.array_equal(counts.cpu().numpy().view(np.uint32), counts_want), counts
+            assert np.array_equal(first.cpu().numpy().view(np.uint32), first_want), first
+    finally:
+        lib.sela_hip_debug_decode_recurrence(-1)
