@@ -1536,7 +1536,14 @@ struct TeamPlan {
     static constexpr int kKStride = 104;                       // doubles per block: its reflection coefficients, in the dead rings until they are quantised
     static constexpr int kQBase = kSmallBase;                  // the quantised coefficients of the wave's blocks wait for their tails where the tail's plan keeps
     static constexpr int kQStride = 104;                       //   ac[] for k_encode_blocks (832 bytes it does not use here): 100 x int8, the order, an escape mark
-    static constexpr int kLdsBytes = kRingBytes > kCwBase + kCoefWordsCap * 4 ? kRingBytes : kCwBase + kCoefWordsCap * 4;
+    // the Schur recursion's repack areas of the teams of 16 (team_schur_repack), behind the blocks' k[]: gen0's and gen1's columns
+    // side by side.  (Eight teams of 8 would only have room for one of the two at a time, at 13.0 KB: built and measured)
+    static constexpr int kSchurBase = B * kKStride;            // doubles
+    static constexpr int kSchurStride = P == 16 ? 2 * P * G : 0; // doubles per block
+    static constexpr int kSchurBytes = P == 16 ? (kSchurBase + B * kSchurStride) * 8 : 0;
+    static constexpr int kTailBytes = kCwBase + kCoefWordsCap * 4;
+    static constexpr int kLdsBytes = kRingBytes > kTailBytes ? kRingBytes : kTailBytes;
+    static_assert(kSchurBytes <= kLdsBytes, "the repack areas fit the kernel's LDS");
     static_assert(G + kTeamAhead <= kTeamWin && kChunk % kTeamWin == 0 && kRing % kChunk == 0 && kStride % 32 == (P == 8 ? 24 : 16) && kStride >= kRing + kTeamMirror, "team plan");
     static_assert((G * P - 1) + kChunk + kChunk <= kRing && 2 * kTeamMeanChunk <= kRing, "the ring must hold the lags' reach, the chunk in use and the chunk being written");
     static_assert(kLdsBytes * 12 <= 160 * 1024, "twelve waves per CU");
@@ -1794,6 +1801,86 @@ __device__ __forceinline__ void team_ac_steps(double (&W)[kTeamWin], double (&M)
         team_ac_steps<G, R0 + 1>(W, M, acc, addr_w, addr_m);
 }
 
+// ---- the Schur recursion of a team in phases (round 9) ---------------------------------------------------------------
+// Stage i of the reference (src/lpc/residue_generator.cpp:60-67) updates columns j < 100 - i and reads gen1[j + 1], so it
+// needs columns 0 .. 100 - i and nothing else: a triangle of 4950 column updates.  With G columns per lane through all 99
+// stages a team updates 99 G P of them (teams of 16: 11,088), and a dead REGISTER costs what a live one does -- lane 0 keeps
+// all G alive until stage 100 - G.  So the recursion runs in phases of g = G, G - 1, .. 1 columns per lane (column c in lane
+// c / g, register c % g), each with its own unrolled stage body of 4 g FP64 instructions, and between two phases the team
+// repacks gen0 / gen1 through LDS (team_schur_repack).  The operations on the live columns are the same ones on the same
+// operands in the same order: only where a column is kept changes.
+//
+// When may the phase with g columns per lane start?  It holds columns 0 .. P g - 1, and its last column takes "gen1[P g]"
+// from the next lane through wave_shl1_zero as before: the next team's column 0, or zero behind the wave's last lane --
+// wrong either way, since the reference's column P g is neither.  What keeps the live columns right is WHEN the phase
+// starts, not what its last lane is fed (a row-bounded shift that gives a team's last lane a zero was considered and changes
+// nothing: a zero is as wrong as the neighbour's column): column P g - 1 is wrong after the phase's first stage i0 whatever
+// it was fed, and from there what is wrong moves down one column per stage, to column P g - 1 - t after stage i0 + t.
+// Stage i0 + t + 1 reads columns <= 99 - i0 - t.  So with
+//     P g - 1 >= 100 - i0,   i0 = 101 - P g   (teams of 16: stages 5, 21, 37, 53, 69, 85 for g = 6 .. 1)
+// stage i0 finds every column it reads (<= 100 - i0) held and right, and every later stage reads below what is wrong: the
+// same argument that the one-phase loop made for column G P - 1 >= 103 from stage 1, once per phase.  Columns a repack
+// drops (>= P g) are dead for the same reason.  NaNs and infinities of a degenerate block cross a repack as bit patterns.
+template <int P>
+struct TeamSchur {
+    static constexpr int G = TeamPlan<P>::G;
+    // Teams of 8 stay on one phase, G = 13 through all stages: phased (13 -> 1 at stages 5, 13, .. 93) they issue 2.4 % fewer
+    // vector instructions and are no faster, see DESIGN.md 9.
+    static constexpr bool kPhased = P == 16;
+    static constexpr int kFirstStage(int g) { return g >= G || !kPhased ? 1 : kMaxOrder + 1 - P * g; } // i0 above
+    static constexpr int kEndStage(int g) { return g == 1 || !kPhased ? kMaxOrder : kFirstStage(g - 1); }
+};
+
+// gFrom -> gTo columns per lane: column c from lane c / gFrom, register c % gFrom, to lane c / gTo, register c % gTo.
+// (Through LDS: 2 gFrom stores, 2 gTo loads and no VALU beyond a few addresses.  ds_bpermute moves 32 bits a time from a
+// register that is the same for all lanes -- here the source register differs by lane, a select chain per column.)
+template <int P, int gFrom, int gTo>
+__device__ __forceinline__ void team_schur_repack(double (&g0)[TeamPlan<P>::G], double (&g1)[TeamPlan<P>::G], double* __restrict__ area, int p)
+{
+    double* const w = area + gFrom * p;
+    const double* const r = area + gTo * p;
+#pragma unroll
+    for (int c = 0; c < gFrom; c++) {
+        w[c] = g0[c];
+        w[P * gFrom + c] = g1[c];
+    }
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < gTo; c++) {
+        g0[c] = r[c];
+        g1[c] = r[P * gFrom + c];
+    }
+    wave_sync(); // (the next repack writes the same area)
+}
+
+// stages kFirstStage(g) .. kEndStage(g) - 1 with g columns per lane, then the phases below g
+template <int P, int g>
+__device__ __forceinline__ void team_schur_phases(double (&g0)[TeamPlan<P>::G], double (&g1)[TeamPlan<P>::G], double& ki, double& err,
+    bool keeper, double* __restrict__ k_b, double* __restrict__ area, int p)
+{
+    using S = TeamSchur<P>;
+    static_assert(S::kFirstStage(g) >= 1 && S::kFirstStage(g) < S::kEndStage(g) && P * g - 1 >= kMaxOrder - S::kFirstStage(g), "a phase starts when its last column is dead");
+#pragma unroll 1
+    for (int i = S::kFirstStage(g); i < S::kEndStage(g); i++) {
+        const double crossing = wave_shl1_zero(g1[0]);
+#pragma unroll
+        for (int r = 0; r < g; r++) {
+            const double sa = r + 1 < g ? g1[r + 1] : crossing; // gen1[j + 1], old
+            g1[r] = sa + ki * g0[r];
+            g0[r] = sa * ki + g0[r];
+        }
+        const double first = team_first<P>(g1[0]);
+        ki = -first / err;
+        err += first * ki;
+        if (keeper)
+            k_b[i] = ki;
+    }
+    if constexpr (S::kPhased && g > 1) {
+        team_schur_repack<P, g, g - 1>(g0, g1, area, p);
+        team_schur_phases<P, g - 1>(g0, g1, ki, err, keeper, k_b, area, p);
+    }
+}
+
 template <int kMode, int P>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_encode_teams(
     const int16_t* __restrict__ pcm, uint32_t n_frames, uint32_t channels, uint32_t n_sig, BlockMeta* __restrict__ meta,
@@ -1988,7 +2075,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     // Lane p holds columns j = G p + r of gen0 / gen1.  Stage i reads gen1[j + 1] (old): the next register, and for the
     // lane's last column the first register of the next lane.  Columns beyond 99 hold zeros (and what leaks in from the
     // next team's first column); stage i only uses columns below 100 - i, and what is wrong moves down one column per
-    // stage from column G P - 1 >= 103: it never gets there.
+    // stage from column G P - 1 >= 103: it never gets there.  Teams of 16 then drop to fewer columns per lane as the live
+    // triangle shrinks (TeamSchur / team_schur_phases above, where the same argument is made for every phase).
     {
         double g0[G], g1[G];
         const double next_first = wave_shl1_zero(acc[0]); // ac[G (p + 1)]
@@ -2004,21 +2092,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         err += g * ki;
         if (keeper)
             k_b[0] = ki;
-#pragma unroll 1
-        for (int i = 1; i < kMaxOrder; i++) {
-            const double crossing = wave_shl1_zero(g1[0]);
-#pragma unroll
-            for (int r = 0; r < G; r++) {
-                const double sa = r + 1 < G ? g1[r + 1] : crossing; // gen1[j + 1], old
-                g1[r] = sa + ki * g0[r];
-                g0[r] = sa * ki + g0[r];
-            }
-            g = team_first<P>(g1[0]);
-            ki = -g / err;
-            err += g * ki;
-            if (keeper)
-                k_b[i] = ki;
-        }
+        double* const area = reinterpret_cast<double*>(lds) + Plan::kSchurBase + b * Plan::kSchurStride;
+        team_schur_phases<P, G>(g0, g1, ki, err, keeper, k_b, area, p);
     }
     wave_sync();
     if (kMode == 2)
