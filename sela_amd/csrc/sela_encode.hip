@@ -212,17 +212,25 @@ __device__ __forceinline__ void rice_plan(const uint32_t (&u)[V], uint32_t n, ui
     lane_quotients = pa;
 }
 
-// x = s / 32767 (src/lpc/residue_generator.cpp:12-18) without the ~30-instruction IEEE division:
-// q0 = s * RN(1/32767), one residual fma, one correction fma.  The result equals the correctly rounded
-// quotient for EVERY |s| <= 70000 (exhaustive check: tests/test_host_logic.py::test_scale_division_is_exact);
-// 16-bit channels and their difference stay within 65535.
+// x = s / 32767 (src/lpc/residue_generator.cpp:12-18) without the ~30-instruction IEEE division, in TWO FP64 instructions,
+// for 16-bit channels and the difference of two: |s| <= 65536 ONLY.
+//   1/32767 = 2^-15 / (1 - 2^-15) = 2^-15 + 2^-30 + 2^-45 + 2^-60 + ..   Split it into a head of three terms and the rest:
+//   C1 = 2^-15 + 2^-30 + 2^-45 has 31 significant bits, so q = s * C1 (s: 17 bits) has at most 48 and is EXACT;
+//   C2 = RN(1/32767 - C1) = 2^-60 (1 + 2^-15 + 2^-30 + 2^-45 + ..) rounded, relative error 2^-53;
+//   x = fma(s, C2, q) rounds s * C2 + q ONCE, and s * C2 + q = s / 32767 (1 + d) with |d| <= 2^-53 2^-45 = 2^-98: such a
+//   sum rounds as the quotient does unless the quotient lies within 2^-98 (relative) of a rounding boundary -- and
+//   s / 32767 with a 17-bit s is either exact (s a multiple of 32767) or at least 1 / (32767 2^53) away from every 54-bit
+//   binary fraction of its binade: about 2^-69 relative.
+// Checked for every s in [-65536, 65536] with exact rationals (tests/test_scale17_exact.py), where the plain product
+// s * RN(1/32767) is wrong for 1280 values: the correction stays.  The any-length route's samples have up to 32 bits, so
+// its s * C1 is not exact: it keeps the three-instruction form (scale_any in sela_generic.hip) and must not call this one.
 __device__ __forceinline__ double scale_sample(int32_t s)
 {
-    constexpr double r = 1.0 / SELA_SAMPLE_SCALE;
+    constexpr double c1 = 0x1.00020004p-15, c2 = 0x1.0002000400080p-60;
+    static_assert(c1 == 1.0 / 32768 + 1.0 / (1 << 30) + 1.0 / (1ll << 45) && SELA_SAMPLE_SCALE == 32767.0, "the constants are those of a division by 32767");
     const double x = (double)s;
-    const double q0 = x * r;
-    const double e = __builtin_fma(-SELA_SAMPLE_SCALE, q0, x);
-    return __builtin_fma(e, r, q0);
+    const double q = x * c1; // exact
+    return __builtin_fma(x, c2, q);
 }
 
 // Signal `sig` of stereo PCM from the loaded words (left in the low half, right in the high half): 0: l, 1: r, 2: l - r
@@ -244,6 +252,21 @@ __device__ __forceinline__ void unpack_stereo(uint32_t sig, const uint32_t (&w)[
         for (int i = 0; i < kN; i++)
             raw[i] = (int32_t)(int16_t)(w[i] & 0xFFFFu) - ((int32_t)w[i] >> 16);
     }
+}
+
+// The same without a branch, for a caller that would hold the three forms' code several times over (the chunk loop of the teams of
+// 16, four copies): one v_dot2_i32_i16 per word, l * m0 + r * m1 with the multipliers (1, 0), (0, 1) or (1, -1) packed in a
+// word that is the wave's.  Exact: two products of 16-bit numbers and their sum in 32 bits, not saturated.  (unpack_stereo
+// there, whose results leave the branch in registers: the compiler extracts the low halves ahead of the branch into registers
+// of their own and copies whichever form was taken back where the paths meet, eight to ten moves per four samples.  The three
+// forms as single instructions with destinations of their own come without moves and count and run the same as this one,
+// with a dozen scalar instructions and two taken branches per chunk: built and measured)
+__device__ __forceinline__ uint32_t stereo_pick(uint32_t sig) { return sig == 0 ? 0x00000001u : sig == 1 ? 0x00010000u : 0xFFFF0001u; }
+__device__ __forceinline__ int32_t unpack_stereo_picked(uint32_t pick, uint32_t w)
+{
+    int32_t s; // (written out: from the builtin the compiler takes the two-operand form that accumulates, and clears its destination first)
+    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(s) : "v"(w), "s"(pick));
+    return s;
 }
 
 // ---- mean chain operand fetch (see k_encode_blocks): E[m..m+7] and O[m..m+7] by broadcast reads ------
@@ -1519,6 +1542,9 @@ constexpr int kTeamWin = 16;                                // window registers 
 constexpr int kTeamAhead = 3;                               // steps a fetch runs ahead of its use
 constexpr int kTeamMeanChunk = 64;                          // the mean's chunks (two of them in a ring)
 
+template <int I>
+struct IntConstant { static constexpr int value = I; }; // a compile-time number as a function argument
+
 template <int P>
 struct TeamPlan {
     static constexpr int B = kWave / P;                        // blocks per wave
@@ -1971,11 +1997,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int i = kChunk + p; i < Plan::kStride; i += P)
             ring_b[i] = 0.0;
         const int mine = kStep == 1 ? p * kPer : p; // this lane's samples of a chunk: mine + kStep i
+        // What is fetched ahead of the chunk in use.  Teams of 8: the samples of chunks c + 1 and c + 2, unpacked.  Teams of 16: the
+        // loaded words of the odd and of the even chunks, unpacked when they are staged -- two sets that take turns, so that no
+        // set is ever copied into the other (as team_row_mean_sum holds them).
         int32_t raw_a[kPer], raw_b[kPer];
+        uint32_t w_a[kPer], w_b[kPer];
+        const bool stereo = channels == 2;
         team_load_raw<kPer, kStep>(fp, channels, sig, mine, raw_a);
         team_stage<kPer, kStep, true, true, kRing>(ring_b, mine, raw_a, mean);
-        team_load_raw<kPer, kStep>(fp, channels, sig, kChunk + mine, raw_a);
-        team_load_raw<kPer, kStep>(fp, channels, sig, 2 * kChunk + mine, raw_b);
+        if constexpr (P == 16) {
+            if (stereo) {
+                team_fetch<kPer, kStep, true>(fp, channels, sig, kChunk + mine, w_a);
+                team_fetch<kPer, kStep, true>(fp, channels, sig, 2 * kChunk + mine, w_b);
+            } else {
+                team_fetch<kPer, kStep, false>(fp, channels, sig, kChunk + mine, w_a);
+                team_fetch<kPer, kStep, false>(fp, channels, sig, 2 * kChunk + mine, w_b);
+            }
+        } else {
+            team_load_raw<kPer, kStep>(fp, channels, sig, kChunk + mine, raw_a);
+            team_load_raw<kPer, kStep>(fp, channels, sig, 2 * kChunk + mine, raw_b);
+        }
         wave_sync();
         const uint32_t ring_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)ring_b;
         double W[kTeamWin], M[4];
@@ -1983,7 +2024,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int i = 0; i < kTeamWin; i++)
             W[i] = 0.0; // c[negative]
         uint32_t idx_w = (uint32_t)((kRing - G * p) % kRing); // position of index -G p
-        uint32_t idx_m = 0, pos_stage = kChunk;               // positions of index j0 / of the chunk staged next
         uint32_t addr_w = ring_addr + 8 * idx_w, addr_m = ring_addr;
         // the fetches of steps 0, 1, 2
         asm volatile("ds_read_b64 %0, %6\n\tds_read_b64 %3, %7\n\t"
@@ -1994,23 +2034,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                      : "memory");
         M[3] = 0.0;
         constexpr int kChunks = kBlock / kChunk;
-        auto trips = [&]() { // the kChunk steps of a chunk
-#pragma unroll 1
-            for (int it = 0; it < kChunk / kTeamWin; it++) {
-                team_ac_steps<G, 0>(W, M, acc, addr_w, addr_m);
-                idx_w += kTeamWin;
-                idx_w = idx_w >= (uint32_t)kRing ? idx_w - kRing : idx_w;
-                idx_m += kTeamWin;
-                idx_m = idx_m >= (uint32_t)kRing ? idx_m - kRing : idx_m;
-                addr_w = ring_addr + 8 * idx_w;
-                addr_m = ring_addr + 8 * idx_m;
-            }
-        };
-        auto stage_next = [&](const int32_t (&raw)[kPer]) { // the next chunk over the oldest one, which no lag reaches any more
-            team_stage<kPer, kStep, true, true, kRing>(ring_b, (int)pos_stage + mine, raw, mean);
-            pos_stage += kChunk;
-            pos_stage = pos_stage >= (uint32_t)kRing ? 0u : pos_stage;
-        };
         // Priorities (team_priorities, a launch argument; 0 = none).  The SIMD's arbiter serves the OLDEST of its waves first, at equal
         // priority: of three waves that start together, the first keeps nearly the whole SIMD to itself, finishes after 0.51 M
         // cycles and leaves the last one to walk its second half alone, at a lone wave's issue rate, until 0.96 M
@@ -2023,20 +2046,104 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         // (round 5): sela_hip_encode_device passes it when no other stream of the library has work pending, 0 otherwise
         // (sela_capi.hip, "does a device-pointer launch have the device to itself?").
         constexpr int kPrio2From = (int)(0.27 * kChunks), kPrio1From = (int)(0.71 * kChunks);
-#pragma unroll 1
-        for (int c = 0; c < kChunks; c++) { // (the PCM of a chunk is fetched two chunks ahead)
-            if (c == kPrio2From)
-                set_wave_priority((int)((team_priorities >> 8) & 0xFF));
-            if (c == kPrio1From)
-                set_wave_priority((int)((team_priorities >> 16) & 0xFF));
-            if (c + 1 < kChunks)
-                stage_next(raw_a); // chunk c + 1
+        if constexpr (P == 16) {
+            // Teams of 16 (round 10): four chunks of 64 are one revolution of the ring of 256, so the chunk loop runs four chunks per
+            // trip and in each of its four copies the place of the next chunk, the word set that holds it and whether it reaches
+            // the mirror are constants: every ds_write_b64 a constant offset from one per-lane base, and the mirror's lane test
+            // (entries 0 .. 23: sample 0 of every lane, sample 1 of lanes 0 .. 7) made once in front of the loop.  The two word
+            // sets take turns, so none is copied into the other.  The fetch is never under a condition (a word set that is
+            // loaded on one path only gets copied where the paths meet, and the copy waits for the load): behind the block's end
+            // it takes chunk 31 again, like team_row_mean_sum -- nothing beyond the block is read.  Its address is the wave's
+            // (scalar) plus a lane offset that never changes: one vector instruction per chunk.
+            // The 16-step trips stay an inner loop in each copy (all sixteen of a revolution unrolled would be 30 KB of code) and
+            // keep four address instructions: the multiplier's address moves on by 128 bytes and returns to the ring's start at
+            // the top of a revolution; the window's wraps at a point of the lane's own, as a byte offset mod 2048.
+            static_assert(kRing == 4 * kChunk && kChunks % 4 == 0 && kStep == P && kPer * P == kChunk && (kRing & (kRing - 1)) == 0, "a revolution is four chunks; lane p stages samples p, p + 16, ..");
+            static_assert(kTeamMirror > P && kTeamMirror <= 2 * P, "the mirror takes sample 0 of every lane and sample 1 of the lanes below kTeamMirror - P");
+            static_assert(kPrio2From % 4 == 0 && kPrio1From % 4 == 2, "where the priority changes in the unrolled loop");
+            double* const stage_b = ring_b + p;
+            const bool in_mirror_twice = p < kTeamMirror - P;
+            const uint32_t* const wave_words = reinterpret_cast<const uint32_t*>(pcm) + (size_t)frame0 * kBlock; // stereo: a word per sample pair
+            const uint32_t lane_word = (my_frame - frame0) * (uint32_t)kBlock + (uint32_t)p;
+            const uint32_t pick = stereo ? stereo_pick(sig) : 0x00000001u; // (other channel counts: team_fetch left the sample, which fits 16 bits, in the word)
+            uint32_t off_w = 8 * idx_w;
+            auto chunk_copy = [&](auto kc, int c, uint32_t (&w)[kPer]) { // chunk c = 4 r + k: stage chunk c + 1 from w, fetch chunk c + 3 into w, 64 steps
+                constexpr int k = decltype(kc)::value;
+                constexpr int pos = (k + 1) % 4 * kChunk; // over the oldest chunk, which no lag reaches any more
+                if (k != 3 || c + 1 < kChunks) {
 #pragma unroll
-            for (int i = 0; i < kPer; i++)
-                raw_a[i] = raw_b[i];
-            if (c + 3 < kChunks)
-                team_load_raw<kPer, kStep>(fp, channels, sig, (c + 3) * kChunk + mine, raw_b);
-            trips();
+                    for (int i = 0; i < kPer; i++) {
+                        const double x = scale_sample(unpack_stereo_picked(pick, w[i])) - mean;
+                        stage_b[pos + i * P] = x;
+                        if (pos == 0 && i == 0)
+                            stage_b[kRing] = x;
+                        if (pos == 0 && i == 1 && in_mirror_twice)
+                            stage_b[kRing + P] = x;
+                    }
+                }
+                const int ahead = min(c + 3, kChunks - 1);
+                if (stereo) {
+                    const uint32_t* const from = wave_words + ahead * kChunk;
+#pragma unroll
+                    for (int u = 0; u < kPer; u++)
+                        w[u] = from[lane_word + (uint32_t)(u * P)];
+                } else {
+                    team_fetch<kPer, kStep, false>(fp, channels, sig, ahead * kChunk + p, w);
+                }
+#pragma unroll 1
+                for (int it = 0; it < kChunk / kTeamWin; it++) { // the kChunk steps of a chunk
+                    team_ac_steps<G, 0>(W, M, acc, addr_w, addr_m);
+                    off_w = (off_w + 8 * kTeamWin) & (8 * kRing - 1);
+                    addr_w = ring_addr + off_w;
+                    addr_m += 8 * kTeamWin;
+                }
+            };
+#pragma unroll 1
+            for (int c = 0; c < kChunks; c += 4) { // (the PCM of a chunk is fetched two chunks ahead)
+                if (c == kPrio2From)
+                    set_wave_priority((int)((team_priorities >> 8) & 0xFF));
+                addr_m = ring_addr; // index j0 = 64 c is at the ring's start again
+                chunk_copy(IntConstant<0>(), c, w_a);
+                chunk_copy(IntConstant<1>(), c + 1, w_b);
+                if (c + 2 == kPrio1From)
+                    set_wave_priority((int)((team_priorities >> 16) & 0xFF));
+                chunk_copy(IntConstant<2>(), c + 2, w_a);
+                chunk_copy(IntConstant<3>(), c + 3, w_b);
+            }
+        } else {
+            uint32_t idx_m = 0, pos_stage = kChunk; // positions of index j0 / of the chunk staged next
+            auto trips = [&]() { // the kChunk steps of a chunk
+#pragma unroll 1
+                for (int it = 0; it < kChunk / kTeamWin; it++) {
+                    team_ac_steps<G, 0>(W, M, acc, addr_w, addr_m);
+                    idx_w += kTeamWin;
+                    idx_w = idx_w >= (uint32_t)kRing ? idx_w - kRing : idx_w;
+                    idx_m += kTeamWin;
+                    idx_m = idx_m >= (uint32_t)kRing ? idx_m - kRing : idx_m;
+                    addr_w = ring_addr + 8 * idx_w;
+                    addr_m = ring_addr + 8 * idx_m;
+                }
+            };
+            auto stage_next = [&](const int32_t (&raw)[kPer]) { // the next chunk over the oldest one, which no lag reaches any more
+                team_stage<kPer, kStep, true, true, kRing>(ring_b, (int)pos_stage + mine, raw, mean);
+                pos_stage += kChunk;
+                pos_stage = pos_stage >= (uint32_t)kRing ? 0u : pos_stage;
+            };
+#pragma unroll 1
+            for (int c = 0; c < kChunks; c++) { // (the PCM of a chunk is fetched two chunks ahead)
+                if (c == kPrio2From)
+                    set_wave_priority((int)((team_priorities >> 8) & 0xFF));
+                if (c == kPrio1From)
+                    set_wave_priority((int)((team_priorities >> 16) & 0xFF));
+                if (c + 1 < kChunks)
+                    stage_next(raw_a); // chunk c + 1
+#pragma unroll
+                for (int i = 0; i < kPer; i++)
+                    raw_a[i] = raw_b[i];
+                if (c + 3 < kChunks)
+                    team_load_raw<kPer, kStep>(fp, channels, sig, (c + 3) * kChunk + mine, raw_b);
+                trips();
+            }
         }
         // (three fetches past the end are in flight: land them before the rings are reused)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(W[0]), "+v"(W[1]), "+v"(W[2]), "+v"(M[0]), "+v"(M[1]), "+v"(M[2]));
