@@ -25,6 +25,9 @@ public:
     // Also build the data::SelaFrame objects in SelaFile::selaFrames (API fidelity).  Tools that only
     // write the file can switch this off: the byte stream is complete without them.
     static bool materializeFrames;
+    // Residues against the decoder's rounding (SELA_HIP_ENCODE_LOSSLESS): every frame decodes back exactly,
+    // with any decoder of the format.  Off: the reference's stream bit for bit.
+    bool lossless = false;
     explicit Encoder(std::ifstream& in) : ifStream(in) {}
     file::SelaFile process();
 };
@@ -42,13 +45,13 @@ public:
 // File to file (what the reference's main.cpp:29-41 does with process() + writeToFile()): the same
 // streaming read, and finished frames / samples are written out while later pieces are still on the device.
 // Return the number of frames coded.
-size_t encodeFile(std::ifstream& in, std::ofstream& out);
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless = false); // (lossless: as Encoder::lossless)
 size_t decodeFile(std::ifstream& in, std::ofstream& out);
 // The same by path -- what the CLI's -e / -d use: the file is read with several pread()s in flight on a small pool of I/O
 // threads (sela_host/fileio.hpp) while earlier pieces are on the device, and finished ranges are written by a task of
 // that pool -- over pages allocated in one go while the input was still on its way -- while later pieces are being coded.
 // One thread reads or writes a page-cache file at a few GB/s; the device codes 10 G samples/s.
-size_t encodeFile(const std::string& inPath, const std::string& outPath);
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false);
 size_t decodeFile(const std::string& inPath, const std::string& outPath);
 // Decoding for a consumer that takes the samples in order (the player, sela_host/player.hpp): begin() once the header is
 // known, then ready(pcm, n) -- on the calling thread -- whenever the first n interleaved samples of pcm are final (n only
@@ -66,6 +69,7 @@ void setIoThreads(unsigned n);
 
 // ---- verification: does this .sela give this WAV back? ---------------------------------------------------------------
 // The codec reproduces the reference bit for bit, and the reference is not lossless on every frame;
+// Encoder::lossless / encodeFile(..., true) avoid that loss;
 // the encoder also drops the WAV's samples beyond the last whole 2048-sample frame.  verifyFile() says which frames of a
 // .sela come back different from the WAV (sela_hip_verify: compared on the GPU, nothing decoded into host memory) and what
 // of the WAV the .sela never held.  A .sela whose frames say other lengths is compared at the positions decodeFile writes them.

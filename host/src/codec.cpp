@@ -49,7 +49,7 @@ size_t optimisticBytes(size_t frames, uint32_t channels)
 // still READS the old block on another thread (WriteBehind) must be through with it by then.
 template <typename Need, typename Drain>
 void streamEncode(Need need, size_t piece, int16_t* pcm, size_t frames, uint32_t channels, sela_host::PinnedBuffer<uint8_t>& bytes,
-    std::vector<uint64_t>& offsets, Drain drain, const std::function<void()>& beforeRealloc = {})
+    std::vector<uint64_t>& offsets, Drain drain, const std::function<void()>& beforeRealloc = {}, uint32_t options = 0 /* SELA_HIP_ENCODE_* */)
 {
     const size_t frameSamples = kBlock * channels;
     offsets.assign(frames + 1, 0);
@@ -59,7 +59,7 @@ void streamEncode(Need need, size_t piece, int16_t* pcm, size_t frames, uint32_t
             beforeRealloc(); // (resize frees the block the sink was draining from)
         bytes.resize(attempt == 0 ? optimisticBytes(frames, channels) : sela_hip_encode_bound_bytes((uint32_t)frames, channels));
         sela_hip_job* job = nullptr;
-        if (sela_hip_encode_begin(&job, channels, (uint32_t)frames, bytes.data(), bytes.size(), offsets.data()) != SELA_HIP_OK)
+        if (sela_hip_encode_begin_opt(&job, channels, (uint32_t)frames, bytes.data(), bytes.size(), offsets.data(), options) != SELA_HIP_OK)
             gpuFailure("Encoder");
         int rc = SELA_HIP_OK;
         for (size_t f0 = 0; f0 < frames && rc == SELA_HIP_OK; f0 += piece) {
@@ -353,7 +353,7 @@ file::SelaFile Encoder::process()
     sela_host::PinnedBuffer<uint8_t> bytes;
     std::vector<uint64_t> offsets;
     streamEncode(StreamReader{ ifStream, wavFile.pcm.data(), kBlock * channels }, kPieceFrames, wavFile.pcm.data(), frames, channels, bytes, offsets,
-        [](const uint8_t*, size_t) {});
+        [](const uint8_t*, size_t) {}, {}, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
     const size_t coded = frames * kBlock * channels;
     if (wavFile.pcm.size() > coded && !readExact(ifStream, wavFile.pcm.data() + coded, (wavFile.pcm.size() - coded) * 2))
         throw data::Exception("data subChunk is shorter than its header says");
@@ -383,7 +383,7 @@ file::WavFile Decoder::process()
     return out;
 }
 
-size_t encodeFile(std::ifstream& in, std::ofstream& out)
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless)
 {
     file::WavFile wav;
     const size_t dataBytes = wav.readHeader(in);
@@ -406,7 +406,7 @@ size_t encodeFile(std::ifstream& in, std::ofstream& out)
             out.write(reinterpret_cast<const char*>(p + written), (std::streamsize)(done - written));
             written = done;
         }
-    });
+    }, {}, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
     return frames;
 }
 
@@ -669,12 +669,12 @@ SelaInfo probeSela(const std::string& path)
 // kFeedFrames, sink(bytes, final) is told whenever more of the output is final.  Returns the total.
 template <typename Sink>
 size_t encodeRange(const sela_host::PosixFile& in, const WavInfo& info, size_t first, size_t n, sela_host::PinnedBuffer<int16_t>& pcm,
-    sela_host::PinnedBuffer<uint8_t>& bytes, std::vector<uint64_t>& offsets, Sink sink, const std::function<void()>& sinkQuiesce = {})
+    sela_host::PinnedBuffer<uint8_t>& bytes, std::vector<uint64_t>& offsets, Sink sink, const std::function<void()>& sinkQuiesce = {}, uint32_t options = 0)
 {
     const size_t frameBytes = kBlock * info.channels * 2;
     pcm.resize(n * kBlock * info.channels);
     sela_host::ReadAhead ahead(in, pcm.data(), info.dataOffset + first * frameBytes, n * frameBytes, kFeedFrames * frameBytes, kIoSubBytes);
-    streamEncode([&](size_t upTo) { ahead.need(upTo * frameBytes); }, kFeedFrames, pcm.data(), n, info.channels, bytes, offsets, sink, sinkQuiesce);
+    streamEncode([&](size_t upTo) { ahead.need(upTo * frameBytes); }, kFeedFrames, pcm.data(), n, info.channels, bytes, offsets, sink, sinkQuiesce, options);
     ahead.finish();
     return bytes.size();
 }
@@ -685,7 +685,7 @@ size_t expectedSelaBytes(const WavInfo& info) { return info.frames * kBlock * in
 
 void setIoThreads(unsigned n) { sela_host::IoPool::configure(n); }
 
-size_t encodeFile(const std::string& inPath, const std::string& outPath)
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless)
 {
     const WavInfo info = probeWav(inPath);
     const sela_host::PosixFile in = sela_host::PosixFile::openForRead(inPath);
@@ -698,7 +698,8 @@ size_t encodeFile(const std::string& inPath, const std::string& outPath)
     std::vector<uint64_t> offsets;
     // (the pages of the output are allocated in one go while the input is read and coded: audio codes to about 3/4)
     sela_host::WriteBehind behind(out, 15, kIoSubBytes, expectedSelaBytes(info));
-    const size_t total = encodeRange(in, info, 0, info.frames, pcm, bytes, offsets, [&](const uint8_t* p, size_t done) { behind.drain(p, done); }, [&] { behind.quiesce(); });
+    const size_t total = encodeRange(in, info, 0, info.frames, pcm, bytes, offsets, [&](const uint8_t* p, size_t done) { behind.drain(p, done); }, [&] { behind.quiesce(); },
+        lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
     behind.finish(&total);
     return info.frames;
 }

@@ -1,5 +1,8 @@
 // sela_cli.cpp -- command line front end of the MI355X SELA host:
 //   sela_mi355x -e in.wav out.sela     encode
+//   sela_mi355x -e --lossless in.wav out.sela   encode with the residues taken against the decoder's rounding: every frame comes
+//                                      back exactly from any decoder of the format (plain -e is the reference's stream bit for bit,
+//                                      a few frames in ten thousand of which do not: -v lists them)
 //   sela_mi355x -d in.sela out.wav     decode
 //   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
 //                                      what of in.wav it never held; exit 0: all of it comes back exactly, 3: a frame differs or
@@ -31,7 +34,8 @@ namespace {
 int usage(const std::string& program)
 {
     std::cout << "Usage:\n\n"
-              << "Encoding a file:\n" << program << " -e path/to/input.wav path/to/output.sela\n\n"
+              << "Encoding a file (--lossless: every frame decodes back exactly; without it the reference's stream bit for bit):\n"
+              << program << " -e [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Decoding a file:\n" << program << " -d path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
@@ -95,6 +99,14 @@ int run(int argc, char** argv)
 {
     const std::string program = argv[0];
     const std::string verb = argc > 1 ? argv[1] : "";
+    for (int i = 2; i < argc; i++) // (--lossless is -e's alone: anywhere else it is refused, not ignored)
+        if (std::string(argv[i]) == "--lossless" && !(verb == "-e" && i == 2 && argc == 5))
+            return usage(program);
+    if (verb == "-e" && argc == 5 && std::string(argv[2]) == "--lossless") {
+        std::cout << "Encoding (lossless): " << argv[3] << std::endl;
+        sela::encodeFile(std::string(argv[3]), std::string(argv[4]), true);
+        return 0;
+    }
     if ((verb == "-E" || verb == "-D") && argc >= 4) {
         const int rc = batch(verb, argc, argv);
         return rc == 2 ? usage(program) : rc;

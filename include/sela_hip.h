@@ -26,6 +26,10 @@
  *             back to back.  frame_offsets[f] is the byte offset of frame f in that stream,
  *             frame_offsets[n_frames] its total size.  Every frame size is a multiple of 4.
  *
+ * The plain encode calls write the reference's stream bit for bit -- which a few frames in ten thousand do not decode back to
+ * their PCM.  The *_opt calls with SELA_HIP_ENCODE_LOSSLESS write a stream every decoder of the format reads back
+ * exactly (see "encode options" below); the verify calls tell the two apart frame by frame.
+ *
  * All functions return 0 on success or a negative SELA_HIP_E* code; they never throw and never
  * fall back to a CPU implementation.  sela_hip_last_error() gives a thread-local message.
  *
@@ -355,7 +359,8 @@ int sela_hip_decode_n_status_error(const uint32_t* status /* [4], host copy */);
 
 /* ---- verification: a stream against its PCM, frame by frame ----------------------------------------------
  * The codec reproduces the reference bit for bit, and the reference is not lossless on every frame.  These calls
- * say which frames of a stream come back different from the PCM they were made from, and where: what sela_hip_decode_n_device
+ * say which frames of a stream come back different from the PCM they were made from, and where (a caller avoids the loss with
+ * SELA_HIP_ENCODE_LOSSLESS, "encode options" below): what sela_hip_decode_n_device
  * does, with a compare where it stores -- on the 2048-sample route (up to eight channels) in one kernel that writes no PCM at all.
  *   d_pcm          int16, the layout sela_hip_decode writes: frame f at d_pcm + sample_offsets[f] * channels.  Read only.
  *   d_diff_counts  [n_frames]: the (sample, channel) values of frame f that sela_hip_decode_n_device would have written
@@ -439,6 +444,39 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
     const int32_t* samples /* [n_frames][channels][stride] */, const uint32_t* lengths /* [n_frames * channels] or NULL */,
     uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
 
+/* ---- encode options: the lossless mode ----------------------------------------------------------------------
+ * The reference's encoder predicts with (2^34 + sum) >> 35 and its decoder with -((2^34 - sum) >> 35): where 2^34 + sum is a
+ * multiple of 2^35 the two differ by one, and the frame does not come back as it went in.  With SELA_HIP_ENCODE_LOSSLESS the
+ * residues are taken against the DECODER's prediction, so that every decoder of the format -- the reference's included --
+ * rebuilds every sample exactly.  Order, coefficients, Rice coding, the stereo rule and the frame layout are what they are; the
+ * stream differs from the plain call's only in frames that hold such a tie (one residue by 1, and what follows from it).
+ *
+ * Every *_opt call takes exactly the arguments of its namesake and a trailing `options` word:
+ *   options == 0                an alias of the namesake (it calls it).
+ *   a bit not defined here      SELA_HIP_EINVAL.
+ *   SELA_HIP_ENCODE_LOSSLESS with d_trace != NULL: SELA_HIP_EINVAL (the trace is the reference's arithmetic).
+ * In both error cases nothing is enqueued.  Workspace sizes, bounds, alignment, status words, errors and graph capture are the
+ * namesake's, and so is the choice of kernels.  The host-pointer one-shot calls with options != 0 do not go through the
+ * coalescer; a thread with a streaming job open gets them from the any-length route, which leaves that job alone.  For a
+ * streaming job the option belongs to the job: feed / end are sela_hip_encode_feed / sela_hip_encode_end.
+ * The stage calls (sela_hip_lpc_encode*) have no option: their residues stay the reference's class's. */
+#define SELA_HIP_ENCODE_LOSSLESS 1u
+int sela_hip_encode_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream,
+    uint32_t options);
+int sela_hip_encode_n_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes,
+    void* stream, uint32_t options);
+int sela_hip_encode_i32_device_opt(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes,
+    void* stream, uint32_t options);
+int sela_hip_encode_opt(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
+    size_t frames_cap, uint64_t* frame_offsets_out, uint32_t options);
+int sela_hip_encode_i32_opt(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out, uint32_t options);
+int sela_hip_encode_ragged_i32_opt(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out,
+    size_t frame_cap, size_t* frame_bytes, uint32_t options);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel
@@ -461,6 +499,9 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
 typedef struct sela_hip_job sela_hip_job;
 int sela_hip_encode_begin(sela_hip_job** job, uint32_t channels, uint32_t total_frames, uint8_t* frames_out, size_t frames_cap,
     uint64_t* frame_offsets_out /* [total_frames + 1] */);
+/* (options: see "encode options" above; they hold for every feed of the job) */
+int sela_hip_encode_begin_opt(sela_hip_job** job, uint32_t channels, uint32_t total_frames, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out /* [total_frames + 1] */, uint32_t options);
 int sela_hip_encode_feed(sela_hip_job* job, const int16_t* pcm, uint32_t n_frames, uint32_t* frames_final, uint64_t* bytes_final);
 int sela_hip_encode_end(sela_hip_job* job, uint32_t* frames_final, uint64_t* bytes_final);
 int sela_hip_decode_begin(sela_hip_job** job, uint32_t channels, uint32_t total_frames, int16_t* pcm_out);

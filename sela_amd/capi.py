@@ -37,7 +37,11 @@ EXPORTS = [
     "sela_hip_encode_i32_workspace_bytes", "sela_hip_encode_i32_device", "sela_hip_encode_n_device", "sela_hip_encode_status_error",
     "sela_hip_verify_workspace_bytes", "sela_hip_verify_device", "sela_hip_verify_payload_device", "sela_hip_verify",
     "sela_hip_verify_i32_workspace_bytes", "sela_hip_verify_i32_device", "sela_hip_verify_payload_i32_device", "sela_hip_verify_i32",
+    "sela_hip_encode_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
+    "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt",
 ]
+ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
+
 
 
 # the test hooks include/sela_hip_debug.h declares (not part of the boundary)
@@ -152,6 +156,17 @@ def lib() -> C.CDLL:
     L.sela_hip_encode_i32_device.restype = C.c_int
     L.sela_hip_encode_n_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]
     L.sela_hip_encode_n_device.restype = C.c_int
+    # the *_opt calls: their namesakes' arguments and a trailing options word (SELA_HIP_ENCODE_LOSSLESS)
+    L.sela_hip_encode_device_opt.argtypes = L.sela_hip_encode_device.argtypes + [u32]
+    L.sela_hip_encode_i32_device_opt.argtypes = L.sela_hip_encode_i32_device.argtypes + [u32]
+    L.sela_hip_encode_n_device_opt.argtypes = L.sela_hip_encode_n_device.argtypes + [u32]
+    L.sela_hip_encode_opt.argtypes = L.sela_hip_encode.argtypes + [u32]
+    L.sela_hip_encode_i32_opt.argtypes = [vp, u32, u32, u32, vp, sz, vp, u32]
+    L.sela_hip_encode_ragged_i32_opt.argtypes = [vp, vp, u32, vp, sz, vp, u32]
+    L.sela_hip_encode_begin_opt.argtypes = [C.POINTER(C.c_void_p), u32, u32, vp, sz, vp, u32]
+    for name in ("sela_hip_encode_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
+                 "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt"):
+        getattr(L, name).restype = C.c_int
     L.sela_hip_encode_status_error.argtypes = [vp]
     L.sela_hip_encode_status_error.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]

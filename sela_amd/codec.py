@@ -38,10 +38,16 @@ class EncodedFrames:
 
 
 class Encoder:
-    """Reusable device buffers for encoding batches of up to `max_frames` frames on the current device."""
+    """Reusable device buffers for encoding batches of up to `max_frames` frames on the current device.
+    lossless: SELA_HIP_ENCODE_LOSSLESS -- residues against the decoder's rounding, so that every frame decodes back exactly
+    (not together with with_trace: the trace is the reference's arithmetic)."""
 
-    def __init__(self, max_frames: int, channels: int, device=None, with_trace: bool = False):
+    def __init__(self, max_frames: int, channels: int, device=None, with_trace: bool = False, lossless: bool = False):
         import torch
+
+        if lossless and with_trace:
+            raise ValueError("lossless and with_trace exclude each other")
+        self.options = capi.ENCODE_LOSSLESS if lossless else 0
 
         self.torch = torch
         self.lib = capi.lib()
@@ -70,10 +76,13 @@ class Encoder:
         n_frames = pcm.shape[0]
         assert pcm.shape[1] == BLOCK and pcm.shape[2] == self.channels and n_frames <= self.max_frames
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(self.lib.sela_hip_encode_device(
-            pcm.data_ptr(), n_frames, self.channels, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
-            status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-            self.trace.data_ptr() if self.trace is not None else None, stream))
+        args = (pcm.data_ptr(), n_frames, self.channels, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+                status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                self.trace.data_ptr() if self.trace is not None else None, stream)
+        if self.options:
+            capi.check(self.lib.sela_hip_encode_device_opt(*args, self.options))
+        else:
+            capi.check(self.lib.sela_hip_encode_device(*args))
         return EncodedFrames(self.frames, self.offsets[: n_frames + 1], status, n_frames, self.channels)
 
     def traces(self, n_frames: int):
@@ -485,10 +494,12 @@ class Encoder32:
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
     asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the host route's
     estimate -- 4.5 bytes per sample, which holds noise of up to 20 bits -- not the certain bound; a call that did not fit says
-    so in check(), and needed_bytes() is what it needs."""
+    so in check(), and needed_bytes() is what it needs.  lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder."""
 
-    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, capacity=None, device=None):
+    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, capacity=None, device=None, lossless: bool = False):
         import torch
+
+        self.options = capi.ENCODE_LOSSLESS if lossless else 0
 
         self.torch = torch
         self.lib = capi.lib()
@@ -514,14 +525,14 @@ class Encoder32:
         n_frames = samples.shape[0]
         if samples.dtype == torch.int32:
             assert tuple(samples.shape[1:]) == (self.channels, self.n)
-            call = self.lib.sela_hip_encode_i32_device
+            call = self.lib.sela_hip_encode_i32_device_opt if self.options else self.lib.sela_hip_encode_i32_device
         else:
             assert samples.dtype == torch.int16 and tuple(samples.shape[1:]) == (self.n, self.channels)
-            call = self.lib.sela_hip_encode_n_device
+            call = self.lib.sela_hip_encode_n_device_opt if self.options else self.lib.sela_hip_encode_n_device
         assert n_frames <= self.max_frames
         stream = torch.cuda.current_stream(self.device).cuda_stream
         capi.check(call(samples.data_ptr(), n_frames, self.channels, self.n, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
-                        self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+                        self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream, *((self.options,) if self.options else ())))
         self.n_frames = n_frames
         return self.frames, self.offsets[: n_frames + 1], self.status
 
@@ -548,16 +559,19 @@ def encode_status_error(status) -> int:
 
 
 # ---- host-pointer API on numpy arrays (what the C++ host calls) --------------------------------------
-def encode_host(pcm: np.ndarray):
+def encode_host(pcm: np.ndarray, lossless: bool = False):
     """pcm: int16 [n_frames, n, channels] (n = 2048: the fast kernels; anything else in 1..65535: the any-length route)
-    -> (frames uint8[...], offsets uint64[n_frames+1])."""
+    -> (frames uint8[...], offsets uint64[n_frames+1]).  lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_opt)."""
     lib = capi.lib()
     p = np.ascontiguousarray(pcm, dtype=np.int16)
     n_frames, n, ch = p.shape
     cap = max(2 * p.nbytes, 4096) if n == BLOCK else int(lib.sela_hip_encode_bound_bytes_n(n_frames, ch, n))
     frames = np.empty(cap, np.uint8)
     offs = np.zeros(n_frames + 1, np.uint64)
-    capi.check(lib.sela_hip_encode(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
+    if lossless:
+        capi.check(lib.sela_hip_encode_opt(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS))
+    else:
+        capi.check(lib.sela_hip_encode(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
     return frames[: int(offs[n_frames])].copy(), offs
 
 
@@ -587,20 +601,25 @@ def index_samples(frames: np.ndarray, offsets: np.ndarray, channels: int):
     return so, int(largest)
 
 
-def encode_i32(samples: np.ndarray):
-    """frame::FrameEncoder on data::WavFrame values: samples int32 [n_frames, channels, n] -> (frames uint8[...], offsets)."""
+def encode_i32(samples: np.ndarray, lossless: bool = False):
+    """frame::FrameEncoder on data::WavFrame values: samples int32 [n_frames, channels, n] -> (frames uint8[...], offsets).
+    lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_i32_opt)."""
     lib = capi.lib()
     p = np.ascontiguousarray(samples, dtype=np.int32)
     n_frames, ch, n = p.shape
     cap = int(lib.sela_hip_encode_bound_bytes_n(n_frames, ch, n))
     frames = np.empty(max(cap, 16), np.uint8)
     offs = np.zeros(n_frames + 1, np.uint64)
-    capi.check(lib.sela_hip_encode_i32(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
+    if lossless:
+        capi.check(lib.sela_hip_encode_i32_opt(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS))
+    else:
+        capi.check(lib.sela_hip_encode_i32(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
     return frames[: int(offs[n_frames])].copy(), offs
 
 
-def encode_ragged(channels) -> bytes:
-    """frame::FrameEncoder on a data::WavFrame whose channels differ in length: list of int32 arrays -> the frame's bytes."""
+def encode_ragged(channels, lossless: bool = False) -> bytes:
+    """frame::FrameEncoder on a data::WavFrame whose channels differ in length: list of int32 arrays -> the frame's bytes.
+    lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_ragged_i32_opt)."""
     lib = capi.lib()
     chans = [np.ascontiguousarray(c, dtype=np.int32).ravel() for c in channels]
     flat = np.concatenate(chans)
@@ -608,7 +627,10 @@ def encode_ragged(channels) -> bytes:
     cap = 4 + sum(int(lib.sela_hip_encode_bound_bytes_n(1, 1, len(c))) for c in chans)
     out = np.empty(cap, np.uint8)
     used = C.c_size_t(0)
-    capi.check(lib.sela_hip_encode_ragged_i32(flat.ctypes.data, lengths.ctypes.data, len(chans), out.ctypes.data, cap, C.byref(used)))
+    if lossless:
+        capi.check(lib.sela_hip_encode_ragged_i32_opt(flat.ctypes.data, lengths.ctypes.data, len(chans), out.ctypes.data, cap, C.byref(used), capi.ENCODE_LOSSLESS))
+    else:
+        capi.check(lib.sela_hip_encode_ragged_i32(flat.ctypes.data, lengths.ctypes.data, len(chans), out.ctypes.data, cap, C.byref(used)))
     return out[: used.value].tobytes()
 
 

@@ -32,7 +32,8 @@ void set_encode_hashes(int on);
 hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, sela_hip_trace* d_trace, hipStream_t stream,
     hipEvent_t* ev, uint64_t* d_phase_cycles, const EncodeHostLink* link, int force_plain_fir, int self_blocks_override, int team_lanes,
-    int32_t* d_trace_residues = nullptr, uint32_t priorities = 0, int phase = 0, const uint64_t* plan_base = nullptr, bool plan_accumulate = false);
+    int32_t* d_trace_residues = nullptr, uint32_t priorities = 0, int phase = 0, const uint64_t* plan_base = nullptr, bool plan_accumulate = false,
+    bool lossless = false);
 uint32_t encode_split_frames(uint32_t n_frames, uint32_t channels, int permille);
 hipError_t launch_stage_rice_encode(const int32_t* d_values, const uint64_t* d_value_offsets, uint32_t n_streams, uint32_t* d_k, uint32_t* d_word_counts,
     uint32_t* d_words, const uint64_t* d_word_offsets, uint32_t* d_status, hipStream_t stream);
@@ -51,7 +52,8 @@ hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32
 void generic_release();
 void generic_shutdown();
 size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
-int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out);
+int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out,
+    bool lossless = false);
 uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint64_t* sample_offsets, bool* all_standard);
 int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
     uint32_t* counts_out, int16_t* pcm_out, const uint64_t* sample_offsets);
@@ -82,7 +84,7 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false);
 } // namespace sela
 
 namespace {
@@ -503,6 +505,7 @@ struct EncodeFeed {      // one feed of an encode job = one launch
 
 struct sela_hip_job {
     bool encode = false;
+    bool lossless = false; // encode: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_begin_opt), for every feed
     uint32_t channels = 0, total_frames = 0;
     uint32_t fed = 0;      // frames handed to feed() so far
     int error = SELA_HIP_OK;
@@ -639,7 +642,7 @@ hipError_t issue_encode_feed(sela_hip_job* job, EncodeFeed& feed, size_t index, 
     }
     uint32_t* d_status = reinterpret_cast<uint32_t*>(pos + 2);
     e = sela::launch_encode(static_cast<const int16_t*>(ctx().enc_pcm.ptr), feed.n_frames, job->channels, job->out_mapped, job->frames_cap, nullptr, d_status,
-        ctx().enc_workspace.ptr, nullptr, s, nullptr, nullptr, &link, g_force_plain_fir, g_self_blocks, 0);
+        ctx().enc_workspace.ptr, nullptr, s, nullptr, nullptr, &link, g_force_plain_fir, g_self_blocks, 0, nullptr, 0, 0, nullptr, false, job->lossless);
     if (e == hipSuccess && !feed.done)
         e = hipEventCreateWithFlags(&feed.done, hipEventDisableTiming);
     if (e == hipSuccess)
@@ -1364,8 +1367,10 @@ size_t sela_hip_encode_bound_bytes(uint32_t n_frames, uint32_t channels)
     return (size_t)n_frames * sela_frame_bytes(channels, channels * (uint32_t)sela::kSlotWords);
 }
 
-int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream)
+namespace {
+// sela_hip_encode_device and, with lossless, sela_hip_encode_device_opt: the checks, the choice of kernels, the launch
+int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream, bool lossless)
 {
     if (channels == 0 || channels > 255)
         return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
@@ -1408,20 +1413,20 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
                 e = hipStreamWaitEvent(side, sp.begun[dev], 0);
             if (e == hipSuccess) // the first half's blocks, on the caller's stream
                 e = sela::launch_encode(d_pcm, first, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, nullptr, st, nullptr, nullptr, nullptr,
-                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1);
+                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1, nullptr, false, lossless);
             if (e == hipSuccess) // the second half's, beside them
                 e = sela::launch_encode(pcm2, rest, channels, d_frames, frames_cap, d_frame_offsets + first, d_status, ws2, nullptr, side, nullptr, nullptr, nullptr,
-                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1);
+                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1, nullptr, false, lossless);
             if (e == hipSuccess)
                 e = hipEventRecord(sp.half_done[dev], side);
             if (e == hipSuccess) // the first half's plan + assemble, under the second half's tail
                 e = sela::launch_encode(d_pcm, first, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, nullptr, st, nullptr, nullptr, nullptr,
-                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2);
+                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2, nullptr, false, lossless);
             if (e == hipSuccess)
                 e = hipStreamWaitEvent(st, sp.half_done[dev], 0);
             if (e == hipSuccess) // the second half's frames behind the first's
                 e = sela::launch_encode(pcm2, rest, channels, d_frames, frames_cap, d_frame_offsets + first, d_status, ws2, nullptr, st, nullptr, nullptr, nullptr,
-                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2, d_frame_offsets + first, true);
+                    g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2, d_frame_offsets + first, true, lossless);
             sp.last[d_workspace] = std::make_pair(n_frames, first);
             g_launches_split.fetch_add(1, std::memory_order_relaxed);
             split_done = true;
@@ -1430,7 +1435,7 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
     if (!split_done) {
         e = sela::launch_encode(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
             d_trace, st, ev, g_phase_cycles, use_fused ? &fused : nullptr, g_force_plain_fir, g_self_blocks, g_team_lanes, nullptr,
-            priorities);
+            priorities, 0, nullptr, false, lossless);
         if (n_frames) {
             std::lock_guard<std::mutex> lock(splitter().mu);
             const auto it = splitter().last.find(d_workspace);
@@ -1444,6 +1449,36 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
         if (!stream_is_capturing(static_cast<hipStream_t>(stream)))
             flights().note(dev, static_cast<hipStream_t>(stream));
     return SELA_HIP_OK;
+}
+
+// what every *_opt call asks first; SELA_HIP_OK or the failure, reported
+int check_encode_options(uint32_t options)
+{
+    if (options & ~(uint32_t)SELA_HIP_ENCODE_LOSSLESS)
+        return fail(SELA_HIP_EINVAL, "options: a bit this library does not know (SELA_HIP_ENCODE_LOSSLESS is the only one)");
+    return SELA_HIP_OK;
+}
+} // namespace
+
+int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream)
+{
+    return encode_device_call(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, d_trace, stream, false);
+}
+
+int sela_hip_encode_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_device(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, d_trace, stream);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (d_trace)
+        return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS with d_trace: the trace is the reference's arithmetic");
+    if (g_phase_cycles)
+        return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS while sela_hip_debug_phase_buffer is set: the phase counts are the plain kernels'");
+    return encode_device_call(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, nullptr, stream, true);
 }
 
 namespace {
@@ -1649,7 +1684,7 @@ int sela_hip_decode_status_error(const uint32_t* status)
 namespace {
 // what sela_hip_encode_i32_device and sela_hip_encode_n_device check alike, then the launch; no lease, no coalescer, no wait
 int encode_i32_device_call(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, size_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, bool lossless = false)
 {
     if (channels == 0 || channels > 255)
         return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
@@ -1664,7 +1699,7 @@ int encode_i32_device_call(const void* d_input, bool in16, uint32_t n_frames, ui
     if (workspace_bytes < sela::encode_i32_device_workspace_bytes(n_frames, channels, n))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_i32_workspace_bytes()");
     const hipError_t e = sela::launch_encode_i32_device(d_input, in16, n_frames, channels, n, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-        static_cast<hipStream_t>(stream));
+        static_cast<hipStream_t>(stream), lossless);
     return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "encode_i32 launch");
 }
 } // namespace
@@ -1686,6 +1721,32 @@ int sela_hip_encode_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t c
 {
     return encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
         workspace_bytes, stream);
+}
+
+int sela_hip_encode_i32_device_opt(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_i32_device(d_samples, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+            workspace_bytes, stream);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    return encode_i32_device_call(d_samples, false, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+        workspace_bytes, stream, true);
+}
+
+int sela_hip_encode_n_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_n_device(d_pcm, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+            workspace_bytes, stream);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    return encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+        workspace_bytes, stream, true);
 }
 
 // the any-length route's checks after its plan, in its order (flags_error, then the capacity: generic_encode in sela_capi_generic.hip)
@@ -2010,6 +2071,20 @@ int sela_hip_encode_begin(sela_hip_job** job, uint32_t channels, uint32_t total_
     return SELA_HIP_OK;
 }
 
+int sela_hip_encode_begin_opt(sela_hip_job** job, uint32_t channels, uint32_t total_frames, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_begin(job, channels, total_frames, frames_out, frames_cap, frame_offsets_out);
+    int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    rc = sela_hip_encode_begin(job, channels, total_frames, frames_out, frames_cap, frame_offsets_out);
+    if (rc == SELA_HIP_OK)
+        (*job)->lossless = true; // (nothing is launched before the first feed)
+    return rc;
+}
+
 int sela_hip_encode_feed(sela_hip_job* job, const int16_t* pcm, uint32_t n_frames, uint32_t* frames_final, uint64_t* bytes_final)
 {
     if (!job || !job->encode || (n_frames && !pcm) || (uint64_t)job->fed + n_frames > job->total_frames)
@@ -2085,10 +2160,10 @@ int sela_hip_decode_end(sela_hip_job* job, uint32_t* frames_final)
 namespace {
 
 // One call, as it is: a job of one feed.
-int encode_now(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out)
+int encode_now(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out, uint32_t options = 0)
 {
     sela_hip_job* job = nullptr;
-    int rc = sela_hip_encode_begin(&job, channels, n_frames, frames_out, frames_cap, frame_offsets_out);
+    int rc = sela_hip_encode_begin_opt(&job, channels, n_frames, frames_out, frames_cap, frame_offsets_out, options);
     if (rc != SELA_HIP_OK)
         return rc;
     rc = sela_hip_encode_feed(job, pcm, n_frames, nullptr, nullptr);
@@ -2206,6 +2281,25 @@ int sela_hip_encode(const int16_t* pcm, uint32_t n_frames, uint32_t channels, ui
     return submit_small(Coalescer::kEncode, call);
 }
 
+// options != 0: past the coalescer (its batches are the plain call's).  2048-sample frames go to the fast kernels as a job of one
+// feed -- unless the thread has a job open, which is left alone: then, and for every other length, the any-length route.
+int sela_hip_encode_opt(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
+    size_t frames_cap, uint64_t* frame_offsets_out, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode(pcm, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (samples_per_channel == 0 || samples_per_channel > 65535)
+        return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
+    if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!pcm || !frames_out)))
+        return fail(SELA_HIP_EINVAL, "bad argument");
+    if (samples_per_channel != SELA_HIP_SAMPLES_PER_FRAME || (g_lease.held && g_lease.held->job_open))
+        return sela::generic_encode(pcm, true, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, true);
+    return encode_now(pcm, n_frames, channels, frames_out, frames_cap, frame_offsets_out, options);
+}
+
 namespace {
 // the fast route: 2048 samples per channel and frame
 int decode_standard(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* pcm_out)
@@ -2300,10 +2394,27 @@ int sela_hip_encode_i32(const int32_t* samples, uint32_t n_frames, uint32_t chan
     return submit_small(Coalescer::kEncode32, call);
 }
 
+// options != 0: straight to the any-length route (past the coalescer, whose batches are the plain call's)
+int sela_hip_encode_i32_opt(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out, uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_i32(samples, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (samples_per_channel == 0 || samples_per_channel > 65535)
+        return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
+    if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!samples || !frames_out)))
+        return fail(SELA_HIP_EINVAL, "bad argument");
+    return sela::generic_encode(samples, false, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, true);
+}
+
+namespace {
 // One frame whose channels differ in length (src/frame/frame_encoder.cpp:11-102): every channel is a block of its own -- coded
 // as a one-channel frame of its own length by the any-length kernels -- and the frame is their subframes, renamed, behind one
 // sync word; the second channel of an exactly-stereo frame against the difference channel 0 - channel 1 over its own length.
-int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap, size_t* frame_bytes)
+int encode_ragged_call(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap, size_t* frame_bytes, bool lossless)
 {
     if (channels == 0 || channels > 255 || !samples || !lengths || !frame_out || !frame_bytes)
         return fail(SELA_HIP_EINVAL, "bad argument");
@@ -2318,7 +2429,7 @@ int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, 
     auto mono = [&](const int32_t* x, uint32_t n, std::vector<uint8_t>& bytes, uint32_t& words) -> int {
         bytes.resize(sela::generic_encode_bound_bytes(1, 1, n));
         uint64_t offs[2] = { 0, 0 };
-        const int rc = sela::generic_encode(x, false, 1, 1, n, bytes.data(), bytes.size(), offs);
+        const int rc = sela::generic_encode(x, false, 1, 1, n, bytes.data(), bytes.size(), offs, lossless);
         if (rc != SELA_HIP_OK)
             return rc;
         bytes.resize((size_t)offs[1]);
@@ -2361,6 +2472,23 @@ int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, 
     }
     *frame_bytes = at;
     return SELA_HIP_OK;
+}
+} // namespace
+
+int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap, size_t* frame_bytes)
+{
+    return encode_ragged_call(samples, lengths, channels, frame_out, frame_cap, frame_bytes, false);
+}
+
+int sela_hip_encode_ragged_i32_opt(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap, size_t* frame_bytes,
+    uint32_t options)
+{
+    if (options == 0)
+        return sela_hip_encode_ragged_i32(samples, lengths, channels, frame_out, frame_cap, frame_bytes);
+    const int rc = check_encode_options(options);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    return encode_ragged_call(samples, lengths, channels, frame_out, frame_cap, frame_bytes, true);
 }
 
 int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,

@@ -274,7 +274,7 @@ size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t
 constexpr size_t kEagerBytes = (size_t)4 << 20;
 
 int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap,
-    uint64_t* frame_offsets_out)
+    uint64_t* frame_offsets_out, bool lossless /* SELA_HIP_ENCODE_LOSSLESS */)
 {
     if (device_ready() != SELA_HIP_OK)
         return SELA_HIP_ENODEV;
@@ -332,7 +332,7 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
         if (e == hipSuccess)
             e = hipMemsetAsync(d_words, 0, (est_words + 2) * 4, st);
         if (e == hipSuccess)
-            e = launch_generic_analyse(d_in, in16, cf, channels, n_sig, n, d_sig, d_res, d_q, d_meta, st);
+            e = launch_generic_analyse(d_in, in16, cf, channels, n_sig, n, d_sig, d_res, d_q, d_meta, st, lossless);
         if (e == hipSuccess)
             e = launch_generic_plan(d_meta, cf, channels, n_sig, base_bytes, d_offsets, d_word_base, d_chosen, d_status, d_head + 2, st);
         if (e == hipSuccess)

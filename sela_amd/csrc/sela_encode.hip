@@ -437,6 +437,8 @@ __device__ __forceinline__ const double* fir_group_coefs(const double* a_f, int 
 // far).  Slow, out of line, and never needed by 16-bit audio (its predictors stay below 2^37: the
 // dequantisation tables cap every reflection coefficient); tests reach it through
 // sela_hip_debug_force_plain_fir, which sends every block of the PRODUCT instantiation down this branch.
+// kDecoderRounding (the lossless mode): the decoder's prediction -(int32)((2^34 - sum) >> 35) instead.
+template <bool kDecoderRounding>
 __device__ __attribute__((noinline)) void fir_plain(int order, int lane, const int32_t* sT, const int64_t* a, uint32_t* pred_out)
 {
 #pragma unroll 1
@@ -447,7 +449,10 @@ __device__ __attribute__((noinline)) void fir_plain(int order, int lane, const i
             const int e = kPadS + 32 * lane + t - j;
             sum += (uint64_t)a[j] * (uint64_t)(int64_t)sT[e + (e >> 5)];
         }
-        pred_out[t * 64 + lane] = (uint32_t)(int32_t)((int64_t)sum >> SELA_Q_SHIFT);
+        if constexpr (kDecoderRounding)
+            pred_out[t * 64 + lane] = 0u - (uint32_t)(int32_t)((int64_t)(((uint64_t)1 << SELA_Q_SHIFT) - sum) >> SELA_Q_SHIFT);
+        else
+            pred_out[t * 64 + lane] = (uint32_t)(int32_t)((int64_t)sum >> SELA_Q_SHIFT);
     }
 }
 
@@ -1150,7 +1155,8 @@ __device__ __attribute__((noinline)) void finish_group(const FuseArgs& fa, uint3
         (void)group_arrive(fa.groups_done, fa.tag, n_groups);
 }
 
-// kMode: 0 = product, 1 = also write the analysis trace, 2 = also write per-phase cycle counts, 3 = product + two hash words per block (hash_term)
+// kMode: 0 = product, 1 = also write the analysis trace, 2 = also write per-phase cycle counts, 3 = product + two hash words per block (hash_term),
+//        4 = product with the residues taken against the decoder's rounding (lossless, sela_encode_tail.inc)
 // (debug hook sela_hip_debug_phase_buffer; 16 uint64 per block).
 #define SELA_STAMP(n)                 \
     do {                              \
@@ -2696,7 +2702,8 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
     int32_t* d_trace_residues /* with d_trace and team_lanes 0: every block's residues, [block][2048]; or nullptr */,
     uint32_t priorities /* wave priorities by quarters of a wave's work, e.g. 0x00010203 falling; 0: none (the caller knows whether the launch has the device to itself) */,
     int phase /* 0: everything; 1: the blocks only; 2: plan + assemble only (a launch split over two streams, sela_capi.hip) */,
-    const uint64_t* plan_base /* phase 2: where the frames before these end (device), or null */, bool plan_accumulate)
+    const uint64_t* plan_base /* phase 2: where the frames before these end (device), or null */, bool plan_accumulate,
+    bool lossless /* the kMode 4 instantiations: residues against the decoder's rounding; not with d_trace or d_phase_cycles */)
 {
     const uint32_t n_sig = sela_hip_signals_per_frame(channels);
     const size_t blocks = (size_t)n_frames * n_sig;
@@ -2724,6 +2731,8 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
 
     if (link && (d_trace || d_phase_cycles))
         return hipErrorInvalidValue; // (the analysis trace and the phase counts are the device-pointer path's)
+    if (lossless && (d_trace || d_phase_cycles))
+        return hipErrorInvalidValue; // (the trace is the reference's arithmetic; the phase counts are the product kernels')
     if (phase != 0 && (link || n_frames == 0))
         return hipErrorInvalidValue;
     if (phase != 2) {
@@ -2829,6 +2838,8 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
                 SELA_LAUNCH_TEAMS(3, 8);
             else if (d_trace)
                 SELA_LAUNCH_TEAMS(1, 8);
+            else if (lossless)
+                SELA_LAUNCH_TEAMS(4, 8);
             else
                 SELA_LAUNCH_TEAMS(0, 8);
         } else {
@@ -2838,6 +2849,8 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
                 SELA_LAUNCH_TEAMS(3, 16);
             else if (d_trace)
                 SELA_LAUNCH_TEAMS(1, 16);
+            else if (lossless)
+                SELA_LAUNCH_TEAMS(4, 16);
             else
                 SELA_LAUNCH_TEAMS(0, 16);
         }
@@ -2849,6 +2862,10 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
         hipLaunchKernelGGL((k_encode_blocks<3, false>), grid, wg, 0, stream, d_pcm, n_frames, channels, n_sig, meta, slots, rings, ring_owner, ticket, d_trace, d_phase_cycles, force_plain_fir, mean_out, mean_ready, n_workers, self_blocks, total_e, fa);
     else if (d_trace)
         hipLaunchKernelGGL((k_encode_blocks<1, false>), grid, wg, 0, stream, d_pcm, n_frames, channels, n_sig, meta, slots, rings, ring_owner, ticket, d_trace, d_phase_cycles, force_plain_fir, mean_out, mean_ready, n_workers, self_blocks, total_e, fa);
+    else if (link && lossless)
+        hipLaunchKernelGGL((k_encode_blocks<4, true>), grid, wg, 0, stream, d_pcm, n_frames, channels, n_sig, meta, slots, rings, ring_owner, ticket, d_trace, d_phase_cycles, force_plain_fir, mean_out, mean_ready, n_workers, self_blocks, total_e, fa);
+    else if (lossless)
+        hipLaunchKernelGGL((k_encode_blocks<4, false>), grid, wg, 0, stream, d_pcm, n_frames, channels, n_sig, meta, slots, rings, ring_owner, ticket, d_trace, d_phase_cycles, force_plain_fir, mean_out, mean_ready, n_workers, self_blocks, total_e, fa);
     else if (link)
         hipLaunchKernelGGL((k_encode_blocks<0, true>), grid, wg, 0, stream, d_pcm, n_frames, channels, n_sig, meta, slots, rings, ring_owner, ticket, d_trace, d_phase_cycles, force_plain_fir, mean_out, mean_ready, n_workers, self_blocks, total_e, fa);
     else

@@ -87,7 +87,9 @@
     SELA_STAMP(7);
     // ---- residues (src/lpc/residue_generator.cpp:98-119) -----------------------------------------------
     // r[i] = s[i] - (int32)((2^34 + sum_{j=1..order} a[j] s[i-j]) >> 35), samples before the block
-    // count as absent (0).  Integer arithmetic is associative, so the taps are accumulated per sample in
+    // count as absent (0).  kMode 4 (lossless, DESIGN.md 5.16) subtracts the DECODER's prediction instead,
+    // -(int32)((2^34 - sum) >> 35) (src/lpc/sample_generator.cpp:25-28): the same number unless 2^34 + sum is a
+    // multiple of 2^35, and one less there.  Integer arithmetic is associative, so the taps are accumulated per sample in
     // any order -- and, where no partial sum can leave 53 bits, in FP64 (the three forms below).
     //
     // Lane l owns the 32 CONSECUTIVE samples 32l .. 32l+31 (the layout the Rice packer wants) and
@@ -152,7 +154,10 @@
         uint32_t pred_u[kPerLane];
         if (!single && !split) {
             uint32_t* const plain_pred = slots + (size_t)block_id * kSlotWords; // 2048 words of the block's own slot
-            fir_plain(order, lane, sT, sm->a, plain_pred);
+            if constexpr (kMode == 4)
+                fir_plain<true>(order, lane, sT, sm->a, plain_pred);
+            else
+                fir_plain<false>(order, lane, sT, sm->a, plain_pred);
 #pragma unroll
             for (int t = 0; t < kPerLane; t++) {
                 pred_u[t] = plain_pred[t * 64 + lane];
@@ -194,9 +199,15 @@
                 for (int j0 = 0; j0 < order; j0 += 32)
                     fir_taps_f64<0>(j0, order, fir_group_window(sT, lane, j0), fir_group_coefs(c_first, j0), win_f, acc_f);
 #pragma unroll
-                for (int t = 0; t < kPerLane; t++) // floor(sum / 2^35): |.| < 2^18
-                    pred_u[t] = (uint32_t)(int32_t)__builtin_floor(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT)));
+                for (int t = 0; t < kPerLane; t++) { // floor(sum / 2^35): |.| < 2^18
+                    if constexpr (kMode == 4) // the decoder's rounding, -floor(1 - sum / 2^35) = ceil(sum / 2^35) - 1: one less than the floor exactly at a tie
+                        pred_u[t] = (uint32_t)((int32_t)__builtin_ceil(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT))) - 1);
+                    else
+                        pred_u[t] = (uint32_t)(int32_t)__builtin_floor(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT)));
+                }
             } else {
+                // (lossless: ceil(sum / 2^35) - 1, and ceil((H + L / 2^20) / 2^15) = ceil(ceil(H + L / 2^20) / 2^15) = ceil((H + ceil(L / 2^20)) / 2^15)
+                // for the whole number H of the second pass: the same two passes with both floors turned into ceilings)
 #pragma unroll 1
                 for (int pass = 0; pass < 2; pass++) {
                     const double* const coef = pass ? c_second : c_first;
@@ -208,12 +219,20 @@
                         fir_taps_f64<0>(j0, order, fir_group_window(sT, lane, j0), fir_group_coefs(coef, j0), win_f, acc_f);
                     const double down = pass ? 1.0 / (double)((int64_t)1 << (SELA_Q_SHIFT - 20)) : 1.0 / 1048576.0;
 #pragma unroll
-                    for (int t = 0; t < kPerLane; t++) // floor(L / 2^20), then floor(sum / 2^15)
-                        acc_f[t] = __builtin_floor(acc_f[t] * down);
+                    for (int t = 0; t < kPerLane; t++) { // floor(L / 2^20), then floor(sum / 2^15)
+                        if constexpr (kMode == 4)
+                            acc_f[t] = __builtin_ceil(acc_f[t] * down);
+                        else
+                            acc_f[t] = __builtin_floor(acc_f[t] * down);
+                    }
                 }
 #pragma unroll
-                for (int t = 0; t < kPerLane; t++)
-                    pred_u[t] = (uint32_t)(int32_t)acc_f[t];
+                for (int t = 0; t < kPerLane; t++) {
+                    if constexpr (kMode == 4)
+                        pred_u[t] = (uint32_t)((int32_t)acc_f[t] - 1);
+                    else
+                        pred_u[t] = (uint32_t)(int32_t)acc_f[t];
+                }
             }
         }
 #pragma unroll

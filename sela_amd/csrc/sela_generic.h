@@ -19,7 +19,7 @@ struct GenericSubInfo { // one per (frame, subframe position), written by k_gene
 
 size_t generic_encode_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_generic_analyse(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, int32_t* d_sig,
-    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream);
+    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless = false /* DESIGN.md 5.16 */);
 hipError_t launch_generic_plan(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint64_t base_bytes, uint64_t* d_frame_offsets,
     uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream);
 hipError_t launch_generic_emit(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, const int32_t* d_res, const int32_t* d_q,
@@ -84,7 +84,7 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream);
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false);
 hipError_t launch_lpc_decode_any(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, uint32_t n, int32_t* d_samples,
     int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
 

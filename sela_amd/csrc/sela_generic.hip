@@ -364,7 +364,9 @@ __device__ __forceinline__ void rice_plan_convex(Load load, uint32_t n, int lane
     best_bits = ta + (uint64_t)n * (1 + k);
 }
 
-template <bool kIn16>
+// kLossless: the residues are taken against the DECODER's prediction -(int32)((2^34 - sum) >> 35)
+// (src/lpc/sample_generator.cpp:25-28) -- the encoder's, less one where 2^34 + sum is a multiple of 2^35.
+template <bool kIn16, bool kLossless>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAVES, SELA_GEN_WAVES))) void k_generic_analyse(const void* __restrict__ input, uint32_t n_frames, uint32_t channels,
     uint32_t n_sig, uint32_t n, int32_t* __restrict__ sig_ws, int32_t* __restrict__ res_ws, int32_t* __restrict__ q_ws, GenericMeta* __restrict__ meta, uint32_t force_wrap_taps /* tests: every block on the 64-bit wrap-around taps */)
 {
@@ -628,7 +630,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
             int32_t rr[kGenPerLane];
 #pragma unroll
             for (int t = 0; t < kGenPerLane; t++) { // floor(sum / 2^35): |.| < 2^18
-                const int32_t pred = (int32_t)__builtin_floor(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT)));
+                int32_t pred;
+                if constexpr (kLossless) // -floor(1 - sum / 2^35) = ceil(sum / 2^35) - 1: one less than the floor exactly at a tie
+                    pred = (int32_t)__builtin_ceil(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT))) - 1;
+                else
+                    pred = (int32_t)__builtin_floor(acc_f[t] * (1.0 / (double)((int64_t)1 << SELA_Q_SHIFT)));
                 rr[t] = (int32_t)((uint32_t)mine_s[t] - (uint32_t)pred);
             }
             const uint32_t first = i0 + (uint32_t)kGenPerLane * (uint32_t)lane;
@@ -659,7 +665,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
                 temp += (uint64_t)lds.a[j] * (uint64_t)(int64_t)win;
             }
             if (valid) {
-                const int32_t rt = (int32_t)((uint32_t)mine - (uint32_t)(int32_t)((int64_t)temp >> SELA_Q_SHIFT));
+                uint32_t pred;
+                if constexpr (kLossless)
+                    pred = 0u - (uint32_t)(int32_t)((int64_t)(((uint64_t)1 << SELA_Q_SHIFT) - temp) >> SELA_Q_SHIFT);
+                else
+                    pred = (uint32_t)(int32_t)((int64_t)temp >> SELA_Q_SHIFT);
+                const int32_t rt = (int32_t)((uint32_t)mine - pred);
                 r[i0 + lane] = rt;
                 t0_lane += zigzag32(rt);
                 wide |= (rt >= (1 << 30)) || (rt < -(1 << 30));
@@ -1601,16 +1612,20 @@ static std::atomic<int> g_force_wrap_taps{0};
 void set_generic_wrap_taps(int on) { g_force_wrap_taps.store(on, std::memory_order_relaxed); }
 
 hipError_t launch_generic_analyse(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, int32_t* d_sig,
-    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream)
+    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless)
 {
     const uint32_t blocks = n_frames * n_sig;
     if (blocks == 0)
         return hipSuccess;
     const uint32_t wrap = g_force_wrap_taps.load(std::memory_order_relaxed) ? 1u : 0u;
-    if (in16)
-        hipLaunchKernelGGL(k_generic_analyse<true>, dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+    if (in16 && lossless)
+        hipLaunchKernelGGL((k_generic_analyse<true, true>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+    else if (lossless)
+        hipLaunchKernelGGL((k_generic_analyse<false, true>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+    else if (in16)
+        hipLaunchKernelGGL((k_generic_analyse<true, false>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
     else
-        hipLaunchKernelGGL(k_generic_analyse<false>, dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+        hipLaunchKernelGGL((k_generic_analyse<false, false>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
     return hipGetLastError();
 }
 
@@ -2002,7 +2017,7 @@ size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, u
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: analyse, plan (base 0, the offsets straight into the
 // caller's, the status words written whole) and write, all on `stream`, nothing waited for.  Arguments checked by the caller.
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream)
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless)
 {
     const EncodeI32Layout l = encode_i32_layout(n_frames, channels, n);
     unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
@@ -2014,7 +2029,7 @@ hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_f
     uint32_t* const d_chosen = reinterpret_cast<uint32_t*>(base + l.chosen);
     uint64_t* const d_total = reinterpret_cast<uint64_t*>(base + l.total);
     const uint32_t n_sig = channels == 2 ? 3u : channels;
-    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream);
+    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream, lossless);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets, d_word_base,
