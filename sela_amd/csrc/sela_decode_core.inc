@@ -29,7 +29,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // ---- per-wave LDS scratch --------------------------------------------------------------------------------
 struct SynthTables {
     union {
-        int64_t a[104];     // Q35 predictor (the reflection coefficients never touch LDS here: dequantised into registers)
+        int64_t a[104];     // Q35 predictor; in front of it the dequantised reflection coefficients, which the step-up's stages read back one by one (step_up_from_q)
         uint64_t tab[192];  // synthesis coefficient table (build_synth_table), replaces a[]: entries 1 .. 191 are read
     };
 };

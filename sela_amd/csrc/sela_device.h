@@ -295,11 +295,104 @@ __device__ inline void step_up_regs(double k_lo, double k_hi, int64_t* a, int or
     wave_sync();
 }
 
+// The same recursion with k_i read from LDS: one 64-bit read at an address that is the wave's (every lane gets the value, no
+// lane is asked for it), issued kStepAhead stages before the stage that uses it -- 6 vector instructions a stage and one address per group where
+// step_up_regs has 8 and, as compiled, a copy (its two v_readlane_b32 among them), and no k_lo / k_hi alive across the loop.  The stages go in groups of kStepAhead so
+// that the values in flight sit in registers addressed statically; the group that holds stages 60 .. 63 changes from the
+// one-register form to the two-register form in its middle.  kd[] must be readable up to kd[order + kStepAhead - 1] (what lies
+// behind the order is fetched and never used); kd may be a[] itself (the decoders, step_up_from_q): every read is behind the
+// last stage's operands, and a[] is stored from them.
+constexpr int kStepAhead = 4;
+// (volatile: every read stays one ds_read_b64 at its place -- merged into 128-bit reads they all moved to the middle of a
+// group, into registers of their own, and were copied from there)
+typedef const volatile __attribute__((address_space(3))) uint64_t* LdsStepK;
+__device__ __forceinline__ double step_up_k(LdsStepK kd, int i) { return __builtin_bit_cast(double, (uint64_t)kd[i]); }
+
+template <typename K>
+__device__ inline void step_up_lds(const K* kd_in, int64_t* a, int order, int lane, uint32_t& flags)
+{
+    static_assert(sizeof(K) == 8, "64-bit words");
+    const LdsStepK kd = (LdsStepK)kd_in;
+    double t_lo = lane == 0 ? 1.0 : 0.0, r_lo = lane == 1 ? 1.0 : 0.0; // degree 0: A = [1], R[m] = A[1 - m]
+    double t_hi = 0.0, r_hi = 0.0;
+    double pf[kStepAhead];
+#pragma unroll
+    for (int u = 0; u < kStepAhead; u++)
+        pf[u] = step_up_k(kd, u);
+    // The first stage needs them anyway; said here, with nothing scalar in flight behind it (a clock read in front of this
+    // function is), the waits inside the loops count LDS reads only and leave the younger ones in flight.
+    __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0)
+    // while the mirror of the new degree (i + 2 elements) fits lanes 0..63, the second register is all zeros
+    auto stage_lo = [&](double ki) {
+        const double tn = t_lo + ki * r_lo;
+        const double rn = r_lo + ki * t_lo;
+        t_lo = tn;
+        r_lo = wave_shr1_zero(rn);
+    };
+    auto stage_hi = [&](double ki) {
+        const double tn_lo = t_lo + ki * r_lo, rn_lo = r_lo + ki * t_lo;
+        const double tn_hi = t_hi + ki * r_hi, rn_hi = r_hi + ki * t_hi;
+        t_lo = tn_lo;
+        t_hi = tn_hi;
+        const double carry = read_lane(rn_lo, 63); // crosses from the first register into the second
+        r_lo = wave_shr1_zero(rn_lo);
+        r_hi = wave_shr1(carry, rn_hi);
+    };
+    static_assert(kStepAhead == 4 && 60 % kStepAhead == 0, "stages 60 .. 63 are one group");
+    const int n_whole = (order < 60 ? order : 60) & ~(kStepAhead - 1);
+    int i = 0;
+    for (; i < n_whole; i += kStepAhead) {
+#pragma unroll
+        for (int u = 0; u < kStepAhead; u++) {
+            stage_lo(pf[u]);
+            pf[u] = step_up_k(kd, i + kStepAhead + u); // (behind the stage: into the registers it has just read)
+        }
+    }
+    if (order < 60) { // up to three stages more, their k fetched already
+#pragma unroll
+        for (int u = 0; u < kStepAhead - 1; u++)
+            if (i + u < order)
+                stage_lo(pf[u]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < kStepAhead; u++)
+            if (60 + u < order) {
+                if (u < 2)
+                    stage_lo(pf[u]);
+                else
+                    stage_hi(pf[u]);
+                pf[u] = step_up_k(kd, 64 + u);
+            }
+        for (i = 64; i < order; i += kStepAhead) {
+#pragma unroll
+            for (int u = 0; u < kStepAhead; u++)
+                if (i + u < order) {
+                    stage_hi(pf[u]);
+                    pf[u] = step_up_k(kd, i + kStepAhead + u);
+                }
+        }
+    }
+    if (lane == 0)
+        a[0] = 0;
+    else if (lane <= order)
+        a[lane] = q35_trunc(-t_lo, flags);
+    if (lane + 64 <= order)
+        a[lane + 64] = q35_trunc(-t_hi, flags);
+    wave_sync();
+}
+
+// kFromLds false: the form of step_up_regs, for a kernel that has no registers for the values in flight (k_generic_analyse:
+// three spilled registers more).
+template <bool kFromLds = true>
 __device__ inline void step_up(const double* kd, int64_t* a, int order, int lane, uint32_t& flags)
 {
-    const double k_lo = lane < order ? kd[lane] : 0.0;
-    const double k_hi = lane + 64 < order ? kd[lane + 64] : 0.0;
-    step_up_regs(k_lo, k_hi, a, order, lane, flags);
+    if constexpr (kFromLds) {
+        step_up_lds(kd, a, order, lane, flags);
+    } else {
+        const double k_lo = lane < order ? kd[lane] : 0.0;
+        const double k_hi = lane + 64 < order ? kd[lane + 64] : 0.0;
+        step_up_regs(k_lo, k_hi, a, order, lane, flags);
+    }
 }
 
 // The decoders' way to the predictor: quantised reflection coefficients `lane` (q_lo) and `lane + 64` (q_hi) -> a[0 .. order].
@@ -308,13 +401,25 @@ __device__ inline void step_up(const double* kd, int64_t* a, int order, int lane
 // (The lane as dequant() sees it is opaque, in every decoder: the compiler otherwise selects the lane's table in front of
 // whatever parse precedes this and carries the pointer through it -- two spilled registers in k_verify_frames, two more
 // registers in k_decode_frames, which the budget of seven waves per SIMD does not have.)
+// kParkInA: a[] has room for 104 words, and the dequantised coefficients are parked in it, where the stages read them back one
+// by one (step_up_lds): a[] is free until the stores behind the last stage.  Without it (k_generic_decode, whose a[] ends at
+// the largest order) the coefficients stay in two registers and every stage reads its own out with two v_readlane_b32.
+template <bool kParkInA = true>
 __device__ __forceinline__ void step_up_from_q(uint32_t order, int32_t q_lo, int32_t q_hi, int64_t* a, int lane, uint32_t& flags)
 {
     int table_lane = lane;
     asm volatile("" : "+v"(table_lane));
     const double k_lo = (uint32_t)lane < order ? (order <= 1 ? 0.0 : dequant(table_lane, q_lo, flags)) : 0.0;
     const double k_hi = (uint32_t)lane + 64 < order ? dequant(64, q_hi, flags) : 0.0; // (coefficients 2 and up share one table)
-    step_up_regs(k_lo, k_hi, a, (int)order, lane, flags);
+    if constexpr (kParkInA) {
+        a[lane] = __builtin_bit_cast(int64_t, k_lo);
+        if (lane < kMaxOrder + kStepAhead - 64)
+            a[lane + 64] = __builtin_bit_cast(int64_t, k_hi);
+        wave_sync();
+        step_up_lds(a, a, (int)order, lane, flags);
+    } else {
+        step_up_regs(k_lo, k_hi, a, (int)order, lane, flags);
+    }
 }
 
 // ---- launch helpers of the 2048-sample decoder (sela_decode.hip), shared with sela_verify.hip -------------------------------

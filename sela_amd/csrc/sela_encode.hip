@@ -98,6 +98,14 @@ __device__ __forceinline__ void or_bits_both(uint32_t* buf, uint32_t pos, uint32
     atomicOr(w + 1, (uint32_t)(wide >> 32));
 }
 
+// (1 << n) - 1 for n <= 31 in one instruction (the compiler makes the shift and a v_not_b32 of it)
+__device__ __forceinline__ uint32_t low_ones(uint32_t n)
+{
+    uint32_t m;
+    asm("v_bfm_b32 %0, %1, 0" : "=v"(m) : "v"(n));
+    return m;
+}
+
 // Append one Golomb-Rice codeword (src/rice/rice_encoder.cpp:41-53): u >> k ones, a zero, then the
 // low k bits MSB first.  Stream bit t lives at bit t%32 of word t/32, so the MSB-first remainder is
 // the bit-reversed remainder in stream order.
@@ -161,19 +169,20 @@ __device__ __forceinline__ uint64_t rice_shifted_sum(const uint32_t (&u)[V], uin
     return wave_sum_40(part); // V <= 32 values below 2^32 each
 }
 
-// lane_or = the OR of the lane's values (an upper bound of each); lane_quotients = sum(u >> best_k) of THIS lane's values
-// (what the packer's scan needs).
+// lane_top = the largest of the lane's values (v_max3_u32: two values to an instruction, as their OR was -- which bounded
+// them too, but up to twice too high: the packer's test on it sent 74 % of the bench track's blocks down the long way where
+// 56 % have a long codeword); lane_quotients = sum(u >> best_k) of THIS lane's values (what the packer's scan needs).
 template <int V>
-__device__ __forceinline__ void rice_plan(const uint32_t (&u)[V], uint32_t n, uint32_t& best_k, uint64_t& best_bits, uint32_t& lane_or, uint32_t& lane_quotients)
+__device__ __forceinline__ void rice_plan(const uint32_t (&u)[V], uint32_t n, uint32_t& best_k, uint64_t& best_bits, uint32_t& lane_top, uint32_t& lane_quotients)
 {
     constexpr uint32_t kLast = SELA_MAX_RICE_PARAM - 1;
-    lane_or = 0;
+    lane_top = 0;
 #pragma unroll
     for (int t = 0; t < V; t++)
-        lane_or |= u[t];
+        lane_top = max(lane_top, u[t]);
     // 16-bit audio leaves residues below 2^19: then every sum below fits 32 bits (2048 values below 2^20), and the adds of
     // a lane go two to an instruction
-    const bool small = !__any((lane_or >> 20) != 0);
+    const bool small = !__any((lane_top >> 20) != 0);
     uint32_t p0, pa, pb, pc;
     const uint64_t t0 = rice_shifted_sum<V>(u, 0, small, p0);
     const uint64_t mean = n ? t0 / n : 0;

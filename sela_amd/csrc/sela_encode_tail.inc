@@ -253,16 +253,19 @@
     uint32_t cu[2];
     cu[0] = 2 * lane < order ? zigzag32(sm->q[2 * lane]) : 0u;
     cu[1] = 2 * lane + 1 < order ? zigzag32(sm->q[2 * lane + 1]) : 0u;
-    uint32_t coef_k, coef_or, coef_quotients;
+    uint32_t coef_k, coef_top, coef_quotients;
     uint64_t coef_bits;
-    rice_plan<2>(cu, (uint32_t)order, coef_k, coef_bits, coef_or, coef_quotients);
+    rice_plan<2>(cu, (uint32_t)order, coef_k, coef_bits, coef_top, coef_quotients);
     const uint32_t coef_words = words_for_bits(coef_bits);
 
     if (__any(wide))
         flags |= SELA_HIP_FLAG_RICE_RANGE;
-    uint32_t res_k, res_or, res_quotients; // (res_or: unused here)
+    uint32_t res_k, res_top, res_quotients;
     uint64_t res_bits;
-    rice_plan<kPerLane>(ru, (uint32_t)kBlock, res_k, res_bits, res_or, res_quotients);
+    rice_plan<kPerLane>(ru, (uint32_t)kBlock, res_k, res_bits, res_top, res_quotients);
+    // Is any residue codeword longer than a word?  Once for the block and the same for every lane: the longest is that of the
+    // largest value, (max >> k) + 1 + k bits.
+    const bool res_all_short = (wave_max_u32(res_top) >> res_k) + 1 + res_k <= 32;
     uint32_t res_words = words_for_bits(res_bits);
     if (res_words > (uint32_t)kResWordsCap || coef_words > (uint32_t)kCoefWordsCap) {
         flags |= SELA_HIP_FLAG_WORDS_CAP;
@@ -319,15 +322,31 @@
         // A codeword that fits a word (all but spikes in quiet blocks) is put together in a register -- the unary part and the
         // bit-reversed remainder -- and OR-ed into the two words it may touch, without a branch; longer ones go through an
         // out-of-line helper.
+        if (res_all_short) {
+            // No codeword of the block is longer than a word (decided once, above): the same words without the test, the
+            // masking and the call -- 11 vector instructions a codeword.  ones <= 31 - k here.
+            uint32_t k_v = res_k, rem_at = 32 - res_k; // (k in ONE vector register for all 32 v_bfe_u32, which take one scalar operand)
+            asm volatile("" : "+v"(k_v));
+            asm volatile("" : "+s"(rem_at));
 #pragma unroll
-        for (int t = 0; t < kPerLane; t++) {
-            const uint32_t u = ru[t], ones = u >> res_k, len = ones + 1 + res_k;
-            if (len <= 32) {
-                const uint32_t rem = __builtin_amdgcn_ubfe(__brev(u), 32 - res_k, res_k); // low k bits of u, reversed: the top k bits of brev(u) (k = 0: a field of no bits)
-                or_bits_both(out_words, pos, ((1u << ones) - 1u) | (rem << ((ones + 1) & 31))); // (ones + 1 = 32 only with k = 0, rem = 0)
-                pos += len;
-            } else {
-                pos = put_long_codeword(out_words, pos, u, res_k);
+            for (int t = 0; t < kPerLane; t++) {
+                const uint32_t u = ru[t], ones = u >> res_k;
+                const uint32_t rem = __builtin_amdgcn_ubfe(__brev(u), rem_at, k_v);
+                const uint32_t next = ones + 1;
+                or_bits_both(out_words, pos, low_ones(ones) | (rem << (next & 31))); // (ones + 1 = 32 only with k = 0, rem = 0)
+                pos = pos + next + k_v;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < kPerLane; t++) {
+                const uint32_t u = ru[t], ones = u >> res_k, len = ones + 1 + res_k;
+                if (len <= 32) {
+                    const uint32_t rem = __builtin_amdgcn_ubfe(__brev(u), 32 - res_k, res_k); // low k bits of u, reversed: the top k bits of brev(u) (k = 0: a field of no bits)
+                    or_bits_both(out_words, pos, ((1u << ones) - 1u) | (rem << ((ones + 1) & 31))); // (ones + 1 = 32 only with k = 0, rem = 0)
+                    pos += len;
+                } else {
+                    pos = put_long_codeword(out_words, pos, u, res_k);
+                }
             }
         }
     }

@@ -564,7 +564,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
         }
     }
     wave_sync();
-    step_up(lds.kk, lds.a, order, lane, flags);
+    step_up<false>(lds.kk, lds.a, order, lane, flags); // (registers: see step_up)
     for (int i = lane; i < kMaxOrder; i += 64)
         q_ws[(size_t)b * kMaxOrder + i] = i < order ? lds.q[i] : 0;
 
@@ -1163,7 +1163,7 @@ __global__ __launch_bounds__(64) void k_generic_decode(const uint8_t* __restrict
         const uint32_t o = order;
         const int32_t q_lo = (uint32_t)lane < o ? q_lds[lane] : 0;
         const int32_t q_hi = (uint32_t)lane + 64 < o ? q_lds[lane + 64] : 0;
-        step_up_from_q(o, q_lo, q_hi, a_lds, lane, flags);
+        step_up_from_q<false>(o, q_lo, q_hi, a_lds, lane, flags); // (a_lds ends at the largest order: no room to park them)
     }
     // lane l: a[l + 1], a[l + 65] (0 beyond the order)
     const uint64_t a_lo = (uint32_t)lane + 1 <= order ? (uint64_t)a_lds[lane + 1] : 0;
