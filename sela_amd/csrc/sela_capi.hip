@@ -22,70 +22,8 @@
 #include <vector>
 
 #include "sela_coalescer.h"
-#include "sela_device.h"
-
-namespace sela {
-size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels);
-int encode_team_lanes(uint32_t n_frames, uint32_t channels, int forced);
-void set_keep_both_candidates(int on);
-void set_encode_hashes(int on);
-hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, sela_hip_trace* d_trace, hipStream_t stream,
-    hipEvent_t* ev, uint64_t* d_phase_cycles, const EncodeHostLink* link, int force_plain_fir, int self_blocks_override, int team_lanes,
-    int32_t* d_trace_residues = nullptr, uint32_t priorities = 0, int phase = 0, const uint64_t* plan_base = nullptr, bool plan_accumulate = false,
-    bool lossless = false);
-uint32_t encode_split_frames(uint32_t n_frames, uint32_t channels, int permille);
-hipError_t launch_stage_rice_encode(const int32_t* d_values, const uint64_t* d_value_offsets, uint32_t n_streams, uint32_t* d_k, uint32_t* d_word_counts,
-    uint32_t* d_words, const uint64_t* d_word_offsets, uint32_t* d_status, hipStream_t stream);
-hipError_t launch_stage_lpc_decode(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, int32_t* d_samples,
-    int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
-hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_word_offsets, const uint32_t* d_k, const uint64_t* d_value_offsets,
-    uint32_t n_streams, int32_t* d_values, uint32_t* d_status, hipStream_t stream);
-hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
-    int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles,
-    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0, const uint32_t* d_n_found = nullptr, bool zero_status = true);
-int decode_waves(uint32_t channels);
-size_t index_workspace_bytes(uint64_t payload_bytes);
-hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
-    uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
-// the any-length / 32-bit route (sela_capi_generic.hip)
-void generic_release();
-void generic_shutdown();
-size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
-int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out,
-    bool lossless = false);
-uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint64_t* sample_offsets, bool* all_standard);
-int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
-    uint32_t* counts_out, int16_t* pcm_out, const uint64_t* sample_offsets);
-int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out);
-int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);
-size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels);
-uint32_t decode_max_channels();
-int generic_standard_first_mode();
-size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
-hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
-    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
-size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
-hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
-    uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
-    hipStream_t stream);
-size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
-hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
-    uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
-    int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
-int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
-    uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
-size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
-size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride);
-hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
-    uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
-    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
-int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
-    const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
-size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
-hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false);
-} // namespace sela
+#include "sela_host.h"
+#include "sela_lease.h"
 
 namespace {
 
@@ -102,11 +40,70 @@ int fail_hip(hipError_t e, const char* where)
     return fail(e == hipErrorOutOfMemory ? SELA_HIP_ENOMEM : SELA_HIP_ENODEV, std::string(where) + ": " + hipGetErrorString(e));
 }
 
+// ---- the verdicts on what the kernels report (sela_host.h): one ordered table per direction ---------------------------------------
+struct Verdict {
+    uint32_t flag;
+    uint32_t routes; // the decoder's routes (1 << sela::DecodeRoute) this row speaks for
+    int code;
+    bool named; // the text opens with the caller's name
+    const char* text;
+};
+constexpr uint32_t kEveryRoute = ~0u, kLpcOnly = 1u << sela::kRouteLpc;
+// What the reference itself leaves undefined (COEF_OVERFLOW, Q_RANGE, SHORT_BLOCK) is reported, never decoded silently.
+const Verdict kDecodeVerdicts[] = {
+    { SELA_HIP_FLAG_STRIDE, kEveryRoute, SELA_HIP_ECAPACITY, false, "stride is smaller than the largest samplesPerChannel of the stream (status[2])" },
+    { SELA_HIP_FLAG_BAD_FRAME, 1u << sela::kRouteDevice32, SELA_HIP_EFORMAT, false,
+        "malformed frame (decreasing offsets, sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, or channels of different lengths)" },
+    { SELA_HIP_FLAG_BAD_FRAME, 1u << sela::kRouteHost32, SELA_HIP_EFORMAT, false,
+        "malformed frame (sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, or channels of different lengths)" },
+    { SELA_HIP_FLAG_BAD_FRAME, 1u << sela::kRouteFast, SELA_HIP_EFORMAT, false, "malformed frame stream (bad sync word or subframe header)" },
+    { SELA_HIP_FLAG_BAD_FRAME, 1u << sela::kRouteWalk, SELA_HIP_EFORMAT, false,
+        "malformed frame stream (the header walk breaks, frame offsets decrease, or no subframe says a length)" },
+    { SELA_HIP_FLAG_BAD_FRAME, kLpcOnly, SELA_HIP_EINVAL, true, "order outside 0..100" },
+    { SELA_HIP_FLAG_RICE_OVERRUN, kEveryRoute, SELA_HIP_EFORMAT, false, "a Rice stream ended before all its values were read" },
+    { SELA_HIP_FLAG_COEF_OVERFLOW, kEveryRoute, SELA_HIP_ERANGE, true, "a predictor coefficient left the int64 range" },
+    { SELA_HIP_FLAG_Q_RANGE, kEveryRoute, SELA_HIP_ERANGE, true,
+        "a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)" },
+    { SELA_HIP_FLAG_SHORT_BLOCK, ~kLpcOnly, SELA_HIP_ERANGE, true,
+        "a subframe without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)" },
+    { SELA_HIP_FLAG_SHORT_BLOCK, kLpcOnly, SELA_HIP_ERANGE, true,
+        "a block without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)" },
+    { SELA_HIP_FLAG_INTERNAL, kEveryRoute, SELA_HIP_ENODEV, true, "a bounded wait inside a kernel ran out" },
+};
+const Verdict kEncodeVerdicts[] = {
+    { SELA_HIP_FLAG_SHORT_BLOCK, kEveryRoute, SELA_HIP_ERANGE, true,
+        "a block is not longer than its predictor order (the reference reads past its vector there, src/lpc/residue_generator.cpp:104-110)" },
+    { SELA_HIP_FLAG_RICE_RANGE, kEveryRoute, SELA_HIP_ERANGE, true, "a residue is beyond the reference's int32 zig-zag (|value| >= 2^30)" },
+    { SELA_HIP_FLAG_COEF_OVERFLOW, kEveryRoute, SELA_HIP_ERANGE, true, "a predictor coefficient left the int64 range" },
+    { SELA_HIP_FLAG_WORDS_CAP, kEveryRoute, SELA_HIP_ERANGE, true, "a Rice stream needs more words than a subframe's 16-bit count can say" },
+};
+template <size_t N>
+int judge(const Verdict (&table)[N], uint32_t flags, uint32_t route, const char* who)
+{
+    for (const Verdict& v : table)
+        if ((flags & v.flag) && (v.routes & route))
+            return fail(v.code, v.named ? std::string(who) + ": " + v.text : std::string(v.text));
+    return SELA_HIP_OK;
+}
+
 } // namespace
 namespace sela {
 int report_error(int code, const std::string& what) { return fail(code, what); }
 int report_hip_error(hipError_t e, const char* where) { return fail_hip(e, where); }
+int device_ready()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(SELA_HIP_ENODEV, "no HIP device visible (the SELA MI355X path has no CPU fallback)");
+    return SELA_HIP_OK;
 }
+int check_frame_offsets(const uint64_t* frame_offsets, uint32_t n_frames)
+{
+    return frame_offsets_ascend(frame_offsets, n_frames) ? SELA_HIP_OK : fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+}
+int judge_decode(uint32_t flags, uint32_t judged, DecodeRoute route, const char* who) { return judge(kDecodeVerdicts, flags & judged, 1u << route, who); }
+int judge_encode(uint32_t flags, uint32_t judged, const char* who) { return judge(kEncodeVerdicts, flags & judged, kEveryRoute, who); }
+} // namespace sela
 namespace {
 
 // ---- page-locked host memory (sela_hip_host_alloc) ---------------------------------------------------------
@@ -257,7 +254,7 @@ struct ChunkSet { // one chunk of a decode job in flight
     hipEvent_t copied_in = nullptr, ran = nullptr, copied_out = nullptr;
 };
 
-struct HostContext {
+struct HostContext : sela::CurrentDevice {
     ChunkSet set[kSets];
     DeviceBuffer status;      // device-side status words (decode kernels of a job report through job_flags instead)
     // encode jobs: one launch per feed (see job_feed_encode)
@@ -343,77 +340,37 @@ struct HostContext {
             *s = nullptr;
         }
     }
+    // what the lease asks of it (sela_lease.h)
+    static constexpr size_t kParked = 16; // more idle ones than this are freed instead (a context holds up to a few hundred MB of HBM)
+    static HostContext* make(int dev);
+    bool serves(int) const { return true; } // (a thread keeps its context when it changes device: bind_current_device)
+    void tidy();
+    void destroy() { release(); }
 };
-// A thread's context is LEASED: creating one (four streams, 25 events, a dozen device and page-locked buffers) takes the
-// runtime about 10 ms -- three times what a 3-minute track takes file to file -- and host programs start threads per job
-// (one worker per GPU and batch, the player's decoder).  A thread that ends, or calls sela_hip_thread_release(), parks its
-// context; the next thread that needs one on that device takes it over warm.  sela_hip_shutdown() frees the parked ones.
-struct ContextPark {
-    std::mutex mu;
-    std::vector<HostContext*> idle;
-};
-ContextPark& park()
-{
-    static ContextPark* p = new ContextPark; // (never destroyed: threads may end after the statics have)
-    return *p;
-}
+// A thread's context is LEASED (sela_lease.h): creating one (four streams, 25 events, a dozen device and page-locked buffers)
+// takes the runtime about 10 ms -- three times what a 3-minute track takes file to file.
 std::atomic<int> g_contexts_created{ 0 }; // debug: sela_hip_debug_contexts_created
-constexpr size_t kParkedContexts = 16; // more than this many idle ones are freed instead (a context holds up to a few hundred MB of HBM)
+void staged_path_release(int device);     // (below)
 
-void staged_path_release(int device); // (below)
-
-struct ContextLease {
-    HostContext* held = nullptr;
-    HostContext& get()
-    {
-        if (!held) {
-            int dev = -1;
-            (void)hipGetDevice(&dev);
-            ContextPark& p = park();
-            {
-                std::lock_guard<std::mutex> lock(p.mu);
-                for (size_t i = p.idle.size(); i-- > 0 && !held;)
-                    if (p.idle[i]->device == dev) {
-                        held = p.idle[i];
-                        p.idle.erase(p.idle.begin() + (long)i);
-                    }
-            }
-            if (!held) {
-                held = new HostContext;
-                g_contexts_created.fetch_add(1, std::memory_order_relaxed);
-            }
-        }
-        return *held;
-    }
-    void give_back()
-    {
-        if (!held)
-            return;
-        HostContext* c = held;
-        held = nullptr;
-        if (c->job_open) { // a thread that ended in the middle of a job: nothing of it may be left in flight or marked
-            c->sync_all();
-            c->release();
-            c->job_open = false;
-            if (c->staged_device >= 0) // (its job held the device's staging path: nobody else will give it back)
-                staged_path_release(c->staged_device);
-            c->staged_device = -1;
-        }
-        ContextPark& p = park();
-        {
-            std::lock_guard<std::mutex> lock(p.mu);
-            if (c->device >= 0 && p.idle.size() < kParkedContexts) {
-                p.idle.push_back(c);
-                return;
-            }
-        }
-        c->release();
-        delete c;
-    }
-    ~ContextLease() { give_back(); }
-};
-thread_local ContextLease g_lease;
-inline HostContext& ctx() { return g_lease.get(); }
+HostContext* HostContext::make(int)
+{
+    g_contexts_created.fetch_add(1, std::memory_order_relaxed);
+    return new HostContext; // (bound to the device, and filled, by the job that begins on it)
+}
+void HostContext::tidy()
+{
+    if (!job_open)
+        return;
+    // a thread that ended in the middle of a job: nothing of it may be left in flight or marked
+    sync_all();
+    release();
+    job_open = false;
+    if (staged_device >= 0) // (its job held the device's staging path: nobody else will give it back)
+        staged_path_release(staged_device);
+    staged_device = -1;
+}
+thread_local sela::ContextLease<HostContext> g_lease;
+inline HostContext& ctx() { return g_lease.held ? *g_lease.held : *g_lease.get(HostContext::current_device()); }
 
 // Per-thread kernel timing (bench.py's roofline leg): events bracketing the kernels of the last call.
 struct KernelTiming {
@@ -1000,16 +957,7 @@ int job_end(sela_hip_job* job, uint32_t* frames_final, uint64_t* bytes_final)
     delete job;
     if (rc != SELA_HIP_OK)
         return rc;
-    if (seen_flags & SELA_HIP_FLAG_BAD_FRAME)
-        return fail(SELA_HIP_EFORMAT, "malformed frame stream (bad sync word or subframe header)");
-    if (seen_flags & SELA_HIP_FLAG_RICE_OVERRUN)
-        return fail(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
-    // (the same policy as the any-length route, sela_capi_generic.hip: what the reference leaves undefined is reported)
-    if (seen_flags & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return fail(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
-    if (seen_flags & SELA_HIP_FLAG_Q_RANGE)
-        return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-    return SELA_HIP_OK;
+    return sela::judge_decode(seen_flags, sela::kJudgeJob, sela::kRouteFast, "decode"); // (not SHORT_BLOCK, not INTERNAL)
 }
 
 
@@ -1210,14 +1158,6 @@ struct Scratch {
     }
 };
 
-int stage_device_ready()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(SELA_HIP_ENODEV, "no HIP device visible (the SELA MI355X path has no CPU fallback)");
-    return SELA_HIP_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -1256,23 +1196,8 @@ void sela_hip_thread_release(void)
 
 void sela_hip_shutdown(void)
 {
-    g_lease.give_back();
+    g_lease.shutdown();
     sela::generic_shutdown();
-    std::vector<HostContext*> idle;
-    {
-        std::lock_guard<std::mutex> lock(park().mu);
-        idle.swap(park().idle);
-    }
-    int before = -1;
-    (void)hipGetDevice(&before);
-    for (HostContext* c : idle) { // (streams and buffers are freed on the device they belong to)
-        if (c->device >= 0)
-            (void)hipSetDevice(c->device);
-        c->release();
-        delete c;
-    }
-    if (before >= 0)
-        (void)hipSetDevice(before);
     flights().release_all();
     splitter().release_all();
     pool().trim();
@@ -1451,11 +1376,12 @@ int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channel
     return SELA_HIP_OK;
 }
 
-// what every *_opt call asks first; SELA_HIP_OK or the failure, reported
-int check_encode_options(uint32_t options)
+// what every *_opt call asks first: SELA_HIP_OK and whether the call is a lossless one, or the refusal, reported
+int encode_options(uint32_t options, bool* lossless)
 {
     if (options & ~(uint32_t)SELA_HIP_ENCODE_LOSSLESS)
         return fail(SELA_HIP_EINVAL, "options: a bit this library does not know (SELA_HIP_ENCODE_LOSSLESS is the only one)");
+    *lossless = options != 0;
     return SELA_HIP_OK;
 }
 } // namespace
@@ -1469,16 +1395,15 @@ int sela_hip_encode_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t cha
 int sela_hip_encode_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, sela_hip_trace* d_trace, void* stream, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_device(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, d_trace, stream);
-    const int rc = check_encode_options(options);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
     if (rc != SELA_HIP_OK)
         return rc;
-    if (d_trace)
+    if (lossless && d_trace)
         return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS with d_trace: the trace is the reference's arithmetic");
-    if (g_phase_cycles)
+    if (lossless && g_phase_cycles)
         return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS while sela_hip_debug_phase_buffer is set: the phase counts are the plain kernels'");
-    return encode_device_call(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, nullptr, stream, true);
+    return encode_device_call(d_pcm, n_frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, workspace_bytes, d_trace, stream, lossless);
 }
 
 namespace {
@@ -1523,6 +1448,8 @@ int decode_device_launch(const uint8_t* d_frames, const uint64_t* d_frame_offset
             g_phase_cycles, nullptr, g_recurrence_form, synth_priorities, d_n_found);
     });
 }
+
+int launched(hipError_t e, const char* what) { return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, what); }
 
 // the index's own checks (sela_hip_index_frames_device); SELA_HIP_OK or the failure, reported
 int check_index_args(const uint8_t* d_payload, size_t payload_bytes, uint32_t channels, const uint64_t* d_frame_offsets, const uint32_t* d_n_frames,
@@ -1570,9 +1497,8 @@ int sela_hip_index_frames_device(const uint8_t* d_payload, size_t payload_bytes,
         return rc;
     if (workspace_bytes < sela::index_workspace_bytes(payload_bytes))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes()");
-    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace,
-        static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "index launch");
+    return launched(sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream)),
+        "index launch");
 }
 
 int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
@@ -1597,11 +1523,73 @@ int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_byte
         static_cast<unsigned char*>(d_workspace) + index_bytes, stream, d_n_frames);
 }
 
-// ---- the 32-bit decode on device pointers --------------------------------------------------------
+// ---- the decode and verify calls of any length on device pointers, each in two forms ---------------
+// A call is its own check of its arguments, its workspace formula and its launch.  What it is given -- frames with their
+// offsets, or a payload that the device indexes first -- is a FORM, and the form runs the call:
+//   frames:  the call's check; d_frames and its offsets; the capacity; the launch.
+//   payload: the index's checks; the call's check; the capacity of both workspaces; launch_index; the launch on the rest of the
+//            workspace with the device's own count of frames.
+// check: n_frames -> SELA_HIP_OK or the failure, reported; launch: (d_frames, d_frame_offsets, max_frames, d_n_found, d_workspace)
+// -> the same.  Nothing is allocated on the way to the launch.  (sela_hip_decode_device and its payload twin, above, check other
+// things -- no stride, no pointer without frames -- and would need a shape of their own: they stay written out.)
+extern "C++" {
 namespace {
-// what sela_hip_decode_i32_device and the payload call check alike; SELA_HIP_OK or the failure, reported
-int check_decode_i32_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* d_samples_out, const uint32_t* d_counts_out,
-    const uint32_t* d_status, const void* d_workspace)
+struct DeviceCall {
+    const char* name; // "decode_i32": the capacity's text names sela_hip_<name>_workspace_bytes()
+    size_t (*workspace_bytes)(uint32_t max_frames, uint32_t channels, uint32_t stride); // SIZE_MAX: more than any device holds
+    uint32_t channels, stride;
+    void* d_workspace;
+    size_t capacity;
+    hipStream_t stream;
+};
+
+struct FramesForm {
+    const uint8_t* d_frames;
+    const uint64_t* d_frame_offsets;
+    uint32_t n_frames;
+    template <typename Check, typename Launch>
+    int operator()(const DeviceCall& c, Check check, Launch launch) const
+    {
+        const int rc = check(n_frames);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        if (!d_frame_offsets || (n_frames && !d_frames))
+            return fail(SELA_HIP_EINVAL, "null device pointer");
+        if ((uintptr_t)d_frames & 3)
+            return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
+        const size_t need = c.workspace_bytes(n_frames, c.channels, c.stride);
+        if (need == SIZE_MAX || c.capacity < need)
+            return fail(SELA_HIP_ECAPACITY, std::string("workspace smaller than sela_hip_") + c.name + "_workspace_bytes()");
+        return launch(d_frames, d_frame_offsets, n_frames, static_cast<const uint32_t*>(nullptr), c.d_workspace);
+    }
+};
+
+struct PayloadForm {
+    const uint8_t* d_payload;
+    size_t payload_bytes;
+    uint32_t max_frames;
+    uint64_t* d_frame_offsets;
+    uint32_t* d_n_frames;
+    template <typename Check, typename Launch>
+    int operator()(const DeviceCall& c, Check check, Launch launch) const
+    {
+        int rc = check_index_args(d_payload, payload_bytes, c.channels, d_frame_offsets, d_n_frames, c.d_workspace);
+        if (rc == SELA_HIP_OK)
+            rc = check(max_frames);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), own_bytes = c.workspace_bytes(max_frames, c.channels, c.stride);
+        if (own_bytes == SIZE_MAX || c.capacity < index_bytes + own_bytes)
+            return fail(SELA_HIP_ECAPACITY, std::string("workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_") + c.name + "_workspace_bytes()");
+        rc = launched(sela::launch_index(d_payload, payload_bytes, max_frames, c.channels, d_frame_offsets, d_n_frames, c.d_workspace, c.stream), "index launch");
+        if (rc != SELA_HIP_OK)
+            return rc;
+        return launch(d_payload, d_frame_offsets, max_frames, d_n_frames, static_cast<unsigned char*>(c.d_workspace) + index_bytes);
+    }
+};
+
+// what every one of these calls checks first, and how it says that a pointer is missing
+int check_frames_shape(uint32_t n_frames, uint32_t channels, uint32_t stride)
 {
     if (channels == 0 || channels > 255)
         return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
@@ -1609,11 +1597,97 @@ int check_decode_i32_args(uint32_t n_frames, uint32_t channels, uint32_t stride,
         return fail(SELA_HIP_EINVAL, "stride must not be 0");
     if ((uint64_t)n_frames * channels >= (1ull << 31))
         return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
-    if (!d_status || !d_workspace || (n_frames && (!d_samples_out || !d_counts_out)))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
     return SELA_HIP_OK;
 }
+int need_pointers(bool all_there) { return all_there ? SELA_HIP_OK : fail(SELA_HIP_EINVAL, "null device pointer"); }
+
+// sela_hip_decode_i32_device / sela_hip_decode_payload_i32_device (5.11)
+template <typename Form>
+int decode_i32_call(const Form& form, uint32_t channels, uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "decode_i32", sela::decode_i32_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            const int rc = check_frames_shape(n_frames, channels, stride);
+            return rc != SELA_HIP_OK ? rc : need_pointers(d_status && d_workspace && (!n_frames || (d_samples_out && d_counts_out)));
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_decode_i32_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_samples_out, d_counts_out,
+                                d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), c.stream),
+                "decode_i32 launch");
+        });
+}
+
+// sela_hip_decode_n_device / sela_hip_decode_payload_n_device (5.13)
+template <typename Form>
+int decode_n_call(const Form& form, uint32_t channels, uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "decode_n", sela::decode_n_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            const int rc = check_frames_shape(n_frames, channels, stride);
+            return rc != SELA_HIP_OK ? rc : need_pointers(d_status && d_workspace && (!n_frames || d_pcm_out));
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launch_with_priorities(max_frames, stream, "decode_n launch", [&](uint32_t synth_priorities) {
+                return sela::launch_decode_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_ws,
+                    sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
+// sela_hip_verify_device / sela_hip_verify_payload_device (5.14): the decode_n call with the compare's arrays
+template <typename Form>
+int verify_call(const Form& form, uint32_t channels, uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff,
+    uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "verify", sela::verify_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || (d_pcm && d_diff_counts && d_first_diff)));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_pcm & 1) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_pcm must be 2-byte aligned, d_diff_counts and d_first_diff 4-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launch_with_priorities(max_frames, stream, "verify launch", [&](uint32_t synth_priorities) {
+                return sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff,
+                    d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
+// sela_hip_verify_i32_device / sela_hip_verify_payload_i32_device (5.15): the decode_i32 call with the compare's arrays
+template <typename Form>
+int verify_i32_call(const Form& form, uint32_t channels, uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts,
+    uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "verify_i32", sela::verify_i32_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || (d_samples && d_diff_counts && d_first_diff)));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_samples & 3) || ((uintptr_t)d_lengths & 3) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_samples, d_lengths, d_diff_counts and d_first_diff must be 4-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_verify_i32_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_diff_counts,
+                                d_first_diff, d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), c.stream),
+                "verify_i32 launch");
+        });
+}
 } // namespace
+} // extern "C++"
 
 size_t sela_hip_decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
@@ -1623,61 +1697,24 @@ size_t sela_hip_decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channel
 int sela_hip_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
     int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = check_decode_i32_args(n_frames, channels, stride, d_samples_out, d_counts_out, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    if (!d_frame_offsets || (n_frames && !d_frames))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if ((uintptr_t)d_frames & 3)
-        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
-    if (workspace_bytes < sela::decode_i32_workspace_bytes(n_frames, channels, stride))
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_decode_i32_workspace_bytes()");
-    const hipError_t e = sela::launch_decode_i32_device(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_samples_out, d_counts_out,
-        d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "decode_i32 launch");
+    return decode_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_samples_out, d_counts_out, d_sample_offsets, d_status, d_workspace,
+        workspace_bytes, stream);
 }
 
 int sela_hip_decode_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
     int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
     void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
-    if (rc == SELA_HIP_OK)
-        rc = check_decode_i32_args(max_frames, channels, stride, d_samples_out, d_counts_out, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), decode_bytes = sela::decode_i32_workspace_bytes(max_frames, channels, stride);
-    if (decode_bytes == SIZE_MAX || workspace_bytes < index_bytes + decode_bytes)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_i32_workspace_bytes()");
-    hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "index launch");
-    e = sela::launch_decode_i32_device(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_samples_out, d_counts_out, d_sample_offsets,
-        d_status, static_cast<unsigned char*>(d_workspace) + index_bytes, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "decode_i32 launch");
+    return decode_i32_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_samples_out, d_counts_out,
+        d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
 }
 
-// sela_hip_decode_i32's checks after its walk, in its order (sela_hip_decode_i32 above, generic_decode in sela_capi_generic.hip)
+// sela_hip_decode_i32's verdict on the device's status words
 int sela_hip_decode_status_error(const uint32_t* status)
 {
     if (!status)
         return fail(SELA_HIP_EINVAL, "null pointer");
-    const uint32_t flags = status[0];
-    if (flags & SELA_HIP_FLAG_STRIDE)
-        return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (status[2])");
-    if ((flags & SELA_HIP_FLAG_BAD_FRAME) || status[1])
-        return fail(SELA_HIP_EFORMAT, "malformed frame (decreasing offsets, sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, or channels of different lengths)");
-    if (flags & SELA_HIP_FLAG_RICE_OVERRUN)
-        return fail(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
-    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return fail(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
-    if (flags & SELA_HIP_FLAG_Q_RANGE)
-        return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-    if (flags & SELA_HIP_FLAG_SHORT_BLOCK)
-        return fail(SELA_HIP_ERANGE, "decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)");
-    if (flags & SELA_HIP_FLAG_INTERNAL)
-        return fail(SELA_HIP_ENODEV, "decode: a bounded wait inside a kernel ran out");
-    return SELA_HIP_OK;
+    return sela::judge_decode(status[0] | (status[1] ? SELA_HIP_FLAG_BAD_FRAME : 0u), ~0u, sela::kRouteDevice32, "decode");
 }
 
 // ---- the any-length / 32-bit encode on device pointers ------------------------------------------
@@ -1698,9 +1735,9 @@ int encode_i32_device_call(const void* d_input, bool in16, uint32_t n_frames, ui
         return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned, the samples aligned to their type");
     if (workspace_bytes < sela::encode_i32_device_workspace_bytes(n_frames, channels, n))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_i32_workspace_bytes()");
-    const hipError_t e = sela::launch_encode_i32_device(d_input, in16, n_frames, channels, n, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-        static_cast<hipStream_t>(stream), lossless);
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "encode_i32 launch");
+    return launched(sela::launch_encode_i32_device(d_input, in16, n_frames, channels, n, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
+                        static_cast<hipStream_t>(stream), lossless),
+        "encode_i32 launch");
 }
 } // namespace
 
@@ -1726,73 +1763,33 @@ int sela_hip_encode_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t c
 int sela_hip_encode_i32_device_opt(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_i32_device(d_samples, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-            workspace_bytes, stream);
-    const int rc = check_encode_options(options);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    return encode_i32_device_call(d_samples, false, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-        workspace_bytes, stream, true);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
+    return rc != SELA_HIP_OK ? rc : encode_i32_device_call(d_samples, false, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status,
+                                        d_workspace, workspace_bytes, stream, lossless);
 }
 
 int sela_hip_encode_n_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames, size_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_n_device(d_pcm, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-            workspace_bytes, stream);
-    const int rc = check_encode_options(options);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    return encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-        workspace_bytes, stream, true);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
+    return rc != SELA_HIP_OK ? rc : encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status,
+                                        d_workspace, workspace_bytes, stream, lossless);
 }
 
-// the any-length route's checks after its plan, in its order (flags_error, then the capacity: generic_encode in sela_capi_generic.hip)
+// the any-length route's verdict after its plan (generic_encode in sela_capi_generic.hip): the flags, then the capacity
 int sela_hip_encode_status_error(const uint32_t* status)
 {
     if (!status)
         return fail(SELA_HIP_EINVAL, "null pointer");
-    const uint32_t flags = status[0];
-    if (flags & SELA_HIP_FLAG_SHORT_BLOCK)
-        return fail(SELA_HIP_ERANGE, "encode: a block is not longer than its predictor order (the reference reads past its vector there, src/lpc/residue_generator.cpp:104-110)");
-    if (flags & SELA_HIP_FLAG_RICE_RANGE)
-        return fail(SELA_HIP_ERANGE, "encode: a residue is beyond the reference's int32 zig-zag (|value| >= 2^30)");
-    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return fail(SELA_HIP_ERANGE, "encode: a predictor coefficient left the int64 range");
-    if (flags & SELA_HIP_FLAG_WORDS_CAP)
-        return fail(SELA_HIP_ERANGE, "encode: a Rice stream needs more words than a subframe's 16-bit count can say");
+    const int rc = sela::judge_encode(status[0], sela::kJudgeEncode, "encode");
+    if (rc != SELA_HIP_OK)
+        return rc;
     if (status[1])
         return fail(SELA_HIP_ECAPACITY, "d_frames too small: status[1] frames were not written (d_frame_offsets[n_frames] bytes are needed)");
     return SELA_HIP_OK;
 }
-
-// ---- the int16 decode of any length on device pointers ----------------------------------------------------
-namespace {
-// what sela_hip_decode_n_device and the payload call check alike; SELA_HIP_OK or the failure, reported
-int check_decode_n_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm_out, const uint32_t* d_status, const void* d_workspace)
-{
-    if (channels == 0 || channels > 255)
-        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
-    if (stride == 0)
-        return fail(SELA_HIP_EINVAL, "stride must not be 0");
-    if ((uint64_t)n_frames * channels >= (1ull << 31))
-        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
-    if (!d_status || !d_workspace || (n_frames && !d_pcm_out))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    return SELA_HIP_OK;
-}
-
-int decode_n_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
-    int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
-{
-    return launch_with_priorities(max_frames, stream, "decode_n launch", [&](uint32_t synth_priorities) {
-        return sela::launch_decode_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_workspace,
-            sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
-    });
-}
-} // namespace
 
 size_t sela_hip_decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
@@ -1802,88 +1799,30 @@ size_t sela_hip_decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels,
 int sela_hip_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
     int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = check_decode_n_args(n_frames, channels, stride, d_pcm_out, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    if (!d_frame_offsets || (n_frames && !d_frames))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if ((uintptr_t)d_frames & 3)
-        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
-    const size_t need = sela::decode_n_workspace_bytes(n_frames, channels, stride);
-    if (need == SIZE_MAX || workspace_bytes < need)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_decode_n_workspace_bytes()");
-    return decode_n_launch(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_workspace, stream);
+    return decode_n_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_pcm_out, d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
 }
 
 int sela_hip_decode_payload_n_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
     int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
     size_t workspace_bytes, void* stream)
 {
-    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
-    if (rc == SELA_HIP_OK)
-        rc = check_decode_n_args(max_frames, channels, stride, d_pcm_out, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), decode_bytes = sela::decode_n_workspace_bytes(max_frames, channels, stride);
-    if (decode_bytes == SIZE_MAX || workspace_bytes < index_bytes + decode_bytes)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_n_workspace_bytes()");
-    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "index launch");
-    return decode_n_launch(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_pcm_out, d_sample_offsets, d_status,
-        static_cast<unsigned char*>(d_workspace) + index_bytes, stream);
+    return decode_n_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_pcm_out, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
 }
 
-// sela_hip_decode's code, by the route the device took (status[3]): the streaming job's mapping behind the fast kernels
-// (job_end), generic_decode's order behind the any-length route, EFORMAT where the host call's walk refuses the stream
+// sela_hip_decode's verdict, by the route the device took (status[3]): the any-length route's as sela_hip_decode_i32's, the fast
+// kernels' as the streaming job's, and a stream the header walk refused: malformed, whatever else it says
 int sela_hip_decode_n_status_error(const uint32_t* status)
 {
     if (!status)
         return fail(SELA_HIP_EINVAL, "null pointer");
-    const uint32_t flags = status[0];
-    if (flags & SELA_HIP_FLAG_STRIDE)
-        return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (status[2])");
+    const uint32_t flags = status[0] | (status[1] ? SELA_HIP_FLAG_BAD_FRAME : 0u);
     if (status[3] == 2)
-        return sela_hip_decode_status_error(status);
-    if ((flags & SELA_HIP_FLAG_BAD_FRAME) || status[1])
-        return fail(SELA_HIP_EFORMAT, status[3] == 1 ? "malformed frame stream (bad sync word or subframe header)"
-                                                     : "malformed frame stream (the header walk breaks, frame offsets decrease, or no subframe says a length)");
-    if (status[3] != 1)
-        return SELA_HIP_OK;
-    if (flags & SELA_HIP_FLAG_RICE_OVERRUN)
-        return fail(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
-    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return fail(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
-    if (flags & SELA_HIP_FLAG_Q_RANGE)
-        return fail(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-    return SELA_HIP_OK;
+        return sela::judge_decode(flags, ~0u, sela::kRouteDevice32, "decode");
+    if (status[3] == 1)
+        return sela::judge_decode(flags, SELA_HIP_FLAG_STRIDE | sela::kJudgeJob, sela::kRouteFast, "decode");
+    return sela::judge_decode(flags, SELA_HIP_FLAG_STRIDE | SELA_HIP_FLAG_BAD_FRAME, sela::kRouteWalk, "decode");
 }
-
-// ---- verification: a stream against its PCM -----------------------------------------------------------------
-namespace {
-// what sela_hip_verify_device and the payload call check alike (check_decode_n_args with the two arrays); SELA_HIP_OK or the failure
-int check_verify_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm, const uint32_t* d_diff_counts, const uint32_t* d_first_diff,
-    const uint32_t* d_status, const void* d_workspace)
-{
-    const int rc = check_decode_n_args(n_frames, channels, stride, d_pcm, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    if (n_frames && (!d_diff_counts || !d_first_diff))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if (((uintptr_t)d_pcm & 1) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3))
-        return fail(SELA_HIP_EINVAL, "d_pcm must be 2-byte aligned, d_diff_counts and d_first_diff 4-byte aligned");
-    return SELA_HIP_OK;
-}
-
-int verify_launch(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
-    const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, void* stream)
-{
-    return launch_with_priorities(max_frames, stream, "verify launch", [&](uint32_t synth_priorities) {
-        return sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets,
-            d_status, d_workspace, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, static_cast<hipStream_t>(stream));
-    });
-}
-} // namespace
 
 size_t sela_hip_verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
@@ -1893,37 +1832,16 @@ size_t sela_hip_verify_workspace_bytes(uint32_t max_frames, uint32_t channels, u
 int sela_hip_verify_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = check_verify_args(n_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    if (!d_frame_offsets || (n_frames && !d_frames))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if ((uintptr_t)d_frames & 3)
-        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
-    const size_t need = sela::verify_workspace_bytes(n_frames, channels, stride);
-    if (need == SIZE_MAX || workspace_bytes < need)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_verify_workspace_bytes()");
-    return verify_launch(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets, d_status, d_workspace,
-        stream);
+    return verify_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets, d_status, d_workspace,
+        workspace_bytes, stream);
 }
 
 int sela_hip_verify_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, const int16_t* d_pcm,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
     void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
-    if (rc == SELA_HIP_OK)
-        rc = check_verify_args(max_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), verify_bytes = sela::verify_workspace_bytes(max_frames, channels, stride);
-    if (verify_bytes == SIZE_MAX || workspace_bytes < index_bytes + verify_bytes)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_verify_workspace_bytes()");
-    const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "index launch");
-    return verify_launch(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_pcm, d_diff_counts, d_first_diff, d_sample_offsets, d_status,
-        static_cast<unsigned char*>(d_workspace) + index_bytes, stream);
+    return verify_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_pcm, d_diff_counts, d_first_diff,
+        d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
 }
 
 // Host pointers, synchronous: on the any-length route's leased context and stream (generic_verify), past the coalescer; the
@@ -1940,26 +1858,6 @@ int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     return sela::generic_verify(frames, frame_offsets, n_frames, channels, pcm, diff_counts, first_diff, lossy_frames, g_recurrence_form);
 }
 
-// ---- verification of 32-bit and ragged streams: a stream against its int32 samples ---------------------------
-namespace {
-// what sela_hip_verify_i32_device and the payload call check alike (check_decode_i32_args with the compare's arrays)
-int check_verify_i32_args(uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths,
-    const uint32_t* d_diff_counts, const uint32_t* d_first_diff, const uint32_t* d_status, const void* d_workspace)
-{
-    if (channels == 0 || channels > 255)
-        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
-    if (stride == 0)
-        return fail(SELA_HIP_EINVAL, "stride must not be 0");
-    if ((uint64_t)n_frames * channels >= (1ull << 31))
-        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
-    if (!d_status || !d_workspace || (n_frames && (!d_samples || !d_diff_counts || !d_first_diff)))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if (((uintptr_t)d_samples & 3) || ((uintptr_t)d_lengths & 3) || ((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3))
-        return fail(SELA_HIP_EINVAL, "d_samples, d_lengths, d_diff_counts and d_first_diff must be 4-byte aligned");
-    return SELA_HIP_OK;
-}
-} // namespace
-
 size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return sela::verify_i32_workspace_bytes(max_frames, channels, stride);
@@ -1969,39 +1867,16 @@ int sela_hip_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_
     const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status,
     void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    const int rc = check_verify_i32_args(n_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    if (!d_frame_offsets || (n_frames && !d_frames))
-        return fail(SELA_HIP_EINVAL, "null device pointer");
-    if ((uintptr_t)d_frames & 3)
-        return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned");
-    const size_t need = sela::verify_i32_workspace_bytes(n_frames, channels, stride);
-    if (need == SIZE_MAX || workspace_bytes < need)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_verify_i32_workspace_bytes()");
-    const hipError_t e = sela::launch_verify_i32_device(d_frames, d_frame_offsets, n_frames, nullptr, channels, stride, d_samples, d_lengths, d_diff_counts,
-        d_first_diff, d_sample_offsets, d_status, d_workspace, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "verify_i32 launch");
+    return verify_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff, d_sample_offsets,
+        d_status, d_workspace, workspace_bytes, stream);
 }
 
 int sela_hip_verify_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
     const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets,
     uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    int rc = check_index_args(d_payload, payload_bytes, channels, d_frame_offsets, d_n_frames, d_workspace);
-    if (rc == SELA_HIP_OK)
-        rc = check_verify_i32_args(max_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff, d_status, d_workspace);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), verify_bytes = sela::verify_i32_workspace_bytes(max_frames, channels, stride);
-    if (verify_bytes == SIZE_MAX || workspace_bytes < index_bytes + verify_bytes)
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_verify_i32_workspace_bytes()");
-    hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-        return fail_hip(e, "index launch");
-    e = sela::launch_verify_i32_device(d_payload, d_frame_offsets, max_frames, d_n_frames, channels, stride, d_samples, d_lengths, d_diff_counts, d_first_diff,
-        d_sample_offsets, d_status, static_cast<unsigned char*>(d_workspace) + index_bytes, sela::generic_standard_first_mode(), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, "verify_i32 launch");
+    return verify_i32_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_samples, d_lengths, d_diff_counts,
+        d_first_diff, d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
 }
 
 // Host pointers, synchronous: sela_hip_decode_i32's checks in its order, then chunks of frames on the any-length route's leased
@@ -2017,9 +1892,8 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
         return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
     if (n_frames == 0)
         return SELA_HIP_OK;
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
     const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
     if (largest > stride)
         return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (see sela_hip_index_samples)");
@@ -2074,14 +1948,13 @@ int sela_hip_encode_begin(sela_hip_job** job, uint32_t channels, uint32_t total_
 int sela_hip_encode_begin_opt(sela_hip_job** job, uint32_t channels, uint32_t total_frames, uint8_t* frames_out, size_t frames_cap,
     uint64_t* frame_offsets_out, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_begin(job, channels, total_frames, frames_out, frames_cap, frame_offsets_out);
-    int rc = check_encode_options(options);
+    bool lossless = false;
+    int rc = encode_options(options, &lossless);
     if (rc != SELA_HIP_OK)
         return rc;
     rc = sela_hip_encode_begin(job, channels, total_frames, frames_out, frames_cap, frame_offsets_out);
     if (rc == SELA_HIP_OK)
-        (*job)->lossless = true; // (nothing is launched before the first feed)
+        (*job)->lossless = lossless; // (nothing is launched before the first feed)
     return rc;
 }
 
@@ -2214,8 +2087,7 @@ struct HipBackend {
     static std::string last_error() { return sela_hip_last_error(); }
     static void after_batch() // (both routes' leases: whoever leads next takes them over instead of creating a set of its own)
     {
-        g_lease.give_back();
-        sela::generic_release();
+        sela_hip_thread_release();
     }
 };
 using sela::kCoalesceFrames;
@@ -2286,11 +2158,12 @@ int sela_hip_encode(const int16_t* pcm, uint32_t n_frames, uint32_t channels, ui
 int sela_hip_encode_opt(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
     size_t frames_cap, uint64_t* frame_offsets_out, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode(pcm, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
-    const int rc = check_encode_options(options);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
     if (rc != SELA_HIP_OK)
         return rc;
+    if (!lossless)
+        return sela_hip_encode(pcm, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
     if (samples_per_channel == 0 || samples_per_channel > 65535)
         return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
     if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!pcm || !frames_out)))
@@ -2341,9 +2214,8 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (rc != SELA_HIP_EFORMAT || n_frames == 0)
         return rc;
     const std::string first_error = first_is_standard ? std::string(sela_hip_last_error()) : std::string("malformed frame stream");
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
     bool standard = true;
     std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
     const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), &standard);
@@ -2367,9 +2239,8 @@ uint32_t sela_hip_index_samples(const uint8_t* frames, const uint64_t* frame_off
                 sample_offsets[f] = 0;
         return 0;
     }
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return 0;
+    if (!sela::frame_offsets_ascend(frame_offsets, n_frames))
+        return 0;
     return sela::generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets, nullptr);
 }
 
@@ -2398,11 +2269,12 @@ int sela_hip_encode_i32(const int32_t* samples, uint32_t n_frames, uint32_t chan
 int sela_hip_encode_i32_opt(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out, size_t frames_cap,
     uint64_t* frame_offsets_out, uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_i32(samples, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
-    const int rc = check_encode_options(options);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
     if (rc != SELA_HIP_OK)
         return rc;
+    if (!lossless)
+        return sela_hip_encode_i32(samples, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out);
     if (samples_per_channel == 0 || samples_per_channel > 65535)
         return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
     if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!samples || !frames_out)))
@@ -2483,12 +2355,9 @@ int sela_hip_encode_ragged_i32(const int32_t* samples, const uint32_t* lengths, 
 int sela_hip_encode_ragged_i32_opt(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out, size_t frame_cap, size_t* frame_bytes,
     uint32_t options)
 {
-    if (options == 0)
-        return sela_hip_encode_ragged_i32(samples, lengths, channels, frame_out, frame_cap, frame_bytes);
-    const int rc = check_encode_options(options);
-    if (rc != SELA_HIP_OK)
-        return rc;
-    return encode_ragged_call(samples, lengths, channels, frame_out, frame_cap, frame_bytes, true);
+    bool lossless = false;
+    const int rc = encode_options(options, &lossless);
+    return rc != SELA_HIP_OK ? rc : encode_ragged_call(samples, lengths, channels, frame_out, frame_cap, frame_bytes, lossless);
 }
 
 int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
@@ -2498,9 +2367,8 @@ int sela_hip_decode_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
         return fail(SELA_HIP_EINVAL, "bad argument");
     if (n_frames == 0)
         return SELA_HIP_OK;
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return fail(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
     const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
     if (largest > stride)
         return fail(SELA_HIP_ECAPACITY, "stride is smaller than the largest samplesPerChannel of the stream (see sela_hip_index_samples)");
@@ -2522,7 +2390,7 @@ int sela_hip_lpc_encode_n(const int32_t* samples, uint32_t n_blocks, uint32_t sa
     if (samples_per_block == 0 || samples_per_block > (1u << 24))
         return fail(SELA_HIP_EINVAL, "samples_per_block must be 1 .. 2^24");
     if (n_blocks == 0)
-        return stage_device_ready();
+        return sela::device_ready();
     return sela::generic_lpc_encode(samples, n_blocks, samples_per_block, order_out, q_out, residues_out);
 }
 
@@ -2534,7 +2402,7 @@ int sela_hip_lpc_decode_n(const int32_t* order, const int32_t* q, const int32_t*
     if (samples_per_block == 0 || samples_per_block > (1u << 24))
         return fail(SELA_HIP_EINVAL, "samples_per_block must be 1 .. 2^24");
     if (n_blocks == 0)
-        return stage_device_ready();
+        return sela::device_ready();
     return sela::generic_lpc_decode(order, q, residues, n_blocks, samples_per_block, samples_out, coefs_out);
 }
 
@@ -2542,7 +2410,7 @@ int sela_hip_lpc_encode(const int32_t* samples, uint32_t n_blocks, int32_t* orde
 {
     if (n_blocks && (!samples || !order_out || !q_out || !residues_out))
         return fail(SELA_HIP_EINVAL, "null pointer");
-    if (stage_device_ready() != SELA_HIP_OK)
+    if (sela::device_ready() != SELA_HIP_OK)
         return SELA_HIP_ENODEV;
     if (n_blocks == 0)
         return SELA_HIP_OK;
@@ -2597,7 +2465,7 @@ int sela_hip_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* r
 {
     if (n_blocks && (!order || !q || (samples_out && !residues) || (!samples_out && !coefs_out)))
         return fail(SELA_HIP_EINVAL, "null pointer");
-    if (stage_device_ready() != SELA_HIP_OK)
+    if (sela::device_ready() != SELA_HIP_OK)
         return SELA_HIP_ENODEV;
     if (n_blocks == 0)
         return SELA_HIP_OK;
@@ -2625,13 +2493,7 @@ int sela_hip_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* r
         e = hipMemcpy(coefs_out, d_coefs, (size_t)n_blocks * kCoefs * sizeof(int64_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess)
         return fail_hip(e, "lpc_decode");
-    if (status[0] & SELA_HIP_FLAG_BAD_FRAME)
-        return fail(SELA_HIP_EINVAL, "lpc_decode: order outside 0..100");
-    if (status[0] & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return fail(SELA_HIP_ERANGE, "lpc_decode: a predictor coefficient left the int64 range");
-    if (status[0] & SELA_HIP_FLAG_Q_RANGE)
-        return fail(SELA_HIP_ERANGE, "lpc_decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-    return SELA_HIP_OK;
+    return sela::judge_decode(status[0], sela::kJudgeLpc, sela::kRouteLpc, "lpc_decode"); // (the fast kernels' blocks are 2048 samples: never SHORT_BLOCK)
 }
 
 int sela_hip_rice_encode(const int32_t* values, const uint64_t* value_offsets, uint32_t n_streams, uint32_t* k_out, uint32_t* word_counts_out,
@@ -2639,7 +2501,7 @@ int sela_hip_rice_encode(const int32_t* values, const uint64_t* value_offsets, u
 {
     if (n_streams && (!value_offsets || !k_out || !word_counts_out || !word_offsets))
         return fail(SELA_HIP_EINVAL, "null pointer");
-    if (stage_device_ready() != SELA_HIP_OK)
+    if (sela::device_ready() != SELA_HIP_OK)
         return SELA_HIP_ENODEV;
     if (n_streams == 0)
         return SELA_HIP_OK;
@@ -2687,7 +2549,7 @@ int sela_hip_rice_decode(const uint32_t* words, const uint64_t* word_offsets, co
 {
     if (n_streams && (!word_offsets || !k || !value_offsets))
         return fail(SELA_HIP_EINVAL, "null pointer");
-    if (stage_device_ready() != SELA_HIP_OK)
+    if (sela::device_ready() != SELA_HIP_OK)
         return SELA_HIP_ENODEV;
     if (n_streams == 0)
         return SELA_HIP_OK;

@@ -17,13 +17,8 @@
 #include <string>
 #include <vector>
 
-#include "sela_device.h"
-#include "sela_generic.h"
-
-namespace sela {
-int report_error(int code, const std::string& what);      // sela_capi.hip: sets the thread's last error, returns code
-int report_hip_error(hipError_t e, const char* where);    // (ENOMEM for an allocation failure, ENODEV otherwise)
-}
+#include "sela_host.h"
+#include "sela_lease.h"
 
 namespace {
 
@@ -68,8 +63,7 @@ struct Arena { // one device allocation, handed out in aligned pieces for the le
 
 // What a calling thread needs on a device: scratch and a stream of its own (threads that code a frame at a time through the
 // frame classes run side by side on the device instead of taking turns on the default stream).  Leased like the fast path's
-// contexts (sela_capi.hip): a thread that ends -- programs start threads per job -- parks its set for the next thread on
-// that device instead of paying a stream and an allocation again; sela_hip_shutdown() frees the parked ones.
+// contexts (sela_lease.h): a thread that ends parks its set for the next thread on that device.
 struct PinnedScratch { // page-locked host memory for what a call reads back first (status words, offsets, a small call's whole output)
     uint8_t* base = nullptr;
     size_t cap = 0;
@@ -93,37 +87,6 @@ struct PinnedScratch { // page-locked host memory for what a call reads back fir
         return base;
     }
 };
-
-struct GenericContext {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    Arena arena;
-    PinnedScratch pinned;
-    void destroy()
-    {
-        int before = -1;
-        (void)hipGetDevice(&before);
-        if (device >= 0 && before != device)
-            (void)hipSetDevice(device);
-        arena.release();
-        pinned.release();
-        if (stream)
-            (void)hipStreamDestroy(stream);
-        stream = nullptr;
-        if (before >= 0 && before != device)
-            (void)hipSetDevice(before);
-    }
-};
-struct ContextPark {
-    std::mutex mu;
-    std::vector<GenericContext*> idle;
-};
-ContextPark& park()
-{
-    static ContextPark* p = new ContextPark; // (never destroyed: threads may end after the statics)
-    return *p;
-}
-constexpr size_t kParked = 64;
 
 // A context's stream.  The runtime serves all streams through a few hardware queues (four) and gives a new stream the queue with the
 // fewest streams on it at that moment; two contexts whose streams share a queue take turns on the device instead of running side
@@ -156,58 +119,51 @@ hipError_t fresh_stream(int dev, hipStream_t* out)
     return hipSuccess;
 }
 
-struct Lease {
-    GenericContext* held = nullptr;
-    ~Lease() { give_back(); }
-    void give_back()
+struct GenericContext : sela::CurrentDevice {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    Arena arena;
+    PinnedScratch pinned;
+    hipError_t open() { return stream ? hipSuccess : fresh_stream(device, &stream); } // (on the context's device, before its first use)
+    // what the lease asks of it (sela_lease.h)
+    static constexpr size_t kParked = 64;
+    static GenericContext* make(int dev)
     {
-        if (!held)
-            return;
-        GenericContext* c = held;
-        held = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(park().mu);
-            if (park().idle.size() < kParked) {
-                park().idle.push_back(c);
-                return;
-            }
-        }
-        c->destroy();
-        delete c;
-    }
-    // the calling thread's context on its current device (null + an error code when the runtime refuses)
-    GenericContext* get(hipError_t& err)
-    {
-        int dev = -1;
-        err = hipGetDevice(&dev);
-        if (err != hipSuccess)
-            return nullptr;
-        if (held && held->device == dev)
-            return held;
-        give_back();
-        {
-            // the context parked LAST: the few that are in use at a time stay the same few, and those are the ones whose streams were
-            // created one after the other (see fresh_stream)
-            std::lock_guard<std::mutex> lock(park().mu);
-            for (size_t i = park().idle.size(); i-- > 0;)
-                if (park().idle[i]->device == dev) {
-                    held = park().idle[i];
-                    park().idle.erase(park().idle.begin() + (ptrdiff_t)i);
-                    return held;
-                }
-        }
         GenericContext* c = new GenericContext;
         c->device = dev;
-        err = fresh_stream(dev, &c->stream);
-        if (err != hipSuccess) {
-            delete c;
-            return nullptr;
-        }
-        held = c;
-        return held;
+        return c;
+    }
+    bool serves(int dev) const { return device == dev; } // (its stream and scratch are that device's: another device, another context)
+    void tidy() {}
+    void destroy()
+    {
+        arena.release();
+        pinned.release();
+        if (stream)
+            (void)hipStreamDestroy(stream);
+        stream = nullptr;
     }
 };
-thread_local Lease g_lease;
+thread_local sela::ContextLease<GenericContext> g_lease;
+
+// What every entry point of the route opens with: a device, and the calling thread's context on it.
+struct Call {
+    int rc; // SELA_HIP_OK, or the failure, reported
+    GenericContext* ctx = nullptr;
+    Call()
+    {
+        if ((rc = sela::device_ready()) != SELA_HIP_OK)
+            return;
+        int dev = -1;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess && (ctx = g_lease.get(dev)))
+            e = ctx->open();
+        if (e != hipSuccess)
+            rc = sela::report_hip_error(e, "the calling thread's scratch and stream");
+    }
+    Arena& arena() const { return ctx->arena; }
+    hipStream_t stream() const { return ctx->stream; }
+};
 
 std::atomic<int> g_standard_first_mode{-1}; // sela_hip_debug_standard_first
 std::atomic<int> g_standard_chunks{0};
@@ -216,46 +172,13 @@ std::atomic<long long> g_segment_subframes{0}; // subframes k_decode_subframes32
 constexpr size_t kPiece = 256; // what take() may add per piece
 constexpr size_t kChunkBudget = (size_t)768 << 20; // device scratch per chunk of frames
 
-int device_ready()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return sela::report_error(SELA_HIP_ENODEV, "no HIP device visible (the SELA MI355X path has no CPU fallback)");
-    return SELA_HIP_OK;
-}
-
-int flags_error(uint32_t flags, const char* who)
-{
-    if (flags & SELA_HIP_FLAG_SHORT_BLOCK)
-        return sela::report_error(SELA_HIP_ERANGE, std::string(who) + ": a block is not longer than its predictor order (the reference reads past its vector there, src/lpc/residue_generator.cpp:104-110)");
-    if (flags & SELA_HIP_FLAG_RICE_RANGE)
-        return sela::report_error(SELA_HIP_ERANGE, std::string(who) + ": a residue is beyond the reference's int32 zig-zag (|value| >= 2^30)");
-    if (flags & SELA_HIP_FLAG_COEF_OVERFLOW)
-        return sela::report_error(SELA_HIP_ERANGE, std::string(who) + ": a predictor coefficient left the int64 range");
-    if (flags & SELA_HIP_FLAG_WORDS_CAP)
-        return sela::report_error(SELA_HIP_ERANGE, std::string(who) + ": a Rice stream needs more words than a subframe's 16-bit count can say");
-    return SELA_HIP_OK;
-}
-
 } // namespace
 
 namespace sela {
 
 void generic_release() { g_lease.give_back(); }
 int generic_standard_first_mode() { return g_standard_first_mode.load(std::memory_order_relaxed); }
-void generic_shutdown()
-{
-    g_lease.give_back();
-    std::vector<GenericContext*> idle;
-    {
-        std::lock_guard<std::mutex> lock(park().mu);
-        idle.swap(park().idle);
-    }
-    for (GenericContext* c : idle) {
-        c->destroy();
-        delete c;
-    }
-}
+void generic_shutdown() { g_lease.shutdown(); }
 
 size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
 {
@@ -276,13 +199,10 @@ constexpr size_t kEagerBytes = (size_t)4 << 20;
 int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap,
     uint64_t* frame_offsets_out, bool lossless /* SELA_HIP_ENCODE_LOSSLESS */)
 {
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& g_arena = call.arena();
     const uint32_t n_sig = channels == 2 ? 3u : channels;
     const size_t in_frame_bytes = (size_t)n * channels * (in16 ? 2 : 4);
     const size_t est_frame_bytes = ((size_t)n * channels * 9) / 2 + (size_t)channels * 192 + 64; // words and frame bytes, each (a subframe: 12 bytes of header, up to 32 coefficient words)
@@ -291,7 +211,7 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
     uint64_t base_bytes = 0;
     frame_offsets_out[0] = 0;
-    const hipStream_t st = ctx->stream;
+    const hipStream_t st = call.stream();
     for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const uint32_t cf = std::min(chunk, n_frames - f0);
         const size_t blocks = (size_t)cf * n_sig, subs = (size_t)cf * channels;
@@ -318,7 +238,7 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
         if (!g_arena.fits())
             return report_error(SELA_HIP_ENOMEM, "generic encode: internal scratch estimate too small");
         const bool eager = est_bytes <= kEagerBytes;
-        uint8_t* const pin = ctx->pinned.reserve(head_words * 8 + (eager ? est_bytes : 0));
+        uint8_t* const pin = call.ctx->pinned.reserve(head_words * 8 + (eager ? est_bytes : 0));
         std::vector<uint64_t> head_pageable;
         uint64_t* head = reinterpret_cast<uint64_t*>(pin);
         if (!pin) {
@@ -349,7 +269,7 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
         std::memcpy(status, head, 16);
         const uint64_t total_words = head[2];
         std::memcpy(frame_offsets_out + f0, head + 3, ((size_t)cf + 1) * 8);
-        const int rc = flags_error(status[0], "encode");
+        const int rc = judge_encode(status[0], kJudgeEncode, "encode");
         if (rc != SELA_HIP_OK)
             return rc;
         const uint64_t chunk_bytes = frame_offsets_out[f0 + cf] - base_bytes;
@@ -432,21 +352,17 @@ uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offs
 int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
     uint32_t* counts_out, int16_t* pcm_out, const uint64_t* sample_offsets)
 {
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return report_error(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& g_arena = call.arena();
+    if (check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
     if (stride == 0)
         stride = 1;
     const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 4) + 16 + (size_t)channels * stride * (pcm_out ? 2 : 0);
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
-    const hipStream_t st = ctx->stream;
+    const hipStream_t st = call.stream();
     for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const uint32_t cf = std::min(chunk, n_frames - f0);
         const size_t subs = (size_t)cf * channels;
@@ -486,7 +402,7 @@ int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
             user_locked = hipPointerGetAttributes(&attr, user_out) == hipSuccess && attr.type == hipMemoryTypeHost;
             (void)hipGetLastError(); // (ordinary memory is not an error)
         }
-        uint8_t* const pin = ctx->pinned.reserve(tail_bytes + offsets_bytes + (eager && !user_locked ? out_bytes : 0));
+        uint8_t* const pin = call.ctx->pinned.reserve(tail_bytes + offsets_bytes + (eager && !user_locked ? out_bytes : 0));
         const uint64_t* offsets_src = frame_offsets + f0;
         if (pin) {
             std::memcpy(pin + tail_bytes, frame_offsets + f0, ((size_t)cf + 1) * 8);
@@ -535,18 +451,10 @@ int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
             }
         }
         const uint32_t* const status = tail;
-        if (status[0] & SELA_HIP_FLAG_BAD_FRAME)
-            return report_error(SELA_HIP_EFORMAT, "malformed frame (sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, or channels of different lengths)");
-        if (status[0] & SELA_HIP_FLAG_RICE_OVERRUN)
-            return report_error(SELA_HIP_EFORMAT, "a Rice stream ended before all its values were read");
-        // what the reference itself leaves undefined is reported, never decoded silently (one policy: here, in the streaming
-        // jobs' sela_hip_decode_end and in sela_hip_lpc_decode[_n])
-        if (status[0] & SELA_HIP_FLAG_COEF_OVERFLOW)
-            return report_error(SELA_HIP_ERANGE, "decode: a predictor coefficient left the int64 range");
-        if (status[0] & SELA_HIP_FLAG_Q_RANGE)
-            return report_error(SELA_HIP_ERANGE, "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-        if (status[0] & SELA_HIP_FLAG_SHORT_BLOCK)
-            return report_error(SELA_HIP_ERANGE, "decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)");
+        // (what the reference itself leaves undefined is reported, never decoded silently: the decoders' one policy, sela_host.h)
+        const int verdict = judge_decode(status[0], kJudgeJob | SELA_HIP_FLAG_SHORT_BLOCK, kRouteHost32, "decode");
+        if (verdict != SELA_HIP_OK)
+            return verdict;
         if (!pcm_out)
             std::memcpy(counts_out + (size_t)f0 * channels, tail + 4, subs * 4);
         if (eager_out) {
@@ -562,169 +470,168 @@ int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     return SELA_HIP_OK;
 }
 
-// sela_hip_verify: launch_verify_n_device on chunks of frames, on the calling thread's context and stream.  The
-// stride is the stream's largest samplesPerChannel (the host's walk), a chunk's PCM lies where sela_hip_decode writes it
-// (sample_offsets, relative to the chunk's first frame), and every chunk's status words are judged as
-// sela_hip_decode_n_status_error judges them: the first chunk that fails ends the call with that code.
+// sela_hip_verify and sela_hip_verify_i32: the *_device launch on chunks of frames, on the calling thread's
+// context and stream.  Per chunk the frames, their offsets and the reference data go in; status (4 x u32) | diff_counts [cf] |
+// first_diff [cf] come back in one piece behind the chunk's ONE wait; the first chunk whose status words fail ends the call with
+// that code.  What the two calls differ in is their `Ref`: the reference data (its bytes, its pieces of the arena, its upload),
+// the launch and the judge.
+namespace {
+struct VerifyPcm { // int16, interleaved, where sela_hip_decode writes it (sample_offsets); judged as sela_hip_decode_n_status_error judges
+    const int16_t* pcm;
+    const uint64_t* sample_offsets;
+    uint32_t channels, stride;
+    int recurrence_form;
+    int16_t* d_pcm;
+    uint64_t values(uint32_t f0, uint32_t cf) const { return (sample_offsets[f0 + cf] - sample_offsets[f0]) * channels; }
+    size_t bytes(uint32_t f0, uint32_t cf) const { return (size_t)values(f0, cf) * 2; }
+    void take(Arena& arena, uint32_t f0, uint32_t cf) { d_pcm = arena.take<int16_t>((size_t)values(f0, cf)); }
+    hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
+    {
+        const uint64_t n = values(f0, cf);
+        return n ? hipMemcpyAsync(d_pcm, pcm + sample_offsets[f0] * channels, (size_t)n * 2, hipMemcpyHostToDevice, st) : hipSuccess;
+    }
+    hipError_t launch(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, uint32_t* d_tail, void* d_ws, int mode, hipStream_t st) const
+    {
+        return launch_verify_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode, recurrence_form,
+            0, st);
+    }
+    int judge(const uint32_t* tail) const
+    {
+        const uint32_t route_status[4] = { tail[0], tail[1], 0, tail[3] };
+        return sela_hip_decode_n_status_error(route_status);
+    }
+};
+struct VerifySamples { // int32 [frame][channel][stride], lengths or null; judged as sela_hip_decode_status_error judges
+    const int32_t* samples;
+    const uint32_t* lengths;
+    uint32_t channels, stride;
+    int32_t* d_samples;
+    uint32_t* d_lengths;
+    size_t bytes(uint32_t, uint32_t cf) const { return (size_t)cf * channels * stride * 4 + (size_t)cf * channels * 4; }
+    void take(Arena& arena, uint32_t, uint32_t cf)
+    {
+        d_samples = arena.take<int32_t>((size_t)cf * channels * stride);
+        d_lengths = lengths ? arena.take<uint32_t>((size_t)cf * channels) : nullptr;
+    }
+    hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
+    {
+        const size_t subs = (size_t)cf * channels;
+        hipError_t e = hipMemcpyAsync(d_samples, samples + (size_t)f0 * channels * stride, subs * stride * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && lengths)
+            e = hipMemcpyAsync(d_lengths, lengths + (size_t)f0 * channels, subs * 4, hipMemcpyHostToDevice, st);
+        return e;
+    }
+    hipError_t launch(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, uint32_t* d_tail, void* d_ws, int mode, hipStream_t st) const
+    {
+        return launch_verify_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_samples, d_lengths, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode, st);
+    }
+    int judge(const uint32_t* tail) const
+    {
+        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
+        return sela_hip_decode_status_error(decode_status);
+    }
+};
+
+template <typename Ref>
+int verify_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), Ref ref, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    Arena& g_arena = call.arena();
+    const std::string name(who);
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const hipStream_t st = call.stream();
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    uint32_t lossy = 0;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
+        const size_t ws_bytes = workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, name + ": the chunk is too large");
+        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + ref.bytes(f0, cf) + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
+        hipError_t e = g_arena.reserve(need);
+        if (e != hipSuccess)
+            return report_hip_error(e, (name + ": scratch").c_str());
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
+        ref.take(g_arena, f0, cf);
+        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, name + ": internal scratch estimate too small");
+        std::vector<uint64_t> local((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = ref.upload(f0, cf, st);
+        if (e == hipSuccess)
+            e = ref.launch(d_frames, d_offsets, cf, d_tail, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, who);
+        const int rc = ref.judge(tail.data());
+        if (rc != SELA_HIP_OK)
+            return rc;
+        std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
+        std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
+        lossy += tail[2];
+    }
+    if (lossy_frames)
+        *lossy_frames = lossy;
+    return SELA_HIP_OK;
+}
+} // namespace
+
+// The stride is the stream's largest samplesPerChannel (the host's walk).
 int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
     uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form)
 {
     if (lossy_frames)
         *lossy_frames = 0;
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
-    for (uint32_t f = 0; f < n_frames; f++)
-        if (frame_offsets[f + 1] < frame_offsets[f])
-            return report_error(SELA_HIP_EFORMAT, "frame offsets must not decrease");
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    if (check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
     std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
     const uint32_t largest = generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), nullptr);
     if (n_frames && largest == 0)
         return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
     const uint32_t stride = std::max(largest, 1u);
     const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2 + 2) + (size_t)channels * sizeof(GenericSubInfo) + 64;
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
-    const hipStream_t st = ctx->stream;
-    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
-    uint32_t lossy = 0;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
-        const uint64_t s0 = sample_offsets[f0], chunk_values = (sample_offsets[f0 + cf] - s0) * channels;
-        const size_t ws_bytes = verify_workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, "verify: the chunk is too large");
-        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + (size_t)chunk_values * 2 + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
-        hipError_t e = g_arena.reserve(need);
-        if (e != hipSuccess)
-            return report_hip_error(e, "verify: scratch");
-        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
-        int16_t* d_pcm = g_arena.take<int16_t>((size_t)chunk_values);
-        // what the host reads back, in one piece: status (4 x u32) | diff_counts [cf] | first_diff [cf]
-        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
-        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
-        if (!g_arena.fits())
-            return report_error(SELA_HIP_ENOMEM, "verify: internal scratch estimate too small");
-        std::vector<uint64_t> local((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && chunk_values)
-            e = hipMemcpyAsync(d_pcm, pcm + s0 * channels, (size_t)chunk_values * 2, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_verify_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode,
-                recurrence_form, 0, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, "verify");
-        const uint32_t route_status[4] = { tail[0], tail[1], 0, tail[3] };
-        const int rc = sela_hip_decode_n_status_error(route_status);
-        if (rc != SELA_HIP_OK)
-            return rc;
-        std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
-        std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
-        lossy += tail[2];
-    }
-    if (lossy_frames)
-        *lossy_frames = lossy;
-    return SELA_HIP_OK;
+    return verify_chunks(call, "verify", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_workspace_bytes,
+        VerifyPcm{ pcm, sample_offsets.data(), channels, stride, recurrence_form, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
-// sela_hip_verify_i32: launch_verify_i32_device on chunks of frames, on the calling thread's context and stream.
-// The caller has walked the stream (the offsets never decrease, the largest samplesPerChannel fits the stride); every chunk's
-// status words are judged as sela_hip_decode_status_error judges them: the first chunk that fails ends the call with that code.
+// The caller has walked the stream: the offsets never decrease, the largest samplesPerChannel fits the stride.
 int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
 {
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
     const size_t per_frame = (size_t)channels * stride * 12 + (size_t)channels * (sizeof(GenericSubInfo) + 8) + 64;
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
-    const hipStream_t st = ctx->stream;
-    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
-    uint32_t lossy = 0;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const size_t subs = (size_t)cf * channels;
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
-        const size_t ws_bytes = verify_i32_workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, "verify_i32: the chunk is too large");
-        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + subs * stride * 4 + subs * 4 + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
-        hipError_t e = g_arena.reserve(need);
-        if (e != hipSuccess)
-            return report_hip_error(e, "verify_i32: scratch");
-        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
-        int32_t* d_samples = g_arena.take<int32_t>(subs * stride);
-        uint32_t* d_lengths = lengths ? g_arena.take<uint32_t>(subs) : nullptr;
-        // what the host reads back, in one piece: status (4 x u32) | diff_counts [cf] | first_diff [cf]
-        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
-        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
-        if (!g_arena.fits())
-            return report_error(SELA_HIP_ENOMEM, "verify_i32: internal scratch estimate too small");
-        std::vector<uint64_t> local((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_samples, samples + (size_t)f0 * channels * stride, subs * stride * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && lengths)
-            e = hipMemcpyAsync(d_lengths, lengths + (size_t)f0 * channels, subs * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_verify_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_samples, d_lengths, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws,
-                mode, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, "verify_i32");
-        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
-        const int rc = sela_hip_decode_status_error(decode_status);
-        if (rc != SELA_HIP_OK)
-            return rc;
-        std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
-        std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
-        lossy += tail[2];
-    }
-    if (lossy_frames)
-        *lossy_frames = lossy;
-    return SELA_HIP_OK;
+    return verify_chunks(call, "verify_i32", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_i32_workspace_bytes,
+        VerifySamples{ samples, lengths, channels, stride, nullptr, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out)
 {
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& g_arena = call.arena();
     const size_t per_block = (size_t)n * 12 + kMaxOrder * 4 + sizeof(GenericMeta) + 16;
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_blocks, kChunkBudget / per_block));
     std::vector<GenericMeta> meta;
-    const hipStream_t st = ctx->stream;
+    const hipStream_t st = call.stream();
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += chunk) {
         const uint32_t cb = std::min(chunk, n_blocks - b0);
         hipError_t e = g_arena.reserve((size_t)cb * per_block + 8 * kPiece);
@@ -757,7 +664,7 @@ int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, in
             flags |= meta[i].flags;
         }
         // (a residue beyond the zig-zag's range or a long Rice stream is the Rice stage's business, not this one's)
-        const int rc = flags_error(flags & (SELA_HIP_FLAG_SHORT_BLOCK | SELA_HIP_FLAG_COEF_OVERFLOW), "lpc_encode");
+        const int rc = judge_encode(flags, SELA_HIP_FLAG_SHORT_BLOCK | SELA_HIP_FLAG_COEF_OVERFLOW, "lpc_encode");
         if (rc != SELA_HIP_OK)
             return rc;
     }
@@ -766,15 +673,12 @@ int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, in
 
 int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out)
 {
-    if (device_ready() != SELA_HIP_OK)
-        return SELA_HIP_ENODEV;
-    hipError_t ctx_err = hipSuccess;
-    GenericContext* const ctx = g_lease.get(ctx_err);
-    if (!ctx)
-        return report_hip_error(ctx_err, "the calling thread's scratch and stream");
-    Arena& g_arena = ctx->arena;
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& g_arena = call.arena();
     constexpr size_t kCoefs = kMaxOrder + 1;
-    const hipStream_t st = ctx->stream;
+    const hipStream_t st = call.stream();
     const size_t per_block = (size_t)n * 8 + kMaxOrder * 4 + 4 + kCoefs * 8;
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_blocks, kChunkBudget / per_block));
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += chunk) {
@@ -812,14 +716,9 @@ int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* re
             e = hipStreamSynchronize(st);
         if (e != hipSuccess)
             return report_hip_error(e, "lpc_decode");
-        if (status[0] & SELA_HIP_FLAG_BAD_FRAME)
-            return report_error(SELA_HIP_EINVAL, "lpc_decode: order outside 0..100");
-        if (status[0] & SELA_HIP_FLAG_COEF_OVERFLOW)
-            return report_error(SELA_HIP_ERANGE, "lpc_decode: a predictor coefficient left the int64 range");
-        if (status[0] & SELA_HIP_FLAG_Q_RANGE)
-            return report_error(SELA_HIP_ERANGE, "lpc_decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)");
-        if (status[0] & SELA_HIP_FLAG_SHORT_BLOCK)
-            return report_error(SELA_HIP_ERANGE, "lpc_decode: a block without samples or not longer than its predictor order (the reference writes past its vector, src/lpc/sample_generator.cpp:14-22)");
+        const int verdict = judge_decode(status[0], kJudgeLpc | SELA_HIP_FLAG_SHORT_BLOCK, kRouteLpc, "lpc_decode");
+        if (verdict != SELA_HIP_OK)
+            return verdict;
     }
     return SELA_HIP_OK;
 }

@@ -51,7 +51,7 @@
 // header's field carries) are decoded by k_decode_frames_wide, eight subframes at a time.
 #include <atomic>
 
-#include "sela_device.h"
+#include "sela_host.h"
 
 namespace sela {
 

@@ -5,8 +5,7 @@
 // touch: misaligned or malformed frames, streams that run dry, coefficients outside the tables.
 #include <hip/hip_runtime.h>
 
-#include "sela_device.h"
-#include "sela_generic.h"
+#include "sela_host.h"
 
 namespace sela {
 

@@ -29,7 +29,7 @@
 #include <random>
 #include <vector>
 
-#include "sela_device.h"
+#include "sela_host.h"
 
 namespace sela {
 

@@ -20,15 +20,9 @@
 #include <algorithm>
 #include <atomic>
 
-#include "sela_device.h"
-#include "sela_generic.h"
+#include "sela_host.h"
 
 namespace sela {
-
-// the 2048-sample decoder (sela_decode.hip): route 1 of sela_hip_decode_n_device
-hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* d_pcm_out, uint32_t* d_status,
-    void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles, uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities,
-    const uint32_t* d_n_found, bool zero_status);
 
 namespace {
 

@@ -1,0 +1,97 @@
+// sela_host.h -- every host function of libsela_hip.so that one translation unit defines and another calls, declared once.
+// Included by the file that defines a function and by every file that calls it, so a changed parameter is a compile error;
+// default arguments appear here and nowhere else.  (The any-length route's launches and records: sela_generic.h, included.)
+#ifndef SELA_HOST_H_
+#define SELA_HOST_H_
+
+#include <string>
+
+#include "sela_device.h"
+#include "sela_generic.h"
+
+namespace sela {
+
+// ---- sela_encode.hip -----------------------------------------------------------------------------------------------------------
+size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels);
+int encode_team_lanes(uint32_t n_frames, uint32_t channels, int forced);
+uint32_t encode_split_frames(uint32_t n_frames, uint32_t channels, int permille);
+void set_keep_both_candidates(int on);
+void set_encode_hashes(int on);
+hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, sela_hip_trace* d_trace, hipStream_t stream,
+    hipEvent_t* ev, uint64_t* d_phase_cycles, const EncodeHostLink* link, int force_plain_fir, int self_blocks_override, int team_lanes,
+    int32_t* d_trace_residues = nullptr, uint32_t priorities = 0, int phase = 0, const uint64_t* plan_base = nullptr, bool plan_accumulate = false,
+    bool lossless = false);
+hipError_t launch_stage_rice_encode(const int32_t* d_values, const uint64_t* d_value_offsets, uint32_t n_streams, uint32_t* d_k, uint32_t* d_word_counts,
+    uint32_t* d_words, const uint64_t* d_word_offsets, uint32_t* d_status, hipStream_t stream);
+
+// ---- sela_decode.hip, sela_index.inc (decode_waves: sela_device.h) ----------------------------------------------------------------
+size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels);
+uint32_t decode_max_channels();
+hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
+    int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles,
+    uint8_t* frame_flags, int recurrence_form, uint32_t synth_priorities = 0, const uint32_t* d_n_found = nullptr, bool zero_status = true);
+hipError_t launch_stage_lpc_decode(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, int32_t* d_samples,
+    int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
+hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_word_offsets, const uint32_t* d_k, const uint64_t* d_value_offsets,
+    uint32_t n_streams, int32_t* d_values, uint32_t* d_status, hipStream_t stream);
+size_t index_workspace_bytes(uint64_t payload_bytes);
+hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
+
+// ---- sela_capi.hip: what the any-length route's host side shares with the boundary --------------------------------------------
+int report_error(int code, const std::string& what);   // sets the thread's last error, returns code
+int report_hip_error(hipError_t e, const char* where); // (ENOMEM for an allocation failure, ENODEV otherwise)
+int device_ready();                                    // SELA_HIP_OK, or ENODEV reported: there is no CPU fallback
+inline bool frame_offsets_ascend(const uint64_t* frame_offsets, uint32_t n_frames)
+{
+    for (uint32_t f = 0; f < n_frames; f++)
+        if (frame_offsets[f + 1] < frame_offsets[f])
+            return false;
+    return true;
+}
+int check_frame_offsets(const uint64_t* frame_offsets, uint32_t n_frames); // SELA_HIP_OK, or EFORMAT reported: "frame offsets must not decrease"
+struct CurrentDevice { // how a leased context (sela_lease.h) asks for the calling thread's device
+    static int current_device()
+    {
+        int dev = -1;
+        return hipGetDevice(&dev) == hipSuccess ? dev : -1;
+    }
+    static void set_device(int dev) { (void)hipSetDevice(dev); }
+};
+
+// The verdicts on what the kernels report: ONE policy per direction, an ordered table of (flag, code, text) each.  A call
+// names the conditions it judges (`judged`) and opens the texts that name their caller (`who`: "decode", "lpc_decode",
+// "encode", "lpc_encode"); the first row that is set and judged is reported, else SELA_HIP_OK.
+enum DecodeRoute { // whose frames they were: a malformed one reads differently by the route that met it
+    kRouteDevice32, // sela_hip_decode_i32_device, the any-length route of sela_hip_decode_n_device (status[3] == 2)
+    kRouteHost32,   // generic_decode: decreasing offsets were refused before the device saw them
+    kRouteFast,     // the 2048-sample kernels: the streaming jobs, status[3] == 1
+    kRouteWalk,     // sela_hip_decode_n_device when the header walk broke (status[3] == 0)
+    kRouteLpc,      // the LPC stage on its own: blocks, and an order that is an argument (EINVAL)
+};
+constexpr uint32_t kJudgeJob = SELA_HIP_FLAG_BAD_FRAME | SELA_HIP_FLAG_RICE_OVERRUN | SELA_HIP_FLAG_COEF_OVERFLOW | SELA_HIP_FLAG_Q_RANGE; // the jobs' verdict: not SHORT_BLOCK, not INTERNAL
+constexpr uint32_t kJudgeLpc = SELA_HIP_FLAG_BAD_FRAME | SELA_HIP_FLAG_COEF_OVERFLOW | SELA_HIP_FLAG_Q_RANGE;
+constexpr uint32_t kJudgeEncode = SELA_HIP_FLAG_SHORT_BLOCK | SELA_HIP_FLAG_RICE_RANGE | SELA_HIP_FLAG_COEF_OVERFLOW | SELA_HIP_FLAG_WORDS_CAP;
+int judge_decode(uint32_t flags, uint32_t judged, DecodeRoute route, const char* who);
+int judge_encode(uint32_t flags, uint32_t judged, const char* who);
+
+// ---- sela_capi_generic.hip: the any-length / 32-bit route on host pointers ---------------------------------------------------
+void generic_release();
+void generic_shutdown();
+int generic_standard_first_mode();
+size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
+int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out,
+    bool lossless = false);
+uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint64_t* sample_offsets, bool* all_standard);
+int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
+    uint32_t* counts_out, int16_t* pcm_out, const uint64_t* sample_offsets);
+int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, const int16_t* pcm, uint32_t* diff_counts,
+    uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
+int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
+    const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
+int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out);
+int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);
+
+} // namespace sela
+#endif

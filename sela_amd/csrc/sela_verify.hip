@@ -17,8 +17,7 @@
 //                      k_verify_combine adds a frame's slices up.
 //
 // Per frame: diff_count[f], first_diff[f] (0xFFFFFFFF: nothing differs); status[2] counts the frames with a difference.
-#include "sela_device.h"
-#include "sela_generic.h"
+#include "sela_host.h"
 
 namespace sela {
 

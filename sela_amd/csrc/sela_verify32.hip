@@ -17,8 +17,7 @@
 //
 // Per frame: diff_count[f] = sum over the channels of #{ i < min(m, L) : decoded != original } + |m - L| (m: the decoder's
 // count, L: the original's length), first_diff[f] = the smallest c * stride + i (0xFFFFFFFF: nothing differs).
-#include "sela_device.h"
-#include "sela_generic.h"
+#include "sela_host.h"
 
 namespace sela {
 

@@ -35,6 +35,32 @@ def test_status_words_give_the_host_calls_code(status, code):
     assert codec.decode_status_error(np.array(status, np.int64)) == code  # (the int32 tensor's bit patterns are taken as uint32)
 
 
+T_STRIDE = "stride is smaller than the largest samplesPerChannel of the stream (status[2])"
+T_BAD = ("malformed frame (decreasing offsets, sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, "
+         "or channels of different lengths)")
+T_OVERRUN = "a Rice stream ended before all its values were read"
+T_COEF = "decode: a predictor coefficient left the int64 range"
+T_Q = "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)"
+T_SHORT = ("decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, "
+           "src/lpc/sample_generator.cpp:14-22)")
+T_INTERNAL = "decode: a bounded wait inside a kernel ran out"
+
+
+@pytest.mark.parametrize("status, code, text", [
+    ([STRIDE | BAD, 3, 4096, 0], ECAPACITY, T_STRIDE),
+    ([BAD | COEF | Q | SHORT, 2, 0, 0], EFORMAT, T_BAD),
+    ([0, 1, 0, 0], EFORMAT, T_BAD),
+    ([OVERRUN | COEF, 0, 700, 0], EFORMAT, T_OVERRUN),
+    ([COEF | Q, 0, 700, 0], ERANGE, T_COEF),
+    ([Q | SHORT | INTERNAL, 0, 3, 0], ERANGE, T_Q),
+    ([SHORT | INTERNAL, 0, 3, 0], ERANGE, T_SHORT),
+    ([INTERNAL, 0, 2048, 0], ENODEV, T_INTERNAL),
+])
+def test_status_words_give_the_host_calls_text(status, code, text):
+    assert codec.decode_status_error(np.array(status, np.uint32)) == code
+    assert capi.lib().sela_hip_last_error().decode() == text
+
+
 def test_status_error_of_a_null_pointer():
     assert capi.lib().sela_hip_decode_status_error(None) == EINVAL
 

@@ -65,6 +65,41 @@ def test_the_any_length_route_maps_as_the_i32_call():
         assert codec.decode_n_status_error(st) == codec.decode_status_error(st[:3] + [0]), st
 
 
+T_STRIDE = "stride is smaller than the largest samplesPerChannel of the stream (status[2])"
+T_BAD = {
+    NONE: "malformed frame stream (the header walk breaks, frame offsets decrease, or no subframe says a length)",
+    FAST: "malformed frame stream (bad sync word or subframe header)",
+    ANY: ("malformed frame (decreasing offsets, sync word, sizes, an order above 100, a Rice parameter above 31, a channel or parent that does not exist, "
+          "or channels of different lengths)"),
+}
+T_OVERRUN = "a Rice stream ended before all its values were read"
+T_COEF = "decode: a predictor coefficient left the int64 range"
+T_Q = "decode: a quantised reflection coefficient outside [-64, 63] (the reference indexes past its tables, src/lpc/linear_predictor.cpp:23-26)"
+T_SHORT = ("decode: a subframe without samples or not longer than its predictor order (the reference writes past its vector, "
+           "src/lpc/sample_generator.cpp:14-22)")
+T_INTERNAL = "decode: a bounded wait inside a kernel ran out"
+
+
+@pytest.mark.parametrize("status, code, text", [
+    ([STRIDE | BAD, 0, 4096, NONE], ECAPACITY, T_STRIDE),
+    ([STRIDE | BAD, 0, 4096, FAST], ECAPACITY, T_STRIDE),
+    ([STRIDE | BAD, 0, 4096, ANY], ECAPACITY, T_STRIDE),
+    ([BAD, 0, 700, NONE], EFORMAT, T_BAD[NONE]),
+    ([0, 1, 2048, FAST], EFORMAT, T_BAD[FAST]),
+    ([BAD | SHORT, 2, 700, ANY], EFORMAT, T_BAD[ANY]),
+    ([OVERRUN | COEF | Q, 0, 2048, FAST], EFORMAT, T_OVERRUN),
+    ([OVERRUN | COEF | Q, 0, 700, ANY], EFORMAT, T_OVERRUN),
+    ([COEF | Q, 0, 2048, FAST], ERANGE, T_COEF),
+    ([Q | SHORT, 0, 2048, FAST], ERANGE, T_Q),
+    ([Q | SHORT, 0, 700, ANY], ERANGE, T_Q),
+    ([SHORT | INTERNAL, 0, 3, ANY], ERANGE, T_SHORT),
+    ([INTERNAL, 0, 700, ANY], ENODEV, T_INTERNAL),
+])
+def test_status_words_give_the_host_calls_text(status, code, text):
+    assert codec.decode_n_status_error(np.array(status, np.uint32)) == code
+    assert capi.lib().sela_hip_last_error().decode() == text
+
+
 def test_status_error_of_a_null_pointer():
     assert capi.lib().sela_hip_decode_n_status_error(None) == EINVAL
 

@@ -12,7 +12,7 @@ Q, COEF, RICE, WORDS, SHORT = capi.FLAG_Q_RANGE, capi.FLAG_COEF_OVERFLOW, capi.F
 
 @pytest.mark.parametrize("status, code", [
     ([0, 0, 0, 0], OK),
-    ([Q, 0, 0, 0], OK),                        # (the host call codes such a frame: flags_error leaves Q_RANGE alone)
+    ([Q, 0, 0, 0], OK),                        # (the host call codes such a frame: the encoder's verdict leaves Q_RANGE alone)
     ([SHORT, 0, 0, 0], ERANGE),
     ([RICE, 0, 0, 0], ERANGE),
     ([COEF, 0, 0, 0], ERANGE),
@@ -27,6 +27,19 @@ Q, COEF, RICE, WORDS, SHORT = capi.FLAG_Q_RANGE, capi.FLAG_COEF_OVERFLOW, capi.F
 def test_status_words_give_the_host_calls_code(status, code):
     assert codec.encode_status_error(np.array(status, np.uint32)) == code
     assert codec.encode_status_error(np.array(status, np.int64)) == code  # (the int32 tensor's bit patterns are taken as uint32)
+
+
+@pytest.mark.parametrize("status, code, text", [
+    ([SHORT | RICE, 5, 0, 0], ERANGE,
+     "encode: a block is not longer than its predictor order (the reference reads past its vector there, src/lpc/residue_generator.cpp:104-110)"),
+    ([RICE | COEF, 0xFFFFFFFF, 0, 0], ERANGE, "encode: a residue is beyond the reference's int32 zig-zag (|value| >= 2^30)"),
+    ([COEF | WORDS, 0, 0, 0], ERANGE, "encode: a predictor coefficient left the int64 range"),
+    ([Q | WORDS, 0, 0, 0], ERANGE, "encode: a Rice stream needs more words than a subframe's 16-bit count can say"),
+    ([Q, 3875, 0, 0], ECAPACITY, "d_frames too small: status[1] frames were not written (d_frame_offsets[n_frames] bytes are needed)"),
+])
+def test_status_words_give_the_host_calls_text(status, code, text):
+    assert codec.encode_status_error(np.array(status, np.uint32)) == code
+    assert capi.lib().sela_hip_last_error().decode() == text
 
 
 def test_status_error_of_a_null_pointer():

@@ -320,6 +320,54 @@ def test_threads_take_over_parked_contexts(gpu):
     assert np.array_equal(frames, expect[0][0]) and np.array_equal(offsets, expect[0][1])
 
 
+def test_threads_take_over_parked_contexts_of_both_routes(gpu):
+    """The any-length route's twin of the test above: a thread that codes a 300-sample 17-bit frame (the any-length route's
+    context) and a 2048-sample frame (the fast path's) holds one context of each kind; both are parked when it ends or
+    calls sela_hip_thread_release, taken over by the next thread, and freed by sela_hip_shutdown.  Six threads one after the
+    other, then three at once, then the test's own thread after a shutdown: every result is the one computed first."""
+    import threading
+    from sela_amd import capi, codec
+
+    lib = capi.lib()
+    odd = np.ascontiguousarray(np.clip(2 * synth_frames(1, 2, 3)[0, :300].T.astype(np.int32) + 1, -65535, 65535)[None])
+    pcm = synth_frames(1, 2, 7)
+
+    def both():
+        odd_frames, odd_offsets = codec.encode_i32(odd)
+        odd_back = codec.decode_i32(odd_frames, odd_offsets, 2)
+        frames, offsets = codec.encode_host(pcm)
+        back = codec.decode_host(frames, offsets, 2)
+        return (odd_frames.tobytes(), odd_offsets.tobytes(), np.array(odd_back[0]).tobytes(), frames.tobytes(), offsets.tobytes(), back.tobytes())
+
+    expect = both()
+    assert np.array_equal(np.array(codec.decode_i32(*codec.encode_i32(odd), 2)[0]), odd[0]) and np.array_equal(codec.decode_host(*codec.encode_host(pcm), 2), pcm)
+    problems = []
+
+    def work(i, release):
+        try:
+            if both() != expect:
+                problems.append("thread %d differs" % i)
+            if release:
+                lib.sela_hip_thread_release()
+        except Exception as e:  # noqa: BLE001 -- reported below, from the test's thread
+            problems.append("thread %d: %r" % (i, e))
+
+    for i in range(6):
+        t = threading.Thread(target=work, args=(i, i % 2 == 0))
+        t.start()
+        t.join(120)
+        assert not t.is_alive()
+    threads = [threading.Thread(target=work, args=(6 + i, i % 2 == 0)) for i in range(3)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(120)
+    assert not any(t.is_alive() for t in threads)
+    assert not problems, problems
+    lib.sela_hip_shutdown()
+    assert both() == expect
+
+
 @pytest.mark.parametrize("channels,pinned_io", [(2, True), (2, False), (1, True), (5, False)])
 def test_streaming_jobs_with_random_feeds(gpu, channels, pinned_io):
     """Encode and decode jobs fed in pieces of random sizes (1 frame to 1500, sixteen jobs each), from page-locked and from

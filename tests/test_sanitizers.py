@@ -83,3 +83,18 @@ def test_call_coalescer_under_tsan(tmp_path):
     if os.path.exists(lib):
         syms = subprocess.run(["nm", "-DC", lib], capture_output=True, text=True).stdout
         assert "StubBackend" not in syms
+
+
+def test_context_lease_under_tsan(tmp_path):
+    """The lease both routes of the host-pointer API keep their per-thread contexts on (sela_lease.h), instantiated on a stub
+    context instead of streams and device memory: 16 threads on two devices lease, switch device, release or simply end, and
+    overflow the park's cap while the park is shut down under them -- no context held twice or destroyed twice, none lost,
+    none left after the last shutdown, no race."""
+    exe = tmp_path / "lease_tsan"
+    _run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", "-I" + os.path.join(ROOT, "sela_amd", "csrc"),
+          os.path.join(ROOT, "tests", "c", "lease_stress.cpp"), "-o", str(exe)])
+    r = subprocess.run(_tsan([str(exe), "16", "2000"]), capture_output=True, text=True, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    assert r.returncode == 0 and " 0 failures" in r.stdout and "ThreadSanitizer" not in r.stderr, (r.stdout, r.stderr[-3000:])
+    lib = os.path.join(ROOT, "sela_amd", "libsela_hip.so")
+    if os.path.exists(lib):
+        assert "StubContext" not in subprocess.run(["nm", "-DC", lib], capture_output=True, text=True).stdout
