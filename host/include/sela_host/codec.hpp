@@ -53,6 +53,11 @@ size_t decodeFile(std::ifstream& in, std::ofstream& out);
 // One thread reads or writes a page-cache file at a few GB/s; the device codes 10 G samples/s.
 size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false);
 size_t decodeFile(const std::string& inPath, const std::string& outPath);
+// Samples [startSample, startSample + sampleCount) per channel of a .sela of 2048-sample frames, as a WAV of exactly the samples
+// delivered: only the frames the range touches are copied to the device and decoded (sela_hip_decode_windows).  The count is cut
+// at the stream's end; a start at or past the end is a data::Exception, and no file is written then.  Returns the samples per
+// channel written.
+size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, uint64_t startSample, uint64_t sampleCount);
 // Decoding for a consumer that takes the samples in order (the player, sela_host/player.hpp): begin() once the header is
 // known, then ready(pcm, n) -- on the calling thread -- whenever the first n interleaved samples of pcm are final (n only
 // grows; pcm is the caller's buffer `into`, sized here before the first call, so the samples outlive the decoding: a player is

@@ -753,6 +753,41 @@ size_t decodeFile(const std::string& inPath, const std::string& outPath)
     return frames;
 }
 
+// A range of a file's samples: the file is read and indexed as verifyFile does, the range is one window of the whole stream
+// (sela_hip_decode_windows copies and decodes the frames it touches and no others; a range longer than the call's 2^24 samples
+// goes in pieces of that length).  Nothing is created before the samples are there.
+size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, uint64_t startSample, uint64_t sampleCount)
+{
+    const SelaInfo info = probeSela(selaPath);
+    const uint32_t channels = info.header.channels;
+    std::vector<uint8_t> payload(info.payload + 8);
+    if (info.payload)
+        sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
+    std::vector<uint64_t> offsets(info.announced + 1, 0);
+    const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
+    const uint64_t streamSamples = (uint64_t)found * kBlock;
+    if (startSample >= streamSamples)
+        throw data::Exception("Decode: --start " + std::to_string(startSample) + " is at or past the end of the stream (" + std::to_string(streamSamples)
+            + " samples per channel)");
+    const uint64_t count = std::min(sampleCount, streamSamples - startSample);
+    std::vector<int16_t> pcm((size_t)count * channels);
+    const uint64_t piece = (uint64_t)1 << 24;
+    for (uint64_t done = 0; done < count; done += piece) {
+        const sela_hip_window window = { startSample + done, 0, found };
+        if (sela_hip_decode_windows(payload.data(), offsets.data(), found, channels, &window, 1, (uint32_t)std::min(piece, count - done), SELA_HIP_WINDOW_I16_INTERLEAVED,
+                pcm.data() + (size_t)done * channels, nullptr)
+            != SELA_HIP_OK)
+            gpuFailure("Decode");
+    }
+    const sela_host::PosixFile out = sela_host::PosixFile::create(wavPath);
+    uint8_t header[44];
+    wavHeaderBytes(header, info.header.sampleRate, (uint16_t)channels, 16, (uint32_t)(pcm.size() * 2));
+    out.writeAt(header, 44, 0);
+    if (!pcm.empty())
+        out.writeAt(pcm.data(), pcm.size() * 2, 44);
+    return (size_t)count;
+}
+
 size_t decodeFileTo(const std::string& inPath, DecodedStream& to, sela_host::PinnedBuffer<int16_t>& pcm)
 {
     const SelaInfo info = probeSela(inPath);

@@ -4,6 +4,8 @@
 //                                      back exactly from any decoder of the format (plain -e is the reference's stream bit for bit,
 //                                      a few frames in ten thousand of which do not: -v lists them)
 //   sela_mi355x -d in.sela out.wav     decode
+//   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
+//                                      the frames the range touches are decoded and no others
 //   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
 //                                      what of in.wav it never held; exit 0: all of it comes back exactly, 3: a frame differs or
 //                                      the headers disagree, 4: only tail samples are missing, 1: an error
@@ -36,7 +38,8 @@ int usage(const std::string& program)
     std::cout << "Usage:\n\n"
               << "Encoding a file (--lossless: every frame decodes back exactly; without it the reference's stream bit for bit):\n"
               << program << " -e [--lossless] path/to/input.wav path/to/output.sela\n\n"
-              << "Decoding a file:\n" << program << " -d path/to/input.sela path/to/output.wav\n\n"
+              << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only):\n"
+              << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
@@ -95,6 +98,15 @@ int batch(const std::string& verb, int argc, char** argv)
     return 0;
 }
 
+// all of `text` as an unsigned decimal number
+bool parseCount(const std::string& text, uint64_t* value)
+{
+    if (text.empty() || text.size() > 19 || text.find_first_not_of("0123456789") != std::string::npos)
+        return false;
+    *value = std::strtoull(text.c_str(), nullptr, 10);
+    return true;
+}
+
 int run(int argc, char** argv)
 {
     const std::string program = argv[0];
@@ -102,6 +114,20 @@ int run(int argc, char** argv)
     for (int i = 2; i < argc; i++) // (--lossless is -e's alone: anywhere else it is refused, not ignored)
         if (std::string(argv[i]) == "--lossless" && !(verb == "-e" && i == 2 && argc == 5))
             return usage(program);
+    // (--start / --count are -d's alone, together, in that place: anywhere else they are refused, not ignored)
+    const bool ranged = verb == "-d" && argc == 8 && std::string(argv[2]) == "--start" && std::string(argv[4]) == "--count";
+    for (int i = 2; i < argc; i++)
+        if ((std::string(argv[i]) == "--start" && !(ranged && i == 2)) || (std::string(argv[i]) == "--count" && !(ranged && i == 4)))
+            return usage(program);
+    if (ranged) {
+        uint64_t start = 0, count = 0;
+        if (!parseCount(argv[3], &start) || !parseCount(argv[5], &count))
+            return usage(program);
+        std::cout << "Decoding: " << argv[6] << ", samples " << start << " + " << count << std::endl;
+        const size_t written = sela::decodeFileRange(std::string(argv[6]), std::string(argv[7]), start, count);
+        std::cout << written << " samples per channel" << std::endl;
+        return 0;
+    }
     if (verb == "-e" && argc == 5 && std::string(argv[2]) == "--lossless") {
         std::cout << "Encoding (lossless): " << argv[3] << std::endl;
         sela::encodeFile(std::string(argv[3]), std::string(argv[4]), true);

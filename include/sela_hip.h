@@ -444,6 +444,60 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
     const int32_t* samples /* [n_frames][channels][stride] */, const uint32_t* lengths /* [n_frames * channels] or NULL */,
     uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
 
+/* ---- sample windows of a stream: only the frames they touch are decoded --------------------------------------
+ * Every frame decodes on its own, so one second out of a three-minute track -- a player's seek, a batch of random crops from
+ * compressed tracks that lie in device memory -- costs the nine or ten frames it overlaps.  A window names a STREAM, a run of
+ * consecutive frames of the caller's frame table (one file among many concatenated into one table, or the whole table), and a
+ * start inside it; all windows of a call have one length, window_samples.
+ *   Output sample i of window w (i < window_samples): where start + i < 2048 * n_frames it is exactly the value
+ *   sela_hip_decode_device writes for sample (start + i) % 2048 of table frame first_frame + (start + i) / 2048 -- for every input,
+ *   malformed frames included (a silent channel, a refused parent, a frame that does not say 2048 samples: zeros and
+ *   SELA_HIP_FLAG_BAD_FRAME, as from that call) -- and zero otherwise.  A stream that runs past the table
+ *   (first_frame + n_frames > n_frames_total) is cut at the table's end: nothing outside the table is read.  start may be any
+ *   uint64.  Windows may overlap, repeat and come in any order.
+ *   format         SELA_HIP_WINDOW_I16_INTERLEAVED: d_out is int16 [n_windows][window_samples][channels];
+ *                  SELA_HIP_WINDOW_F32_PLANAR: d_out is float [n_windows][channels][window_samples] holding value / 32768 (exact
+ *                  in binary32).  Every element of d_out is written, by one launch: it needs no initialisation.
+ *   d_window_flags uint32 [n_windows] or NULL, written by the call: the OR of the flag bits of the frames that window touched (a
+ *                  loader drops one bad crop and keeps the batch).
+ *   d_status uint32[4], written by the call: [0] the OR of the flag bits over every frame decoded; [1] the number of (window,
+ *                  frame) decodes that met a malformed frame; [2] the number of windows with a non-zero flag word; [3] zero.
+ *                  n_windows = 0 writes zero status words and nothing else.
+ * Scope: frames of 2048 samples, 1 .. 8 channels, 16-bit samples.  More than 8 channels is SELA_HIP_EINVAL (decode the frames
+ * with sela_hip_decode_device and crop); frames of other lengths are SELA_HIP_FLAG_BAD_FRAME, as from sela_hip_decode_device; 32-bit
+ * output and streams of any other frame length have no window call (random access there needs a search of sample_offsets).
+ * The device call is asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of device data (the
+ * descriptors stay on the device; the launch is shaped by window_samples alone), so a stream being captured into a HIP graph may
+ * take it, and a replay reads whatever d_windows holds then.  d_workspace: sela_hip_decode_windows_workspace_bytes() bytes, no
+ * initialisation, one call at a time.  Apart from d_out, d_window_flags, d_status and the workspace nothing is written.
+ * Errors, found before a device is asked for (nothing is enqueued then) -- SELA_HIP_EINVAL: a null pointer (d_frames and
+ * d_frame_offsets only where n_frames_total > 0, everything but d_status only where n_windows > 0), channels outside 1 .. 8,
+ * window_samples 0 or above 2^24, another format, d_frames not 4-byte aligned, d_windows not 8-byte aligned, d_out not aligned to
+ * its element (2 or 4 bytes), d_window_flags or d_status not 4-byte aligned, or n_windows * cover at or above 2^31, where
+ * cover = (window_samples + 2046) / 2048 + 1 is the most frames a window touches; SELA_HIP_ECAPACITY: a smaller workspace. */
+typedef struct sela_hip_window {
+    uint64_t start;       /* first sample per channel, relative to the stream's first sample */
+    uint32_t first_frame; /* the stream: frames [first_frame, first_frame + n_frames) of the table */
+    uint32_t n_frames;
+} sela_hip_window;        /* 16 bytes; lives in DEVICE memory for the device call */
+#define SELA_HIP_WINDOW_I16_INTERLEAVED 0u
+#define SELA_HIP_WINDOW_F32_PLANAR 1u
+size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+int sela_hip_decode_windows_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out,
+    uint32_t* d_window_flags /* [n_windows] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous: the call above on the calling thread's any-length context and its own stream, past the coalescer;
+ * an open streaming job of the thread is left alone (where sela_hip_verify runs).  Only the frames the windows touch are copied
+ * to the device: the distinct covering frames are staged back to back and the descriptors put on that compacted table.
+ * Returns, after the argument errors above (host pointers need no alignment) and SELA_HIP_EFORMAT for frame offsets that
+ * decrease, what the fast route of sela_hip_decode_n_status_error() makes of the status words: a malformed frame or a dry Rice
+ * stream: SELA_HIP_EFORMAT; a coefficient outside the tables or beyond int64: SELA_HIP_ERANGE.  UNLIKE the sibling host calls,
+ * `out` and `window_flags` are filled in both of these cases: one bad crop must not cost a loader its batch, and window_flags says
+ * which crop it was. */
+int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out,
+    uint32_t* window_flags /* [n_windows] or NULL */);
+
 /* ---- encode options: the lossless mode ----------------------------------------------------------------------
  * The reference's encoder predicts with (2^34 + sum) >> 35 and its decoder with -((2^34 - sum) >> 35): where 2^34 + sum is a
  * multiple of 2^35 the two differ by one, and the frame does not come back as it went in.  With SELA_HIP_ENCODE_LOSSLESS the

@@ -117,6 +117,12 @@ long long sela_hip_debug_segment_subframes(void);
  * (2^34 + sum |a[j]| x max |sample| < 2^53) and on 64-bit wrap-around taps otherwise; on != 0 sends every block down the
  * wrap-around taps. */
 void sela_hip_debug_generic_wrap_taps(int on);
+/* The dynamic LDS, in bytes, that a launch of k_window_frames asks for with this many channels (1 .. 8; else 0): the decoder's. */
+size_t sela_hip_debug_window_lds_bytes(uint32_t channels);
+/* Debug hook (tests; per calling thread): the frame bytes the thread's last sela_hip_decode_windows call copied to the device --
+ * the summed sizes of the distinct frames its windows touched (0 before the first call, and for a call that failed before it
+ * staged anything). */
+uint64_t sela_hip_debug_windows_staged_bytes(void);
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,9 @@ EXPORTS = [
     "sela_hip_verify_i32_workspace_bytes", "sela_hip_verify_i32_device", "sela_hip_verify_payload_i32_device", "sela_hip_verify_i32",
     "sela_hip_encode_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
     "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt",
+    "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
 ]
+WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
 
 
@@ -48,7 +50,7 @@ ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
 DEBUG_EXPORTS = [
     "sela_hip_debug_phase_buffer", "sela_hip_debug_force_plain_fir", "sela_hip_debug_mean_workers", "sela_hip_debug_encode_teams", "sela_hip_debug_encode_kernel", "sela_hip_debug_encode_fused", "sela_hip_debug_priorities", "sela_hip_debug_priorities_adaptive", "sela_hip_debug_launches_alone", "sela_hip_debug_block_forms", "sela_hip_debug_encode_hashes", "sela_hip_debug_standard_first", "sela_hip_debug_standard_chunks", "sela_hip_debug_segment_subframes", "sela_hip_debug_generic_wrap_taps", "sela_hip_debug_encode_split", "sela_hip_debug_launches_split", "sela_hip_debug_keep_both_candidates", "sela_hip_debug_stage_wait",
     "sela_hip_debug_reissued_feeds", "sela_hip_debug_contexts_created", "sela_hip_debug_decode_recurrence", "sela_hip_debug_coalesced", "sela_hip_debug_verify_lds_bytes",
-    "sela_hip_debug_verify_i32_fallback_frames",
+    "sela_hip_debug_verify_i32_fallback_frames", "sela_hip_debug_window_lds_bytes", "sela_hip_debug_windows_staged_bytes",
 ]
 
 
@@ -150,6 +152,12 @@ def lib() -> C.CDLL:
     L.sela_hip_verify_payload_i32_device.restype = C.c_int
     L.sela_hip_verify_i32.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
     L.sela_hip_verify_i32.restype = C.c_int
+    L.sela_hip_decode_windows_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_windows_workspace_bytes.restype = sz
+    L.sela_hip_decode_windows_device.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_windows_device.restype = C.c_int
+    L.sela_hip_decode_windows.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp]
+    L.sela_hip_decode_windows.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]
@@ -240,6 +248,10 @@ def lib() -> C.CDLL:
     L.sela_hip_debug_verify_lds_bytes.restype = sz
     L.sela_hip_debug_verify_i32_fallback_frames.argtypes = [vp, u32, u32, u32]
     L.sela_hip_debug_verify_i32_fallback_frames.restype = C.c_longlong
+    L.sela_hip_debug_window_lds_bytes.argtypes = [u32]
+    L.sela_hip_debug_window_lds_bytes.restype = sz
+    L.sela_hip_debug_windows_staged_bytes.argtypes = []
+    L.sela_hip_debug_windows_staged_bytes.restype = C.c_uint64
     L.sela_hip_host_alloc.argtypes = [sz]
     L.sela_hip_host_alloc.restype = C.c_void_p
     L.sela_hip_host_free.argtypes = [C.c_void_p]

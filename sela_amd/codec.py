@@ -368,6 +368,94 @@ class Verifier:
         capi.check(decode_n_status_error(st))
 
 
+class WindowDecoder:
+    """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
+    device memory -- only the frames a window touches are decoded.  Owns its output, flags, status and workspace
+    on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  planar_float:
+    float32 [n, channels, window_samples] holding value / 32768 instead of int16 [n, window_samples, channels]."""
+
+    def __init__(self, max_windows: int, window_samples: int, channels: int, planar_float: bool = False, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_windows, self.window_samples, self.channels = max_windows, window_samples, channels
+        self.format = capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED
+        with torch.cuda.device(self.device):
+            if planar_float:
+                self.out = torch.empty((max_windows, channels, window_samples), dtype=torch.float32, device=self.device)
+            else:
+                self.out = torch.empty((max_windows, window_samples, channels), dtype=torch.int16, device=self.device)
+            self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_decode_windows_workspace_bytes(max_windows, window_samples, channels))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.n_windows = 0
+
+    @staticmethod
+    def pack(starts, first_frames, n_frames) -> np.ndarray:
+        """The descriptors of sela_hip_window as int64 [n, 2] on the host (send it to the device with torch.from_numpy(...).cuda()):
+        word 0 the start (any uint64, as its bit pattern), word 1 first_frame | n_frames << 32.  Scalars are broadcast."""
+        starts = np.atleast_1d(np.asarray(starts, dtype=np.uint64))
+        first = np.broadcast_to(np.asarray(first_frames, dtype=np.uint64), starts.shape)
+        count = np.broadcast_to(np.asarray(n_frames, dtype=np.uint64), starts.shape)
+        assert (first < 2 ** 32).all() and (count < 2 ** 32).all()
+        packed = np.empty((len(starts), 2), np.uint64)
+        packed[:, 0] = starts
+        packed[:, 1] = first | (count << np.uint64(32))
+        return packed.view(np.int64)
+
+    def decode(self, frames, offsets, n_frames_total: int, windows):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames_total + 1], windows: int64 cuda tensor
+        [n, 2] (pack()) -> the first n windows of the decoder's own output buffer."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= n_frames_total + 1
+        assert windows.dtype == torch.int64 and windows.is_cuda and windows.is_contiguous() and windows.dim() == 2 and windows.shape[1] == 2
+        n = int(windows.shape[0])
+        assert n <= self.max_windows
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_windows_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format,
+            self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        self.n_windows = n
+        return self.out[:n]
+
+    @property
+    def flags(self):
+        """int32 cuda tensor [n]: the OR of the flag bits of the frames each window of the last call touched."""
+        return self.window_flags[: self.n_windows]
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_windows returns for the same batch."""
+        st = self.status.cpu().numpy().copy()
+        # sela_hip_decode_n_status_error judges [0] flag bits and [1] bad frames by the route named in [3]; 1 is the 2048-sample
+        # decoder's, the mapping the host call uses (a malformed frame or a dry Rice stream: EFORMAT; a coefficient outside the
+        # tables or beyond int64: ERANGE).  This call's [2] counts flagged windows, which that function does not read.
+        st[2], st[3] = 0, 1
+        capi.check(decode_n_status_error(st))
+
+
+def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, planar_float: bool = False):
+    """sela_hip_decode_windows on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
+    (int16 [n, window_samples, channels], or float32 [n, channels, window_samples]), the per-window flags (uint32 [n]) and the
+    call's return code -- 0, or EFORMAT / ERANGE (capi.ERRORS) for a batch with a bad frame, whose other windows are good all
+    the same; any other code raises."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
+    n = len(win)
+    out = np.zeros((n, channels, window_samples), np.float32) if planar_float else np.zeros((n, window_samples, channels), np.int16)
+    flags = np.zeros(n, np.uint32)
+    rc = lib.sela_hip_decode_windows(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples,
+                                     capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED, out.ctypes.data, flags.ctypes.data)
+    if rc not in (capi.OK, -5, -6):
+        capi.check(rc)
+    return out, flags, rc
+
+
 def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.ndarray):
     """sela_hip_verify on numpy arrays; pcm: int16 in the layout decode_host returns.  Returns three values:
     diff_counts (uint32 [n_frames]), first_diff (uint32 [n_frames]; 0xFFFFFFFF where nothing differs) and the number of

@@ -1534,21 +1534,25 @@ int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_byte
 // things -- no stride, no pointer without frames -- and would need a shape of their own: they stay written out.)
 extern "C++" {
 namespace {
-struct DeviceCall {
+// Formula: (max_frames, channels, stride) -> bytes.  The calls sized by their table name their sela:: function; a call sized by
+// something else (the windows) brings a closure over what it is sized by.
+template <typename Formula>
+struct DeviceCallOf {
     const char* name; // "decode_i32": the capacity's text names sela_hip_<name>_workspace_bytes()
-    size_t (*workspace_bytes)(uint32_t max_frames, uint32_t channels, uint32_t stride); // SIZE_MAX: more than any device holds
+    Formula workspace_bytes; // SIZE_MAX: more than any device holds
     uint32_t channels, stride;
     void* d_workspace;
     size_t capacity;
     hipStream_t stream;
 };
+using DeviceCall = DeviceCallOf<size_t (*)(uint32_t max_frames, uint32_t channels, uint32_t stride)>;
 
 struct FramesForm {
     const uint8_t* d_frames;
     const uint64_t* d_frame_offsets;
     uint32_t n_frames;
-    template <typename Check, typename Launch>
-    int operator()(const DeviceCall& c, Check check, Launch launch) const
+    template <typename Formula, typename Check, typename Launch>
+    int operator()(const DeviceCallOf<Formula>& c, Check check, Launch launch) const
     {
         const int rc = check(n_frames);
         if (rc != SELA_HIP_OK)
@@ -1570,8 +1574,8 @@ struct PayloadForm {
     uint32_t max_frames;
     uint64_t* d_frame_offsets;
     uint32_t* d_n_frames;
-    template <typename Check, typename Launch>
-    int operator()(const DeviceCall& c, Check check, Launch launch) const
+    template <typename Formula, typename Check, typename Launch>
+    int operator()(const DeviceCallOf<Formula>& c, Check check, Launch launch) const
     {
         int rc = check_index_args(d_payload, payload_bytes, c.channels, d_frame_offsets, d_n_frames, c.d_workspace);
         if (rc == SELA_HIP_OK)
@@ -1660,6 +1664,40 @@ int verify_call(const Form& form, uint32_t channels, uint32_t stride, const int1
             return launch_with_priorities(max_frames, stream, "verify launch", [&](uint32_t synth_priorities) {
                 return sela::launch_verify_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, d_diff_counts, d_first_diff,
                     d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
+// sela_hip_decode_windows_device (5.17), in the frames form: the table is the form's, the windows are the call's.  Its workspace
+// is sized by the windows and not by the table, so its formula is sela_hip_decode_windows_workspace_bytes itself, closed over
+// the call's own arguments (the form asks it only after the check has passed them); the call has no stride.
+int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
+    void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const bool shaped = window_samples >= 1 && window_samples <= (1u << 24);
+    const uint64_t groups = shaped ? (uint64_t)n_windows * sela::window_cover(window_samples) : 0;
+    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) { return sela::window_workspace_bytes(n_windows, window_samples, channels); };
+    const DeviceCallOf<decltype(formula)> c = { "decode_windows", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t) {
+            if (channels == 0 || channels > 8)
+                return fail(SELA_HIP_EINVAL, "channels must be in 1..8: the windows are cut from the on-chip decoder's second pass (more channels: sela_hip_decode_device, then crop)");
+            if (window_samples == 0 || window_samples > (1u << 24))
+                return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+            if (format != SELA_HIP_WINDOW_I16_INTERLEAVED && format != SELA_HIP_WINDOW_F32_PLANAR)
+                return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_I16_INTERLEAVED or SELA_HIP_WINDOW_F32_PLANAR");
+            if (groups >= (1ull << 31))
+                return fail(SELA_HIP_EINVAL, "n_windows * cover must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
+            int rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_windows & 7) || ((uintptr_t)d_out & (format == SELA_HIP_WINDOW_F32_PLANAR ? 3 : 1)) || ((uintptr_t)d_window_flags & 3) || ((uintptr_t)d_status & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_windows must be 8-byte aligned, d_out aligned to its element, d_window_flags and d_status 4-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const uint32_t*, void* d_ws) {
+            return launch_with_priorities((uint32_t)groups, stream, "decode_windows launch", [&](uint32_t synth_priorities) {
+                return sela::launch_window_frames(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows, window_samples, format, d_out, d_window_flags,
+                    d_status, d_ws, c.stream, g_recurrence_form, synth_priorities);
             });
         });
 }
@@ -1856,6 +1894,41 @@ int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (!frame_offsets || (n_frames && (!frames || !pcm || !diff_counts || !first_diff)))
         return fail(SELA_HIP_EINVAL, "null pointer");
     return sela::generic_verify(frames, frame_offsets, n_frames, channels, pcm, diff_counts, first_diff, lossy_frames, g_recurrence_form);
+}
+
+size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+{
+    return sela::window_workspace_bytes(n_windows, window_samples, channels);
+}
+
+int sela_hip_decode_windows_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels,
+    const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return windows_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, d_out, d_window_flags, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows (sela_capi_generic.hip) on the
+// any-length route's leased context and stream, past the coalescer; an open streaming job of the thread is left alone.
+int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags)
+{
+    sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
+    if (channels == 0 || channels > 8)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..8: the windows are cut from the on-chip decoder's second pass (more channels: sela_hip_decode, then crop)");
+    if (window_samples == 0 || window_samples > (1u << 24))
+        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+    if (format != SELA_HIP_WINDOW_I16_INTERLEAVED && format != SELA_HIP_WINDOW_F32_PLANAR)
+        return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_I16_INTERLEAVED or SELA_HIP_WINDOW_F32_PLANAR");
+    if ((uint64_t)n_windows * sela::window_cover(window_samples) >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_windows * cover must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
+    if ((n_windows && (!windows || !out)) || !frame_offsets || (n_frames_total && !frames))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_windows == 0)
+        return SELA_HIP_OK;
+    return sela::generic_decode_windows(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags,
+        g_recurrence_form);
 }
 
 size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)

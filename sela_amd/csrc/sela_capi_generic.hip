@@ -19,6 +19,7 @@
 
 #include "sela_host.h"
 #include "sela_lease.h"
+#include "sela_window_plan.h"
 
 namespace {
 
@@ -622,6 +623,87 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
         VerifySamples{ samples, lengths, channels, stride, nullptr, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
+// sela_hip_decode_windows: the *_device launch on chunks of WINDOWS, on the calling thread's context and stream.
+// Per chunk only the frames its windows touch go in (plan_windows: the distinct covering frames back to back, the descriptors
+// on that compacted table; runs of neighbouring frames are gathered with one memcpy each, the whole with one copy); status
+// (4 x u32) | window flags [cw] and the output come back behind the chunk's ONE wait.  The verdict is given at the end, on
+// the flags of all chunks: the output and the flags are the caller's either way.
+namespace {
+thread_local uint64_t g_windows_staged_bytes = 0; // sela_hip_debug_windows_staged_bytes
+}
+void windows_staged_bytes_reset() { g_windows_staged_bytes = 0; }
+
+int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    if (check_frame_offsets(frame_offsets, n_frames_total) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    Arena& g_arena = call.arena();
+    const hipStream_t st = call.stream();
+    const size_t out_per_window = (size_t)window_samples * channels * (format == SELA_HIP_WINDOW_F32_PLANAR ? 4 : 2);
+    // (an estimate for the chunk's size only -- what a chunk needs is reserved exactly below: a 16-bit frame is about 5 bytes a sample at most)
+    const size_t per_window = out_per_window + (size_t)window_cover(window_samples) * channels * kBlock * (sizeof(int32_t) + 5) + 64;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_windows, kChunkBudget / per_window));
+    WindowPlan plan;
+    std::vector<uint8_t> staged;
+    std::vector<uint32_t> tail;
+    uint32_t flags = 0;
+    for (uint32_t w0 = 0; w0 < n_windows; w0 += chunk) {
+        const uint32_t cw = std::min(chunk, n_windows - w0);
+        plan_windows(frame_offsets, n_frames_total, windows + w0, cw, window_samples, &plan);
+        const size_t in_bytes = (size_t)plan.staged_bytes(), n_staged = plan.frames.size(), out_bytes = (size_t)cw * out_per_window;
+        const size_t ws_bytes = window_workspace_bytes(cw, window_samples, channels);
+        hipError_t e = g_arena.reserve(in_bytes + 8 + (n_staged + 1) * 8 + (size_t)cw * sizeof(sela_hip_window) + out_bytes + (4 + (size_t)cw) * 4 + ws_bytes + 8 * kPiece);
+        if (e != hipSuccess)
+            return report_hip_error(e, "decode_windows: scratch");
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>(n_staged + 1);
+        sela_hip_window* d_windows = g_arena.take<sela_hip_window>(cw);
+        uint8_t* d_out = g_arena.take<uint8_t>(out_bytes);
+        uint32_t* d_tail = g_arena.take<uint32_t>(4 + (size_t)cw);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "decode_windows: internal scratch estimate too small");
+        staged.resize(in_bytes);
+        for (size_t i = 0; i < n_staged;) { // a run of neighbouring frames is one piece of the caller's stream
+            size_t k = i + 1;
+            while (k < n_staged && plan.frames[k] == plan.frames[k - 1] + 1)
+                k++;
+            if (plan.offsets[k] > plan.offsets[i])
+                std::memcpy(staged.data() + plan.offsets[i], frames + frame_offsets[plan.frames[i]], (size_t)(plan.offsets[k] - plan.offsets[i]));
+            i = k;
+        }
+        g_windows_staged_bytes += in_bytes;
+        tail.assign(4 + (size_t)cw, 0);
+        uint8_t* const user_out = static_cast<uint8_t*>(out) + (size_t)w0 * out_per_window;
+        if (in_bytes)
+            e = hipMemcpyAsync(d_frames, staged.data(), in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, plan.offsets.data(), (n_staged + 1) * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_windows, plan.windows.data(), (size_t)cw * sizeof(sela_hip_window), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_window_frames(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, d_out, d_tail + 4, d_tail, d_ws, st,
+                recurrence_form, 0);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(user_out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "decode_windows");
+        flags |= tail[0] | (tail[1] ? SELA_HIP_FLAG_BAD_FRAME : 0u);
+        if (window_flags)
+            std::memcpy(window_flags + w0, tail.data() + 4, (size_t)cw * 4);
+    }
+    // the fast route's verdict (sela_hip_decode_n_status_error, status[3] == 1) -- with the output and the flags already delivered
+    return judge_decode(flags, SELA_HIP_FLAG_STRIDE | kJudgeJob, kRouteFast, "decode_windows");
+}
+
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out)
 {
     const Call call;
@@ -731,3 +813,5 @@ int sela_hip_debug_standard_chunks(void) { return g_standard_chunks.load(std::me
 long long sela_hip_debug_segment_subframes(void) { return g_segment_subframes.load(std::memory_order_relaxed); }
 void sela_hip_debug_generic_wrap_taps(int on) { sela::set_generic_wrap_taps(on); }
 }
+
+extern "C" uint64_t sela_hip_debug_windows_staged_bytes(void) { return sela::g_windows_staged_bytes; }

@@ -39,6 +39,13 @@ size_t index_workspace_bytes(uint64_t payload_bytes);
 hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
     uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
 
+// ---- sela_window.hip: sample windows of a stream ---------------------------------------------------------------
+uint32_t window_cover(uint32_t window_samples); // the most frames a window of that length touches: the grid's second extent
+size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
+    int recurrence_form, uint32_t synth_priorities);
+
 // ---- sela_capi.hip: what the any-length route's host side shares with the boundary --------------------------------------------
 int report_error(int code, const std::string& what);   // sets the thread's last error, returns code
 int report_hip_error(hipError_t e, const char* where); // (ENOMEM for an allocation failure, ENODEV otherwise)
@@ -90,6 +97,9 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
 int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
+int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form);
+void windows_staged_bytes_reset(); // sela_hip_debug_windows_staged_bytes of the calling thread back to 0: the entry point's first act
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out);
 int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);
 
