@@ -28,6 +28,9 @@ public:
     // Residues against the decoder's rounding (SELA_HIP_ENCODE_LOSSLESS): every frame decodes back exactly,
     // with any decoder of the format.  Off: the reference's stream bit for bit.
     bool lossless = false;
+    // Channel pairs (sela_hip_encode_paired): every odd channel may be stored as the difference against the even
+    // channel before it, in a stream every decoder of the format reads.  One and two channels: the same bytes either way.
+    bool pairChannels = false;
     explicit Encoder(std::ifstream& in) : ifStream(in) {}
     file::SelaFile process();
 };
@@ -45,13 +48,13 @@ public:
 // File to file (what the reference's main.cpp:29-41 does with process() + writeToFile()): the same
 // streaming read, and finished frames / samples are written out while later pieces are still on the device.
 // Return the number of frames coded.
-size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless = false); // (lossless: as Encoder::lossless)
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless = false, bool pairChannels = false); // (as Encoder::lossless, ::pairChannels)
 size_t decodeFile(std::ifstream& in, std::ofstream& out);
 // The same by path -- what the CLI's -e / -d use: the file is read with several pread()s in flight on a small pool of I/O
 // threads (sela_host/fileio.hpp) while earlier pieces are on the device, and finished ranges are written by a task of
 // that pool -- over pages allocated in one go while the input was still on its way -- while later pieces are being coded.
 // One thread reads or writes a page-cache file at a few GB/s; the device codes 10 G samples/s.
-size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false);
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false, bool pairChannels = false);
 size_t decodeFile(const std::string& inPath, const std::string& outPath);
 // Samples [startSample, startSample + sampleCount) per channel of a .sela of 2048-sample frames, as a WAV of exactly the samples
 // delivered: only the frames the range touches are copied to the device and decoded (sela_hip_decode_windows).  The count is cut

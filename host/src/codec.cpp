@@ -107,6 +107,41 @@ void streamEncode(Need need, size_t piece, int16_t* pcm, size_t frames, uint32_t
     }
 }
 
+// streamEncode's arguments with channel pairs.  The streaming jobs have no paired form: every `piece` frames,
+// as they arrive, go through the paired one-shot call (sela_hip_encode_paired: the any-length route, in its own chunks), and their
+// bytes are appended.  A piece that does not fit what is left of `bytes` is coded again after `bytes` has grown by that piece's
+// certain bound.
+template <typename Need, typename Drain>
+void pairedEncode(Need need, size_t piece, const int16_t* pcm, size_t frames, uint32_t channels, sela_host::PinnedBuffer<uint8_t>& bytes,
+    std::vector<uint64_t>& offsets, Drain drain, const std::function<void()>& beforeRealloc = {}, uint32_t options = 0 /* SELA_HIP_ENCODE_* */)
+{
+    const size_t frameSamples = kBlock * channels;
+    offsets.assign(frames + 1, 0);
+    piece = std::max<size_t>(piece, 1);
+    bytes.resize(optimisticBytes(frames, channels));
+    std::vector<uint64_t> local(piece + 1);
+    size_t at = 0;
+    for (size_t f0 = 0; f0 < frames; f0 += piece) {
+        const size_t nf = std::min<size_t>(piece, frames - f0);
+        need(f0 + nf);
+        int rc = sela_hip_encode_paired(pcm + f0 * frameSamples, (uint32_t)nf, channels, (uint32_t)kBlock, bytes.data() + at, bytes.size() - at, local.data(), options);
+        if (rc == SELA_HIP_ECAPACITY) { // (not reached by 16-bit WAV input, which codes below the 18 bits a sample optimisticBytes allows:
+                                        // the guard streamEncode keeps too; it codes the whole piece again)
+            if (beforeRealloc)
+                beforeRealloc(); // (resize frees the block the sink was draining from)
+            bytes.resize(at + sela_hip_encode_bound_bytes_n((uint32_t)(frames - f0), channels, (uint32_t)kBlock));
+            rc = sela_hip_encode_paired(pcm + f0 * frameSamples, (uint32_t)nf, channels, (uint32_t)kBlock, bytes.data() + at, bytes.size() - at, local.data(), options);
+        }
+        if (rc != SELA_HIP_OK)
+            gpuFailure("Encoder");
+        for (size_t i = 0; i <= nf; i++)
+            offsets[f0 + i] = at + local[i];
+        at += (size_t)local[nf];
+        drain(bytes.data(), at);
+    }
+    bytes.resize(at);
+}
+
 // need() of a file that is read with the calling thread's own ifstream reads
 struct StreamReader {
     std::ifstream& in;
@@ -352,8 +387,13 @@ file::SelaFile Encoder::process()
     const size_t frames = wavFile.frameCount(); // tail samples beyond the last whole frame are dropped
     sela_host::PinnedBuffer<uint8_t> bytes;
     std::vector<uint64_t> offsets;
-    streamEncode(StreamReader{ ifStream, wavFile.pcm.data(), kBlock * channels }, kPieceFrames, wavFile.pcm.data(), frames, channels, bytes, offsets,
-        [](const uint8_t*, size_t) {}, {}, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
+    const uint32_t options = lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u;
+    if (pairChannels)
+        pairedEncode(StreamReader{ ifStream, wavFile.pcm.data(), kBlock * channels }, kPieceFrames, wavFile.pcm.data(), frames, channels, bytes, offsets,
+            [](const uint8_t*, size_t) {}, {}, options);
+    else
+        streamEncode(StreamReader{ ifStream, wavFile.pcm.data(), kBlock * channels }, kPieceFrames, wavFile.pcm.data(), frames, channels, bytes, offsets,
+            [](const uint8_t*, size_t) {}, {}, options);
     const size_t coded = frames * kBlock * channels;
     if (wavFile.pcm.size() > coded && !readExact(ifStream, wavFile.pcm.data() + coded, (wavFile.pcm.size() - coded) * 2))
         throw data::Exception("data subChunk is shorter than its header says");
@@ -383,7 +423,7 @@ file::WavFile Decoder::process()
     return out;
 }
 
-size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless)
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless, bool pairChannels)
 {
     file::WavFile wav;
     const size_t dataBytes = wav.readHeader(in);
@@ -401,12 +441,17 @@ size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless)
     sela_host::PinnedBuffer<uint8_t> bytes;
     std::vector<uint64_t> offsets;
     size_t written = 0;
-    streamEncode(StreamReader{ in, wav.pcm.data(), kBlock * channels }, kPieceFrames, wav.pcm.data(), frames, channels, bytes, offsets, [&](const uint8_t* p, size_t done) {
+    const auto drain = [&](const uint8_t* p, size_t done) {
         if (done > written) { // finished frames go to disk while later pieces are on the device
             out.write(reinterpret_cast<const char*>(p + written), (std::streamsize)(done - written));
             written = done;
         }
-    }, {}, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
+    };
+    const uint32_t options = lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u;
+    if (pairChannels)
+        pairedEncode(StreamReader{ in, wav.pcm.data(), kBlock * channels }, kPieceFrames, wav.pcm.data(), frames, channels, bytes, offsets, drain, {}, options);
+    else
+        streamEncode(StreamReader{ in, wav.pcm.data(), kBlock * channels }, kPieceFrames, wav.pcm.data(), frames, channels, bytes, offsets, drain, {}, options);
     return frames;
 }
 
@@ -669,12 +714,16 @@ SelaInfo probeSela(const std::string& path)
 // kFeedFrames, sink(bytes, final) is told whenever more of the output is final.  Returns the total.
 template <typename Sink>
 size_t encodeRange(const sela_host::PosixFile& in, const WavInfo& info, size_t first, size_t n, sela_host::PinnedBuffer<int16_t>& pcm,
-    sela_host::PinnedBuffer<uint8_t>& bytes, std::vector<uint64_t>& offsets, Sink sink, const std::function<void()>& sinkQuiesce = {}, uint32_t options = 0)
+    sela_host::PinnedBuffer<uint8_t>& bytes, std::vector<uint64_t>& offsets, Sink sink, const std::function<void()>& sinkQuiesce = {}, uint32_t options = 0,
+    bool pairChannels = false)
 {
     const size_t frameBytes = kBlock * info.channels * 2;
     pcm.resize(n * kBlock * info.channels);
     sela_host::ReadAhead ahead(in, pcm.data(), info.dataOffset + first * frameBytes, n * frameBytes, kFeedFrames * frameBytes, kIoSubBytes);
-    streamEncode([&](size_t upTo) { ahead.need(upTo * frameBytes); }, kFeedFrames, pcm.data(), n, info.channels, bytes, offsets, sink, sinkQuiesce, options);
+    if (pairChannels)
+        pairedEncode([&](size_t upTo) { ahead.need(upTo * frameBytes); }, kFeedFrames, pcm.data(), n, info.channels, bytes, offsets, sink, sinkQuiesce, options);
+    else
+        streamEncode([&](size_t upTo) { ahead.need(upTo * frameBytes); }, kFeedFrames, pcm.data(), n, info.channels, bytes, offsets, sink, sinkQuiesce, options);
     ahead.finish();
     return bytes.size();
 }
@@ -685,7 +734,7 @@ size_t expectedSelaBytes(const WavInfo& info) { return info.frames * kBlock * in
 
 void setIoThreads(unsigned n) { sela_host::IoPool::configure(n); }
 
-size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless)
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless, bool pairChannels)
 {
     const WavInfo info = probeWav(inPath);
     const sela_host::PosixFile in = sela_host::PosixFile::openForRead(inPath);
@@ -699,7 +748,7 @@ size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lo
     // (the pages of the output are allocated in one go while the input is read and coded: audio codes to about 3/4)
     sela_host::WriteBehind behind(out, 15, kIoSubBytes, expectedSelaBytes(info));
     const size_t total = encodeRange(in, info, 0, info.frames, pcm, bytes, offsets, [&](const uint8_t* p, size_t done) { behind.drain(p, done); }, [&] { behind.quiesce(); },
-        lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u);
+        lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u, pairChannels);
     behind.finish(&total);
     return info.frames;
 }

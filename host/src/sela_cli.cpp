@@ -3,6 +3,9 @@
 //   sela_mi355x -e --lossless in.wav out.sela   encode with the residues taken against the decoder's rounding: every frame comes
 //                                      back exactly from any decoder of the format (plain -e is the reference's stream bit for bit,
 //                                      a few frames in ten thousand of which do not: -v lists them)
+//   sela_mi355x -e --pair-channels [--lossless] in.wav out.sela   encode a file of more than two channels with every odd channel
+//                                      stored as the difference against the even channel before it where that takes fewer words
+//                                      (any decoder of the format reads it; one and two channels: the same bytes as without)
 //   sela_mi355x -d in.sela out.wav     decode
 //   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
 //                                      the frames the range touches are decoded and no others
@@ -38,6 +41,8 @@ int usage(const std::string& program)
     std::cout << "Usage:\n\n"
               << "Encoding a file (--lossless: every frame decodes back exactly; without it the reference's stream bit for bit):\n"
               << program << " -e [--lossless] path/to/input.wav path/to/output.sela\n\n"
+              << "Encoding a multichannel file with adjacent channels paired (odd channels as differences where that is smaller):\n"
+              << program << " -e --pair-channels [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only):\n"
               << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
@@ -111,9 +116,18 @@ int run(int argc, char** argv)
 {
     const std::string program = argv[0];
     const std::string verb = argc > 1 ? argv[1] : "";
-    for (int i = 2; i < argc; i++) // (--lossless is -e's alone: anywhere else it is refused, not ignored)
-        if (std::string(argv[i]) == "--lossless" && !(verb == "-e" && i == 2 && argc == 5))
+    // (--pair-channels is -e's alone, right behind it; --lossless is -e's alone too, behind the verb or behind --pair-channels:
+    // anywhere else they are refused, not ignored)
+    const bool paired = verb == "-e" && (argc == 5 || argc == 6) && std::string(argv[2]) == "--pair-channels";
+    const bool pairedLossless = paired && argc == 6 && std::string(argv[3]) == "--lossless";
+    if (paired && argc == 6 && !pairedLossless)
+        return usage(program);
+    for (int i = 2; i < argc; i++) {
+        if (std::string(argv[i]) == "--pair-channels" && !(paired && i == 2))
             return usage(program);
+        if (std::string(argv[i]) == "--lossless" && !(verb == "-e" && i == 2 && argc == 5) && !(pairedLossless && i == 3))
+            return usage(program);
+    }
     // (--start / --count are -d's alone, together, in that place: anywhere else they are refused, not ignored)
     const bool ranged = verb == "-d" && argc == 8 && std::string(argv[2]) == "--start" && std::string(argv[4]) == "--count";
     for (int i = 2; i < argc; i++)
@@ -126,6 +140,11 @@ int run(int argc, char** argv)
         std::cout << "Decoding: " << argv[6] << ", samples " << start << " + " << count << std::endl;
         const size_t written = sela::decodeFileRange(std::string(argv[6]), std::string(argv[7]), start, count);
         std::cout << written << " samples per channel" << std::endl;
+        return 0;
+    }
+    if (paired) {
+        std::cout << "Encoding (channel pairs" << (pairedLossless ? ", lossless" : "") << "): " << argv[argc - 2] << std::endl;
+        sela::encodeFile(std::string(argv[argc - 2]), std::string(argv[argc - 1]), pairedLossless, true);
         return 0;
     }
     if (verb == "-e" && argc == 5 && std::string(argv[2]) == "--lossless") {

@@ -482,6 +482,54 @@ int main(int argc, char** argv)
             CHECK(sela::decodeFile(dir + "/forms_obj.sela", dir + "/forms_path.wav") == 2300);
             const std::string wa = slurp(dir + "/forms_obj.wav"), wb = slurp(dir + "/forms_stream.wav"), wc = slurp(dir + "/forms_path.wav");
             CHECK(wa.size() == 44 + (size_t)2300 * 2048 * ch * 2 && wa == wb && wa == wc);
+            // channel pairs through the same three forms: six channels, more frames than either form's piece
+            // (1024 by stream, 2048 by path), pairs (0,1) and (4,5) near-copies, lossless -- one stream from all three, smaller than
+            // the plain one, and the decoder gives the samples back
+            {
+                const uint32_t ch6 = 6;
+                const size_t frames6 = 2100;
+                std::vector<int16_t> six((size_t)ch6 * (2048 * frames6 + 55));
+                int w6[6] = { 0, 0, 0, 0, 0, 0 };
+                for (size_t i = 0; i < six.size(); i++) {
+                    x = x * 1664525u + 1013904223u;
+                    const size_t c = i % ch6;
+                    if (c == 1 || c == 5) { // the even channel before it, nearly
+                        six[i] = (int16_t)(six[i - 1] + (int)((x >> 27) & 3) - 1);
+                        continue;
+                    }
+                    int& smp = w6[c];
+                    smp += (int)((x >> 21) & 511) - 256;
+                    smp = smp > 30000 ? 30000 : (smp < -30000 ? -30000 : smp);
+                    six[i] = (int16_t)smp;
+                }
+                const std::string wav6 = dir + "/pairs.wav";
+                {
+                    file::WavFile w(48000, (uint16_t)ch6, std::vector<int16_t>(six));
+                    std::ofstream out(wav6, std::ios::binary);
+                    w.writeToFile(out);
+                }
+                {
+                    std::ifstream in(wav6, std::ios::binary);
+                    sela::Encoder enc(in);
+                    enc.lossless = enc.pairChannels = true;
+                    file::SelaFile sf = enc.process();
+                    CHECK(sf.selaHeader.numFrames == frames6 && sf.selaHeader.channels == ch6);
+                    std::ofstream out(dir + "/pairs_obj.sela", std::ios::binary);
+                    sf.writeToFile(out);
+                }
+                {
+                    std::ifstream in(wav6, std::ios::binary);
+                    std::ofstream out(dir + "/pairs_stream.sela", std::ios::binary);
+                    CHECK(sela::encodeFile(in, out, true, true) == frames6);
+                }
+                CHECK(sela::encodeFile(wav6, dir + "/pairs_path.sela", true, true) == frames6);
+                CHECK(sela::encodeFile(wav6, dir + "/pairs_plain.sela", true, false) == frames6);
+                const std::string pa = slurp(dir + "/pairs_obj.sela"), pb = slurp(dir + "/pairs_stream.sela"), pc = slurp(dir + "/pairs_path.sela");
+                CHECK(pa.size() > 15 && pa == pb && pa == pc && pa.size() < slurp(dir + "/pairs_plain.sela").size());
+                CHECK(sela::decodeFile(dir + "/pairs_obj.sela", dir + "/pairs_back.wav") == frames6);
+                const std::string back6 = slurp(dir + "/pairs_back.wav");
+                CHECK(back6.size() == 44 + frames6 * 2048 * ch6 * 2 && std::memcmp(back6.data() + 44, six.data(), back6.size() - 44) == 0);
+            }
             // a hand-made file whose frames say 2048, 700, 3000 and 700 samples (fewer per frame than 2048 on average: a decoder
             // that wrote 2048-sample frames before it found out has written too much): the stream variant of decodeFile must
             // leave exactly what the variant by path and the object path leave

@@ -531,6 +531,48 @@ int sela_hip_encode_i32_opt(const int32_t* samples, uint32_t n_frames, uint32_t 
 int sela_hip_encode_ragged_i32_opt(const int32_t* samples, const uint32_t* lengths, uint32_t channels, uint8_t* frame_out,
     size_t frame_cap, size_t* frame_bytes, uint32_t options);
 
+/* ---- channel pairs: difference coding for any number of channels ----------------------------------------------
+ * The format lets any subframe be stored as a difference against a parent channel (type 1, parentChannelNumber), and every
+ * decoder rebuilds parent - difference (src/frame/frame_decoder.cpp:39-69).  The plain calls use that, as the reference does,
+ * for the second channel of an exactly-stereo frame only.  The paired calls use it for every pair of adjacent channels.
+ * The rule, for a frame of C channels of n samples each:
+ *   Channels are paired (2p, 2p + 1), p = 0 .. C / 2 - 1; an odd last channel is alone.
+ *   Channel 2p is always an independent subframe (type 0, parent 2p).
+ *   Channel 2p + 1 has two candidates: its own signal, and d[j] = ch[2p][j] - ch[2p + 1][j] (int32 wrap-around, as the stereo
+ *     frame's difference).  The difference is stored (type 1, parent 2p) iff its coef_words + res_words is STRICTLY FEWER
+ *     (src/frame/frame_encoder.cpp:64-72).  A candidate flagged SELA_HIP_FLAG_WORDS_CAP / _RICE_RANGE is treated as the plain
+ *     call treats it in a stereo frame.
+ *   Subframes appear in channel order.  There are C + C / 2 signals per frame: 0 .. C - 1 the channels, C + p pair p's
+ *     difference (sela_hip_paired_signals_per_frame).  d_status[0] is the OR over all candidates of all pairs.
+ * The frame equals, byte for byte, the sync word followed by the two subframes of the reference's stereo frame of
+ * (ch[2p], ch[2p + 1]) for every pair, then the reference's mono subframe of an odd last channel -- each with its channel byte
+ * renumbered, and its parent byte where type == 1.  For C = 1 and C = 2 the bytes are the plain call's.  With
+ * SELA_HIP_ENCODE_LOSSLESS every candidate's residues are the lossless mode's.  A parent is always an independent channel of the
+ * same length: nothing a decoder of the format could refuse is produced.
+ * options: 0 or SELA_HIP_ENCODE_LOSSLESS; anything else is SELA_HIP_EINVAL, reported before the call's other checks.
+ * The device calls are sela_hip_encode_i32_device / sela_hip_encode_n_device in everything else: layouts, alignment, asynchronous
+ * on `stream` with no allocation, no host wait and no host read of device data (graph capture), d_frame_offsets always written in
+ * full, frames beyond frames_cap counted in d_status[1] and not written, n_frames = 0, sela_hip_encode_status_error, and
+ * SELA_HIP_EINVAL where n_frames x signals per frame reaches 2^31.  The workspace, sela_hip_encode_paired_workspace_bytes()
+ * bytes, does not depend on the data.  They run on the any-length kernels for every shape, 2048 x int16 included.
+ * The host calls run where the lossless one-shot calls run: the any-length route in its chunks of frames, past the coalescer; an
+ * open streaming job of the thread is left alone.
+ * sela_hip_encode_bound_bytes_n() bounds a paired stream as it stands: it allows every subframe one candidate's slot (12 header
+ * bytes, 32 coefficient words, the residue words of the worst Rice parameter), and a stored subframe is still one candidate --
+ * a difference whose residues leave the zig-zag's range is SELA_HIP_ERANGE as the stereo frame's is. */
+uint32_t sela_hip_paired_signals_per_frame(uint32_t channels); /* channels + channels / 2 */
+size_t sela_hip_encode_paired_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel);
+int sela_hip_encode_paired_i32_device(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options);
+int sela_hip_encode_paired_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options);
+int sela_hip_encode_paired_i32(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames + 1] */, uint32_t options);
+int sela_hip_encode_paired(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
+    size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames + 1] */, uint32_t options);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

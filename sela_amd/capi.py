@@ -40,6 +40,8 @@ EXPORTS = [
     "sela_hip_encode_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
     "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt",
     "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
+    "sela_hip_paired_signals_per_frame", "sela_hip_encode_paired_workspace_bytes", "sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device",
+    "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
@@ -174,6 +176,17 @@ def lib() -> C.CDLL:
     L.sela_hip_encode_begin_opt.argtypes = [C.POINTER(C.c_void_p), u32, u32, vp, sz, vp, u32]
     for name in ("sela_hip_encode_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
                  "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt"):
+        getattr(L, name).restype = C.c_int
+    # the paired calls: the plain calls' arguments and their own options word
+    L.sela_hip_paired_signals_per_frame.argtypes = [u32]
+    L.sela_hip_paired_signals_per_frame.restype = u32
+    L.sela_hip_encode_paired_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_encode_paired_workspace_bytes.restype = sz
+    L.sela_hip_encode_paired_i32_device.argtypes = L.sela_hip_encode_i32_device.argtypes + [u32]
+    L.sela_hip_encode_paired_n_device.argtypes = L.sela_hip_encode_n_device.argtypes + [u32]
+    L.sela_hip_encode_paired_i32.argtypes = [vp, u32, u32, u32, vp, sz, vp, u32]
+    L.sela_hip_encode_paired.argtypes = [vp, u32, u32, u32, vp, sz, vp, u32]
+    for name in ("sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device", "sela_hip_encode_paired_i32", "sela_hip_encode_paired"):
         getattr(L, name).restype = C.c_int
     L.sela_hip_encode_status_error.argtypes = [vp]
     L.sela_hip_encode_status_error.restype = C.c_int

@@ -582,12 +582,15 @@ class Encoder32:
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
     asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the host route's
     estimate -- 4.5 bytes per sample, which holds noise of up to 20 bits -- not the certain bound; a call that did not fit says
-    so in check(), and needed_bytes() is what it needs.  lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder."""
+    so in check(), and needed_bytes() is what it needs.  lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder.
+    paired: the sela_hip_encode_paired_*_device calls -- every odd channel may be stored as the difference
+    against the even channel before it, in a stream every decoder of the format reads."""
 
-    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, capacity=None, device=None, lossless: bool = False):
+    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, capacity=None, device=None, lossless: bool = False, paired: bool = False):
         import torch
 
         self.options = capi.ENCODE_LOSSLESS if lossless else 0
+        self.paired = bool(paired)
 
         self.torch = torch
         self.lib = capi.lib()
@@ -596,7 +599,7 @@ class Encoder32:
         if capacity is None:
             capacity = max_frames * ((samples_per_channel * channels * 9) // 2 + channels * 192 + 64)
         self.capacity = max(int(capacity), 4)
-        ws = int(self.lib.sela_hip_encode_i32_workspace_bytes(max_frames, channels, samples_per_channel))
+        ws = int((self.lib.sela_hip_encode_paired_workspace_bytes if paired else self.lib.sela_hip_encode_i32_workspace_bytes)(max_frames, channels, samples_per_channel))
         with torch.cuda.device(self.device):
             self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
             self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
@@ -613,14 +616,23 @@ class Encoder32:
         n_frames = samples.shape[0]
         if samples.dtype == torch.int32:
             assert tuple(samples.shape[1:]) == (self.channels, self.n)
-            call = self.lib.sela_hip_encode_i32_device_opt if self.options else self.lib.sela_hip_encode_i32_device
+            kind = "i32"
         else:
             assert samples.dtype == torch.int16 and tuple(samples.shape[1:]) == (self.n, self.channels)
-            call = self.lib.sela_hip_encode_n_device_opt if self.options else self.lib.sela_hip_encode_n_device
+            kind = "n"
         assert n_frames <= self.max_frames
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(call(samples.data_ptr(), n_frames, self.channels, self.n, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
-                        self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream, *((self.options,) if self.options else ())))
+        args = [samples.data_ptr(), n_frames, self.channels, self.n, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+                self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream]
+        if self.paired:  # (its own options word, always)
+            call = getattr(self.lib, "sela_hip_encode_paired_%s_device" % kind)
+            args.append(self.options)
+        elif self.options:
+            call = getattr(self.lib, "sela_hip_encode_%s_device_opt" % kind)
+            args.append(self.options)
+        else:
+            call = getattr(self.lib, "sela_hip_encode_%s_device" % kind)
+        capi.check(call(*args))
         self.n_frames = n_frames
         return self.frames, self.offsets[: n_frames + 1], self.status
 
@@ -647,16 +659,19 @@ def encode_status_error(status) -> int:
 
 
 # ---- host-pointer API on numpy arrays (what the C++ host calls) --------------------------------------
-def encode_host(pcm: np.ndarray, lossless: bool = False):
+def encode_host(pcm: np.ndarray, lossless: bool = False, paired: bool = False):
     """pcm: int16 [n_frames, n, channels] (n = 2048: the fast kernels; anything else in 1..65535: the any-length route)
-    -> (frames uint8[...], offsets uint64[n_frames+1]).  lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_opt)."""
+    -> (frames uint8[...], offsets uint64[n_frames+1]).  lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_opt).
+    paired: sela_hip_encode_paired (the any-length route for every n)."""
     lib = capi.lib()
     p = np.ascontiguousarray(pcm, dtype=np.int16)
     n_frames, n, ch = p.shape
     cap = max(2 * p.nbytes, 4096) if n == BLOCK else int(lib.sela_hip_encode_bound_bytes_n(n_frames, ch, n))
     frames = np.empty(cap, np.uint8)
     offs = np.zeros(n_frames + 1, np.uint64)
-    if lossless:
+    if paired:
+        capi.check(lib.sela_hip_encode_paired(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS if lossless else 0))
+    elif lossless:
         capi.check(lib.sela_hip_encode_opt(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS))
     else:
         capi.check(lib.sela_hip_encode(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
@@ -689,16 +704,18 @@ def index_samples(frames: np.ndarray, offsets: np.ndarray, channels: int):
     return so, int(largest)
 
 
-def encode_i32(samples: np.ndarray, lossless: bool = False):
+def encode_i32(samples: np.ndarray, lossless: bool = False, paired: bool = False):
     """frame::FrameEncoder on data::WavFrame values: samples int32 [n_frames, channels, n] -> (frames uint8[...], offsets).
-    lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_i32_opt)."""
+    lossless: SELA_HIP_ENCODE_LOSSLESS (sela_hip_encode_i32_opt).  paired: sela_hip_encode_paired_i32."""
     lib = capi.lib()
     p = np.ascontiguousarray(samples, dtype=np.int32)
     n_frames, ch, n = p.shape
     cap = int(lib.sela_hip_encode_bound_bytes_n(n_frames, ch, n))
     frames = np.empty(max(cap, 16), np.uint8)
     offs = np.zeros(n_frames + 1, np.uint64)
-    if lossless:
+    if paired:
+        capi.check(lib.sela_hip_encode_paired_i32(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS if lossless else 0))
+    elif lossless:
         capi.check(lib.sela_hip_encode_i32_opt(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS))
     else:
         capi.check(lib.sela_hip_encode_i32(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))

@@ -1759,23 +1759,32 @@ int sela_hip_decode_status_error(const uint32_t* status)
 namespace {
 // what sela_hip_encode_i32_device and sela_hip_encode_n_device check alike, then the launch; no lease, no coalescer, no wait
 int encode_i32_device_call(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, size_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, bool lossless = false)
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, bool lossless = false, bool paired = false)
 {
     if (channels == 0 || channels > 255)
         return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
     if (n == 0 || n > 65535)
         return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
-    if ((uint64_t)n_frames * sela_hip_signals_per_frame(channels) >= (1ull << 31))
+    if ((uint64_t)n_frames * sela::generic_signals(channels, paired) >= (1ull << 31))
         return fail(SELA_HIP_EINVAL, "n_frames * signals per frame must stay below 2^31");
     if (!d_frame_offsets || !d_status || !d_workspace || (n_frames && (!d_input || !d_frames)))
         return fail(SELA_HIP_EINVAL, "null device pointer");
     if (((uintptr_t)d_frames & 3) || ((uintptr_t)d_input & (in16 ? 1 : 3)))
         return fail(SELA_HIP_EINVAL, "d_frames must be 4-byte aligned, the samples aligned to their type");
-    if (workspace_bytes < sela::encode_i32_device_workspace_bytes(n_frames, channels, n))
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_i32_workspace_bytes()");
+    if (workspace_bytes < sela::encode_i32_device_workspace_bytes(n_frames, channels, n, paired))
+        return fail(SELA_HIP_ECAPACITY, paired ? "workspace smaller than sela_hip_encode_paired_workspace_bytes()" : "workspace smaller than sela_hip_encode_i32_workspace_bytes()");
     return launched(sela::launch_encode_i32_device(d_input, in16, n_frames, channels, n, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace,
-                        static_cast<hipStream_t>(stream), lossless),
-        "encode_i32 launch");
+                        static_cast<hipStream_t>(stream), lossless, paired),
+        paired ? "encode_paired launch" : "encode_i32 launch");
+}
+
+// what every paired call asks first: its own options word -- 0 or SELA_HIP_ENCODE_LOSSLESS
+int paired_options(uint32_t options, bool* lossless)
+{
+    if (options & ~(uint32_t)SELA_HIP_ENCODE_LOSSLESS)
+        return fail(SELA_HIP_EINVAL, "options: a paired call takes 0 or SELA_HIP_ENCODE_LOSSLESS");
+    *lossless = options != 0;
+    return SELA_HIP_OK;
 }
 } // namespace
 
@@ -1814,6 +1823,32 @@ int sela_hip_encode_n_device_opt(const int16_t* d_pcm, uint32_t n_frames, uint32
     const int rc = encode_options(options, &lossless);
     return rc != SELA_HIP_OK ? rc : encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status,
                                         d_workspace, workspace_bytes, stream, lossless);
+}
+
+// ---- channel pairs: the any-length kernels over channels + channels / 2 signals -----------------------------
+uint32_t sela_hip_paired_signals_per_frame(uint32_t channels) { return sela::generic_signals(channels, true); }
+
+size_t sela_hip_encode_paired_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel)
+{
+    return sela::encode_i32_device_workspace_bytes(n_frames, channels, samples_per_channel, true);
+}
+
+int sela_hip_encode_paired_i32_device(const int32_t* d_samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames,
+    size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
+{
+    bool lossless = false;
+    const int rc = paired_options(options, &lossless);
+    return rc != SELA_HIP_OK ? rc : encode_i32_device_call(d_samples, false, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status,
+                                        d_workspace, workspace_bytes, stream, lossless, true);
+}
+
+int sela_hip_encode_paired_n_device(const int16_t* d_pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* d_frames,
+    size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
+{
+    bool lossless = false;
+    const int rc = paired_options(options, &lossless);
+    return rc != SELA_HIP_OK ? rc : encode_i32_device_call(d_pcm, true, n_frames, channels, samples_per_channel, d_frames, frames_cap, d_frame_offsets, d_status,
+                                        d_workspace, workspace_bytes, stream, lossless, true);
 }
 
 // the any-length route's verdict after its plan (generic_encode in sela_capi_generic.hip): the flags, then the capacity
@@ -2353,6 +2388,36 @@ int sela_hip_encode_i32_opt(const int32_t* samples, uint32_t n_frames, uint32_t 
     if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!samples || !frames_out)))
         return fail(SELA_HIP_EINVAL, "bad argument");
     return sela::generic_encode(samples, false, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, true);
+}
+
+// The paired one-shot calls: where the lossless one-shot calls run -- the any-length route, in its chunks of
+// frames, past the coalescer (whose batches are the plain call's); an open streaming job of the thread is left alone.
+namespace {
+int encode_paired_host(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out, uint32_t options)
+{
+    bool lossless = false;
+    const int rc = paired_options(options, &lossless);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (samples_per_channel == 0 || samples_per_channel > 65535)
+        return fail(SELA_HIP_EINVAL, "samples_per_channel must be 1 .. 65535 (the subframe's field is 16 bits wide)");
+    if (channels == 0 || channels > 255 || !frame_offsets_out || (n_frames && (!input || !frames_out)))
+        return fail(SELA_HIP_EINVAL, "bad argument");
+    return sela::generic_encode(input, in16, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, lossless, true);
+}
+} // namespace
+
+int sela_hip_encode_paired_i32(const int32_t* samples, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out, uint32_t options)
+{
+    return encode_paired_host(samples, false, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, options);
+}
+
+int sela_hip_encode_paired(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out, uint32_t options)
+{
+    return encode_paired_host(pcm, true, n_frames, channels, samples_per_channel, frames_out, frames_cap, frame_offsets_out, options);
 }
 
 namespace {

@@ -198,13 +198,13 @@ size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t
 constexpr size_t kEagerBytes = (size_t)4 << 20;
 
 int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap,
-    uint64_t* frame_offsets_out, bool lossless /* SELA_HIP_ENCODE_LOSSLESS */)
+    uint64_t* frame_offsets_out, bool lossless /* SELA_HIP_ENCODE_LOSSLESS */, bool paired /* sela_hip_encode_paired*: DESIGN.md 5.18 */)
 {
     const Call call;
     if (call.rc != SELA_HIP_OK)
         return call.rc;
     Arena& g_arena = call.arena();
-    const uint32_t n_sig = channels == 2 ? 3u : channels;
+    const uint32_t n_sig = generic_signals(channels, paired);
     const size_t in_frame_bytes = (size_t)n * channels * (in16 ? 2 : 4);
     const size_t est_frame_bytes = ((size_t)n * channels * 9) / 2 + (size_t)channels * 192 + 64; // words and frame bytes, each (a subframe: 12 bytes of header, up to 32 coefficient words)
     const size_t per_frame = (size_t)n_sig * n * 8 + (size_t)n_sig * (kMaxOrder * 4 + sizeof(GenericMeta) + 2 * kPiece) + in_frame_bytes + (size_t)channels * 12 + 8
@@ -253,9 +253,9 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
         if (e == hipSuccess)
             e = hipMemsetAsync(d_words, 0, (est_words + 2) * 4, st);
         if (e == hipSuccess)
-            e = launch_generic_analyse(d_in, in16, cf, channels, n_sig, n, d_sig, d_res, d_q, d_meta, st, lossless);
+            e = launch_generic_analyse(d_in, in16, cf, channels, n_sig, n, d_sig, d_res, d_q, d_meta, st, lossless, paired);
         if (e == hipSuccess)
-            e = launch_generic_plan(d_meta, cf, channels, n_sig, base_bytes, d_offsets, d_word_base, d_chosen, d_status, d_head + 2, st);
+            e = launch_generic_plan(d_meta, cf, channels, n_sig, base_bytes, d_offsets, d_word_base, d_chosen, d_status, d_head + 2, st, paired);
         if (e == hipSuccess)
             e = launch_generic_emit(d_meta, cf, channels, n_sig, n, d_res, d_q, d_chosen, d_word_base, d_words, est_words, d_offsets, base_bytes, d_frames, est_bytes, st);
         if (e == hipSuccess)

@@ -17,11 +17,16 @@ struct GenericSubInfo { // one per (frame, subframe position), written by k_gene
     uint32_t n;
 };
 
+// Signals analysed per frame: the channels, and a difference per pair the plan may store in place of the pair's odd channel --
+// the one pair of an exactly-stereo frame (src/frame/frame_encoder.cpp:18), or with `paired` every pair
+// (2p, 2p + 1), signal channels + p being pair p's difference, in instantiations of k_generic_analyse and k_generic_plan of their own.
+inline uint32_t generic_signals(uint32_t channels, bool paired) { return channels + (paired ? channels / 2 : channels == 2 ? 1u : 0u); }
 size_t generic_encode_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 hipError_t launch_generic_analyse(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, int32_t* d_sig,
-    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless = false /* DESIGN.md 5.16 */);
+    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless = false /* DESIGN.md 5.16 */,
+    bool paired = false /* n_sig = generic_signals(channels, true) */);
 hipError_t launch_generic_plan(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint64_t base_bytes, uint64_t* d_frame_offsets,
-    uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream);
+    uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream, bool paired = false);
 hipError_t launch_generic_emit(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, const int32_t* d_res, const int32_t* d_q,
     const uint32_t* d_chosen, const uint64_t* d_word_base, uint32_t* d_words /* zeroed */, uint64_t words_cap /* a subframe whose words would reach beyond is left out */,
     const uint64_t* d_frame_offsets, uint64_t base_bytes, uint8_t* d_frames, uint64_t frames_cap, hipStream_t stream);
@@ -82,9 +87,9 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
-size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired = false);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false);
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false, bool paired = false);
 hipError_t launch_lpc_decode_any(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, uint32_t n, int32_t* d_samples,
     int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
 

@@ -360,7 +360,7 @@ __device__ __forceinline__ void rice_plan_convex(Load load, uint32_t n, int lane
 
 // kLossless: the residues are taken against the DECODER's prediction -(int32)((2^34 - sum) >> 35)
 // (src/lpc/sample_generator.cpp:25-28) -- the encoder's, less one where 2^34 + sum is a multiple of 2^35.
-template <bool kIn16, bool kLossless>
+template <bool kIn16, bool kLossless, bool kPaired>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAVES, SELA_GEN_WAVES))) void k_generic_analyse(const void* __restrict__ input, uint32_t n_frames, uint32_t channels,
     uint32_t n_sig, uint32_t n, int32_t* __restrict__ sig_ws, int32_t* __restrict__ res_ws, int32_t* __restrict__ q_ws, GenericMeta* __restrict__ meta, uint32_t force_wrap_taps /* tests: every block on the 64-bit wrap-around taps */)
 {
@@ -374,15 +374,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
     int32_t* const r = res_ws + (size_t)b * n;
     uint32_t flags = 0;
 
-    // ---- the signal: a channel, or channel 0 - channel 1 of an exactly-stereo frame (src/frame/frame_encoder.cpp:18-24);
+    // ---- the signal: a channel, or channel 0 - channel 1 of an exactly-stereo frame (src/frame/frame_encoder.cpp:18-24) -- with
+    //      kPaired signal channels + p is channel 2p - channel 2p + 1 of any frame;
     //      x = s / 32767 and its sequential sum (:27-29) ---------------------------------------------------------------------
+    // kPaired is an instantiation of its own, so that the plain calls keep the code they had: with the pair's channel computed for
+    // every signal they were 1 % slower.
+    const bool is_diff = sg >= channels;
+    const uint32_t ca = kPaired && is_diff ? 2 * (sg - channels) : sg; // kPaired: the channel, or the pair's even one
+    // int16, interleaved, an even number of channels: a pair's two samples are one 32-bit word, aligned where the input is
+    const bool pair_word = kPaired && kIn16 && is_diff && !(channels & 1) && !((uintptr_t)input & 3);
     auto load_sample = [&](uint32_t j) -> int32_t {
-        if (kIn16) {
-            const int16_t* pcm = static_cast<const int16_t*>(input) + (size_t)f * n * channels;
-            return sg < channels ? (int32_t)pcm[(size_t)j * channels + sg] : (int32_t)pcm[(size_t)j * channels] - (int32_t)pcm[(size_t)j * channels + 1];
+        if constexpr (kPaired) {
+            if (kIn16) {
+                const int16_t* at = static_cast<const int16_t*>(input) + (size_t)f * n * channels + (size_t)j * channels + ca;
+                if (!is_diff)
+                    return (int32_t)at[0];
+                if (pair_word) {
+                    const uint32_t two = *reinterpret_cast<const uint32_t*>(at);
+                    return (int32_t)(int16_t)two - (int32_t)(int16_t)(two >> 16);
+                }
+                return (int32_t)at[0] - (int32_t)at[1];
+            }
+            const int32_t* at = static_cast<const int32_t*>(input) + ((size_t)f * channels + ca) * n + j;
+            return is_diff ? (int32_t)((uint32_t)at[0] - (uint32_t)at[n]) : at[0];
+        } else {
+            if (kIn16) {
+                const int16_t* pcm = static_cast<const int16_t*>(input) + (size_t)f * n * channels;
+                return sg < channels ? (int32_t)pcm[(size_t)j * channels + sg] : (int32_t)pcm[(size_t)j * channels] - (int32_t)pcm[(size_t)j * channels + 1];
+            }
+            const int32_t* pl = static_cast<const int32_t*>(input) + (size_t)f * channels * n;
+            return sg < channels ? pl[(size_t)sg * n + j] : (int32_t)((uint32_t)pl[j] - (uint32_t)pl[(size_t)n + j]);
         }
-        const int32_t* pl = static_cast<const int32_t*>(input) + (size_t)f * channels * n;
-        return sg < channels ? pl[(size_t)sg * n + j] : (int32_t)((uint32_t)pl[j] - (uint32_t)pl[(size_t)n + j]);
     };
     double sum = 0.0;
     uint32_t mag_lane = 0; // the largest |sample| of this lane
@@ -704,8 +726,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
     }
 }
 
-// ---- plan: the stereo decision, frame sizes, offsets -- one workgroup -----------------------------------------------------
-// src/frame/frame_encoder.cpp:64-72: the difference candidate wins iff its words (coefficients + residues) are FEWER.
+// ---- plan: the pairs' decisions, frame sizes, offsets -- one workgroup ----------------------------------------------------
+// src/frame/frame_encoder.cpp:64-72: the difference candidate wins iff its words (coefficients + residues) are FEWER -- for the
+// second channel of a stereo frame, and with kPaired for the odd channel of every pair (n_sig - channels pairs).
+// sela_generic_plan.inc is the body of both kernels, k_generic_plan and k_paired_plan, below.
 // 1024 threads over tiles of 4096 frames.  Within a tile frame f is sized by thread f mod 1024 -- the records' loads of one pass
 // are independent and coalesced (a thread that walks consecutive frames waits for memory once per frame: the second version,
 // 46 us at 3875 frames; the first version's single thread walking 256 partial sums: 60) -- its subframes' word counts go to LDS;
@@ -714,128 +738,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SELA_GEN_WAV
 // kDevice (sela_hip_encode_i32_device): base_bytes is 0; the frames that end beyond frames_cap are counted, and the status words are
 // written whole (plain stores: the caller's words need no initialisation) -- [0] the flags, [1] that count, [2] and [3] zero.
 constexpr int kPlanThreads = 1024, kPlanTile = 4096;
+// The two kernels: the plain calls' (the stereo frame's one pair, or none) and the paired calls'  -- kernels of their
+// own with one body (sela_generic_plan.inc), so that the plain calls run the code object they ran before there were pairs.
 template <bool kDevice>
 __global__ __launch_bounds__(kPlanThreads) void k_generic_plan(const GenericMeta* __restrict__ meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig,
     uint64_t base_bytes, uint64_t* __restrict__ frame_offsets /* [n_frames + 1], absolute */, uint64_t* __restrict__ word_base /* [n_frames * channels + 1] */,
     uint32_t* __restrict__ chosen /* [n_frames * channels]: signal index */, uint32_t* __restrict__ status, uint64_t* __restrict__ total_words_out, uint64_t frames_cap)
 {
-    constexpr int kWaves = kPlanThreads / 64;
-    __shared__ uint64_t wave_bytes[kWaves], wave_words[kWaves];
-    __shared__ uint32_t frame_words[kPlanTile]; // words of the frames of one tile (their bytes follow: 4 + 12 channels + 4 words)
-    __shared__ uint32_t frame_first_hi[kPlanTile];
-    __shared__ uint32_t all_flags, all_over;
-    const uint32_t t = threadIdx.x;
-    const int lane = t % 64, wave = t / 64;
-    if (t == 0)
-        all_flags = 0, all_over = 0;
-    uint64_t base_b = 0, base_w = 0; // bytes / words of the tiles before this one (the same in every thread)
-    uint32_t my_flags = 0, my_over = 0;
-    for (uint32_t tile0 = 0; tile0 < n_frames; tile0 += kPlanTile) {
-        const uint32_t tile_n = min((uint32_t)kPlanTile, n_frames - tile0);
-        __syncthreads(); // (the tile before has been read)
-        for (uint32_t i = t; i < tile_n; i += kPlanThreads) {
-            const uint32_t f = tile0 + i;
-            uint32_t words = 0;
-            // (values, not pointers, are selected: a record chosen by pointer is loaded again through it -- a chain of dependent
-            // loads, 32 us for 3875 frames)
-            const GenericMeta* const fm = meta + (size_t)f * n_sig;
-            if (channels == 2) {
-                const uint32_t w0 = fm[0].coef_words + fm[0].res_words, w1 = fm[1].coef_words + fm[1].res_words, w2 = fm[2].coef_words + fm[2].res_words;
-                const uint32_t f0 = fm[0].flags, f1 = fm[1].flags, f2 = fm[2].flags;
-                const bool diff = (uint64_t)fm[2].coef_words + fm[2].res_words < (uint64_t)fm[1].coef_words + fm[1].res_words;
-                my_flags |= f0 | f1 | f2; // (both candidates were computed by the reference too: either's trouble is the frame's)
-                chosen[(size_t)f * 2] = 0;
-                chosen[(size_t)f * 2 + 1] = diff ? 2u : 1u;
-                const uint32_t fs = diff ? f2 : f1, ws = diff ? w2 : w1;
-                words = ((f0 & SELA_HIP_FLAG_WORDS_CAP) ? 0u : w0) + ((fs & SELA_HIP_FLAG_WORDS_CAP) ? 0u : ws);
-            } else {
-                for (uint32_t c = 0; c < channels; c++) {
-                    const uint32_t fl = fm[c].flags, w = fm[c].coef_words + fm[c].res_words;
-                    my_flags |= fl;
-                    chosen[(size_t)f * channels + c] = c;
-                    words += (fl & SELA_HIP_FLAG_WORDS_CAP) ? 0u : w; // (<= 255 x 131,070 words: fits)
-                }
-            }
-            frame_words[i] = words;
-        }
-        __syncthreads();
-        const uint32_t per = (tile_n + kPlanThreads - 1) / kPlanThreads;
-        const uint32_t begin = min(t * per, tile_n), end = min(begin + per, tile_n);
-        uint64_t my_words = 0;
-        for (uint32_t i = begin; i < end; i++)
-            my_words += frame_words[i];
-        const uint64_t my_bytes = (uint64_t)(end - begin) * (4 + (uint64_t)channels * SELA_SUBFRAME_HEADER_BYTES) + 4 * my_words;
-        auto scan64 = [&](uint64_t v) -> uint64_t { // inclusive, within the wave
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64);
-                const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
-                if (lane >= d)
-                    v += ((uint64_t)hi << 32) | lo;
-            }
-            return v;
-        };
-        const uint64_t incl_b = scan64(my_bytes), incl_w = scan64(my_words);
-        if (lane == 63)
-            wave_bytes[wave] = incl_b, wave_words[wave] = incl_w;
-        __syncthreads();
-        uint64_t at_w = base_w + incl_w - my_words, tile_b = 0, tile_w = 0;
-        for (int w = 0; w < kWaves; w++) {
-            const uint64_t wb = wave_bytes[w], ww = wave_words[w];
-            if (w < wave)
-                at_w += ww;
-            tile_b += wb, tile_w += ww;
-        }
-        // every frame's first word: an exclusive scan of the run in place (frame_words[i] <- words before frame i in the stream) ...
-        for (uint32_t i = begin; i < end; i++) {
-            const uint32_t w = frame_words[i];
-            frame_words[i] = (uint32_t)(at_w - base_w); // (relative to the tile: 4096 frames x 255 x 131,070 words fit 2^32 only just -- kept in 64 bits below)
-            frame_first_hi[i] = (uint32_t)((at_w - base_w) >> 32);
-            at_w += w;
-        }
-        __syncthreads();
-        // ... and then frame by frame again as in the first pass -- thread f mod 1024, independent loads (the third version: the
-        // run's owner walked its frames' subframes through `chosen`, a chain of dependent loads: 38 us at 3875 frames)
-        for (uint32_t i = t; i < tile_n; i += kPlanThreads) {
-            const uint32_t f = tile0 + i;
-            const uint64_t first = base_w + (((uint64_t)frame_first_hi[i] << 32) | frame_words[i]);
-            uint64_t w_at = first;
-            const GenericMeta* const fm = meta + (size_t)f * n_sig;
-            if (channels == 2) {
-                const uint32_t w0 = fm[0].coef_words + fm[0].res_words, f0 = fm[0].flags;
-                word_base[(size_t)f * 2] = w_at;
-                word_base[(size_t)f * 2 + 1] = w_at + ((f0 & SELA_HIP_FLAG_WORDS_CAP) ? 0u : w0);
-            } else {
-                for (uint32_t c = 0; c < channels; c++) {
-                    const uint32_t fl = fm[c].flags, w = fm[c].coef_words + fm[c].res_words;
-                    word_base[(size_t)f * channels + c] = w_at;
-                    w_at += (fl & SELA_HIP_FLAG_WORDS_CAP) ? 0u : w;
-                }
-            }
-            // bytes before frame f = (frames before it) x (4 + 12 channels) + 4 x (words before it)
-            frame_offsets[f] = base_bytes + (uint64_t)f * (4 + (uint64_t)channels * SELA_SUBFRAME_HEADER_BYTES) + 4 * first;
-            if constexpr (kDevice) { // (the frame's end: the next frame's first word, from the scan)
-                const uint64_t next = i + 1 < tile_n ? base_w + (((uint64_t)frame_first_hi[i + 1] << 32) | frame_words[i + 1]) : base_w + tile_w;
-                my_over += (uint64_t)(f + 1) * (4 + (uint64_t)channels * SELA_SUBFRAME_HEADER_BYTES) + 4 * next > frames_cap;
-            }
-        }
-        base_b += tile_b, base_w += tile_w;
-    }
-    if (my_flags)
-        atomicOr(&all_flags, my_flags);
-    if (kDevice && my_over)
-        atomicAdd(&all_over, my_over);
-    __syncthreads();
-    if (t == 0) {
-        frame_offsets[n_frames] = base_bytes + base_b;
-        word_base[(size_t)n_frames * channels] = base_w;
-        *total_words_out = base_w;
-        if constexpr (kDevice) {
-            status[0] = all_flags, status[1] = all_over, status[2] = 0, status[3] = 0;
-        } else {
-            atomicOr(&status[0], all_flags);
-        }
-    }
+    constexpr bool kPaired = false;
+#include "sela_generic_plan.inc"
+}
+template <bool kDevice>
+__global__ __launch_bounds__(kPlanThreads) void k_paired_plan(const GenericMeta* __restrict__ meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig,
+    uint64_t base_bytes, uint64_t* __restrict__ frame_offsets, uint64_t* __restrict__ word_base, uint32_t* __restrict__ chosen, uint32_t* __restrict__ status,
+    uint64_t* __restrict__ total_words_out, uint64_t frames_cap)
+{
+    constexpr bool kPaired = true;
+#include "sela_generic_plan.inc"
 }
 
 // ---- pack: the chosen candidates' two Rice streams, one wave per subframe ---------------------------------------------------
@@ -1598,7 +1517,7 @@ __global__ __launch_bounds__(kInterleaveThreads) void k_interleave16(const int32
 // ---- launchers --------------------------------------------------------------------------------------------------------------
 size_t generic_encode_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
 {
-    const size_t n_sig = channels == 2 ? 3 : channels, blocks = (size_t)n_frames * n_sig;
+    const size_t n_sig = generic_signals(channels, false), blocks = (size_t)n_frames * n_sig;
     return blocks * n * (4 + 4) + blocks * kMaxOrder * 4 + blocks * sizeof(GenericMeta) + ((size_t)n_frames * channels + 1) * (8 + 4) + 1024;
 }
 
@@ -1606,28 +1525,42 @@ static std::atomic<int> g_force_wrap_taps{0};
 void set_generic_wrap_taps(int on) { g_force_wrap_taps.store(on, std::memory_order_relaxed); }
 
 hipError_t launch_generic_analyse(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint32_t n, int32_t* d_sig,
-    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless)
+    int32_t* d_res, int32_t* d_q, GenericMeta* d_meta, hipStream_t stream, bool lossless, bool paired)
 {
     const uint32_t blocks = n_frames * n_sig;
     if (blocks == 0)
         return hipSuccess;
     const uint32_t wrap = g_force_wrap_taps.load(std::memory_order_relaxed) ? 1u : 0u;
-    if (in16 && lossless)
-        hipLaunchKernelGGL((k_generic_analyse<true, true>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap); };
+    if (paired) {
+        if (in16 && lossless)
+            launch(k_generic_analyse<true, true, true>);
+        else if (lossless)
+            launch(k_generic_analyse<false, true, true>);
+        else if (in16)
+            launch(k_generic_analyse<true, false, true>);
+        else
+            launch(k_generic_analyse<false, false, true>);
+    } else if (in16 && lossless)
+        launch(k_generic_analyse<true, true, false>);
     else if (lossless)
-        hipLaunchKernelGGL((k_generic_analyse<false, true>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+        launch(k_generic_analyse<false, true, false>);
     else if (in16)
-        hipLaunchKernelGGL((k_generic_analyse<true, false>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+        launch(k_generic_analyse<true, false, false>);
     else
-        hipLaunchKernelGGL((k_generic_analyse<false, false>), dim3(blocks), dim3(64), 0, stream, d_input, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, wrap);
+        launch(k_generic_analyse<false, false, false>);
     return hipGetLastError();
 }
 
 hipError_t launch_generic_plan(const GenericMeta* d_meta, uint32_t n_frames, uint32_t channels, uint32_t n_sig, uint64_t base_bytes, uint64_t* d_frame_offsets,
-    uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream)
+    uint64_t* d_word_base, uint32_t* d_chosen, uint32_t* d_status, uint64_t* d_total_words, hipStream_t stream, bool paired)
 {
-    hipLaunchKernelGGL(k_generic_plan<false>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, base_bytes, d_frame_offsets, d_word_base,
-        d_chosen, d_status, d_total_words, (uint64_t)0);
+    if (paired)
+        hipLaunchKernelGGL(k_paired_plan<false>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, base_bytes, d_frame_offsets,
+            d_word_base, d_chosen, d_status, d_total_words, (uint64_t)0);
+    else
+        hipLaunchKernelGGL(k_generic_plan<false>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, base_bytes, d_frame_offsets,
+            d_word_base, d_chosen, d_status, d_total_words, (uint64_t)0);
     return hipGetLastError();
 }
 
@@ -1985,10 +1918,10 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
 struct EncodeI32Layout {
     uint64_t sig, res, q, meta, word_base, chosen, total, bytes;
 };
-static EncodeI32Layout encode_i32_layout(uint32_t n_frames, uint32_t channels, uint32_t n)
+static EncodeI32Layout encode_i32_layout(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired)
 {
     auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    const uint64_t blocks = (uint64_t)n_frames * (channels == 2 ? 3 : channels), subs = (uint64_t)n_frames * channels;
+    const uint64_t blocks = (uint64_t)n_frames * generic_signals(channels, paired), subs = (uint64_t)n_frames * channels;
     EncodeI32Layout l;
     l.sig = 0;
     l.res = l.sig + up(blocks * n * sizeof(int32_t));
@@ -2001,19 +1934,20 @@ static EncodeI32Layout encode_i32_layout(uint32_t n_frames, uint32_t channels, u
     return l;
 }
 
-size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n)
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired)
 {
-    if (channels == 0 || channels > 255 || n == 0 || n > 65535 || (uint64_t)n_frames * (channels == 2 ? 3 : channels) >= (1ull << 31))
+    if (channels == 0 || channels > 255 || n == 0 || n > 65535 || (uint64_t)n_frames * generic_signals(channels, paired) >= (1ull << 31))
         return SIZE_MAX;
-    return (size_t)encode_i32_layout(n_frames, channels, n).bytes;
+    return (size_t)encode_i32_layout(n_frames, channels, n, paired).bytes;
 }
 
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: analyse, plan (base 0, the offsets straight into the
 // caller's, the status words written whole) and write, all on `stream`, nothing waited for.  Arguments checked by the caller.
+// paired (sela_hip_encode_paired_*_device): the same three launches over generic_signals(channels, true) signals.
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
-    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless)
+    uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless, bool paired)
 {
-    const EncodeI32Layout l = encode_i32_layout(n_frames, channels, n);
+    const EncodeI32Layout l = encode_i32_layout(n_frames, channels, n, paired);
     unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
     int32_t* const d_sig = reinterpret_cast<int32_t*>(base + l.sig);
     int32_t* const d_res = reinterpret_cast<int32_t*>(base + l.res);
@@ -2022,12 +1956,16 @@ hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_f
     uint64_t* const d_word_base = reinterpret_cast<uint64_t*>(base + l.word_base);
     uint32_t* const d_chosen = reinterpret_cast<uint32_t*>(base + l.chosen);
     uint64_t* const d_total = reinterpret_cast<uint64_t*>(base + l.total);
-    const uint32_t n_sig = channels == 2 ? 3u : channels;
-    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream, lossless);
+    const uint32_t n_sig = generic_signals(channels, paired);
+    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream, lossless, paired);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets, d_word_base,
-        d_chosen, d_status, d_total, frames_cap);
+    if (paired)
+        hipLaunchKernelGGL(k_paired_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
+            d_word_base, d_chosen, d_status, d_total, frames_cap);
+    else
+        hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
+            d_word_base, d_chosen, d_status, d_total, frames_cap);
     const uint32_t subs = n_frames * channels;
     if (subs)
         hipLaunchKernelGGL(k_generic_write, dim3(subs), dim3(64), 0, stream, d_meta, n_frames, channels, n_sig, n, d_res, d_q, d_chosen, d_word_base,

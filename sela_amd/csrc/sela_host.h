@@ -89,7 +89,7 @@ void generic_shutdown();
 int generic_standard_first_mode();
 size_t generic_encode_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t n);
 int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out,
-    bool lossless = false);
+    bool lossless = false, bool paired = false);
 uint32_t generic_index_samples(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint64_t* sample_offsets, bool* all_standard);
 int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int32_t* samples_out, uint32_t stride,
     uint32_t* counts_out, int16_t* pcm_out, const uint64_t* sample_offsets);
