@@ -31,6 +31,10 @@ public:
     // Channel pairs (sela_hip_encode_paired): every odd channel may be stored as the difference against the even
     // channel before it, in a stream every decoder of the format reads.  One and two channels: the same bytes either way.
     bool pairChannels = false;
+    // The whole file: the samples beyond the last whole 2048-sample frame are folded into a long last frame
+    // (2049 .. 4095 samples; a file below 2048 samples is one frame) instead of dropped.  The 2048-sample frames go through the
+    // streaming job, the last frame through the one-shot call once the job has ended.  Not with pairChannels (data::Exception).
+    bool keepTail = false;
     explicit Encoder(std::ifstream& in) : ifStream(in) {}
     file::SelaFile process();
 };
@@ -48,13 +52,14 @@ public:
 // File to file (what the reference's main.cpp:29-41 does with process() + writeToFile()): the same
 // streaming read, and finished frames / samples are written out while later pieces are still on the device.
 // Return the number of frames coded.
-size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless = false, bool pairChannels = false); // (as Encoder::lossless, ::pairChannels)
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless = false, bool pairChannels = false,
+    bool keepTail = false); // (as Encoder::lossless, ::pairChannels, ::keepTail)
 size_t decodeFile(std::ifstream& in, std::ofstream& out);
 // The same by path -- what the CLI's -e / -d use: the file is read with several pread()s in flight on a small pool of I/O
 // threads (sela_host/fileio.hpp) while earlier pieces are on the device, and finished ranges are written by a task of
 // that pool -- over pages allocated in one go while the input was still on its way -- while later pieces are being coded.
 // One thread reads or writes a page-cache file at a few GB/s; the device codes 10 G samples/s.
-size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false, bool pairChannels = false);
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false, bool pairChannels = false, bool keepTail = false);
 size_t decodeFile(const std::string& inPath, const std::string& outPath);
 // Samples [startSample, startSample + sampleCount) per channel of a .sela of 2048-sample frames, as a WAV of exactly the samples
 // delivered: only the frames the range touches are copied to the device and decoded (sela_hip_decode_windows).  The count is cut

@@ -142,6 +142,42 @@ void pairedEncode(Need need, size_t piece, const int16_t* pcm, size_t frames, ui
     bytes.resize(at);
 }
 
+// keepTail: the frames the streaming job codes, the frames the file holds, and the samples per channel of the
+// long last frame that the one-shot call codes after the job has ended (0: there is none).  The rule itself is the library's
+// (sela_hip_whole_frames / sela_hip_whole_frame); without keepTail the tail is dropped, as the reference's reader drops it.
+struct WholePlan {
+    size_t jobFrames, frames, lastSamples;
+};
+WholePlan wholePlan(size_t samplesPerChannel, bool keepTail)
+{
+    const size_t whole = samplesPerChannel / kBlock;
+    if (!keepTail || samplesPerChannel % kBlock == 0)
+        return { whole, whole, 0 };
+    const size_t frames = (size_t)sela_hip_whole_frames(samplesPerChannel);
+    uint64_t first = 0;
+    uint32_t length = 0;
+    if (sela_hip_whole_frame(samplesPerChannel, frames - 1, &first, &length) != SELA_HIP_OK)
+        gpuFailure("Encoder");
+    return { frames - 1, frames, length };
+}
+
+// The last frame of a file that keeps its tail: `samples` per channel at pcm, through the one-shot call (the any-length route)
+// once the streaming job has ended -> its bytes.
+void encodeLastFrame(const int16_t* pcm, size_t samples, uint32_t channels, uint32_t options, sela_host::PinnedBuffer<uint8_t>& frame)
+{
+    frame.resize(sela_hip_encode_bound_bytes_n(1, channels, (uint32_t)samples));
+    uint64_t local[2] = { 0, 0 };
+    if (sela_hip_encode_opt(pcm, 1, channels, (uint32_t)samples, frame.data(), frame.size(), local, options) != SELA_HIP_OK)
+        gpuFailure("Encoder");
+    frame.resize((size_t)local[1]);
+}
+
+void refusePairedTail(bool keepTail, bool pairChannels)
+{
+    if (keepTail && pairChannels)
+        throw data::Exception("Encoder: keepTail with pairChannels is not supported");
+}
+
 // need() of a file that is read with the calling thread's own ifstream reads
 struct StreamReader {
     std::ifstream& in;
@@ -383,8 +419,10 @@ file::SelaFile Encoder::process()
     const uint32_t channels = wavFile.numChannels;
     if (channels == 0 || channels > 255)
         throw data::Exception("Encoder: unsupported channel count");
+    refusePairedTail(keepTail, pairChannels);
     wavFile.pcm.resize(dataBytes / 2);
-    const size_t frames = wavFile.frameCount(); // tail samples beyond the last whole frame are dropped
+    const WholePlan plan = wholePlan(wavFile.pcm.size() / channels, keepTail);
+    const size_t frames = plan.jobFrames; // (without keepTail: frameCount(), tail samples beyond the last whole frame are dropped)
     sela_host::PinnedBuffer<uint8_t> bytes;
     std::vector<uint64_t> offsets;
     const uint32_t options = lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u;
@@ -398,6 +436,14 @@ file::SelaFile Encoder::process()
     if (wavFile.pcm.size() > coded && !readExact(ifStream, wavFile.pcm.data() + coded, (wavFile.pcm.size() - coded) * 2))
         throw data::Exception("data subChunk is shorter than its header says");
     wavFile.syncChunk();
+    if (plan.lastSamples) { // the long last frame, behind the job's
+        sela_host::PinnedBuffer<uint8_t> last;
+        encodeLastFrame(wavFile.pcm.data() + coded, plan.lastSamples, channels, options, last);
+        const size_t at = bytes.size();
+        bytes.resize(at + last.size());
+        std::memcpy(bytes.data() + at, last.data(), last.size());
+        offsets.push_back(at + last.size());
+    }
     file::SelaFile out(wavFile.sampleRate, wavFile.bitsPerSample, (uint8_t)channels, std::move(bytes), std::move(offsets));
     if (materializeFrames)
         out.materializeFrames();
@@ -423,20 +469,22 @@ file::WavFile Decoder::process()
     return out;
 }
 
-size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless, bool pairChannels)
+size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless, bool pairChannels, bool keepTail)
 {
+    refusePairedTail(keepTail, pairChannels);
     file::WavFile wav;
     const size_t dataBytes = wav.readHeader(in);
     const uint32_t channels = wav.numChannels;
     if (channels == 0 || channels > 255)
         throw data::Exception("Encoder: unsupported channel count");
-    const size_t frames = dataBytes / 2 / channels / kBlock;
-    wav.pcm.resize(frames * kBlock * channels);
+    const WholePlan plan = wholePlan(dataBytes / 2 / channels, keepTail);
+    const size_t frames = plan.jobFrames;
+    wav.pcm.resize((frames * kBlock + plan.lastSamples) * channels);
     file::SelaFile header;
     header.selaHeader.sampleRate = wav.sampleRate;
     header.selaHeader.bitsPerSample = wav.bitsPerSample;
     header.selaHeader.channels = (uint8_t)channels;
-    header.selaHeader.numFrames = (uint32_t)frames;
+    header.selaHeader.numFrames = (uint32_t)plan.frames;
     header.writeHeader(out);
     sela_host::PinnedBuffer<uint8_t> bytes;
     std::vector<uint64_t> offsets;
@@ -452,7 +500,15 @@ size_t encodeFile(std::ifstream& in, std::ofstream& out, bool lossless, bool pai
         pairedEncode(StreamReader{ in, wav.pcm.data(), kBlock * channels }, kPieceFrames, wav.pcm.data(), frames, channels, bytes, offsets, drain, {}, options);
     else
         streamEncode(StreamReader{ in, wav.pcm.data(), kBlock * channels }, kPieceFrames, wav.pcm.data(), frames, channels, bytes, offsets, drain, {}, options);
-    return frames;
+    if (plan.lastSamples) { // the long last frame: its samples read here, coded once the job has ended, appended
+        int16_t* const lastPcm = wav.pcm.data() + frames * kBlock * channels;
+        if (!readExact(in, lastPcm, plan.lastSamples * channels * 2))
+            throw data::Exception("data subChunk is shorter than its header says");
+        sela_host::PinnedBuffer<uint8_t> last;
+        encodeLastFrame(lastPcm, plan.lastSamples, channels, options, last);
+        out.write(reinterpret_cast<const char*>(last.data()), (std::streamsize)last.size());
+    }
+    return plan.frames;
 }
 
 size_t decodeFile(std::ifstream& in, std::ofstream& out)
@@ -734,13 +790,16 @@ size_t expectedSelaBytes(const WavInfo& info) { return info.frames * kBlock * in
 
 void setIoThreads(unsigned n) { sela_host::IoPool::configure(n); }
 
-size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless, bool pairChannels)
+size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless, bool pairChannels, bool keepTail)
 {
-    const WavInfo info = probeWav(inPath);
+    refusePairedTail(keepTail, pairChannels);
+    WavInfo info = probeWav(inPath);
+    const WholePlan plan = wholePlan(info.dataBytes / 2 / info.channels, keepTail);
+    info.frames = plan.jobFrames; // (what the streaming job codes; without keepTail nothing changes)
     const sela_host::PosixFile in = sela_host::PosixFile::openForRead(inPath);
     const sela_host::PosixFile out = sela_host::PosixFile::create(outPath);
     uint8_t header[15];
-    selaHeaderBytes(header, info.rate, info.bps, (uint8_t)info.channels, (uint32_t)info.frames);
+    selaHeaderBytes(header, info.rate, info.bps, (uint8_t)info.channels, (uint32_t)plan.frames);
     out.writeAt(header, 15, 0);
     sela_host::PinnedBuffer<int16_t> pcm;
     sela_host::PinnedBuffer<uint8_t> bytes;
@@ -750,7 +809,17 @@ size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lo
     const size_t total = encodeRange(in, info, 0, info.frames, pcm, bytes, offsets, [&](const uint8_t* p, size_t done) { behind.drain(p, done); }, [&] { behind.quiesce(); },
         lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u, pairChannels);
     behind.finish(&total);
-    return info.frames;
+    if (plan.lastSamples) { // the long last frame: its samples read here, coded once the job has ended, appended
+        const size_t frameBytes = kBlock * info.channels * 2;
+        sela_host::PinnedBuffer<int16_t> lastPcm;
+        lastPcm.resize(plan.lastSamples * info.channels);
+        if (!in.readAt(lastPcm.data(), lastPcm.size() * 2, info.dataOffset + plan.jobFrames * frameBytes))
+            throw data::Exception("data subChunk is shorter than its header says");
+        sela_host::PinnedBuffer<uint8_t> last;
+        encodeLastFrame(lastPcm.data(), plan.lastSamples, info.channels, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u, last);
+        out.writeAt(last.data(), last.size(), 15 + total);
+    }
+    return plan.frames;
 }
 
 size_t decodeFile(const std::string& inPath, const std::string& outPath)

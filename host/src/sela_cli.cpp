@@ -6,6 +6,9 @@
 //   sela_mi355x -e --pair-channels [--lossless] in.wav out.sela   encode a file of more than two channels with every odd channel
 //                                      stored as the difference against the even channel before it where that takes fewer words
 //                                      (any decoder of the format reads it; one and two channels: the same bytes as without)
+//   sela_mi355x -e --keep-tail [--lossless] in.wav out.sela   encode the whole file: the samples beyond the last whole 2048-sample
+//                                      frame are folded into a long last frame instead of dropped (with --lossless, -v then exits 0);
+//                                      not with --pair-channels, not with -E
 //   sela_mi355x -d in.sela out.wav     decode
 //   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
 //                                      the frames the range touches are decoded and no others
@@ -43,6 +46,8 @@ int usage(const std::string& program)
               << program << " -e [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Encoding a multichannel file with adjacent channels paired (odd channels as differences where that is smaller):\n"
               << program << " -e --pair-channels [--lossless] path/to/input.wav path/to/output.sela\n\n"
+              << "Encoding a whole file (the samples beyond the last whole frame are kept, in a long last frame):\n"
+              << program << " -e --keep-tail [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only):\n"
               << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
@@ -116,6 +121,21 @@ int run(int argc, char** argv)
 {
     const std::string program = argv[0];
     const std::string verb = argc > 1 ? argv[1] : "";
+    // (--keep-tail is -e's alone, right behind it, with --lossless behind it or nothing: with --pair-channels, with -E and anywhere
+    // else it is refused, not ignored)
+    for (int i = 2; i < argc; i++) {
+        if (std::string(argv[i]) != "--keep-tail")
+            continue;
+        const bool keepLossless = argc == 6 && std::string(argv[3]) == "--lossless";
+        if (!(verb == "-e" && i == 2 && (argc == 5 || keepLossless)))
+            return usage(program);
+        for (int k = 3; k < argc; k++)
+            if (std::string(argv[k]).rfind("--", 0) == 0 && !(keepLossless && k == 3))
+                return usage(program);
+        std::cout << "Encoding (whole file" << (keepLossless ? ", lossless" : "") << "): " << argv[argc - 2] << std::endl;
+        sela::encodeFile(std::string(argv[argc - 2]), std::string(argv[argc - 1]), keepLossless, false, true);
+        return 0;
+    }
     // (--pair-channels is -e's alone, right behind it; --lossless is -e's alone too, behind the verb or behind --pair-channels:
     // anywhere else they are refused, not ignored)
     const bool paired = verb == "-e" && (argc == 5 || argc == 6) && std::string(argv[2]) == "--pair-channels";

@@ -573,6 +573,56 @@ int sela_hip_encode_paired_i32(const int32_t* samples, uint32_t n_frames, uint32
 int sela_hip_encode_paired(const int16_t* pcm, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint8_t* frames_out,
     size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames + 1] */, uint32_t options);
 
+/* ---- a whole track: the tail kept in a long last frame ---------------------------------------------------------
+ * The reference's WAV reader cuts 2048-sample frames and drops what is left over; the format does not ask for that (a frame says
+ * its own samplesPerChannel).  These calls code all N = n_samples samples per channel of a track.  The rule, with F = N / 2048 and
+ * t = N % 2048:
+ *   N == 0            no frame.
+ *   t == 0            F frames of 2048 samples: the bytes and offsets of sela_hip_encode_device(_opt) on them.
+ *   F >= 1, t > 0     F frames: frames 0 .. F - 2 of 2048 samples, frame F - 1 of 2048 + t (2049 .. 4095) -- the tail is folded into
+ *                     the last whole frame, never a frame of its own (a block of up to a hundred samples is routinely no longer
+ *                     than the order its own analysis picks: SELA_HIP_FLAG_SHORT_BLOCK).
+ *   F == 0, N > 0     one frame of N samples; a short one may be SELA_HIP_FLAG_SHORT_BLOCK / SELA_HIP_ERANGE, exactly as from
+ *                     sela_hip_encode on the same frame.
+ * Frame f starts at sample 2048 * f for every f.  Frames 0 .. F - 2 are byte for byte the plain call's; the last frame is byte for
+ * byte frame::FrameEncoder's for a WavFrame of its length (the stereo decision included), i.e. sela_hip_encode_n_device's.
+ * Host only, no GPU:
+ *   sela_hip_whole_frames(N)                 the number of frames;
+ *   sela_hip_whole_frame(N, f, &first, &len) frame f's first sample and length (SELA_HIP_EINVAL: no such frame, a null pointer);
+ *   sela_hip_encode_whole_bound_bytes        what frames_cap must be to be certain the stream fits (SIZE_MAX beyond size_t);
+ *   sela_hip_encode_whole_workspace_bytes    the device call's workspace for every track of at most max_samples samples per channel:
+ *                                            it does not depend on the data or the device, and grows with max_samples.  The plain
+ *                                            call's workspace for the track's frames, then the any-length call's for one frame of
+ *                                            min(max_samples, 4095) samples, that frame's bound, and 512 bytes.  SIZE_MAX for what
+ *                                            the call refuses.
+ * sela_hip_encode_whole_device: d_pcm int16 [N][channels] interleaved, 4-byte aligned; d_frames 4-byte aligned; d_frame_offsets
+ *   [frames + 1]; d_status uint32[4]; options: 0 or SELA_HIP_ENCODE_LOSSLESS.  Asynchronous on `stream`: no allocation, no host wait,
+ *   no host read of device data, so a stream being captured into a HIP graph may take it.  The contract is sela_hip_encode_n_device's:
+ *   the offsets are always written in full; a frame that ends beyond frames_cap is not written and nothing at or past frames_cap is;
+ *   d_status[0] is the OR of the flag bits of all frames, d_status[1] the number of frames not written, [2] and [3] zero;
+ *   sela_hip_encode_status_error() applies unchanged; N == 0 writes d_frame_offsets[0] = 0 and zero status words.
+ *   Launches: the plain call's three on frames 0 .. F - 2, the any-length call's three on the last frame -- read in place, coded into
+ *   the workspace, on a stream of the library's own between two events (forked from `stream` before the plain launches, joined
+ *   behind them; inside a capture the side stream joins the capture and leaves it at the join) -- and one small kernel on `stream`
+ *   that copies the last frame behind the others, writes d_frame_offsets[F] and folds the two status words together.  With t == 0,
+ *   or a single frame, only the one call it is, on `stream`.
+ *   SELA_HIP_EINVAL: an option bit not defined, channels outside 1..255, frames x signals per frame at 2^31 or more, a null pointer
+ *   (d_pcm and d_frames only where N > 0), a misaligned d_pcm or d_frames; SELA_HIP_ECAPACITY: a smaller workspace.  Nothing is
+ *   enqueued then.
+ * sela_hip_encode_whole: the same stream from HOST pointers, synchronous, on the calling thread's contexts: frames 0 .. F - 2 where
+ *   sela_hip_encode_opt codes them, the last frame on the any-length route, past the coalescer.  A thread with a streaming job open is
+ *   served by the any-length route alone, which leaves that job alone.  Errors are sela_hip_encode_opt's (SELA_HIP_ECAPACITY: frames_out
+ *   too small; frame_offsets_out is not defined then). */
+uint64_t sela_hip_whole_frames(uint64_t n_samples);
+int sela_hip_whole_frame(uint64_t n_samples, uint64_t frame, uint64_t* first_sample, uint32_t* length);
+size_t sela_hip_encode_whole_bound_bytes(uint64_t n_samples, uint32_t channels);
+size_t sela_hip_encode_whole_workspace_bytes(uint64_t max_samples, uint32_t channels);
+int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint32_t channels, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets /* [frames + 1] */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream,
+    uint32_t options);
+int sela_hip_encode_whole(const int16_t* pcm, uint64_t n_samples, uint32_t channels, uint8_t* frames_out, size_t frames_cap,
+    uint64_t* frame_offsets_out /* [frames + 1] */, uint32_t options);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

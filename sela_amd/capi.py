@@ -42,6 +42,8 @@ EXPORTS = [
     "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
     "sela_hip_paired_signals_per_frame", "sela_hip_encode_paired_workspace_bytes", "sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device",
     "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
+    "sela_hip_whole_frames", "sela_hip_whole_frame", "sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes",
+    "sela_hip_encode_whole_device", "sela_hip_encode_whole",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
@@ -188,6 +190,19 @@ def lib() -> C.CDLL:
     L.sela_hip_encode_paired.argtypes = [vp, u32, u32, u32, vp, sz, vp, u32]
     for name in ("sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device", "sela_hip_encode_paired_i32", "sela_hip_encode_paired"):
         getattr(L, name).restype = C.c_int
+    # a whole track with its tail: the sample count is a uint64
+    u64 = C.c_uint64
+    L.sela_hip_whole_frames.argtypes = [u64]
+    L.sela_hip_whole_frames.restype = u64
+    L.sela_hip_whole_frame.argtypes = [u64, u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.sela_hip_whole_frame.restype = C.c_int
+    for name in ("sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes"):
+        getattr(L, name).argtypes = [u64, u32]
+        getattr(L, name).restype = sz
+    L.sela_hip_encode_whole_device.argtypes = [vp, u64, u32, vp, sz, vp, vp, vp, sz, vp, u32]
+    L.sela_hip_encode_whole_device.restype = C.c_int
+    L.sela_hip_encode_whole.argtypes = [vp, u64, u32, vp, sz, vp, u32]
+    L.sela_hip_encode_whole.restype = C.c_int
     L.sela_hip_encode_status_error.argtypes = [vp]
     L.sela_hip_encode_status_error.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]

@@ -651,6 +651,68 @@ class Encoder32:
         return self.frames[: int(offs[-1])].cpu().numpy(), offs
 
 
+def whole_frames(n_samples: int):
+    """The layout of a whole track of n_samples samples per channel (no GPU): a list of (first_sample, length),
+    one per frame -- 2048-sample frames, the tail folded into the last one; one frame for a track below 2048 samples."""
+    lib = capi.lib()
+    first, length = C.c_uint64(), C.c_uint32()
+    out = []
+    for f in range(int(lib.sela_hip_whole_frames(n_samples))):
+        capi.check(lib.sela_hip_whole_frame(n_samples, f, C.byref(first), C.byref(length)))
+        out.append((int(first.value), int(length.value)))
+    return out
+
+
+class WholeEncoder:
+    """sela_hip_encode_whole_device: a whole track of up to max_samples samples per channel, its tail kept in a long last frame
+    (DESIGN.md 5.19).  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
+    asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the certain bound.
+    lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder."""
+
+    def __init__(self, max_samples: int, channels: int, lossless: bool = False, device=None, capacity=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.options = capi.ENCODE_LOSSLESS if lossless else 0
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_samples, self.channels = int(max_samples), int(channels)
+        self.max_frames = int(self.lib.sela_hip_whole_frames(self.max_samples))
+        if capacity is None:
+            capacity = int(self.lib.sela_hip_encode_whole_bound_bytes(self.max_samples, channels))
+        self.capacity = max(int(capacity), 4)
+        ws = int(self.lib.sela_hip_encode_whole_workspace_bytes(self.max_samples, channels))
+        with torch.cuda.device(self.device):
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+            self.offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.n_frames = 0
+
+    def encode(self, pcm):
+        """pcm: int16 cuda tensor [n_samples, channels], contiguous -> (frames uint8 [capacity], offsets int64 [frames + 1],
+        status int32 [4]): the encoder's own buffers, the first offsets[-1] bytes of frames the stream's when check() passes."""
+        torch = self.torch
+        assert pcm.is_cuda and pcm.is_contiguous() and pcm.dtype == torch.int16 and pcm.dim() == 2 and pcm.shape[1] == self.channels
+        n_samples = pcm.shape[0]
+        assert n_samples <= self.max_samples
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_encode_whole_device(pcm.data_ptr(), n_samples, self.channels, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+                                                         self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream, self.options))
+        self.n_frames = int(self.lib.sela_hip_whole_frames(n_samples))
+        return self.frames, self.offsets[: self.n_frames + 1], self.status
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code the host call gives for the same input."""
+        capi.check(encode_status_error(self.status.cpu().numpy()))
+
+    def to_host(self):
+        """check(), then -> (frames uint8 [...], offsets uint64 [frames + 1]) on the host."""
+        self.check()
+        offs = self.offsets[: self.n_frames + 1].cpu().numpy().view(np.uint64)
+        return self.frames[: int(offs[-1])].cpu().numpy(), offs
+
+
 def encode_status_error(status) -> int:
     """sela_hip_encode_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
     st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
@@ -675,6 +737,20 @@ def encode_host(pcm: np.ndarray, lossless: bool = False, paired: bool = False):
         capi.check(lib.sela_hip_encode_opt(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS))
     else:
         capi.check(lib.sela_hip_encode(p.ctypes.data, n_frames, ch, n, frames.ctypes.data, cap, offs.ctypes.data))
+    return frames[: int(offs[n_frames])].copy(), offs
+
+
+def encode_whole_host(pcm: np.ndarray, lossless: bool = False):
+    """sela_hip_encode_whole: pcm int16 [n_samples, channels] -- a whole track, its tail kept in a long last frame
+    -> (frames uint8[...], offsets uint64[frames + 1])."""
+    lib = capi.lib()
+    p = np.ascontiguousarray(pcm, dtype=np.int16)
+    n_samples, ch = p.shape
+    n_frames = int(lib.sela_hip_whole_frames(n_samples))
+    cap = max(int(lib.sela_hip_encode_whole_bound_bytes(n_samples, ch)), 4)
+    frames = np.empty(cap, np.uint8)
+    offs = np.zeros(n_frames + 1, np.uint64)
+    capi.check(lib.sela_hip_encode_whole(p.ctypes.data, n_samples, ch, frames.ctypes.data, cap, offs.ctypes.data, capi.ENCODE_LOSSLESS if lossless else 0))
     return frames[: int(offs[n_frames])].copy(), offs
 
 

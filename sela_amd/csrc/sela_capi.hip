@@ -1200,6 +1200,7 @@ void sela_hip_shutdown(void)
     sela::generic_shutdown();
     flights().release_all();
     splitter().release_all();
+    sela::whole_shutdown();
     pool().trim();
 }
 
@@ -2281,6 +2282,164 @@ int sela_hip_encode_opt(const int16_t* pcm, uint32_t n_frames, uint32_t channels
     return encode_now(pcm, n_frames, channels, frames_out, frames_cap, frame_offsets_out, options);
 }
 
+// ---- a whole track with its tail (the rule, the workspace and the splice: sela_whole.hip) -------------------------
+namespace {
+// The last frame's chain beside the 2048-sample frames' launch: on a stream of the library's own per device, between two events --
+// forked from the caller's stream before the main launch, joined before the splice (the Splitter's plumbing; in a stream that is
+// being captured the side stream joins the capture at the fork and leaves it at the join).  One call at a time enqueues through
+// it; the calls' work still overlaps on the device.
+struct WholeFork {
+    std::mutex mu;
+    hipStream_t side[64] = {};
+    hipEvent_t forked[64] = {}, last_done[64] = {};
+    bool ready(int dev)
+    {
+        if (side[dev])
+            return true;
+        if (hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking) != hipSuccess) {
+            side[dev] = nullptr;
+            return false;
+        }
+        if (hipEventCreateWithFlags(&forked[dev], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&last_done[dev], hipEventDisableTiming) != hipSuccess) {
+            (void)hipStreamDestroy(side[dev]);
+            side[dev] = nullptr;
+            return false;
+        }
+        return true;
+    }
+    void release_all()
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        int before = -1;
+        (void)hipGetDevice(&before);
+        for (int dev = 0; dev < 64; dev++)
+            if (side[dev]) {
+                (void)hipSetDevice(dev);
+                (void)hipStreamSynchronize(side[dev]);
+                (void)hipEventDestroy(forked[dev]);
+                (void)hipEventDestroy(last_done[dev]);
+                (void)hipStreamDestroy(side[dev]);
+                side[dev] = nullptr;
+            }
+        if (before >= 0)
+            (void)hipSetDevice(before);
+    }
+};
+WholeFork& whole_fork()
+{
+    static WholeFork* f = new WholeFork; // (never destroyed: streams outlive the statics' teardown)
+    return *f;
+}
+
+int whole_arguments(uint64_t n_samples, uint32_t channels, const void* pcm, const void* frames, const void* frame_offsets)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (sela_hip_whole_frames(n_samples) * sela_hip_signals_per_frame(channels) >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "frames * signals per frame must stay below 2^31");
+    if (!frame_offsets || (n_samples && (!pcm || !frames)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    return SELA_HIP_OK;
+}
+} // namespace
+
+int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint32_t channels, uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, uint32_t options)
+{
+    bool lossless = false;
+    int rc = encode_options(options, &lossless);
+    if (rc == SELA_HIP_OK)
+        rc = whole_arguments(n_samples, channels, d_pcm, d_frames, d_frame_offsets);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!d_status || !d_workspace)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
+        return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
+    const sela::WholeLayout l = sela::whole_layout(n_samples, channels);
+    if (workspace_bytes < l.bytes)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_whole_workspace_bytes()");
+    if (lossless && g_phase_cycles)
+        return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS while sela_hip_debug_phase_buffer is set: the phase counts are the plain kernels'");
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
+    uint8_t* const base = reinterpret_cast<uint8_t*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    const size_t main_bytes = (size_t)l.last_workspace, last_bytes = (size_t)(l.last_frame - l.last_workspace);
+    if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
+        return encode_i32_device_call(d_pcm, true, 0, channels, 1, d_frames, frames_cap, d_frame_offsets, d_status, base + l.last_workspace, last_bytes, stream, lossless);
+    if (tail == 0) // whole frames only: the plain call, its bytes and offsets
+        return encode_device_call(d_pcm, frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, base, main_bytes, nullptr, stream, lossless);
+    const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
+    const int16_t* const d_last_pcm = d_pcm + (size_t)last * SELA_HIP_SAMPLES_PER_FRAME * channels;
+    if (last == 0) // one frame, of up to 4095 samples: the any-length call as it stands
+        return encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_frames, frames_cap, d_frame_offsets, d_status, base + l.last_workspace, last_bytes, stream,
+            lossless);
+    uint8_t* const d_last_frame = base + l.last_frame;
+    uint64_t* const d_last_offsets = reinterpret_cast<uint64_t*>(base + l.last_head);
+    uint32_t* const d_last_status = reinterpret_cast<uint32_t*>(base + l.last_head + 16);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+        return fail(SELA_HIP_ENODEV, "encode_whole: no current device");
+    WholeFork& wf = whole_fork();
+    std::lock_guard<std::mutex> lock(wf.mu);
+    if (!wf.ready(dev))
+        return fail(SELA_HIP_ENODEV, "encode_whole: no side stream");
+    const hipStream_t side = wf.side[dev];
+    // fork: the side stream follows whatever produced d_pcm, and the workspace's previous user, on the caller's stream
+    hipError_t e = hipEventRecord(wf.forked[dev], st);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(side, wf.forked[dev], 0);
+    if (e != hipSuccess)
+        return fail_hip(e, "encode_whole: fork");
+    // the last frame, read in place and coded into the workspace, on the side stream ...
+    rc = encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_last_frame, (size_t)l.last_cap, d_last_offsets, d_last_status, base + l.last_workspace,
+        last_bytes, side, lossless);
+    if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
+        rc = fail_hip(e, "encode_whole: join");
+    // ... beside it the 2048-sample frames, through the plain call's launches, on the caller's ...
+    if (rc == SELA_HIP_OK)
+        rc = encode_device_call(d_pcm, last, channels, d_frames, frames_cap, d_frame_offsets, d_status, base, main_bytes, nullptr, stream, lossless);
+    // ... the join (also after a failure in between: a side stream that has joined a capture must leave it) ...
+    if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
+        rc = fail_hip(e, "encode_whole: join");
+    if (rc != SELA_HIP_OK)
+        return rc;
+    // ... and the last frame behind them
+    return launched(sela::launch_whole_splice(d_last_frame, d_last_offsets, d_last_status, channels, d_frames, frames_cap, d_frame_offsets, last, d_status, st),
+        "encode_whole splice");
+}
+
+// Host pointers: the 2048-sample frames through sela_hip_encode_opt's route, the last frame through the any-length route -- which
+// leases a context of its own and never meets the coalescer -- and, for a thread with a streaming job open, everything there.
+int sela_hip_encode_whole(const int16_t* pcm, uint64_t n_samples, uint32_t channels, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out,
+    uint32_t options)
+{
+    bool lossless = false;
+    int rc = encode_options(options, &lossless);
+    if (rc == SELA_HIP_OK)
+        rc = whole_arguments(n_samples, channels, pcm, frames_out, frame_offsets_out);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
+    frame_offsets_out[0] = 0;
+    if (frames == 0)
+        return SELA_HIP_OK;
+    const uint32_t whole = tail ? frames - 1 : frames; // frames of 2048 samples
+    if (whole) {
+        const bool job_open = g_lease.held && g_lease.held->job_open;
+        rc = job_open ? sela::generic_encode(pcm, true, whole, channels, SELA_HIP_SAMPLES_PER_FRAME, frames_out, frames_cap, frame_offsets_out, lossless)
+                      : sela_hip_encode_opt(pcm, whole, channels, SELA_HIP_SAMPLES_PER_FRAME, frames_out, frames_cap, frame_offsets_out, options);
+        if (rc != SELA_HIP_OK || !tail)
+            return rc;
+    }
+    const uint64_t before = frame_offsets_out[whole];
+    uint64_t last_offsets[2] = { 0, 0 };
+    rc = sela::generic_encode(pcm + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels, true, 1, channels, (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME),
+        frames_out + before, frames_cap - (size_t)before, last_offsets, lossless);
+    frame_offsets_out[whole + 1] = before + last_offsets[1];
+    return rc;
+}
+
 namespace {
 // the fast route: 2048 samples per channel and frame
 int decode_standard(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* pcm_out)
@@ -2747,3 +2906,7 @@ uint32_t sela_hip_index_frames(const uint8_t* frames, size_t frames_bytes, uint3
 }
 
 } // extern "C"
+
+namespace sela {
+void whole_shutdown() { whole_fork().release_all(); }
+} // namespace sela

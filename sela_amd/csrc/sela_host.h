@@ -46,10 +46,22 @@ hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
 
+// ---- sela_whole.hip: a whole track with its tail ---------------------------------------------------------------
+struct WholeLayout { // the workspace of sela_hip_encode_whole_device, offsets from its 256-byte aligned base
+    uint64_t last_workspace; // the last frame's any-length workspace (the 2048-sample frames' workspace opens the whole)
+    uint64_t last_frame, last_cap; // the last frame's bytes as coded, and their room
+    uint64_t last_head;      // its two offsets (uint64) and its four status words
+    size_t bytes;            // all of it; SIZE_MAX for what the call refuses
+};
+WholeLayout whole_layout(uint64_t max_samples, uint32_t channels);
+hipError_t launch_whole_splice(const uint8_t* d_last_frame, const uint64_t* d_last_offsets, const uint32_t* d_last_status, uint32_t channels, uint8_t* d_frames,
+    uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last, uint32_t* d_status, hipStream_t stream);
+
 // ---- sela_capi.hip: what the any-length route's host side shares with the boundary --------------------------------------------
 int report_error(int code, const std::string& what);   // sets the thread's last error, returns code
 int report_hip_error(hipError_t e, const char* where); // (ENOMEM for an allocation failure, ENODEV otherwise)
 int device_ready();                                    // SELA_HIP_OK, or ENODEV reported: there is no CPU fallback
+void whole_shutdown();                                 // sela_hip_encode_whole_device's side streams and events (sela_hip_shutdown)
 inline bool frame_offsets_ascend(const uint64_t* frame_offsets, uint32_t n_frames)
 {
     for (uint32_t f = 0; f < n_frames; f++)
