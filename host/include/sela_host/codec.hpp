@@ -62,7 +62,8 @@ size_t decodeFile(std::ifstream& in, std::ofstream& out);
 size_t encodeFile(const std::string& inPath, const std::string& outPath, bool lossless = false, bool pairChannels = false, bool keepTail = false);
 size_t decodeFile(const std::string& inPath, const std::string& outPath);
 // Samples [startSample, startSample + sampleCount) per channel of a .sela of 2048-sample frames, as a WAV of exactly the samples
-// delivered: only the frames the range touches are copied to the device and decoded (sela_hip_decode_windows).  The count is cut
+// delivered: only the frames the range touches are copied to the device and decoded (sela_hip_decode_windows_whole: the long last
+// frame of a --keep-tail file is part of the stream).  The count is cut
 // at the stream's end; a start at or past the end is a data::Exception, and no file is written then.  Returns the samples per
 // channel written.
 size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, uint64_t startSample, uint64_t sampleCount);

@@ -872,8 +872,10 @@ size_t decodeFile(const std::string& inPath, const std::string& outPath)
 }
 
 // A range of a file's samples: the file is read and indexed as verifyFile does, the range is one window of the whole stream
-// (sela_hip_decode_windows copies and decodes the frames it touches and no others; a range longer than the call's 2^24 samples
-// goes in pieces of that length).  Nothing is created before the samples are there.
+// (sela_hip_decode_windows_whole copies and decodes the frames it touches and no others; a range longer than the call's 2^24
+// samples goes in pieces of that length).  The stream is read as a whole-track stream (sela_hip.h): a last frame that says 1 .. 4095
+// samples and not 2048 -- the tail a --keep-tail encode kept -- ends the stream where it says.  Nothing is created before the
+// samples are there.
 size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, uint64_t startSample, uint64_t sampleCount)
 {
     const SelaInfo info = probeSela(selaPath);
@@ -883,7 +885,13 @@ size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, 
         sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
     std::vector<uint64_t> offsets(info.announced + 1, 0);
     const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
-    const uint64_t streamSamples = (uint64_t)found * kBlock;
+    uint64_t streamSamples = (uint64_t)found * kBlock;
+    if (found) { // the last frame's length by sela_hip_index_samples' rule: its first subframe's samplesPerChannel
+        SelaSubframeHeader last = {};
+        (void)sela_subframe_read_bytes(payload.data() + offsets[found - 1], offsets[found] - offsets[found - 1], 4, &last);
+        if (last.n >= 1 && last.n <= 4095 && last.n != (uint32_t)kBlock)
+            streamSamples = (uint64_t)(found - 1) * kBlock + last.n;
+    }
     if (startSample >= streamSamples)
         throw data::Exception("Decode: --start " + std::to_string(startSample) + " is at or past the end of the stream (" + std::to_string(streamSamples)
             + " samples per channel)");
@@ -892,8 +900,8 @@ size_t decodeFileRange(const std::string& selaPath, const std::string& wavPath, 
     const uint64_t piece = (uint64_t)1 << 24;
     for (uint64_t done = 0; done < count; done += piece) {
         const sela_hip_window window = { startSample + done, 0, found };
-        if (sela_hip_decode_windows(payload.data(), offsets.data(), found, channels, &window, 1, (uint32_t)std::min(piece, count - done), SELA_HIP_WINDOW_I16_INTERLEAVED,
-                pcm.data() + (size_t)done * channels, nullptr)
+        if (sela_hip_decode_windows_whole(payload.data(), offsets.data(), found, channels, &window, 1, (uint32_t)std::min(piece, count - done),
+                SELA_HIP_WINDOW_I16_INTERLEAVED, pcm.data() + (size_t)done * channels, nullptr)
             != SELA_HIP_OK)
             gpuFailure("Decode");
     }

@@ -498,6 +498,40 @@ int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets
     uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out,
     uint32_t* window_flags /* [n_windows] or NULL */);
 
+/* ---- sample windows of whole-track streams: the long last frame too ---------------------------------------------
+ * sela_hip_encode_whole (5.19) writes streams of 2048-sample frames and ONE last frame of 1 .. 4095 samples, which the calls above
+ * refuse.  These take the same arguments and the same descriptor, make the same argument checks in the same order with the same
+ * codes (nothing is enqueued on a refusal), and read a window's stream as a WHOLE-TRACK stream: let n be the stream's frames
+ * inside the table, L the last of them and n_L what L says its length is by sela_hip_index_samples' rule (its first subframe's
+ * samplesPerChannel).  Where n_L is in 1 .. 4095 and not 2048 the stream holds S = 2048 (n - 1) + n_L samples per channel, and output
+ * sample i of window w is
+ *   start + i < 2048 (n - 1):   what sela_hip_decode_windows_device writes, for every input, malformed frames included;
+ *   2048 (n - 1) <= start + i < S:   exactly the int16 sela_hip_decode_n_device writes for sample start + i - 2048 (n - 1) of frame L
+ *                  decoded alone, where its any-length kernel takes the frame (that call's narrowing, its combine rules for
+ *                  difference channels); SELA_HIP_WINDOW_F32_PLANAR holds that value / 32768;
+ *   otherwise:     zero.
+ * A frame L that kernel declines -- not at a word-aligned place, a header the walk refuses, a subframe longer than 4095 samples or
+ * not longer than its order, channels that disagree about the length or a layout the combine refuses, a Rice stream that runs
+ * dry, a coefficient outside the tables -- leaves its share zero and raises a flag in the window's word and in d_status[0]:
+ * SELA_HIP_FLAG_RICE_OVERRUN, _Q_RANGE or _COEF_OVERFLOW where one was met, SELA_HIP_FLAG_BAD_FRAME otherwise.  Nothing outside
+ * the frame's bytes is read.  Where n_L is 2048, 0 or above 4095 every word written (d_out, d_window_flags, d_status) is what
+ * sela_hip_decode_windows_device writes; so is everything for a frame in front of L that does not say 2048.
+ * d_status[1] also counts the (window, L) decodes that raised SELA_HIP_FLAG_BAD_FRAME; d_status[2] counts each window with a
+ * non-zero flag word once.  The device call is asynchronous and capturable as the one above: its launches are shaped by
+ * window_samples, n_windows and channels alone.  Scope: 1 .. 8 channels, 16-bit output, a last frame of at most 4095 samples.
+ *   workspace = sela_hip_decode_windows_workspace_bytes(n_windows, window_samples, channels)
+ *             + n_windows * (48 + channels * (16 + 4 * 4096)) + 1024
+ * (a copy of each descriptor and a record of its share of L; per channel a record and 4096 decoded 32-bit samples; alignment).
+ * The host call stages the covering frames only, L among them for every window that starts at or behind 2048 (n - 1), and returns
+ * what sela_hip_decode_windows returns, `out` and `window_flags` filled in the SELA_HIP_EFORMAT and SELA_HIP_ERANGE cases too. */
+size_t sela_hip_decode_windows_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+int sela_hip_decode_windows_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out,
+    uint32_t* d_window_flags /* [n_windows] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_decode_windows_whole(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out,
+    uint32_t* window_flags /* [n_windows] or NULL */);
+
 /* ---- encode options: the lossless mode ----------------------------------------------------------------------
  * The reference's encoder predicts with (2^34 + sum) >> 35 and its decoder with -((2^34 - sum) >> 35): where 2^34 + sum is a
  * multiple of 2^35 the two differ by one, and the frame does not come back as it went in.  With SELA_HIP_ENCODE_LOSSLESS the

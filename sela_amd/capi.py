@@ -40,6 +40,7 @@ EXPORTS = [
     "sela_hip_encode_device_opt", "sela_hip_encode_n_device_opt", "sela_hip_encode_i32_device_opt", "sela_hip_encode_opt", "sela_hip_encode_i32_opt",
     "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt",
     "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
+    "sela_hip_decode_windows_whole_workspace_bytes", "sela_hip_decode_windows_whole_device", "sela_hip_decode_windows_whole",
     "sela_hip_paired_signals_per_frame", "sela_hip_encode_paired_workspace_bytes", "sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device",
     "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
     "sela_hip_whole_frames", "sela_hip_whole_frame", "sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes",
@@ -162,6 +163,12 @@ def lib() -> C.CDLL:
     L.sela_hip_decode_windows_device.restype = C.c_int
     L.sela_hip_decode_windows.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp]
     L.sela_hip_decode_windows.restype = C.c_int
+    L.sela_hip_decode_windows_whole_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_windows_whole_workspace_bytes.restype = sz
+    L.sela_hip_decode_windows_whole_device.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_windows_whole_device.restype = C.c_int
+    L.sela_hip_decode_windows_whole.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp]
+    L.sela_hip_decode_windows_whole.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]

@@ -372,9 +372,11 @@ class WindowDecoder:
     """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
     device memory -- only the frames a window touches are decoded.  Owns its output, flags, status and workspace
     on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  planar_float:
-    float32 [n, channels, window_samples] holding value / 32768 instead of int16 [n, window_samples, channels]."""
+    float32 [n, channels, window_samples] holding value / 32768 instead of int16 [n, window_samples, channels].  whole:
+    sela_hip_decode_windows_whole_device -- the streams are whole-track streams, whose last frame of 1 .. 4095
+    samples is decoded too."""
 
-    def __init__(self, max_windows: int, window_samples: int, channels: int, planar_float: bool = False, device=None):
+    def __init__(self, max_windows: int, window_samples: int, channels: int, planar_float: bool = False, device=None, whole: bool = False):
         import torch
 
         self.torch = torch
@@ -382,6 +384,7 @@ class WindowDecoder:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_windows, self.window_samples, self.channels = max_windows, window_samples, channels
         self.format = capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED
+        self.call = self.lib.sela_hip_decode_windows_whole_device if whole else self.lib.sela_hip_decode_windows_device
         with torch.cuda.device(self.device):
             if planar_float:
                 self.out = torch.empty((max_windows, channels, window_samples), dtype=torch.float32, device=self.device)
@@ -389,7 +392,8 @@ class WindowDecoder:
                 self.out = torch.empty((max_windows, window_samples, channels), dtype=torch.int16, device=self.device)
             self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
             self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_decode_windows_workspace_bytes(max_windows, window_samples, channels))
+            sizing = self.lib.sela_hip_decode_windows_whole_workspace_bytes if whole else self.lib.sela_hip_decode_windows_workspace_bytes
+            ws = int(sizing(max_windows, window_samples, channels))
             self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.n_windows = 0
 
@@ -416,7 +420,7 @@ class WindowDecoder:
         n = int(windows.shape[0])
         assert n <= self.max_windows
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(self.lib.sela_hip_decode_windows_device(
+        capi.check(self.call(
             frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format,
             self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
         self.n_windows = n
@@ -437,8 +441,9 @@ class WindowDecoder:
         capi.check(decode_n_status_error(st))
 
 
-def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, planar_float: bool = False):
-    """sela_hip_decode_windows on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
+def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, planar_float: bool = False,
+                        whole: bool = False):
+    """sela_hip_decode_windows (whole: sela_hip_decode_windows_whole) on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
     (int16 [n, window_samples, channels], or float32 [n, channels, window_samples]), the per-window flags (uint32 [n]) and the
     call's return code -- 0, or EFORMAT / ERANGE (capi.ERRORS) for a batch with a bad frame, whose other windows are good all
     the same; any other code raises."""
@@ -449,8 +454,9 @@ def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, 
     n = len(win)
     out = np.zeros((n, channels, window_samples), np.float32) if planar_float else np.zeros((n, window_samples, channels), np.int16)
     flags = np.zeros(n, np.uint32)
-    rc = lib.sela_hip_decode_windows(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples,
-                                     capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED, out.ctypes.data, flags.ctypes.data)
+    call = lib.sela_hip_decode_windows_whole if whole else lib.sela_hip_decode_windows
+    rc = call(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED,
+              out.ctypes.data, flags.ctypes.data)
     if rc not in (capi.OK, -5, -6):
         capi.check(rc)
     return out, flags, rc

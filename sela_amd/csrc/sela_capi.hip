@@ -1673,12 +1673,14 @@ int verify_call(const Form& form, uint32_t channels, uint32_t stride, const int1
 // is sized by the windows and not by the table, so its formula is sela_hip_decode_windows_workspace_bytes itself, closed over
 // the call's own arguments (the form asks it only after the check has passed them); the call has no stride.
 int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
-    void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+    void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, bool whole /* 5.20: the same checks, the long last frame's kernels behind */)
 {
     const bool shaped = window_samples >= 1 && window_samples <= (1u << 24);
     const uint64_t groups = shaped ? (uint64_t)n_windows * sela::window_cover(window_samples) : 0;
-    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) { return sela::window_workspace_bytes(n_windows, window_samples, channels); };
-    const DeviceCallOf<decltype(formula)> c = { "decode_windows", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) {
+        return whole ? sela::window_whole_workspace_bytes(n_windows, window_samples, channels) : sela::window_workspace_bytes(n_windows, window_samples, channels);
+    };
+    const DeviceCallOf<decltype(formula)> c = { whole ? "decode_windows_whole" : "decode_windows", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
     return form(
         c,
         [&](uint32_t) {
@@ -1697,8 +1699,9 @@ int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_windo
         },
         [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const uint32_t*, void* d_ws) {
             return launch_with_priorities((uint32_t)groups, stream, "decode_windows launch", [&](uint32_t synth_priorities) {
-                return sela::launch_window_frames(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows, window_samples, format, d_out, d_window_flags,
-                    d_status, d_ws, c.stream, g_recurrence_form, synth_priorities);
+                const auto launch = whole ? sela::launch_window_whole : sela::launch_window_frames;
+                return launch(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows,
+                    window_samples, format, d_out, d_window_flags, d_status, d_ws, c.stream, g_recurrence_form, synth_priorities);
             });
         });
 }
@@ -1942,13 +1945,27 @@ int sela_hip_decode_windows_device(const uint8_t* d_frames, const uint64_t* d_fr
     void* d_workspace, size_t workspace_bytes, void* stream)
 {
     return windows_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, d_out, d_window_flags, d_status,
-        d_workspace, workspace_bytes, stream);
+        d_workspace, workspace_bytes, stream, false);
+}
+
+// The same call for whole-track streams (5.20): a last frame of 1 .. 4095 samples is decoded by the any-length kernels.
+size_t sela_hip_decode_windows_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+{
+    return sela::window_whole_workspace_bytes(n_windows, window_samples, channels);
+}
+
+int sela_hip_decode_windows_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels,
+    const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return windows_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, d_out, d_window_flags, d_status,
+        d_workspace, workspace_bytes, stream, true);
 }
 
 // Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows (sela_capi_generic.hip) on the
 // any-length route's leased context and stream, past the coalescer; an open streaming job of the thread is left alone.
-int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
-    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags)
+static int windows_host_call(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, bool whole)
 {
     sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
     if (channels == 0 || channels > 8)
@@ -1964,7 +1981,19 @@ int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets
     if (n_windows == 0)
         return SELA_HIP_OK;
     return sela::generic_decode_windows(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags,
-        g_recurrence_form);
+        g_recurrence_form, whole);
+}
+
+int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags)
+{
+    return windows_host_call(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags, false);
+}
+
+int sela_hip_decode_windows_whole(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags)
+{
+    return windows_host_call(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags, true);
 }
 
 size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)

@@ -45,6 +45,13 @@ size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint3
 hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
+uint32_t* window_flag_words(void* d_workspace, uint32_t n_windows, uint32_t window_samples, uint32_t channels); // of a call without d_window_flags
+
+// ---- sela_window_whole.hip: windows that reach a whole-track stream's long last frame --------------------------
+size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
+    int recurrence_form, uint32_t synth_priorities);
 
 // ---- sela_whole.hip: a whole track with its tail ---------------------------------------------------------------
 struct WholeLayout { // the workspace of sela_hip_encode_whole_device, offsets from its 256-byte aligned base
@@ -110,7 +117,8 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
 int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
-    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form);
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form,
+    bool whole = false /* plan_windows_whole and launch_window_whole */);
 void windows_staged_bytes_reset(); // sela_hip_debug_windows_staged_bytes of the calling thread back to 0: the entry point's first act
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out);
 int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);

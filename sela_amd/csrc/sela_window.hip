@@ -149,6 +149,12 @@ size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint3
 {
     return window_residue_bytes(n_windows, window_samples, channels) + (size_t)n_windows * sizeof(uint32_t) + 256;
 }
+// Where a call that passes no d_window_flags keeps them (launch_window_whole's kernels raise flags in the same words).
+uint32_t* window_flag_words(void* d_workspace, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+{
+    unsigned char* const ws = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    return reinterpret_cast<uint32_t*>(ws + window_residue_bytes(n_windows, window_samples, channels));
+}
 
 // Clear, then decode: one serial chain on the caller's stream, capturable.  The arguments have been checked (sela_capi.hip).
 hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
@@ -163,7 +169,7 @@ hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame
         return hipErrorInvalidValue;
     const uint32_t cover = window_cover(window_samples);
     unsigned char* const ws = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    uint32_t* const flags = d_window_flags ? d_window_flags : reinterpret_cast<uint32_t*>(ws + window_residue_bytes(n_windows, window_samples, channels));
+    uint32_t* const flags = d_window_flags ? d_window_flags : window_flag_words(d_workspace, n_windows, window_samples, channels);
     hipLaunchKernelGGL(k_window_clear, dim3((n_windows + kWindowClearThreads - 1) / kWindowClearThreads), dim3(kWindowClearThreads), 0, stream, d_status, flags, n_windows);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess)

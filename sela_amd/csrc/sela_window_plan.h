@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sela_hip.h"
+#include "sela_window_tail.h"
 
 namespace sela {
 
@@ -40,13 +41,16 @@ inline bool window_covering_frames(const sela_hip_window& w, uint32_t n_frames_t
     return true;
 }
 
-inline void plan_windows(const uint64_t* frame_offsets, uint32_t n_frames_total, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples,
-    WindowPlan* plan)
+// The plan for a rule that says which frames a window covers and where it starts among them:
+// cover(window, &a, &b, &start) -> false for a window that touches nothing.
+template <typename Cover>
+inline void plan_windows_by(const uint64_t* frame_offsets, uint32_t n_frames_total, const sela_hip_window* windows, uint32_t n_windows, WindowPlan* plan, Cover cover)
 {
     std::vector<uint32_t> map((size_t)n_frames_total + 1, 0); // first a mark per frame, then the frame's place in the compacted table
     for (uint32_t i = 0; i < n_windows; i++) {
         uint32_t a, b;
-        if (window_covering_frames(windows[i], n_frames_total, window_samples, &a, &b))
+        uint64_t start;
+        if (cover(windows[i], &a, &b, &start))
             for (uint32_t f = a; f < b; f++)
                 map[f] = 1;
     }
@@ -63,15 +67,63 @@ inline void plan_windows(const uint64_t* frame_offsets, uint32_t n_frames_total,
     plan->windows.resize(n_windows);
     for (uint32_t i = 0; i < n_windows; i++) {
         uint32_t a, b;
+        uint64_t start;
         sela_hip_window& out = plan->windows[i];
-        if (window_covering_frames(windows[i], n_frames_total, window_samples, &a, &b)) {
-            out.start = windows[i].start % SELA_HIP_SAMPLES_PER_FRAME; // = start - 2048 * (a - first_frame)
+        if (cover(windows[i], &a, &b, &start)) {
+            out.start = start;
             out.first_frame = map[a];
             out.n_frames = b - a;
         } else {
             out.start = 0, out.first_frame = 0, out.n_frames = 0; // an empty stream: zeros
         }
     }
+}
+
+inline void plan_windows(const uint64_t* frame_offsets, uint32_t n_frames_total, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples,
+    WindowPlan* plan)
+{
+    plan_windows_by(frame_offsets, n_frames_total, windows, n_windows, plan, [&](const sela_hip_window& w, uint32_t* a, uint32_t* b, uint64_t* start) {
+        *start = w.start % SELA_HIP_SAMPLES_PER_FRAME; // = start - 2048 * (a - first_frame)
+        return window_covering_frames(w, n_frames_total, window_samples, a, b);
+    });
+}
+
+// ---- whole-track streams: sela_hip_decode_windows_whole --------------------------------------------------------
+// The device call takes the LAST frame of a descriptor's stream for the long one when it says 1 .. 4095 samples and not 2048
+// (frame_says_samples on the host's bytes here, on the staged ones there).  So, for a stream of n frames inside the table whose
+// last frame L says such a length:
+//   * a window with start / 2048 >= n - 1 covers L and nothing else -- not nothing, as it would among 2048-sample frames;
+//     start' = start - 2048 (n - 1), any uint64;
+//   * every other window covers what it covered, L included where it reaches it.
+// A compacted stream that ends in front of L ends on one of the 2048-sample run, which the device must not take for a long last
+// frame: where such a frame says 1 .. 4095 and not 2048 (a malformed stream), the frame behind it is staged too and the compacted
+// stream ends on that one, outside the window.
+inline bool window_covering_frames_whole(const uint8_t* frames, const uint64_t* frame_offsets, const sela_hip_window& w, uint32_t n_frames_total,
+    uint32_t window_samples, uint32_t* a, uint32_t* b, uint64_t* start)
+{
+    const uint32_t n = window_stream_frames(w, n_frames_total);
+    if (window_samples == 0 || n == 0)
+        return false;
+    const uint32_t last = w.first_frame + n - 1;
+    if (w.start / SELA_HIP_SAMPLES_PER_FRAME >= n - 1 && tail_length(frame_says_samples(frames, frame_offsets, last))) {
+        *a = last, *b = last + 1;
+        *start = w.start - (uint64_t)SELA_HIP_SAMPLES_PER_FRAME * (n - 1);
+        return true;
+    }
+    if (!window_covering_frames(w, n_frames_total, window_samples, a, b))
+        return false;
+    *start = w.start % SELA_HIP_SAMPLES_PER_FRAME;
+    if (*b <= last && tail_length(frame_says_samples(frames, frame_offsets, *b - 1)))
+        (*b)++;
+    return true;
+}
+
+inline void plan_windows_whole(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, const sela_hip_window* windows, uint32_t n_windows,
+    uint32_t window_samples, WindowPlan* plan)
+{
+    plan_windows_by(frame_offsets, n_frames_total, windows, n_windows, plan, [&](const sela_hip_window& w, uint32_t* a, uint32_t* b, uint64_t* start) {
+        return window_covering_frames_whole(frames, frame_offsets, w, n_frames_total, window_samples, a, b, start);
+    });
 }
 
 } // namespace sela
