@@ -53,6 +53,8 @@
 
 #include "sela_host.h"
 
+#include "sela_synth.h"
+
 namespace sela {
 
 #include "sela_decode_core.inc" // the parser, the synthesis, the header walk: shared with sela_decode32.hip

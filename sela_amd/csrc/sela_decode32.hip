@@ -7,6 +7,8 @@
 
 #include "sela_host.h"
 
+#include "sela_synth.h"
+
 namespace sela {
 
 #include "sela_decode_core.inc"

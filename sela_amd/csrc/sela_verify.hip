@@ -19,6 +19,8 @@
 // Per frame: diff_count[f], first_diff[f] (0xFFFFFFFF: nothing differs); status[2] counts the frames with a difference.
 #include "sela_host.h"
 
+#include "sela_synth.h"
+
 namespace sela {
 
 #include "sela_decode_core.inc"

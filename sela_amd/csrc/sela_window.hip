@@ -28,6 +28,8 @@
 // global output, which a clipped store does not have; streams of any other length need a search of sample_offsets).
 #include "sela_host.h"
 
+#include "sela_synth.h"
+
 namespace sela {
 
 #include "sela_decode_core.inc"

@@ -30,6 +30,8 @@
 #include "sela_host.h"
 #include "sela_window_tail.h"
 
+#include "sela_synth.h"
+
 namespace sela {
 
 #include "sela_decode_core.inc"
