@@ -123,6 +123,22 @@ size_t sela_hip_debug_window_lds_bytes(uint32_t channels);
  * the summed sizes of the distinct frames its windows touched (0 before the first call, and for a call that failed before it
  * staged anything). */
 uint64_t sela_hip_debug_windows_staged_bytes(void);
+/* Test hook (no device needed): the pieces a device-pointer call cuts its workspace into, from the description its launch and its
+ * *_workspace_bytes function both run (sela_amd/csrc/sela_workspace.h).  Writes up to `capacity` pairs (offset from the workspace
+ * pointer aligned up to 256, bytes) in the order the pieces are taken -- a workspace that holds another call's lists that call's
+ * own pieces where they lie -- and returns how many there are; -1 for a `call` it does not know and for a shape whose sizing
+ * function returns SIZE_MAX.  The shape, as the call's sizing function takes it:
+ *   ENCODE, DECODE: a = n_frames, b = channels            INDEX: a = payload_bytes
+ *   DECODE_I32, DECODE_N, VERIFY, VERIFY_I32: a = max_frames, b = channels, c = stride
+ *   ENCODE_I32, ENCODE_PAIRED: a = n_frames, b = channels, c = samples_per_channel
+ *   WINDOWS, WINDOWS_WHOLE: a = n_windows, b = window_samples, c = channels      ENCODE_WHOLE: a = max_samples, b = channels
+ *   ENCODE_SPLIT (a launch that sela_hip_debug_encode_split cuts in two): a = n_frames, b = channels, c = frames of the first half */
+enum {
+    SELA_HIP_WORKSPACE_ENCODE = 0, SELA_HIP_WORKSPACE_DECODE, SELA_HIP_WORKSPACE_INDEX, SELA_HIP_WORKSPACE_DECODE_I32, SELA_HIP_WORKSPACE_DECODE_N,
+    SELA_HIP_WORKSPACE_VERIFY, SELA_HIP_WORKSPACE_VERIFY_I32, SELA_HIP_WORKSPACE_ENCODE_I32, SELA_HIP_WORKSPACE_ENCODE_PAIRED, SELA_HIP_WORKSPACE_WINDOWS,
+    SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT
+};
+int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
 
 #ifdef __cplusplus
 }

@@ -56,7 +56,11 @@ DEBUG_EXPORTS = [
     "sela_hip_debug_phase_buffer", "sela_hip_debug_force_plain_fir", "sela_hip_debug_mean_workers", "sela_hip_debug_encode_teams", "sela_hip_debug_encode_kernel", "sela_hip_debug_encode_fused", "sela_hip_debug_priorities", "sela_hip_debug_priorities_adaptive", "sela_hip_debug_launches_alone", "sela_hip_debug_block_forms", "sela_hip_debug_encode_hashes", "sela_hip_debug_standard_first", "sela_hip_debug_standard_chunks", "sela_hip_debug_segment_subframes", "sela_hip_debug_generic_wrap_taps", "sela_hip_debug_encode_split", "sela_hip_debug_launches_split", "sela_hip_debug_keep_both_candidates", "sela_hip_debug_stage_wait",
     "sela_hip_debug_reissued_feeds", "sela_hip_debug_contexts_created", "sela_hip_debug_decode_recurrence", "sela_hip_debug_coalesced", "sela_hip_debug_verify_lds_bytes",
     "sela_hip_debug_verify_i32_fallback_frames", "sela_hip_debug_window_lds_bytes", "sela_hip_debug_windows_staged_bytes",
+    "sela_hip_debug_workspace_pieces",
 ]
+# `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
+WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
+                   "encode_whole", "encode_split")
 
 
 class Trace(C.Structure):
@@ -287,6 +291,8 @@ def lib() -> C.CDLL:
     L.sela_hip_debug_window_lds_bytes.restype = sz
     L.sela_hip_debug_windows_staged_bytes.argtypes = []
     L.sela_hip_debug_windows_staged_bytes.restype = C.c_uint64
+    L.sela_hip_debug_workspace_pieces.argtypes = [C.c_int, u64, u32, u32, u64p, C.c_int]
+    L.sela_hip_debug_workspace_pieces.restype = C.c_int
     L.sela_hip_host_alloc.argtypes = [sz]
     L.sela_hip_host_alloc.restype = C.c_void_p
     L.sela_hip_host_free.argtypes = [C.c_void_p]
@@ -311,6 +317,18 @@ def kernel_times(capacity: int = 4):
     buf = (C.c_float * capacity)()
     n = lib().sela_hip_kernel_times(buf, capacity)
     return [float(buf[i]) for i in range(n)]
+
+
+def workspace_pieces(call: str, a: int, b: int = 0, c: int = 0):
+    """The (offset, bytes) of every piece the named call (WORKSPACE_CALLS) cuts its workspace into, or None where its sizing
+    function refuses the shape.  No device (sela_hip_debug_workspace_pieces)."""
+    which = WORKSPACE_CALLS.index(call)
+    n = lib().sela_hip_debug_workspace_pieces(which, a, b, c, None, 0)
+    if n < 0:
+        return None
+    buf = (C.c_uint64 * (2 * n))()
+    assert lib().sela_hip_debug_workspace_pieces(which, a, b, c, C.addressof(buf), n) == n
+    return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
 
 
 def check(rc: int) -> None:

@@ -1117,7 +1117,20 @@ Splitter& splitter()
 }
 std::atomic<int> g_encode_split{ 0 };    // debug (sela_hip_debug_encode_split): 0 never (the product), 1..999: every launch of teams of 16, that share to the first half
 std::atomic<int> g_launches_split{ 0 };
-size_t second_half_offset(uint32_t first, uint32_t channels) { return (sela::encode_workspace_bytes(first, channels) + 255) & ~(size_t)255; }
+// The workspace of a launch cut in two: the first half's, the second half's (each launch_encode's own, sela_workspace.h).
+struct SplitWs {
+    void *first, *second;
+    size_t end; // what both need of the caller's workspace
+};
+SplitWs carve_encode_split(sela::Carve& c, uint32_t first, uint32_t rest, uint32_t channels)
+{
+    sela::Carve a = c.sub(sela::encode_workspace_bytes(first, channels)), b = c.sub(sela::encode_workspace_bytes(rest, channels));
+    if (c.listing()) { // (the halves' own pieces, where they lie)
+        sela::encode_workspace_bytes(first, channels, &a);
+        sela::encode_workspace_bytes(rest, channels, &b);
+    }
+    return { a.base(), b.base(), (size_t)c.end() };
+}
 uint32_t split_of_last_launch(const void* d_workspace, uint32_t n_frames)
 {
     std::lock_guard<std::mutex> lock(splitter().mu);
@@ -1235,10 +1248,15 @@ int sela_hip_debug_block_forms(const void* d_workspace, uint32_t n_frames, uint3
     const size_t n_sig = sela_hip_signals_per_frame(channels);
     if (e == hipSuccess && blocks) {
         const size_t head = first ? (size_t)first * n_sig : blocks;
-        e = hipMemcpy(meta.data(), reinterpret_cast<const void*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255), head * sizeof(sela::BlockMeta), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && first) {
-            const uint8_t* second = static_cast<const uint8_t*>(d_workspace) + second_half_offset(first, channels);
-            e = hipMemcpy(meta.data() + head, reinterpret_cast<const void*>(((uintptr_t)second + 255) & ~(uintptr_t)255), (blocks - head) * sizeof(sela::BlockMeta), hipMemcpyDeviceToHost);
+        if (!first)
+            e = hipMemcpy(meta.data(), sela::encode_block_records(d_workspace, n_frames, channels), blocks * sizeof(sela::BlockMeta), hipMemcpyDeviceToHost);
+        else {
+            sela::Carve c(d_workspace);
+            const SplitWs halves = carve_encode_split(c, first, n_frames - first, channels);
+            e = hipMemcpy(meta.data(), sela::encode_block_records(halves.first, first, channels), head * sizeof(sela::BlockMeta), hipMemcpyDeviceToHost);
+            if (e == hipSuccess)
+                e = hipMemcpy(meta.data() + head, sela::encode_block_records(halves.second, n_frames - first, channels), (blocks - head) * sizeof(sela::BlockMeta),
+                    hipMemcpyDeviceToHost);
         }
     }
     if (e != hipSuccess)
@@ -1318,10 +1336,12 @@ int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channel
     const uint32_t priorities = launch_priorities(st, dev);
     // cut in two?  (see Splitter)
     uint32_t first = 0;
+    SplitWs halves = {};
     const int split_mode = g_encode_split.load(std::memory_order_relaxed);
     if (dev >= 0 && n_frames && split_mode > 0 && !ev && !d_trace && !g_phase_cycles && !use_fused && g_team_lanes < 0 && !stream_is_capturing(st)) {
         first = sela::encode_split_frames(n_frames, channels, split_mode);
-        if (first && second_half_offset(first, channels) + sela::encode_workspace_bytes(n_frames - first, channels) > workspace_bytes)
+        sela::Carve c(d_workspace);
+        if (first && (halves = carve_encode_split(c, first, n_frames - first, channels)).end > workspace_bytes)
             first = 0;
     }
     hipError_t e = hipSuccess;
@@ -1331,7 +1351,7 @@ int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channel
         std::unique_lock<std::mutex> lock(sp.mu, std::try_to_lock); // (one split launch at a time per process: a second caller is not alone anyway)
         if (lock.owns_lock() && sp.ready(dev)) {
             const uint32_t rest = n_frames - first;
-            void* const ws2 = static_cast<uint8_t*>(d_workspace) + second_half_offset(first, channels);
+            void* const ws2 = halves.second;
             const int16_t* const pcm2 = d_pcm + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels;
             const hipStream_t side = sp.side[dev];
             e = hipEventRecord(sp.begun[dev], st);
@@ -1452,6 +1472,18 @@ int decode_device_launch(const uint8_t* d_frames, const uint64_t* d_frame_offset
 
 int launched(hipError_t e, const char* what) { return e == hipSuccess ? SELA_HIP_OK : fail_hip(e, what); }
 
+// A payload call's workspace: the index's, then the call's own, each its launch's own description (sela_workspace.h).
+struct PayloadWs {
+    void* own;
+    size_t end; // what both need of the caller's workspace
+};
+PayloadWs carve_payload(void* d_workspace, size_t payload_bytes, size_t own_bytes)
+{
+    sela::Carve c(d_workspace);
+    c.sub(sela::index_workspace_bytes(payload_bytes)); // (launch_index is given d_workspace itself: the same base)
+    return { c.sub(own_bytes).base(), (size_t)c.end() };
+}
+
 // the index's own checks (sela_hip_index_frames_device); SELA_HIP_OK or the failure, reported
 int check_index_args(const uint8_t* d_payload, size_t payload_bytes, uint32_t channels, const uint64_t* d_frame_offsets, const uint32_t* d_n_frames,
     const void* d_workspace)
@@ -1513,15 +1545,14 @@ int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_byte
         return fail(SELA_HIP_EINVAL, "too many channels for the on-chip decoder (sela_hip_decode_max_channels)");
     if (!d_status || (max_frames && !d_pcm_out))
         return fail(SELA_HIP_EINVAL, "null device pointer");
-    const size_t index_bytes = sela::index_workspace_bytes(payload_bytes);
-    if (workspace_bytes < index_bytes + sela::decode_workspace_bytes(max_frames, channels))
+    const PayloadWs ws = carve_payload(d_workspace, payload_bytes, sela::decode_workspace_bytes(max_frames, channels));
+    if (workspace_bytes < ws.end)
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_decode_workspace_bytes()");
     const hipError_t e = sela::launch_index(d_payload, payload_bytes, max_frames, channels, d_frame_offsets, d_n_frames, d_workspace,
         static_cast<hipStream_t>(stream));
     if (e != hipSuccess)
         return fail_hip(e, "index launch");
-    return decode_device_launch(d_payload, d_frame_offsets, max_frames, channels, d_pcm_out, d_status,
-        static_cast<unsigned char*>(d_workspace) + index_bytes, stream, d_n_frames);
+    return decode_device_launch(d_payload, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, ws.own, stream, d_n_frames);
 }
 
 // ---- the decode and verify calls of any length on device pointers, each in two forms ---------------
@@ -1583,13 +1614,14 @@ struct PayloadForm {
             rc = check(max_frames);
         if (rc != SELA_HIP_OK)
             return rc;
-        const size_t index_bytes = sela::index_workspace_bytes(payload_bytes), own_bytes = c.workspace_bytes(max_frames, c.channels, c.stride);
-        if (own_bytes == SIZE_MAX || c.capacity < index_bytes + own_bytes)
+        const size_t own_bytes = c.workspace_bytes(max_frames, c.channels, c.stride);
+        const PayloadWs ws = carve_payload(c.d_workspace, payload_bytes, own_bytes == SIZE_MAX ? 0 : own_bytes);
+        if (own_bytes == SIZE_MAX || c.capacity < ws.end)
             return fail(SELA_HIP_ECAPACITY, std::string("workspace smaller than sela_hip_index_workspace_bytes() + sela_hip_") + c.name + "_workspace_bytes()");
         rc = launched(sela::launch_index(d_payload, payload_bytes, max_frames, c.channels, d_frame_offsets, d_n_frames, c.d_workspace, c.stream), "index launch");
         if (rc != SELA_HIP_OK)
             return rc;
-        return launch(d_payload, d_frame_offsets, max_frames, d_n_frames, static_cast<unsigned char*>(c.d_workspace) + index_bytes);
+        return launch(d_payload, d_frame_offsets, max_frames, d_n_frames, ws.own);
     }
 };
 
@@ -2043,12 +2075,43 @@ long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uin
 {
     if (!d_workspace || sela::verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
         return -1;
-    const unsigned char* const base = reinterpret_cast<const unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
     uint32_t left = 0;
     if (hipDeviceSynchronize() != hipSuccess
-        || hipMemcpy(&left, base + sela::verify_i32_ctl_offset(max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
+        || hipMemcpy(&left, sela::verify_i32_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
     return (long long)left;
+}
+
+// Test hook (include/sela_hip_debug.h): the pieces of a call's workspace, from the description its launch runs.  No device.
+int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity)
+{
+    sela::CarvePieces pieces = { offset_bytes_pairs, offset_bytes_pairs && capacity > 0 ? capacity : 0, 0 };
+    sela::Carve at(&pieces);
+    const uint32_t a32 = (uint32_t)a;
+    size_t bytes = SIZE_MAX;
+    if (call != SELA_HIP_WORKSPACE_INDEX && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE && a > 0xFFFFFFFFull)
+        return -1;
+    switch (call) {
+    case SELA_HIP_WORKSPACE_ENCODE: bytes = sela::encode_workspace_bytes(a32, b, &at); break;
+    case SELA_HIP_WORKSPACE_DECODE: bytes = sela::decode_workspace_bytes(a32, b, &at); break;
+    case SELA_HIP_WORKSPACE_INDEX: bytes = sela::index_workspace_bytes(a, &at); break;
+    case SELA_HIP_WORKSPACE_DECODE_I32: bytes = sela::decode_i32_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_DECODE_N: bytes = sela::decode_n_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_VERIFY: bytes = sela::verify_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_VERIFY_I32: bytes = sela::verify_i32_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_ENCODE_I32: bytes = sela::encode_i32_device_workspace_bytes(a32, b, c, false, &at); break;
+    case SELA_HIP_WORKSPACE_ENCODE_PAIRED: bytes = sela::encode_i32_device_workspace_bytes(a32, b, c, true, &at); break;
+    case SELA_HIP_WORKSPACE_WINDOWS: bytes = sela::window_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_WINDOWS_WHOLE: bytes = sela::window_whole_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_ENCODE_WHOLE: bytes = sela::whole_workspace_bytes(a, b, &at); break;
+    case SELA_HIP_WORKSPACE_ENCODE_SPLIT:
+        if (c == 0 || c >= a32)
+            return -1;
+        bytes = carve_encode_split(at, c, a32 - c, b).end;
+        break;
+    default: return -1;
+    }
+    return bytes == SIZE_MAX ? -1 : pieces.count;
 }
 
 // ---- streaming jobs (host pointers) ----------------------------------------------------------------------------
@@ -2385,26 +2448,25 @@ int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint3
         return fail(SELA_HIP_EINVAL, "null pointer");
     if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
         return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
-    const sela::WholeLayout l = sela::whole_layout(n_samples, channels);
-    if (workspace_bytes < l.bytes)
+    if (workspace_bytes < sela::whole_workspace_bytes(n_samples, channels))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_whole_workspace_bytes()");
     if (lossless && g_phase_cycles)
         return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS while sela_hip_debug_phase_buffer is set: the phase counts are the plain kernels'");
     const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
-    uint8_t* const base = reinterpret_cast<uint8_t*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    const size_t main_bytes = (size_t)l.last_workspace, last_bytes = (size_t)(l.last_frame - l.last_workspace);
+    sela::Carve carve(d_workspace);
+    const sela::WholeWs w = sela::carve_whole(carve, n_samples, channels);
     if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
-        return encode_i32_device_call(d_pcm, true, 0, channels, 1, d_frames, frames_cap, d_frame_offsets, d_status, base + l.last_workspace, last_bytes, stream, lossless);
+        return encode_i32_device_call(d_pcm, true, 0, channels, 1, d_frames, frames_cap, d_frame_offsets, d_status, w.last_workspace, w.last_bytes, stream, lossless);
     if (tail == 0) // whole frames only: the plain call, its bytes and offsets
-        return encode_device_call(d_pcm, frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, base, main_bytes, nullptr, stream, lossless);
+        return encode_device_call(d_pcm, frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, w.main_workspace, w.main_bytes, nullptr, stream, lossless);
     const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
     const int16_t* const d_last_pcm = d_pcm + (size_t)last * SELA_HIP_SAMPLES_PER_FRAME * channels;
     if (last == 0) // one frame, of up to 4095 samples: the any-length call as it stands
-        return encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_frames, frames_cap, d_frame_offsets, d_status, base + l.last_workspace, last_bytes, stream,
+        return encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_frames, frames_cap, d_frame_offsets, d_status, w.last_workspace, w.last_bytes, stream,
             lossless);
-    uint8_t* const d_last_frame = base + l.last_frame;
-    uint64_t* const d_last_offsets = reinterpret_cast<uint64_t*>(base + l.last_head);
-    uint32_t* const d_last_status = reinterpret_cast<uint32_t*>(base + l.last_head + 16);
+    uint8_t* const d_last_frame = w.last_frame;
+    uint64_t* const d_last_offsets = w.last_offsets;
+    uint32_t* const d_last_status = w.last_status;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
@@ -2421,13 +2483,13 @@ int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint3
     if (e != hipSuccess)
         return fail_hip(e, "encode_whole: fork");
     // the last frame, read in place and coded into the workspace, on the side stream ...
-    rc = encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_last_frame, (size_t)l.last_cap, d_last_offsets, d_last_status, base + l.last_workspace,
-        last_bytes, side, lossless);
+    rc = encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_last_frame, w.last_cap, d_last_offsets, d_last_status, w.last_workspace, w.last_bytes,
+        side, lossless);
     if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
         rc = fail_hip(e, "encode_whole: join");
     // ... beside it the 2048-sample frames, through the plain call's launches, on the caller's ...
     if (rc == SELA_HIP_OK)
-        rc = encode_device_call(d_pcm, last, channels, d_frames, frames_cap, d_frame_offsets, d_status, base, main_bytes, nullptr, stream, lossless);
+        rc = encode_device_call(d_pcm, last, channels, d_frames, frames_cap, d_frame_offsets, d_status, w.main_workspace, w.main_bytes, nullptr, stream, lossless);
     // ... the join (also after a failure in between: a side stream that has joined a capture must leave it) ...
     if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
         rc = fail_hip(e, "encode_whole: join");

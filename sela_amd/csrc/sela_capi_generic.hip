@@ -23,22 +23,24 @@
 
 namespace {
 
+using sela::Carve;
 using sela::GenericMeta;
 using sela::GenericSubInfo;
 
 struct Arena { // one device allocation, handed out in aligned pieces for the length of a call
     uint8_t* base = nullptr;
-    size_t cap = 0, used = 0;
-    bool fits() const { return used <= cap; } // (asked after the pieces are taken: the callers' size estimates are checked, not trusted)
+    size_t cap = 0;
+    Carve carve; // the pieces of the call in hand (sela_workspace.h), from `base`: hipMalloc's alignment is the carve's
+    bool fits() const { return carve.end() <= cap; } // (asked after the pieces are taken: the callers' size estimates are checked, not trusted)
     void release()
     {
         if (base)
             (void)hipFree(base);
-        base = nullptr, cap = used = 0;
+        base = nullptr, cap = 0, carve = Carve();
     }
     hipError_t reserve(size_t bytes)
     {
-        used = 0;
+        carve = Carve(base);
         if (base && bytes <= cap)
             return hipSuccess;
         release();
@@ -51,15 +53,11 @@ struct Arena { // one device allocation, handed out in aligned pieces for the le
             return e;
         }
         cap = want;
+        carve = Carve(base);
         return hipSuccess;
     }
     template <typename T>
-    T* take(size_t count)
-    {
-        const size_t at = (used + 255) & ~(size_t)255;
-        used = at + std::max<size_t>(count, 1) * sizeof(T);
-        return reinterpret_cast<T*>(base + at);
-    }
+    T* take(size_t count) { return carve.take<T>(std::max<size_t>(count, 1)); }
 };
 
 // What a calling thread needs on a device: scratch and a stream of its own (threads that code a frame at a time through the
@@ -286,7 +284,7 @@ int generic_encode(const void* input, bool in16, uint32_t n_frames, uint32_t cha
             }
         } else { // (rare: data that codes to more than 4.5 bytes per sample) pack and assemble again, at the plan's exact sizes
             uint8_t* extra = nullptr;
-            const size_t words_bytes = (((size_t)total_words + 2) * 4 + 255) & ~(size_t)255;
+            const size_t words_bytes = (size_t)workspace_up(((size_t)total_words + 2) * 4); // (of an allocation of this call's own, no workspace: the frames behind the words)
             e = hipMalloc(reinterpret_cast<void**>(&extra), words_bytes + chunk_bytes + 256);
             if (e != hipSuccess)
                 return report_hip_error(e, "generic encode: stream scratch");

@@ -239,9 +239,10 @@ size_t decode_lds_bytes(uint32_t channels) { return decode_lds_bytes_for(channel
 uint32_t decode_max_channels() { return (uint32_t)kDecMaxChannels; }
 
 // Generic mode parks the residues of a subframe here (int32[2048]); the usual path never touches it.
-size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels)
+int32_t* carve_decode(Carve& c, uint32_t n_frames, uint32_t channels) { return c.take<int32_t>((uint64_t)n_frames * channels * kBlock); }
+size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels, Carve* at)
 {
-    return (size_t)n_frames * channels * kBlock * sizeof(int32_t) + 256;
+    return measured(at, [&](Carve& c) { carve_decode(c, n_frames, channels); });
 }
 
 // Which workgroups of a launch run their recurrence in the form for a wave that has its SIMD (nearly) to itself
@@ -375,7 +376,8 @@ hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offset
     const int n_waves = decode_waves(channels);
     if (channels > (uint32_t)kDecMaxChannels)
         return hipErrorInvalidValue;
-    int32_t* ws = reinterpret_cast<int32_t*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    Carve carve(d_workspace);
+    int32_t* const ws = carve_decode(carve, n_frames, channels);
     if (channels > (uint32_t)kDecMaxWaves) { // more channels than a workgroup has waves: rounds (k_decode_frames_wide)
         if (d_phase_cycles)
             return hipErrorInvalidValue; // (the phase counts are the one-wave-per-subframe kernel's)

@@ -2593,21 +2593,52 @@ hipError_t launch_stage_rice_encode(const int32_t* d_values, const uint64_t* d_v
 // ---- host-side launchers (called from sela_capi.hip) ---------------------------------------------------
 namespace sela {
 
-size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels)
+// The workspace (sela_workspace.h): the block records | the slots | finish_group's counts and states | the scalar-operand rings
+// (L2-resident) and their owner words | the worker means and their ready words (64-bit launch tags), per encode index (frames
+// rounded up to a span of 64) | the stereo candidates' sizes (sela_encode_tail.inc).
+constexpr uint64_t kRingDoubles = (uint64_t)kXcds * kRingsPerXcd * kRingLen, kRingOwnerWords = (uint64_t)kXcds * kRingsPerXcd;
+struct EncodeWs {
+    BlockMeta* meta;
+    uint32_t* slots;
+    uint64_t* group_count;
+    GroupState* group_state;
+    double* rings;
+    uint32_t* ring_owner;
+    double* mean_out;
+    uint64_t *mean_ready, *sizes_pub;
+};
+static EncodeWs carve_encode(Carve& c, uint32_t n_frames, uint32_t channels)
 {
     const uint32_t n_sig = sela_hip_signals_per_frame(channels);
-    const size_t blocks = (size_t)n_frames * n_sig;
-    size_t bytes = 0;
-    bytes += (blocks * sizeof(BlockMeta) + 255) & ~(size_t)255;
-    bytes += (blocks * kSlotWords * 4 + 255) & ~(size_t)255;
-    const size_t n_groups = ((size_t)n_frames + kGroupFrames - 1) / kGroupFrames;
-    bytes += ((n_groups * kGroupCountStride * sizeof(uint64_t) + 255) & ~(size_t)255) + ((n_groups * sizeof(GroupState) + 255) & ~(size_t)255); // finish_group
-    bytes += (size_t)kXcds * kRingsPerXcd * kRingLen * sizeof(double) + 256; // scalar-operand rings (L2-resident) ...
-    bytes += (size_t)kXcds * kRingsPerXcd * 4 + 256;                          // ... and their owner words
-    const size_t padded = (((size_t)n_frames + 63) / 64) * 64 * n_sig;        // encode indices (frames rounded up to a span of 64)
-    bytes += 2 * ((padded * sizeof(double) + 255) & ~(size_t)255); // worker means + ready words (64-bit launch tags)
-    bytes += (blocks * sizeof(uint64_t) + 255) & ~(size_t)255;     // the stereo candidates' sizes (sela_encode_tail.inc)
-    return bytes + 256;
+    const uint64_t blocks = (uint64_t)n_frames * n_sig, n_groups = ((uint64_t)n_frames + kGroupFrames - 1) / kGroupFrames;
+    const uint64_t padded = (((uint64_t)n_frames + 63) / 64) * 64 * n_sig;
+    EncodeWs w;
+    w.meta = c.take<BlockMeta>(blocks);
+    w.slots = c.take<uint32_t>(blocks * kSlotWords);
+    w.group_count = c.take<uint64_t>(n_groups * kGroupCountStride);
+    w.group_state = c.take<GroupState>(n_groups);
+    w.rings = c.take<double>(kRingDoubles);
+    w.ring_owner = c.take<uint32_t>(kRingOwnerWords);
+    w.mean_out = c.take<double>(padded);
+    w.mean_ready = c.take<uint64_t>(padded);
+    w.sizes_pub = c.take<uint64_t>(blocks);
+    return w;
+}
+
+// The size has always counted the rings and their owner words as their bytes + 256 each, which is more than the carve's rounding
+// takes: callers have been told that figure, so it stays, as the measure plus this slack.
+constexpr uint64_t kEncodeRingSlack = (kRingDoubles * sizeof(double) + 256 - workspace_up(kRingDoubles * sizeof(double)))
+    + (kRingOwnerWords * 4 + 256 - workspace_up(kRingOwnerWords * 4));
+
+size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels, Carve* at)
+{
+    return measured(at, [&](Carve& c) { carve_encode(c, n_frames, channels); }) + (size_t)kEncodeRingSlack;
+}
+
+const BlockMeta* encode_block_records(const void* d_workspace, uint32_t n_frames, uint32_t channels)
+{
+    Carve c(d_workspace);
+    return carve_encode(c, n_frames, channels).meta;
 }
 
 // Workgroups of k_encode_blocks the current device holds at once: 12 per CU (LDS), cached per device.
@@ -2717,26 +2748,17 @@ hipError_t launch_encode(const int16_t* d_pcm, uint32_t n_frames, uint32_t chann
     const uint32_t n_sig = sela_hip_signals_per_frame(channels);
     const size_t blocks = (size_t)n_frames * n_sig;
     const size_t n_groups = ((size_t)n_frames + kGroupFrames - 1) / kGroupFrames;
-    unsigned char* ws = static_cast<unsigned char*>(d_workspace);
-    ws = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    BlockMeta* meta = reinterpret_cast<BlockMeta*>(ws);
-    ws += (blocks * sizeof(BlockMeta) + 255) & ~(size_t)255;
-    uint32_t* slots = reinterpret_cast<uint32_t*>(ws);
-    ws += (blocks * kSlotWords * 4 + 255) & ~(size_t)255;
-    uint64_t* group_count = reinterpret_cast<uint64_t*>(ws);
-    ws += (n_groups * kGroupCountStride * sizeof(uint64_t) + 255) & ~(size_t)255;
-    GroupState* group_state = reinterpret_cast<GroupState*>(ws);
-    ws += (n_groups * sizeof(GroupState) + 255) & ~(size_t)255;
-    double* rings = reinterpret_cast<double*>(ws);
-    ws += ((size_t)kXcds * kRingsPerXcd * kRingLen * sizeof(double) + 255) & ~(size_t)255;
-    uint32_t* ring_owner = reinterpret_cast<uint32_t*>(ws);
-    ws += ((size_t)kXcds * kRingsPerXcd * 4 + 255) & ~(size_t)255;
-    const size_t padded = (((size_t)n_frames + 63) / 64) * 64 * n_sig;
-    double* mean_out = reinterpret_cast<double*>(ws);
-    ws += (padded * sizeof(double) + 255) & ~(size_t)255;
-    uint64_t* mean_ready = reinterpret_cast<uint64_t*>(ws);
-    ws += (padded * sizeof(uint64_t) + 255) & ~(size_t)255;
-    uint64_t* sizes_pub = reinterpret_cast<uint64_t*>(ws);
+    Carve carve(d_workspace);
+    const EncodeWs ws = carve_encode(carve, n_frames, channels);
+    BlockMeta* const meta = ws.meta;
+    uint32_t* const slots = ws.slots;
+    uint64_t* const group_count = ws.group_count;
+    GroupState* const group_state = ws.group_state;
+    double* const rings = ws.rings;
+    uint32_t* const ring_owner = ws.ring_owner;
+    double* const mean_out = ws.mean_out;
+    uint64_t* const mean_ready = ws.mean_ready;
+    uint64_t* sizes_pub = ws.sizes_pub;
 
     if (link && (d_trace || d_phase_cycles))
         return hipErrorInvalidValue; // (the analysis trace and the phase counts are the device-pointer path's)

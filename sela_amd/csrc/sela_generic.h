@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sela_workspace.h"
+
 namespace sela {
 
 struct GenericMeta { // one per (frame, signal), written by k_generic_analyse
@@ -42,10 +44,15 @@ hipError_t launch_decode_subframes32(const uint8_t* d_frames, const uint64_t* d_
     uint32_t stride, int32_t* d_dec, GenericSubInfo* d_info, uint32_t* d_status, bool standard_path, hipStream_t stream, const uint32_t* d_n_found = nullptr);
 // sela_hip_decode_i32_device / sela_hip_decode_payload_i32_device: the sample index, the fast kernel, the judge
 // and the combine, all on `stream`, nothing waited for.  Arguments checked by the caller; mode as sela_hip_debug_standard_first.
-size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+// (Every *_workspace_bytes here measures its call's one description of the workspace, sela_workspace.h -- `at`: on that Carve,
+// one that lists its pieces or a sub() range of another call's; null: on a fresh one.  SIZE_MAX: more than any device holds.  The
+// four sized by (frames, channels, stride) are passed around as plain functions of those three: the overload without `at`.)
+size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return decode_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
 // sela_hip_decode_n_device / sela_hip_decode_payload_n_device: the sample index, the route taken on the device,
 // both routes' kernels gated by it, the int16 writer.  Arguments checked by the caller.
-size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return decode_n_workspace_bytes(max_frames, channels, stride, nullptr); }
 hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
     hipStream_t stream);
@@ -63,7 +70,8 @@ hipError_t launch_verify_frames(const uint8_t* d_frames, const uint64_t* d_frame
 hipError_t launch_verify_compare(const int16_t* d_decoded, const int16_t* d_pcm, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels,
     uint32_t stride, const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, void* d_parts /* [max_frames][verify_slices()] x 8 bytes */,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, uint32_t* d_status, hipStream_t stream);
-size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return verify_workspace_bytes(max_frames, channels, stride, nullptr); }
 hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
@@ -80,14 +88,15 @@ hipError_t launch_verify32_direct(const int32_t* d_dec, const GenericSubInfo* d_
 hipError_t launch_verify32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
     const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, void* d_parts,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, hipStream_t stream);
-size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
-size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride); // of the two control words, from the aligned base
+size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return verify_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
+const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
 hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
-size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired = false);
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired = false, Carve* at = nullptr);
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless = false, bool paired = false);
 hipError_t launch_lpc_decode_any(const int32_t* d_order, const int32_t* d_q, const int32_t* d_residues, uint32_t n_blocks, uint32_t n, int32_t* d_samples,

@@ -1577,6 +1577,9 @@ hipError_t launch_generic_emit(const GenericMeta* d_meta, uint32_t n_frames, uin
     return hipGetLastError();
 }
 
+// The any-length route's grid of k_generic_combine: a workgroup per (frame, slice of kCombineSlice samples).
+static dim3 combine_grid(uint32_t n_frames, uint32_t stride) { return dim3(n_frames, (stride + kCombineSlice - 1) / kCombineSlice); }
+
 hipError_t launch_generic_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint64_t base_bytes, uint32_t n_frames, uint32_t channels, uint32_t stride,
     int32_t* d_dec, GenericSubInfo* d_info, int32_t* d_all, uint32_t* d_counts, const uint64_t* d_sample_offsets, int16_t* d_pcm_out, uint32_t* d_status,
     bool fast_first, bool standard_path, hipStream_t stream)
@@ -1584,6 +1587,8 @@ hipError_t launch_generic_decode(const uint8_t* d_frames, const uint64_t* d_fram
     const uint32_t subs = n_frames * channels;
     if (subs == 0)
         return hipSuccess;
+    // (the host's two attempts are two calls: one kernel or the other, the count read on the host in between -- not
+    // launch_any_length_subframes, which runs both and lets the device gate the second)
     if (fast_first) {
         const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec, d_info, d_status, standard_path, stream);
         if (e != hipSuccess)
@@ -1591,39 +1596,43 @@ hipError_t launch_generic_decode(const uint8_t* d_frames, const uint64_t* d_fram
     } else
         hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, base_bytes, n_frames, channels, stride, d_dec, d_info, d_status,
             nullptr, nullptr);
-    const dim3 grid(n_frames, (stride + kCombineSlice - 1) / kCombineSlice);
     if (d_pcm_out)
-        hipLaunchKernelGGL(k_generic_combine<true>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all, d_counts,
-            d_sample_offsets, d_pcm_out, d_status, nullptr);
+        hipLaunchKernelGGL(k_generic_combine<true>, combine_grid(n_frames, stride), dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all,
+            d_counts, d_sample_offsets, d_pcm_out, d_status, nullptr);
     else
-        hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all, d_counts,
-            d_sample_offsets, d_pcm_out, d_status, nullptr);
+        hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(n_frames, stride), dim3(kCombineThreads), 0, stream, d_dec, d_info, n_frames, channels, stride, d_all,
+            d_counts, d_sample_offsets, d_pcm_out, d_status, nullptr);
     return hipGetLastError();
 }
 
-// Workspace of the device-pointer 32-bit decode: subframes as decoded, by position | one GenericSubInfo per subframe | the fast
-// kernel's four counters | one SampleTile per 4096 frames; every piece 256-byte aligned, the base too.
-struct DecodeI32Layout {
-    uint64_t dec, info, counters, tiles, bytes;
+// ---- the device-pointer calls' workspaces (sela_workspace.h): one description each, run by the size, the launch and the hooks ---
+// What every decode and verify call opens its workspace with: the subframes as decoded, by position (the fast decoder parks its
+// residues there too: the routes never run together) | one GenericSubInfo per subframe | the counters | one SampleTile per 4096 frames.
+struct DecodeHeadWs {
+    int32_t* dec;
+    GenericSubInfo* info;
+    uint32_t* counters;
+    SampleTile* tiles;
 };
-static DecodeI32Layout decode_i32_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+static DecodeHeadWs carve_decode_head(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t n_counters)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     const uint64_t subs = (uint64_t)max_frames * channels, n_tiles = ((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames;
-    DecodeI32Layout l;
-    l.dec = 0;
-    l.info = l.dec + up(subs * stride * sizeof(int32_t));
-    l.counters = l.info + up(subs * sizeof(GenericSubInfo));
-    l.tiles = l.counters + up(4 * sizeof(uint32_t));
-    l.bytes = l.tiles + up(std::max<uint64_t>(n_tiles, 1) * sizeof(SampleTile)) + 256; // (+ the base's alignment)
-    return l;
+    DecodeHeadWs w;
+    w.dec = c.take<int32_t>(subs * stride);
+    w.info = c.take<GenericSubInfo>(subs);
+    w.counters = c.take<uint32_t>(n_counters);
+    w.tiles = c.take<SampleTile>(std::max<uint64_t>(n_tiles, 1));
+    return w;
 }
 
-size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+// The device-pointer 32-bit decode: the head, with the fast kernel's four counters.
+static DecodeHeadWs carve_decode_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride) { return carve_decode_head(c, max_frames, channels, stride, 4); }
+
+size_t decode_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
 {
     if ((uint64_t)max_frames * channels * stride >= (1ull << 60))
         return SIZE_MAX;
-    return (size_t)decode_i32_layout(max_frames, channels, stride).bytes;
+    return measured(at, [&](Carve& c) { carve_decode_i32(c, max_frames, channels, stride); });
 }
 
 // The sample index (the host's header walk) on `stream`: one launch up to a tile of frames, three above.
@@ -1644,86 +1653,80 @@ static void launch_sample_index(const uint8_t* d_frames, const uint64_t* d_frame
     }
 }
 
-// The host route (generic_decode) on one chunk, with its decisions taken on the device: the sample index and the stride check
-// (the host's header walk), k_decode_subframes32 counting what it leaves alone in the workspace (attempt 0), k_generic_decode over
-// every subframe, each workgroup returning at once unless that count is non-zero (attempt 1: then it decodes every subframe
-// again, as the host's second attempt does), and one combine.  mode 0: the serial kernel alone; 2: the fast kernel by segments.
-hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
-    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+// The any-length route's decode of every subframe, its decisions taken on the device: k_decode_subframes32 counting what it leaves
+// alone in the counters (attempt 0), then k_generic_decode over every subframe, each workgroup returning at once unless that count
+// is non-zero (attempt 1: then it decodes every subframe again, as the host's second attempt does).  mode 0: the serial kernel
+// alone; 2: the fast kernel by segments.  gate: the device's count of frames the route is to touch.  (max_frames * channels is not 0.)
+static hipError_t launch_any_length_subframes(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const DecodeHeadWs& w, uint32_t* d_status, int mode, const uint32_t* gate, hipStream_t stream)
 {
-    const DecodeI32Layout l = decode_i32_layout(max_frames, channels, stride);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.dec);
-    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.info);
-    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.counters);
-    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.tiles);
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, d_counters, d_tiles, stream);
-    const uint32_t subs = max_frames * channels;
-    if (subs == 0)
-        return hipGetLastError();
     if (mode != 0) {
-        const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, d_n_found);
+        const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, w.dec, w.info, w.counters, mode != 2, stream, gate);
         if (e != hipSuccess)
             return e;
     }
-    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
-        d_n_found, mode != 0 ? d_counters + 2 : nullptr);
-    const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
-    hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_samples_out, d_counts_out,
-        nullptr, nullptr, d_status, d_n_found);
+    hipLaunchKernelGGL(k_generic_decode, dim3(max_frames * channels), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, w.dec,
+        w.info, d_status, gate, mode != 0 ? w.counters + 2 : nullptr);
     return hipGetLastError();
 }
 
-// Workspace of the device-pointer int16 decode: subframes as decoded, by position (the fast decoder parks its residues there too:
-// the routes never run together) | one GenericSubInfo per subframe | the counters | one SampleTile per 4096 frames | the sample
-// offsets | above kInterleaveChannels channels, k_generic_combine's channel-major copy; every piece 256-byte aligned, the base too.
-struct DecodeNLayout {
-    uint64_t dec, info, counters, tiles, offsets, all, bytes;
-};
-static DecodeNLayout decode_n_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+// The host route (generic_decode) on one chunk, with its decisions taken on the device: the sample index and the stride check
+// (the host's header walk), the subframes (launch_any_length_subframes), and one combine.
+hipError_t launch_decode_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, int32_t* d_samples_out, uint32_t* d_counts_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    const uint64_t subs = (uint64_t)max_frames * channels, n_tiles = ((uint64_t)max_frames + kSampleTileFrames - 1) / kSampleTileFrames;
-    DecodeNLayout l;
-    l.dec = 0;
-    l.info = l.dec + up(subs * stride * sizeof(int32_t));
-    l.counters = l.info + up(subs * sizeof(GenericSubInfo));
-    l.tiles = l.counters + up(8 * sizeof(uint32_t));
-    l.offsets = l.tiles + up(std::max<uint64_t>(n_tiles, 1) * sizeof(SampleTile));
-    l.all = l.offsets + up(((uint64_t)max_frames + 1) * sizeof(uint64_t));
-    l.bytes = l.all + (channels > kInterleaveChannels ? up(subs * stride * sizeof(int32_t)) : 0) + 256; // (+ the base's alignment)
-    return l;
+    Carve c(d_workspace);
+    const DecodeHeadWs w = carve_decode_i32(c, max_frames, channels, stride);
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.counters, w.tiles, stream);
+    if (max_frames * channels == 0)
+        return hipGetLastError();
+    const hipError_t e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w, d_status, mode, d_n_found, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.dec, w.info, max_frames, channels, stride,
+        d_samples_out, d_counts_out, nullptr, nullptr, d_status, d_n_found);
+    return hipGetLastError();
 }
 
-size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+// The device-pointer int16 decode: the head, with eight counters | the sample offsets | above kInterleaveChannels channels,
+// k_generic_combine's channel-major copy.
+struct DecodeNWs {
+    DecodeHeadWs head;
+    uint64_t* offsets;
+    int32_t* all;
+};
+static DecodeNWs carve_decode_n(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    DecodeNWs w;
+    w.head = carve_decode_head(c, max_frames, channels, stride, 8);
+    w.offsets = c.take<uint64_t>((uint64_t)max_frames + 1);
+    w.all = c.take<int32_t>(channels > kInterleaveChannels ? (uint64_t)max_frames * channels * stride : 0);
+    return w;
+}
+
+size_t decode_n_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
 {
     if ((uint64_t)max_frames * channels * stride >= (1ull << 60))
         return SIZE_MAX;
-    return (size_t)decode_n_layout(max_frames, channels, stride).bytes;
+    return measured(at, [&](Carve& c) { carve_decode_n(c, max_frames, channels, stride); });
 }
 
-// Route 2 of the int16 calls on device pointers (launch_decode_n_device, launch_verify_n_device): k_decode_subframes32 and
-// k_generic_decode as in launch_decode_i32_device, gated by the any-length route's count (counters[6]), then the int16 writer
-// into d_pcm_out at the sample offsets.  (max_frames * channels is not 0.)
+// Route 2 of the int16 calls on device pointers (launch_decode_n_device, launch_verify_n_device): the subframes as in
+// launch_decode_i32_device, gated by the any-length route's count (counters[6]), then the int16 writer into d_pcm_out at the
+// sample offsets.  (max_frames * channels is not 0.)
 static hipError_t launch_any_length_n(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
-    int32_t* d_dec, GenericSubInfo* d_info, int32_t* d_all, uint32_t* d_counters, const uint64_t* d_so, int16_t* d_pcm_out, uint32_t* d_status, int mode,
-    hipStream_t stream)
+    const DecodeNWs& w, const uint64_t* d_so, int16_t* d_pcm_out, uint32_t* d_status, int mode, hipStream_t stream)
 {
-    const uint32_t subs = max_frames * channels;
-    const uint32_t* const n_any = d_counters + 6;
-    if (mode != 0) {
-        const hipError_t e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, n_any);
-        if (e != hipSuccess)
-            return e;
-    }
-    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
-        n_any, mode != 0 ? d_counters + 2 : nullptr);
+    const uint32_t* const n_any = w.head.counters + 6;
+    const hipError_t e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.head, d_status, mode, n_any, stream);
+    if (e != hipSuccess)
+        return e;
     if (channels <= kInterleaveChannels)
-        hipLaunchKernelGGL(k_interleave16, dim3(max_frames, (stride + kInterleaveSlice - 1) / kInterleaveSlice), dim3(kInterleaveThreads), 0, stream, d_dec, d_info,
-            max_frames, channels, stride, d_so, d_pcm_out, d_status, n_any);
+        hipLaunchKernelGGL(k_interleave16, dim3(max_frames, (stride + kInterleaveSlice - 1) / kInterleaveSlice), dim3(kInterleaveThreads), 0, stream, w.head.dec,
+            w.head.info, max_frames, channels, stride, d_so, d_pcm_out, d_status, n_any);
     else
-        hipLaunchKernelGGL(k_generic_combine<true>, dim3(max_frames, (stride + kCombineSlice - 1) / kCombineSlice), dim3(kCombineThreads), 0, stream, d_dec, d_info,
-            max_frames, channels, stride, d_all, nullptr, d_so, d_pcm_out, d_status, n_any);
+        hipLaunchKernelGGL(k_generic_combine<true>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.head.dec, w.head.info, max_frames, channels,
+            stride, w.all, nullptr, d_so, d_pcm_out, d_status, n_any);
     return hipGetLastError();
 }
 
@@ -1735,55 +1738,48 @@ hipError_t launch_decode_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     uint32_t stride, int16_t* d_pcm_out, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form, uint32_t synth_priorities,
     hipStream_t stream)
 {
-    const DecodeNLayout l = decode_n_layout(max_frames, channels, stride);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.dec);
-    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.info);
-    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.counters);
-    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.tiles);
-    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : reinterpret_cast<uint64_t*>(base + l.offsets);
-    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.all);
-    const uint32_t* const n_fast = d_counters + 5;
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, d_counters, d_tiles, stream);
-    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, d_counters);
-    const uint32_t subs = max_frames * channels;
-    if (subs == 0)
+    Carve c(d_workspace);
+    const DecodeNWs w = carve_decode_n(c, max_frames, channels, stride);
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.offsets;
+    const uint32_t* const n_fast = w.head.counters + 5;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, w.head.counters, w.head.tiles, stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, w.head.counters);
+    if (max_frames * channels == 0)
         return hipGetLastError();
     // route 1: frame f at f * 2048 * channels (= sample_offsets[f] * channels there); flags and malformed frames into d_status
-    // as the route's kernels leave them, the words the index wrote kept (no zeroing); its workspace: d_dec, big enough whenever
-    // stride >= 2048, the only case in which the route runs
-    hipError_t e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, d_dec, stream, nullptr, nullptr, nullptr, recurrence_form,
+    // as the route's kernels leave them, the words the index wrote kept (no zeroing); its workspace: the decoded subframes' piece,
+    // big enough whenever stride >= 2048, the only case in which the route runs
+    hipError_t e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, w.head.dec, stream, nullptr, nullptr, nullptr, recurrence_form,
         synth_priorities, n_fast, false);
     if (e != hipSuccess)
         return e;
     // route 2
-    return launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, d_dec, d_info, d_all, d_counters, d_so, d_pcm_out, d_status, mode, stream);
+    return launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, w, d_so, d_pcm_out, d_status, mode, stream);
 }
 
 // ---- verification on the device (sela_hip_verify_device) ----------------------------------------------------
 // Workspace: launch_decode_n_device's | the PCM of the routes that are not fused (as sela_hip_decode_n_device writes it) |
-// k_verify_compare's words per (frame, slice); every piece 256-byte aligned, the base too.
-struct VerifyLayout {
-    DecodeNLayout n;
-    uint64_t pcm, parts, bytes;
+// k_verify_compare's words per (frame, slice).
+struct VerifyWs {
+    DecodeNWs n;
+    int16_t* pcm;
+    uint64_t* parts;
 };
-static VerifyLayout verify_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+static VerifyWs carve_verify(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    VerifyLayout l;
-    l.n = decode_n_layout(max_frames, channels, stride);
-    l.pcm = l.n.bytes - 256;
-    l.parts = l.pcm + up((uint64_t)max_frames * channels * stride * sizeof(int16_t));
-    l.bytes = l.parts + up(std::max<uint64_t>((uint64_t)max_frames * verify_slices(channels, stride), 1) * 8) + 256; // (+ the base's alignment)
-    return l;
+    VerifyWs w;
+    w.n = carve_decode_n(c, max_frames, channels, stride);
+    w.pcm = c.take<int16_t>((uint64_t)max_frames * channels * stride);
+    w.parts = c.take<uint64_t>(std::max<uint64_t>((uint64_t)max_frames * verify_slices(channels, stride), 1));
+    return w;
 }
 
-size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
 {
     // (frames x channels first: the product of all three can wrap 64 bits; the launch calls keep it below 2^31)
     if ((uint64_t)max_frames * channels >= (1ull << 31) || (uint64_t)max_frames * channels * stride >= (1ull << 60))
         return SIZE_MAX;
-    return (size_t)verify_layout(max_frames, channels, stride).bytes;
+    return measured(at, [&](Carve& c) { carve_verify(c, max_frames, channels, stride); });
 }
 
 // launch_decode_n_device with a compare in place of the PCM: the sample index, k_route_n, then
@@ -1802,73 +1798,72 @@ hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_fra
     uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream)
 {
-    const VerifyLayout l = verify_layout(max_frames, channels, stride);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.n.dec);
-    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.n.info);
-    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.n.counters);
-    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.n.tiles);
-    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : reinterpret_cast<uint64_t*>(base + l.n.offsets);
-    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.n.all);
-    int16_t* const d_back = reinterpret_cast<int16_t*>(base + l.pcm);
-    const uint32_t* const n_fast = d_counters + 5;
-    const uint32_t* const n_any = d_counters + 6;
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, d_counters, d_tiles, stream);
-    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, d_counters);
+    Carve c(d_workspace);
+    const VerifyWs w = carve_verify(c, max_frames, channels, stride);
+    const DecodeHeadWs& head = w.n.head;
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.n.offsets;
+    const uint32_t* const n_fast = head.counters + 5;
+    const uint32_t* const n_any = head.counters + 6;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, head.counters, head.tiles, stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, head.counters);
     hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, stream, d_status);
     hipError_t e = hipGetLastError();
-    const uint32_t subs = max_frames * channels;
-    if (e != hipSuccess || subs == 0)
+    if (e != hipSuccess || max_frames * channels == 0)
         return e;
-    // route 1 (its workspace: d_dec, as in launch_decode_n_device)
+    // route 1 (its workspace: the decoded subframes' piece, as in launch_decode_n_device)
     const bool fused = channels <= kVerifyFusedChannels;
     if (fused)
-        e = launch_verify_frames(d_frames, d_frame_offsets, max_frames, channels, d_pcm, d_diff_counts, d_first_diff, d_status, d_dec, stream, recurrence_form,
+        e = launch_verify_frames(d_frames, d_frame_offsets, max_frames, channels, d_pcm, d_diff_counts, d_first_diff, d_status, head.dec, stream, recurrence_form,
             synth_priorities, n_fast);
     else
-        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_back, d_status, d_dec, stream, nullptr, nullptr, nullptr, recurrence_form,
+        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, w.pcm, d_status, head.dec, stream, nullptr, nullptr, nullptr, recurrence_form,
             synth_priorities, n_fast, false);
     if (e != hipSuccess)
         return e;
     // route 2
-    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, d_dec, d_info, d_all, d_counters, d_so, d_back, d_status, mode, stream);
+    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, w.n, d_so, w.pcm, d_status, mode, stream);
     if (e != hipSuccess)
         return e;
-    return launch_verify_compare(d_back, d_pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, base + l.parts, d_diff_counts, d_first_diff,
-        d_status, stream);
+    return launch_verify_compare(w.pcm, d_pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, w.parts, d_diff_counts, d_first_diff, d_status,
+        stream);
 }
 
 // ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
 // Workspace: launch_decode_i32_device's | the fallback's samples by channel, [frames][channels][stride] | its counts | a mark per
-// frame | k_verify32_direct's / _rest's words per (frame, slice) | the two control words; every piece 256-byte aligned, the base too.
-struct VerifyI32Layout {
-    DecodeI32Layout d;
-    uint64_t all, counts, marks, parts, ctl, bytes;
+// frame | k_verify32_direct's / _rest's words per (frame, slice) | the two control words.
+struct VerifyI32Ws {
+    DecodeHeadWs d;
+    int32_t* all;
+    uint32_t *counts, *marks;
+    uint64_t* parts;
+    uint32_t* ctl;
 };
-static VerifyI32Layout verify_i32_layout(uint32_t max_frames, uint32_t channels, uint32_t stride)
+static VerifyI32Ws carve_verify_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     const uint64_t subs = (uint64_t)max_frames * channels;
-    VerifyI32Layout l;
-    l.d = decode_i32_layout(max_frames, channels, stride);
-    l.all = l.d.bytes - 256;
-    l.counts = l.all + up(subs * stride * sizeof(int32_t));
-    l.marks = l.counts + up(subs * sizeof(uint32_t));
-    l.parts = l.marks + up(std::max<uint64_t>(max_frames, 1) * sizeof(uint32_t));
-    l.ctl = l.parts + up(std::max<uint64_t>((uint64_t)max_frames * verify32_slices(stride), 1) * 8);
-    l.bytes = l.ctl + 256 + 256; // (+ the base's alignment)
-    return l;
+    VerifyI32Ws w;
+    w.d = carve_decode_i32(c, max_frames, channels, stride);
+    w.all = c.take<int32_t>(subs * stride);
+    w.counts = c.take<uint32_t>(subs);
+    w.marks = c.take<uint32_t>(std::max<uint64_t>(max_frames, 1));
+    w.parts = c.take<uint64_t>(std::max<uint64_t>((uint64_t)max_frames * verify32_slices(stride), 1));
+    w.ctl = c.take<uint32_t>(2);
+    return w;
 }
 
-size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
 {
     // (frames x channels first: the product of all three can wrap 64 bits; the launch calls keep it below 2^31)
-    if ((uint64_t)max_frames * channels >= (1ull << 31) || decode_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+    if ((uint64_t)max_frames * channels >= (1ull << 31) || (uint64_t)max_frames * channels * stride >= (1ull << 60))
         return SIZE_MAX;
-    return (size_t)verify_i32_layout(max_frames, channels, stride).bytes;
+    return measured(at, [&](Carve& c) { carve_verify_i32(c, max_frames, channels, stride); });
 }
 
-size_t verify_i32_ctl_offset(uint32_t max_frames, uint32_t channels, uint32_t stride) { return (size_t)verify_i32_layout(max_frames, channels, stride).ctl; }
+const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    Carve c(d_workspace);
+    return carve_verify_i32(c, max_frames, channels, stride).ctl;
+}
 
 // launch_decode_i32_device with a compare in place of the combine: the sample index, k_verify32_begin (status[2], the largest
 // samplesPerChannel, becomes the count of frames with a difference; nothing on this route reads it behind the index),
@@ -1881,64 +1876,52 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
-    const VerifyI32Layout l = verify_i32_layout(max_frames, channels, stride);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.d.dec);
-    GenericSubInfo* const d_info = reinterpret_cast<GenericSubInfo*>(base + l.d.info);
-    uint32_t* const d_counters = reinterpret_cast<uint32_t*>(base + l.d.counters);
-    SampleTile* const d_tiles = reinterpret_cast<SampleTile*>(base + l.d.tiles);
-    int32_t* const d_all = reinterpret_cast<int32_t*>(base + l.all);
-    uint32_t* const d_counts = reinterpret_cast<uint32_t*>(base + l.counts);
-    uint32_t* const d_marks = reinterpret_cast<uint32_t*>(base + l.marks);
-    uint32_t* const d_ctl = reinterpret_cast<uint32_t*>(base + l.ctl);
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, d_counters, d_tiles, stream);
-    hipError_t e = launch_verify32_begin(d_status, d_ctl, stream);
-    const uint32_t subs = max_frames * channels;
-    if (e != hipSuccess || subs == 0)
+    Carve c(d_workspace);
+    const VerifyI32Ws w = carve_verify_i32(c, max_frames, channels, stride);
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.d.counters, w.d.tiles, stream);
+    hipError_t e = launch_verify32_begin(d_status, w.ctl, stream);
+    if (e != hipSuccess || max_frames * channels == 0)
         return e;
-    if (mode != 0) {
-        e = launch_decode_subframes32(d_frames, d_frame_offsets, 0, max_frames, channels, stride, d_dec, d_info, d_counters, mode != 2, stream, d_n_found);
-        if (e != hipSuccess)
-            return e;
-    }
-    hipLaunchKernelGGL(k_generic_decode, dim3(subs), dim3(64), 0, stream, d_frames, d_frame_offsets, (uint64_t)0, max_frames, channels, stride, d_dec, d_info, d_status,
-        d_n_found, mode != 0 ? d_counters + 2 : nullptr);
-    e = launch_verify32_direct(d_dec, d_info, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, d_ctl, d_marks, base + l.parts, stream);
+    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.d, d_status, mode, d_n_found, stream);
     if (e != hipSuccess)
         return e;
-    const dim3 grid(max_frames, (stride + kCombineSlice - 1) / kCombineSlice);
-    hipLaunchKernelGGL(k_generic_combine<false>, grid, dim3(kCombineThreads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_all, d_counts, nullptr, nullptr,
-        d_status, d_ctl + 1);
-    return launch_verify32_rest(d_all, d_counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, d_ctl, d_marks, base + l.parts, d_diff_counts,
+    e = launch_verify32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.d.dec, w.d.info, max_frames, channels, stride,
+        w.all, w.counts, nullptr, nullptr, d_status, w.ctl + 1);
+    return launch_verify32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, d_diff_counts,
         d_first_diff, stream);
 }
 
-// Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total; every
-// piece 256-byte aligned, the base too.  No Rice words: k_generic_write packs into the frames.
-struct EncodeI32Layout {
-    uint64_t sig, res, q, meta, word_base, chosen, total, bytes;
+// Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total.  No
+// Rice words: k_generic_write packs into the frames.
+struct EncodeI32Ws {
+    int32_t *sig, *res, *q;
+    GenericMeta* meta;
+    uint64_t* word_base;
+    uint32_t* chosen;
+    uint64_t* total;
 };
-static EncodeI32Layout encode_i32_layout(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired)
+static EncodeI32Ws carve_encode_i32(Carve& c, uint32_t n_frames, uint32_t channels, uint32_t n, bool paired)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     const uint64_t blocks = (uint64_t)n_frames * generic_signals(channels, paired), subs = (uint64_t)n_frames * channels;
-    EncodeI32Layout l;
-    l.sig = 0;
-    l.res = l.sig + up(blocks * n * sizeof(int32_t));
-    l.q = l.res + up(blocks * n * sizeof(int32_t));
-    l.meta = l.q + up(blocks * kMaxOrder * sizeof(int32_t));
-    l.word_base = l.meta + up(blocks * sizeof(GenericMeta));
-    l.chosen = l.word_base + up((subs + 1) * sizeof(uint64_t));
-    l.total = l.chosen + up(subs * sizeof(uint32_t));
-    l.bytes = l.total + up(sizeof(uint64_t)) + 256; // (+ the base's alignment)
-    return l;
+    EncodeI32Ws w;
+    w.sig = c.take<int32_t>(blocks * n);
+    w.res = c.take<int32_t>(blocks * n);
+    w.q = c.take<int32_t>(blocks * kMaxOrder);
+    w.meta = c.take<GenericMeta>(blocks);
+    w.word_base = c.take<uint64_t>(subs + 1);
+    w.chosen = c.take<uint32_t>(subs);
+    w.total = c.take<uint64_t>(1);
+    return w;
 }
 
-size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired)
+size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired, Carve* at)
 {
     if (channels == 0 || channels > 255 || n == 0 || n > 65535 || (uint64_t)n_frames * generic_signals(channels, paired) >= (1ull << 31))
         return SIZE_MAX;
-    return (size_t)encode_i32_layout(n_frames, channels, n, paired).bytes;
+    return measured(at, [&](Carve& c) { carve_encode_i32(c, n_frames, channels, n, paired); });
 }
 
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: analyse, plan (base 0, the offsets straight into the
@@ -1947,31 +1930,23 @@ size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, u
 hipError_t launch_encode_i32_device(const void* d_input, bool in16, uint32_t n_frames, uint32_t channels, uint32_t n, uint8_t* d_frames, uint64_t frames_cap,
     uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, hipStream_t stream, bool lossless, bool paired)
 {
-    const EncodeI32Layout l = encode_i32_layout(n_frames, channels, n, paired);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    int32_t* const d_sig = reinterpret_cast<int32_t*>(base + l.sig);
-    int32_t* const d_res = reinterpret_cast<int32_t*>(base + l.res);
-    int32_t* const d_q = reinterpret_cast<int32_t*>(base + l.q);
-    GenericMeta* const d_meta = reinterpret_cast<GenericMeta*>(base + l.meta);
-    uint64_t* const d_word_base = reinterpret_cast<uint64_t*>(base + l.word_base);
-    uint32_t* const d_chosen = reinterpret_cast<uint32_t*>(base + l.chosen);
-    uint64_t* const d_total = reinterpret_cast<uint64_t*>(base + l.total);
+    Carve c(d_workspace);
+    const EncodeI32Ws w = carve_encode_i32(c, n_frames, channels, n, paired);
     const uint32_t n_sig = generic_signals(channels, paired);
-    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, d_sig, d_res, d_q, d_meta, stream, lossless, paired);
+    hipError_t e = launch_generic_analyse(d_input, in16, n_frames, channels, n_sig, n, w.sig, w.res, w.q, w.meta, stream, lossless, paired);
     if (e != hipSuccess)
         return e;
     if (paired)
-        hipLaunchKernelGGL(k_paired_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
-            d_word_base, d_chosen, d_status, d_total, frames_cap);
+        hipLaunchKernelGGL(k_paired_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, w.meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
+            w.word_base, w.chosen, d_status, w.total, frames_cap);
     else
-        hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, d_meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
-            d_word_base, d_chosen, d_status, d_total, frames_cap);
+        hipLaunchKernelGGL(k_generic_plan<true>, dim3(1), dim3(kPlanThreads), 0, stream, w.meta, n_frames, channels, n_sig, (uint64_t)0, d_frame_offsets,
+            w.word_base, w.chosen, d_status, w.total, frames_cap);
     const uint32_t subs = n_frames * channels;
     if (subs)
-        hipLaunchKernelGGL(k_generic_write, dim3(subs), dim3(64), 0, stream, d_meta, n_frames, channels, n_sig, n, d_res, d_q, d_chosen, d_word_base,
+        hipLaunchKernelGGL(k_generic_write, dim3(subs), dim3(64), 0, stream, w.meta, n_frames, channels, n_sig, n, w.res, w.q, w.chosen, w.word_base,
             d_frame_offsets, d_frames, frames_cap);
     return hipGetLastError();
 }
 
 } // namespace sela
-

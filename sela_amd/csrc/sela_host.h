@@ -12,7 +12,9 @@
 namespace sela {
 
 // ---- sela_encode.hip -----------------------------------------------------------------------------------------------------------
-size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels);
+// (every *_workspace_bytes: the call's one description of its workspace, measured -- `at` as in sela_generic.h)
+size_t encode_workspace_bytes(uint32_t n_frames, uint32_t channels, Carve* at = nullptr);
+const BlockMeta* encode_block_records(const void* d_workspace, uint32_t n_frames, uint32_t channels); // what opens a launch's workspace (device)
 int encode_team_lanes(uint32_t n_frames, uint32_t channels, int forced);
 uint32_t encode_split_frames(uint32_t n_frames, uint32_t channels, int permille);
 void set_keep_both_candidates(int on);
@@ -26,7 +28,8 @@ hipError_t launch_stage_rice_encode(const int32_t* d_values, const uint64_t* d_v
     uint32_t* d_words, const uint64_t* d_word_offsets, uint32_t* d_status, hipStream_t stream);
 
 // ---- sela_decode.hip, sela_index.inc (decode_waves: sela_device.h) ----------------------------------------------------------------
-size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels);
+int32_t* carve_decode(Carve& c, uint32_t n_frames, uint32_t channels); // launch_decode's and launch_verify_frames' one piece
+size_t decode_workspace_bytes(uint32_t n_frames, uint32_t channels, Carve* at = nullptr);
 uint32_t decode_max_channels();
 hipError_t launch_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels,
     int16_t* d_pcm_out, uint32_t* d_status, void* d_workspace, hipStream_t stream, hipEvent_t* ev, uint64_t* d_phase_cycles,
@@ -35,32 +38,40 @@ hipError_t launch_stage_lpc_decode(const int32_t* d_order, const int32_t* d_q, c
     int64_t* d_coefs, uint32_t* d_status, hipStream_t stream);
 hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_word_offsets, const uint32_t* d_k, const uint64_t* d_value_offsets,
     uint32_t n_streams, int32_t* d_values, uint32_t* d_status, hipStream_t stream);
-size_t index_workspace_bytes(uint64_t payload_bytes);
+size_t index_workspace_bytes(uint64_t payload_bytes, Carve* at = nullptr);
 hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
     uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
 
 // ---- sela_window.hip: sample windows of a stream ---------------------------------------------------------------
 uint32_t window_cover(uint32_t window_samples); // the most frames a window of that length touches: the grid's second extent
-size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
 hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
-uint32_t* window_flag_words(void* d_workspace, uint32_t n_windows, uint32_t window_samples, uint32_t channels); // of a call without d_window_flags
+struct WindowWs { // launch_window_frames' pieces; launch_window_whole's workspace opens with them
+    int32_t* residues;   // generic mode's, one block per (workgroup, channel)
+    uint32_t* flag_words; // a word per window, for a call that passes no d_window_flags
+};
+WindowWs carve_windows(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels);
 
 // ---- sela_window_whole.hip: windows that reach a whole-track stream's long last frame --------------------------
-size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
 hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
 
 // ---- sela_whole.hip: a whole track with its tail ---------------------------------------------------------------
-struct WholeLayout { // the workspace of sela_hip_encode_whole_device, offsets from its 256-byte aligned base
-    uint64_t last_workspace; // the last frame's any-length workspace (the 2048-sample frames' workspace opens the whole)
-    uint64_t last_frame, last_cap; // the last frame's bytes as coded, and their room
-    uint64_t last_head;      // its two offsets (uint64) and its four status words
-    size_t bytes;            // all of it; SIZE_MAX for what the call refuses
+struct WholeWs { // the workspace of sela_hip_encode_whole_device
+    void* main_workspace;   // the 2048-sample frames' workspace (encode_workspace_bytes), and its bytes
+    void* last_workspace;   // the last frame's any-length workspace (encode_i32_device_workspace_bytes), and its bytes
+    size_t main_bytes, last_bytes;
+    uint8_t* last_frame;    // the last frame's bytes as coded, and their room
+    size_t last_cap;
+    uint64_t* last_offsets; // its two offsets ...
+    uint32_t* last_status;  // ... and its four status words
 };
-WholeLayout whole_layout(uint64_t max_samples, uint32_t channels);
+WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels); // (arguments that whole_workspace_bytes does not refuse)
+size_t whole_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at = nullptr); // SIZE_MAX for what the call refuses
 hipError_t launch_whole_splice(const uint8_t* d_last_frame, const uint64_t* d_last_offsets, const uint32_t* d_last_status, uint32_t channels, uint8_t* d_frames,
     uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last, uint32_t* d_status, hipStream_t stream);
 

@@ -34,23 +34,6 @@ constexpr uint32_t kIndexOneGroupFrames = 4096;  // max_frames up to this: links
 constexpr uint32_t kIndexOneGroupNodes = 5120;   // ... on LDS while the candidates fit (12 bytes each: 60 KiB); beyond, in the workspace
 constexpr int kIndexLinkBlocks = 1024;           // grid of the device-wide link / round / scatter launches (grid-stride)
 
-// The workspace, for a payload of `words` 32-bit words (every word may be a candidate): six arrays of one uint32 per word
-// (stage_pos / stage_next, reused as the two jump arrays once packed; pos; next; rank; map), the scan's counts and the
-// candidate count.
-struct IndexLayout {
-    size_t stage_pos, stage_next, pos, next, rank, map, counts, misc, bytes;
-};
-inline IndexLayout index_layout(uint64_t words)
-{
-    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t arr = up((size_t)words * 4), blocks = (size_t)((words + kIndexChunkWords - 1) / kIndexChunkWords);
-    IndexLayout l;
-    l.stage_pos = 0, l.stage_next = arr, l.pos = 2 * arr, l.next = 3 * arr, l.rank = 4 * arr, l.map = 5 * arr, l.counts = 6 * arr;
-    l.misc = l.counts + up((blocks + 1) * 4);
-    l.bytes = l.misc + 256 + 256; // (+256: the caller's pointer is aligned up to 256 first)
-    return l;
-}
-
 struct IndexWs {
     uint32_t* stage_pos;  // [words] per workgroup, then jump array A
     uint32_t* stage_next; // [words] per workgroup, then jump array B
@@ -61,6 +44,22 @@ struct IndexWs {
     uint32_t* counts;     // [blocks + 1] candidates per workgroup, then their exclusive scan
     uint32_t* n_cand;     // [1]
 };
+// The workspace (sela_workspace.h), for a payload of `words` 32-bit words (every word may be a candidate): six arrays of one
+// uint32 per word, the scan's counts and the candidate count.
+inline IndexWs carve_index(Carve& c, uint64_t words)
+{
+    const uint64_t blocks = (words + kIndexChunkWords - 1) / kIndexChunkWords;
+    IndexWs ws;
+    ws.stage_pos = c.take<uint32_t>(words);
+    ws.stage_next = c.take<uint32_t>(words);
+    ws.pos = c.take<uint32_t>(words);
+    ws.next = c.take<uint32_t>(words);
+    ws.rank = c.take<uint32_t>(words);
+    ws.map = c.take<uint32_t>(words);
+    ws.counts = c.take<uint32_t>(blocks + 1);
+    ws.n_cand = c.take<uint32_t>(1);
+    return ws;
+}
 
 // The host walk's test of one position (sela_hip_index_frames): the frame's end in words, or kIndexNone.  `off` is a word
 // boundary that holds the sync word, so every subframe of the frame is one too: the word form of the header reader, whose
@@ -275,7 +274,10 @@ __global__ __launch_bounds__(kIndexThreads) void k_index_scatter(IndexWs ws, uin
         atomicAdd(n_frames, mine);
 }
 
-size_t index_workspace_bytes(uint64_t payload_bytes) { return index_layout(payload_bytes / 4).bytes; }
+size_t index_workspace_bytes(uint64_t payload_bytes, Carve* at)
+{
+    return measured(at, [&](Carve& c) { carve_index(c, payload_bytes / 4); });
+}
 
 // Everything on `stream`, nothing waited for.  The caller has checked the arguments (payload 4-byte aligned and below 16 GiB,
 // channels 1..255, workspace of index_workspace_bytes()).
@@ -283,17 +285,8 @@ hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32
     uint32_t* d_n_frames, void* d_workspace, hipStream_t stream)
 {
     const uint32_t words = (uint32_t)(payload_bytes / 4), blocks = (uint32_t)(((uint64_t)words + kIndexChunkWords - 1) / kIndexChunkWords);
-    const IndexLayout l = index_layout(words);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    IndexWs ws;
-    ws.stage_pos = reinterpret_cast<uint32_t*>(base + l.stage_pos);
-    ws.stage_next = reinterpret_cast<uint32_t*>(base + l.stage_next);
-    ws.pos = reinterpret_cast<uint32_t*>(base + l.pos);
-    ws.next = reinterpret_cast<uint32_t*>(base + l.next);
-    ws.rank = reinterpret_cast<uint32_t*>(base + l.rank);
-    ws.map = reinterpret_cast<uint32_t*>(base + l.map);
-    ws.counts = reinterpret_cast<uint32_t*>(base + l.counts);
-    ws.n_cand = reinterpret_cast<uint32_t*>(base + l.misc);
+    Carve carve(d_workspace);
+    const IndexWs ws = carve_index(carve, words);
     uint32_t rounds = 0;
     while (rounds < 32 && (1ull << rounds) < max_frames)
         rounds++;

@@ -215,7 +215,8 @@ hipError_t launch_verify_frames(const uint8_t* d_frames, const uint64_t* d_frame
     if (channels == 0 || channels > (uint32_t)kDecMaxWaves)
         return hipErrorInvalidValue;
     const int n_waves = decode_waves(channels);
-    int32_t* ws = reinterpret_cast<int32_t*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    Carve carve(d_workspace); // (launch_decode's workspace: the route's kernel with a compare for its stores)
+    int32_t* const ws = carve_decode(carve, n_frames, channels);
     const size_t lds = verify_lds_bytes(channels);
     if (lds > 64 * 1024) { // above the default dynamic-LDS limit (more than four channels); per device, so every time
         const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_verify_frames), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -14,28 +14,38 @@ namespace sela {
 
 namespace {
 constexpr uint64_t kFrame = SELA_HIP_SAMPLES_PER_FRAME;
-uint64_t up256(uint64_t b) { return (b + 255) & ~(uint64_t)255; }
 } // namespace
 
 // the longest last frame of any track of at most max_samples samples per channel (0: no frame)
 static uint32_t longest_last_frame(uint64_t max_samples) { return (uint32_t)std::min<uint64_t>(max_samples, 2 * kFrame - 1); }
 
-WholeLayout whole_layout(uint64_t max_samples, uint32_t channels)
+// The 2048-sample frames' workspace | the last frame's any-length workspace | the last frame as coded | its head: two offsets
+// and four status words.  (Every shorter track is served from the same pieces: the sizes grow with the frames and with the length.)
+WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels)
 {
-    WholeLayout l = {};
-    const uint64_t frames = sela_hip_whole_frames(max_samples);
-    if (channels == 0 || channels > 255 || frames * sela_hip_signals_per_frame(channels) >= (1ull << 31)) {
-        l.bytes = SIZE_MAX;
-        return l;
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(max_samples), last = std::max(longest_last_frame(max_samples), 1u);
+    WholeWs w;
+    w.main_bytes = encode_workspace_bytes(frames, channels); // (what the launch needs: the same on every device)
+    w.last_bytes = encode_i32_device_workspace_bytes(1, channels, last);
+    Carve main_ws = c.sub(w.main_bytes), last_ws = c.sub(w.last_bytes);
+    w.main_workspace = main_ws.base();
+    w.last_workspace = last_ws.base();
+    if (c.listing()) { // (the two calls' own pieces, where they lie)
+        encode_workspace_bytes(frames, channels, &main_ws);
+        encode_i32_device_workspace_bytes(1, channels, last, false, &last_ws);
     }
-    // (every shorter track is served from the same two pieces: both sizes grow with the frames and with the length)
-    const uint32_t last = std::max(longest_last_frame(max_samples), 1u);
-    l.last_cap = up256(generic_encode_bound_bytes(1, channels, last));
-    l.last_workspace = up256(encode_workspace_bytes((uint32_t)frames, channels)); // (what the launch needs: the same on every device)
-    l.last_frame = l.last_workspace + up256(encode_i32_device_workspace_bytes(1, channels, last));
-    l.last_head = l.last_frame + l.last_cap;
-    l.bytes = (size_t)(l.last_head + 256 + 256); // (the head: two offsets and four status words; + the base's alignment)
-    return l;
+    w.last_cap = (size_t)workspace_up(generic_encode_bound_bytes(1, channels, last));
+    w.last_frame = c.take<uint8_t>(w.last_cap);
+    w.last_offsets = c.take<uint64_t>(2 + 2); // (the head: the offsets, and the status words behind them)
+    w.last_status = reinterpret_cast<uint32_t*>(w.last_offsets + 2);
+    return w;
+}
+
+size_t whole_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at)
+{
+    if (channels == 0 || channels > 255 || sela_hip_whole_frames(max_samples) * sela_hip_signals_per_frame(channels) >= (1ull << 31))
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_whole(c, max_samples, channels); });
 }
 
 // ---- the splice ---------------------------------------------------------------------------------------------------------------
@@ -102,6 +112,6 @@ size_t sela_hip_encode_whole_bound_bytes(uint64_t n_samples, uint32_t channels)
     return (size_t)((frames - 1) * per_frame) + sela_hip_encode_bound_bytes_n(1, channels, last);
 }
 
-size_t sela_hip_encode_whole_workspace_bytes(uint64_t max_samples, uint32_t channels) { return sela::whole_layout(max_samples, channels).bytes; }
+size_t sela_hip_encode_whole_workspace_bytes(uint64_t max_samples, uint32_t channels) { return sela::whole_workspace_bytes(max_samples, channels); }
 
 } // extern "C"

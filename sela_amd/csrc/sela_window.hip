@@ -142,20 +142,22 @@ uint32_t window_cover(uint32_t window_samples) { return (uint32_t)(((uint64_t)wi
 // The dynamic LDS a launch of k_window_frames asks for (sela_hip_debug_window_lds_bytes: tests hold it against the decoder's).
 size_t window_lds_bytes(uint32_t channels) { return decode_lds_bytes_for(channels, decode_waves(channels)); }
 
-// Generic mode's residues, one block per (workgroup, channel) | a flag word per window for the calls that pass no d_window_flags.
-static size_t window_residue_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+// Generic mode's residues, one block per (workgroup, channel) | a flag word per window for the calls that pass no d_window_flags
+// (launch_window_whole's kernels raise flags in the same words).
+WindowWs carve_windows(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
 {
-    return (size_t)n_windows * window_cover(window_samples) * channels * kBlock * sizeof(int32_t);
+    WindowWs w;
+    w.residues = c.take<int32_t>((uint64_t)n_windows * window_cover(window_samples) * channels * kBlock);
+    w.flag_words = c.take<uint32_t>(n_windows);
+    return w;
 }
-size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+// The header's formula (include/sela_hip.h): the two pieces and the base's alignment.  The residues are whole blocks of 8 KiB,
+// so the flag words start where they end and the carve fits (tests/test_workspace_cpu.py holds every shape to that).
+size_t window_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at)
 {
-    return window_residue_bytes(n_windows, window_samples, channels) + (size_t)n_windows * sizeof(uint32_t) + 256;
-}
-// Where a call that passes no d_window_flags keeps them (launch_window_whole's kernels raise flags in the same words).
-uint32_t* window_flag_words(void* d_workspace, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
-{
-    unsigned char* const ws = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    return reinterpret_cast<uint32_t*>(ws + window_residue_bytes(n_windows, window_samples, channels));
+    if (at)
+        carve_windows(*at, n_windows, window_samples, channels);
+    return (size_t)n_windows * window_cover(window_samples) * channels * kBlock * sizeof(int32_t) + (size_t)n_windows * sizeof(uint32_t) + 256;
 }
 
 // Clear, then decode: one serial chain on the caller's stream, capturable.  The arguments have been checked (sela_capi.hip).
@@ -170,8 +172,9 @@ hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame
     if (channels == 0 || channels > (uint32_t)kDecMaxWaves)
         return hipErrorInvalidValue;
     const uint32_t cover = window_cover(window_samples);
-    unsigned char* const ws = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    uint32_t* const flags = d_window_flags ? d_window_flags : window_flag_words(d_workspace, n_windows, window_samples, channels);
+    Carve carve(d_workspace);
+    const WindowWs ws = carve_windows(carve, n_windows, window_samples, channels);
+    uint32_t* const flags = d_window_flags ? d_window_flags : ws.flag_words;
     hipLaunchKernelGGL(k_window_clear, dim3((n_windows + kWindowClearThreads - 1) / kWindowClearThreads), dim3(kWindowClearThreads), 0, stream, d_status, flags, n_windows);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess)
@@ -188,7 +191,7 @@ hipError_t launch_window_frames(const uint8_t* d_frames, const uint64_t* d_frame
         ? (recurrence_form ? 0u : groups)
         : vec_shift_from_for(groups, n_waves, resident_frames(reinterpret_cast<const void*>(k_window_frames), n_waves, lds, kResidencyWindows));
     hipLaunchKernelGGL(k_window_frames, dim3(n_windows, cover), dim3(n_waves * 64), lds, stream, d_frames, d_frame_offsets, n_frames_total, channels, d_windows,
-        window_samples, format, d_out, flags, d_status, reinterpret_cast<int32_t*>(ws), from, synth_priorities);
+        window_samples, format, d_out, flags, d_status, ws.residues, from, synth_priorities);
     return hipGetLastError();
 }
 

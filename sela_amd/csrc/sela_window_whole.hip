@@ -215,28 +215,34 @@ __global__ __launch_bounds__(kTailStoreThreads) void k_tailwin_store(const int32
     }
 }
 
-// Behind launch_window_frames' own share of the workspace (its formula less the base's alignment, rounded up): the copied
-// descriptors | the tails | the subframe records | the decoded subframes; every piece 256-byte aligned.
-struct WindowWholeLayout {
-    uint64_t copies, tails, subs, dec, bytes;
+// launch_window_frames' own pieces | the copied descriptors | the tails | the subframe records | the decoded subframes.
+struct WindowWholeWs {
+    WindowWs frames;
+    sela_hip_window* copies;
+    WindowTail* tails;
+    TailSub* subs;
+    int32_t* dec;
 };
-static WindowWholeLayout window_whole_layout(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+static WindowWholeWs carve_window_whole(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    WindowWholeLayout l;
-    l.copies = up(window_workspace_bytes(n_windows, window_samples, channels) - 256);
-    l.tails = l.copies + up((uint64_t)n_windows * sizeof(sela_hip_window));
-    l.subs = l.tails + up((uint64_t)n_windows * sizeof(WindowTail));
-    l.dec = l.subs + up((uint64_t)n_windows * channels * sizeof(TailSub));
-    l.bytes = l.dec + (uint64_t)n_windows * channels * kTailStride * sizeof(int32_t);
-    return l;
+    WindowWholeWs w;
+    w.frames = carve_windows(c, n_windows, window_samples, channels);
+    w.copies = c.take<sela_hip_window>(n_windows);
+    w.tails = c.take<WindowTail>(n_windows);
+    w.subs = c.take<TailSub>((uint64_t)n_windows * channels);
+    w.dec = c.take<int32_t>((uint64_t)n_windows * channels * kTailStride);
+    return w;
 }
 
-// The header's formula: at least the layout above plus the base's alignment (four roundings of less than 256 bytes each).
-size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+// The header's formula: the existing call's bytes, the four pieces and kWindowWholeSlack -- the four roundings that put each of
+// them on a multiple of 256, less than 256 bytes each (tests/test_workspace_cpu.py holds the carve of every shape to this size).
+constexpr size_t kWindowWholeSlack = 1024;
+size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at)
 {
+    if (at)
+        carve_window_whole(*at, n_windows, window_samples, channels);
     return window_workspace_bytes(n_windows, window_samples, channels)
-        + (size_t)n_windows * (sizeof(sela_hip_window) + sizeof(WindowTail) + (size_t)channels * (sizeof(TailSub) + kTailStride * sizeof(int32_t))) + 1024;
+        + (size_t)n_windows * (sizeof(sela_hip_window) + sizeof(WindowTail) + (size_t)channels * (sizeof(TailSub) + kTailStride * sizeof(int32_t))) + kWindowWholeSlack;
 }
 
 // Plan, the 2048-sample frames, the tails: one serial chain on the caller's stream, capturable.  The arguments have been checked
@@ -250,14 +256,14 @@ hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_
             d_workspace, stream, recurrence_form, synth_priorities);
     if (channels == 0 || channels > kTailChannels)
         return hipErrorInvalidValue;
-    const WindowWholeLayout l = window_whole_layout(n_windows, window_samples, channels);
-    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
-    sela_hip_window* const d_copies = reinterpret_cast<sela_hip_window*>(base + l.copies);
-    WindowTail* const d_tails = reinterpret_cast<WindowTail*>(base + l.tails);
-    TailSub* const d_subs = reinterpret_cast<TailSub*>(base + l.subs);
-    int32_t* const d_dec = reinterpret_cast<int32_t*>(base + l.dec);
+    Carve carve(d_workspace);
+    const WindowWholeWs w = carve_window_whole(carve, n_windows, window_samples, channels);
+    sela_hip_window* const d_copies = w.copies;
+    WindowTail* const d_tails = w.tails;
+    TailSub* const d_subs = w.subs;
+    int32_t* const d_dec = w.dec;
     // the flag words of a call that passes none: where launch_window_frames keeps them, behind its residues (sela_window.hip)
-    uint32_t* const flags = d_window_flags ? d_window_flags : window_flag_words(d_workspace, n_windows, window_samples, channels);
+    uint32_t* const flags = d_window_flags ? d_window_flags : w.frames.flag_words;
     hipLaunchKernelGGL(k_tailwin_plan, dim3((n_windows + kTailPlanThreads - 1) / kTailPlanThreads), dim3(kTailPlanThreads), 0, stream, d_frames, d_frame_offsets, n_frames_total,
         d_windows, n_windows, window_samples, d_copies, d_tails);
     hipError_t err = hipGetLastError();
