@@ -8,7 +8,6 @@ through k_decode_frames and the 32-bit decoder against the oracle's frame decode
 against oracle.lpc_coeffs.  Encoder: blocks of those orders (the constructions of test_gpu_schur_phases.py) in launches of 1, 3
 and 5 frames on k_encode_blocks and both k_encode_teams: order, coefficients and predictor of the trace instantiation and the
 frame bytes of the product; five of them in lossless mode against the model of tests/lossless_model.py."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -16,45 +15,14 @@ import pytest
 from oracle_lib import oracle
 
 import lossless_model as model
-import wide_cases as wc
 from gpu_common import _encode, gpu  # noqa: F401  (fixture and helper)
+from synth_cases import COEF_OVERFLOW, ORDERS, decoder_frames  # (the decoder's frames: built once for every test of the synthesis)
 from test_gpu_schur_phases import _echo, _noise
 
-ORDERS = [1, 2, 3, 31, 32, 33, 60, 61, 62, 63, 64, 65, 66, 99, 100]
-KINDS = ("random", "all -64", "all 63")
-COEF_OVERFLOW = 2
 # encoder blocks: order -> (construction, argument, seed); the oracle's order of each is asserted below
 ECHO_SEEDS = {1: 8, 2: 10, 3: 8, 31: 0, 32: 0, 33: 0, 60: 0, 61: 1, 62: 0, 63: 0, 64: 0, 65: 0, 66: 1}
 NOISE_SEEDS = {99: 178, 100: 120}  # full-scale white noise
 LAUNCHES = (1, 3, 5, 5, 1)         # frames per launch: the fifteen blocks in turn
-
-
-def _q(order, kind, rng):
-    if kind == "random":
-        return rng.integers(-64, 64, order).astype(np.int32)
-    return np.full(order, -64 if kind == "all -64" else 63, np.int32)
-
-
-@functools.lru_cache(maxsize=None)
-def decoder_frames():
-    """tuple of (label, q of channel 0, q of channel 1, frame bytes, the oracle's int16 [2048, 2], its int32 per channel, its flags)"""
-    o = oracle()
-    out = []
-    for order in ORDERS:
-        for kind in KINDS:
-            rng = np.random.default_rng(1000 + order)
-            qs = [_q(order, kind, rng) for _ in range(2)]
-            subs = [(c, 0, c, qs[c], rng.integers(-300, 300, 2048).astype(np.int32)) for c in range(2)]
-            blob = wc.frame_bytes(o, subs)
-            b = np.frombuffer(blob, np.uint8).copy()
-            pcm = np.zeros((2048, 2), np.int16)
-            fl = C.c_uint32(0)
-            assert o._fdec(b, 2, pcm, C.byref(fl)) == len(blob)
-            wide, used = o.frame_decode_i32(blob, 2)
-            assert used == len(blob)
-            pcm.setflags(write=False)
-            out.append((f"order {order}, {kind}", qs[0], qs[1], blob, pcm, wide, fl.value))
-    return tuple(out)
 
 
 @functools.lru_cache(maxsize=None)
@@ -103,14 +71,20 @@ def _stream(frames):
 
 
 @pytest.mark.gpu
-def test_k_decode_frames_at_every_order(gpu):  # noqa: F811
-    from sela_amd import codec
+@pytest.mark.parametrize("form", [0, 1])
+def test_k_decode_frames_at_every_order(gpu, form):  # noqa: F811
+    """Both recurrence forms of k_decode_frames (a launch of 45 frames would see the lonely-wave form alone)."""
+    from sela_amd import capi, codec
 
     frames = decoder_frames()
     stream, offs = _stream(frames)
     dec = codec.Decoder(len(frames), 2)
-    pcm = dec.decode(gpu.from_numpy(stream).cuda(), gpu.from_numpy(offs.view(np.int64)).cuda(), len(frames))
-    gpu.cuda.synchronize()
+    capi.lib().sela_hip_debug_decode_recurrence(form)
+    try:
+        pcm = dec.decode(gpu.from_numpy(stream).cuda(), gpu.from_numpy(offs.view(np.int64)).cuda(), len(frames))
+        gpu.cuda.synchronize()
+    finally:
+        capi.lib().sela_hip_debug_decode_recurrence(-1)
     dec.check()
     got = pcm.cpu().numpy()
     for i, f in enumerate(frames):

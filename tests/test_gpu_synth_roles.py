@@ -10,6 +10,7 @@ import pytest
 import wide_cases as wc
 from gpu_common import _both_decoders, _build_frame, _decode, gpu  # noqa: F401  (fixture and helpers)
 from oracle_lib import oracle
+from synth_cases import _leaves_in_block, _q, _quiet  # (the builders: shared with tests/test_gpu_synth_matrix.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,29 +21,6 @@ LENGTHS = [64, 65, 128, 129, 191, 192, 2049]
 
 def _stream(frames):
     return np.frombuffer(b"".join(frames), np.uint8).copy(), np.cumsum([0] + [len(f) for f in frames]).astype(np.uint64)
-
-
-def _q(order, rng):
-    q = wc.fold_coefficients(order, rng)
-    assert wc.fits_fold(oracle().lpc_coeffs(order, q)), order  # the synthesis starts in the folded form
-    return q
-
-
-def _quiet(n, rng):
-    return rng.integers(-200, 201, n).astype(np.int32)
-
-
-def _leaves_in_block(order, q, block, n, rng):
-    """Residues below 2^23 in size whose SAMPLES reach 2^23 first inside `block`: quiet noise, then a plateau of 2^23 - 1 from
-    the block's tenth sample on (the strong first coefficient of fold_coefficients carries it past the range)."""
-    o = oracle()
-    r = _quiet(n, rng)
-    r[64 * block + 10: 64 * block + 40] = P23 - 1
-    assert np.abs(r.astype(np.int64)).max() < P23
-    s = o.lpc_synth(order, q, r).astype(np.int64)
-    first = int(np.flatnonzero(np.abs(s) >= P23)[0])
-    assert first // 64 == block, (order, block, first)
-    return r
 
 
 def _check_stage(orders, qs, res, with_2048):
@@ -62,15 +40,22 @@ def _check_stage(orders, qs, res, with_2048):
 
 
 def _check_frames(gpu, frames, ch, label, sixteen=True):  # noqa: F811
-    """k_decode_frames (Decoder.decode), and the 32-bit decoders (k_decode_subframes32 offered; the any-length kernel alone) on
-    the same stream, against the oracle."""
+    """k_decode_frames (Decoder.decode) in both recurrence forms, and the 32-bit decoders (k_decode_subframes32 offered; the
+    any-length kernel alone) on the same stream, against the oracle."""
+    from sela_amd import capi
+
     o = oracle()
     stream, offs = _stream(frames)
     if sixteen:
         want = np.stack([o.frame_decode(f, ch)[0] for f in frames])
-        dev = _decode(gpu, stream, offs, ch)
-        for f in range(len(frames)):
-            assert np.array_equal(dev[f], want[f]), (label, f, "k_decode_frames")
+        for form in (0, 1):  # (launches of this size would see the lonely-wave form alone)
+            capi.lib().sela_hip_debug_decode_recurrence(form)
+            try:
+                dev = _decode(gpu, stream, offs, ch)
+            finally:
+                capi.lib().sela_hip_debug_decode_recurrence(-1)
+            for f in range(len(frames)):
+                assert np.array_equal(dev[f], want[f]), (label, f, "k_decode_frames", form)
     want32 = [o.frame_decode_i32(f, ch)[0] for f in frames]
     offered, alone, took = _both_decoders(stream, offs, ch)
     assert took > 0, label  # (the standard kernel decoded them)
