@@ -193,14 +193,31 @@ struct StreamReader {
     }
 };
 
+// What a file's last frame says when it is the long last frame of a whole-track stream (sela_hip.h): its samples per channel, 1 ..
+// 4095 and not 2048, every subframe saying no more than the first; 0 for any other frame.  offsets: the frame's two.
+constexpr size_t kTailSamples = 4095;
+size_t tailFrameSamples(const uint8_t* frames, const uint64_t* offsets, uint32_t channels)
+{
+    const uint64_t one[2] = { 0, offsets[1] - offsets[0] };
+    uint64_t samples[2] = { 0, 0 };
+    const uint32_t largest = sela_hip_index_samples(frames + offsets[0], one, 1, channels, samples);
+    const size_t n = (size_t)samples[1];
+    return n >= 1 && n <= kTailSamples && n != kBlock && largest == n ? n : 0;
+}
+
 // Decode the frame stream that is arriving in sela.frameBytes front to back (payload bytes behind the 15-byte header;
 // fetch(have, payload) brings more of it in and returns the new number of bytes there) into pcm; drain(samples, n) is
 // told whenever more samples are final.  Fills sela.frameOffsets.  Only frames [firstFrame, firstFrame + maxFrames) are
 // decoded (the batch dispatcher cuts a file between workers; frames before the range are only indexed); pcm holds
 // those frames from its start.
+// wholeTrack (the whole file only): the stream is read as a whole-track stream (sela_hip.h).  When the file's last
+// announced frame says a tail's length -- 1 .. 4095 samples and not 2048, no subframe longer -- it is withheld from the streaming
+// job, decoded by one one-shot call on that frame alone once the job has ended, and drained behind the job's samples: the file is
+// read once and every frame decoded once.  pcm then holds 2048 (frames - 1) + that length samples per channel.
 template <typename Fetch, typename Drain>
 void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::PinnedBuffer<int16_t>& pcm, Drain drain, size_t firstFrame = 0,
-    size_t maxFrames = (size_t)-1, size_t firstFeedFrames = kPieceFrames /* the first feed does not wait for a whole piece (a player wants its first samples early) */)
+    size_t maxFrames = (size_t)-1, size_t firstFeedFrames = kPieceFrames /* the first feed does not wait for a whole piece (a player wants its first samples early) */,
+    bool wholeTrack = false)
 {
     const uint32_t channels = sela.selaHeader.channels;
     if (channels == 0)
@@ -213,7 +230,10 @@ void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::
     if (sela.frameBytes.size() < payload)
         sela.frameBytes.resize(payload);
     sela.frameOffsets.assign(stop + 1, 0);
-    pcm.resize(mine * frameSamples);
+    wholeTrack = wholeTrack && firstFrame == 0 && maxFrames == (size_t)-1 && stop > 0;
+    // (the job keeps pcm.data(): the room of the longest tail is there from the start)
+    pcm.resize(mine * frameSamples + (wholeTrack ? (kTailSamples - kBlock) * channels : 0));
+    size_t tailSamples = 0; // of the withheld last frame, per channel
     sela_hip_job* job = nullptr;
     if (sela_hip_decode_begin(&job, channels, (uint32_t)mine, pcm.data()) != SELA_HIP_OK)
         gpuFailure("Decoder");
@@ -221,7 +241,7 @@ void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::
     bool ended = false; // a frame without a sync word: the stream stops there for good
     int rc = SELA_HIP_OK;
     std::vector<uint64_t> local(kPieceFrames + 1);
-    while (rc == SELA_HIP_OK && ((have < payload && indexed < stop && !ended) || fed < indexed)) {
+    while (rc == SELA_HIP_OK && ((have < payload && indexed < stop && !ended) || fed < (tailSamples ? stop - 1 : indexed))) {
         if (have < payload && indexed < stop && !ended) {
             try {
                 have = fetch(have, payload);
@@ -247,13 +267,16 @@ void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::
             }
         }
         const bool last = have == payload || indexed == stop || ended;
-        if (indexed > fed && (indexed - fed >= (fed == std::min(firstFrame, stop) ? std::min<size_t>(firstFeedFrames, kPieceFrames) : kPieceFrames) || last)) {
+        if (wholeTrack && indexed == stop && tailSamples == 0)
+            tailSamples = tailFrameSamples(sela.frameBytes.data(), sela.frameOffsets.data() + (stop - 1), channels);
+        const size_t feedable = tailSamples ? stop - 1 : indexed; // (the job never sees a withheld frame)
+        if (feedable > fed && (feedable - fed >= (fed == std::min(firstFrame, stop) ? std::min<size_t>(firstFeedFrames, kPieceFrames) : kPieceFrames) || last)) {
             uint32_t done = 0;
             const long long t0 = sela_host::ioTrace ? sela_host::ioNow() : 0;
-            rc = sela_hip_decode_feed(job, sela.frameBytes.data(), sela.frameOffsets.data() + fed, (uint32_t)(indexed - fed), &done);
+            rc = sela_hip_decode_feed(job, sela.frameBytes.data(), sela.frameOffsets.data() + fed, (uint32_t)(feedable - fed), &done);
             if (sela_host::ioTrace)
-                sela_host::ioTrace("decode feed", t0, sela_host::ioNow(), indexed - fed);
-            fed = indexed;
+                sela_host::ioTrace("decode feed", t0, sela_host::ioNow(), feedable - fed);
+            fed = feedable;
             if (rc == SELA_HIP_OK)
                 drain(pcm.data(), (size_t)done * frameSamples);
         } else if (firstFeedFrames < kPieceFrames && fed > std::min(firstFrame, stop)) {
@@ -263,7 +286,7 @@ void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::
             if (rc == SELA_HIP_OK)
                 drain(pcm.data(), (size_t)done * frameSamples);
         }
-        if (have == payload && fed >= indexed)
+        if (have == payload && fed >= (tailSamples ? stop - 1 : indexed))
             break;
     }
     // everything is queued: hand finished samples on while the last chunks are decoded and copied out
@@ -289,7 +312,14 @@ void streamDecode(Fetch fetch, file::SelaFile& sela, size_t payload, sela_host::
     if (firstFrame == 0 && maxFrames == (size_t)-1)
         sela.frameBytes.resize((size_t)sela.frameOffsets.back());
     const size_t decoded = indexed > firstFrame ? indexed - firstFrame : 0;
-    pcm.resize(decoded * frameSamples);
+    if (tailSamples) { // the withheld frame, alone, through the one-shot call's any-length route, behind the job's samples
+        const uint64_t at = sela.frameOffsets[stop - 1], one[2] = { 0, sela.frameOffsets[stop] - at };
+        if (sela_hip_decode(sela.frameBytes.data() + at, one, 1, channels, pcm.data() + (stop - 1) * frameSamples) != SELA_HIP_OK)
+            gpuFailure("Decoder");
+        pcm.resize(((stop - 1) * kBlock + tailSamples) * channels);
+    } else {
+        pcm.resize(decoded * frameSamples);
+    }
     drain(pcm.data(), pcm.size());
 }
 
@@ -455,8 +485,8 @@ file::WavFile Decoder::process()
     const size_t payload = selaFile.readHeader(ifStream);
     sela_host::PinnedBuffer<int16_t> pcm;
     try {
-        streamDecode(StreamFetcher{ ifStream, selaFile }, selaFile, payload, pcm, [](const int16_t*, size_t) {});
-    } catch (const data::Exception&) { // frames that do not say 2048?  (decodeOddStream)
+        streamDecode(StreamFetcher{ ifStream, selaFile }, selaFile, payload, pcm, [](const int16_t*, size_t) {}, 0, (size_t)-1, kPieceFrames, true);
+    } catch (const data::Exception&) { // frames that do not say 2048, other than a whole-track stream's last?  (decodeOddStream)
         ifStream.clear();
         ifStream.seekg(SELA_FILE_HEADER_BYTES, std::ios::beg);
         selaFile.frameBytes.resize(payload);
@@ -525,8 +555,8 @@ size_t decodeFile(std::ifstream& in, std::ofstream& out)
     // which can truncate its file, writes while it decodes.)
     sela_host::PinnedBuffer<int16_t> pcm;
     try {
-        streamDecode(StreamFetcher{ in, sela }, sela, payload, pcm, [](const int16_t*, size_t) {});
-    } catch (const data::Exception&) { // frames that do not say 2048?  (decodeOddStream)
+        streamDecode(StreamFetcher{ in, sela }, sela, payload, pcm, [](const int16_t*, size_t) {}, 0, (size_t)-1, kPieceFrames, true);
+    } catch (const data::Exception&) { // frames that do not say 2048, other than a whole-track stream's last?  (decodeOddStream)
         in.clear();
         in.seekg(SELA_FILE_HEADER_BYTES, std::ios::beg);
         sela.frameBytes.resize(payload);
@@ -538,8 +568,9 @@ size_t decodeFile(std::ifstream& in, std::ofstream& out)
     }
     const size_t frames = sela.frameCount(); // (fewer than announced when the stream ended early: a bad sync word)
     (void)announced;
-    file::WavFile::writeHeader(out, sela.selaHeader.sampleRate, (uint16_t)channels, 16, (uint32_t)(frames * kBlock * channels * 2));
-    out.write(reinterpret_cast<const char*>(pcm.data()), (std::streamsize)(frames * kBlock * channels * 2));
+    // (pcm holds the frames' 2048 samples each, or a whole-track stream's samples with its long last frame's)
+    file::WavFile::writeHeader(out, sela.selaHeader.sampleRate, (uint16_t)channels, 16, (uint32_t)(pcm.size() * 2));
+    out.write(reinterpret_cast<const char*>(pcm.data()), (std::streamsize)(pcm.size() * 2));
     return frames;
 }
 
@@ -845,8 +876,8 @@ size_t decodeFile(const std::string& inPath, const std::string& outPath)
                 ahead.need(upTo);
                 return upTo;
             },
-            sela, info.payload, pcm, [&](const int16_t* p, size_t done) { behind.drain(p, done * 2); });
-    } catch (const data::Exception&) { // frames that do not say 2048?  (decodeOddStream)
+            sela, info.payload, pcm, [&](const int16_t* p, size_t done) { behind.drain(p, done * 2); }, 0, (size_t)-1, kPieceFrames, true);
+    } catch (const data::Exception&) { // frames that do not say 2048, other than a whole-track stream's last?  (decodeOddStream)
         ahead.need(info.payload);
         ahead.finish();
         behind.quiesce();
@@ -861,9 +892,11 @@ size_t decodeFile(const std::string& inPath, const std::string& outPath)
         return sela.frameCount();
     }
     ahead.finish();
-    const size_t frames = sela.frameCount(), decodedBytes = frames * frameBytes;
+    // (a whole-track stream's long last frame adds up to 2047 samples per channel to its 2048: the file grows past what was
+    // allocated for it, and finish() ends it where the samples end)
+    const size_t frames = sela.frameCount(), decodedBytes = pcm.size() * 2;
     behind.finish(&decodedBytes);
-    if (frames != info.announced) { // the stream ended early (bad sync word): the header sizes follow what was decoded
+    if (decodedBytes != info.announced * frameBytes) { // the stream ended early (bad sync word), or its last frame is a long one: the header sizes follow what was decoded
         wavHeaderBytes(header, info.header.sampleRate, (uint16_t)channels, 16, (uint32_t)decodedBytes);
         out.writeAt(header, 44, 0);
         out.truncate(44 + decodedBytes);

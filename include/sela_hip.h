@@ -657,6 +657,56 @@ int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint3
 int sela_hip_encode_whole(const int16_t* pcm, uint64_t n_samples, uint32_t channels, uint8_t* frames_out, size_t frames_cap,
     uint64_t* frame_offsets_out /* [frames + 1] */, uint32_t options);
 
+/* ---- a full decode of a whole-track stream: the 2048-sample decoder with the last frame beside it ----------------
+ * sela_hip_decode_n_device and sela_hip_decode take a stream with ONE frame that does not say 2048 down the any-length route,
+ * every frame of it.  These calls read the stream as the window calls above do (5.20).  Let n be the frame count (the payload
+ * form's is found on the device and stays there), L = n - 1 and n_L what L says its length is by sela_hip_index_samples' rule.
+ *   n_L in 1 .. 4095 and not 2048:   S = 2048 (n - 1) + n_L samples per channel.  Samples [0, 2048 (n - 1)) are word for word what
+ *                  sela_hip_decode_device writes for frames 0 .. n - 2, malformed ones included (zeros, SELA_HIP_FLAG_BAD_FRAME);
+ *                  samples [2048 (n - 1), S) are the int16 sela_hip_decode_n_device writes for frame L decoded alone, interleaved at
+ *                  d_pcm_out + 2048 (n - 1) * channels.  A frame L the any-length kernel declines or whose layout the combine rules
+ *                  refuse raises its flag as the window calls list them, and nothing at or past 2048 (n - 1) * channels is written.
+ *                  d_status[3] = 3.
+ *   any other n_L: S = 2048 n, every word written is sela_hip_decode_device's on all n frames, d_status[3] = 1.
+ *   n == 0:        zero status words, *d_n_samples = 0, nothing else written.
+ * *d_n_samples = S always.  Where S > pcm_capacity (samples per channel): SELA_HIP_FLAG_STRIDE, d_status[3] = 0, nothing is decoded
+ * or written.  Nothing at or past min(S, pcm_capacity) * channels is written on any input.  d_status[0] is the OR of the flags,
+ * d_status[1] the number of malformed frames among 0 .. n - 2 (sela_hip_decode_device's count) plus one for a frame L that is not
+ * decoded, whatever its flag, d_status[2] zero.
+ * sela_hip_decode_whole_status_error (host only, no GPU) maps a host copy of the status words, in this order:
+ *   1. SELA_HIP_FLAG_STRIDE                                                 -> SELA_HIP_ECAPACITY
+ *   2. a malformed frame (SELA_HIP_FLAG_BAD_FRAME) or a dry Rice stream (SELA_HIP_FLAG_RICE_OVERRUN)  -> SELA_HIP_EFORMAT
+ *   3. SELA_HIP_FLAG_COEF_OVERFLOW, SELA_HIP_FLAG_Q_RANGE                   -> SELA_HIP_ERANGE
+ *   4. SELA_HIP_FLAG_INTERNAL                                               -> SELA_HIP_ENODEV
+ *   5. otherwise 0.
+ * Scope: 1 .. 8 channels (more: SELA_HIP_EINVAL, as for the window calls), 16-bit output, a last frame of at most 4095 samples.
+ * SELA_HIP_EINVAL also for a null pointer (d_frames and d_pcm_out only where there are frames) and a d_frames that is not 4-byte
+ * aligned, SELA_HIP_ECAPACITY for a smaller workspace, as sela_hip_decode_n_device; the payload form adds
+ * sela_hip_index_frames_device's checks.  Errors are found before a device is asked for, and nothing is enqueued.
+ * Asynchronous on `stream`: no allocation, no host wait, no host read of device data; the launches are shaped by n_frames /
+ * max_frames and channels alone, so a stream being captured into a HIP graph may take the call.  Launches: a plan kernel of one
+ * thread; the 2048-sample decoder on `stream`, on the plan's count; the last frame's decode and store on a stream of the library's
+ * own between two events, forked behind the plan and joined at the end (inside a capture the side stream joins and leaves it).
+ *   workspace = sela_hip_decode_workspace_bytes(max_frames, channels) + channels * (16 + 4 * 4096) + 1024
+ * (the 2048-sample decoder's; per channel of the last frame a record and 4096 decoded 32-bit samples; the plan's record of L, its
+ * count of frames and alignment); the payload form needs sela_hip_index_workspace_bytes(payload_bytes, max_frames) more.
+ * sela_hip_decode_whole: the same reading of HOST bytes, synchronous.  Frames 0 .. n - 2 go where sela_hip_decode sends a stream of
+ * 2048-sample frames, the last frame through the any-length route's one-shot decode on a context of its own, past the coalescer; a
+ * thread with a streaming job open is served by that route alone, and the job is left alone.  *n_samples = S (0 after an argument
+ * error).  For a whole-track stream -- frames of 2048 samples, with or without a long last one -- it returns 0 where sela_hip_decode
+ * returns 0, with the same bytes in [0, S * channels); otherwise the first code in the order above (SELA_HIP_ECAPACITY: pcm_capacity
+ * < S, nothing written).  A stream with another odd frame is malformed here (SELA_HIP_EFORMAT) and sela_hip_decode's to decode. */
+size_t sela_hip_decode_whole_workspace_bytes(uint32_t max_frames, uint32_t channels);
+int sela_hip_decode_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t n_frames, uint32_t channels,
+    int16_t* d_pcm_out, uint64_t pcm_capacity /* samples per channel */, uint64_t* d_n_samples /* [1] */, uint32_t* d_status /* [4] */, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+int sela_hip_decode_whole_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, int16_t* d_pcm_out,
+    uint64_t pcm_capacity /* samples per channel */, uint64_t* d_n_samples /* [1] */, uint64_t* d_frame_offsets /* [max_frames + 1] */, uint32_t* d_n_frames /* [1] */,
+    uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_decode_whole_status_error(const uint32_t* status /* [4], host copy */);
+int sela_hip_decode_whole(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames + 1] */, uint32_t n_frames, uint32_t channels, int16_t* pcm_out,
+    uint64_t pcm_capacity /* samples per channel */, uint64_t* n_samples);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

@@ -45,6 +45,8 @@ EXPORTS = [
     "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
     "sela_hip_whole_frames", "sela_hip_whole_frame", "sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes",
     "sela_hip_encode_whole_device", "sela_hip_encode_whole",
+    "sela_hip_decode_whole_workspace_bytes", "sela_hip_decode_whole_device", "sela_hip_decode_whole_payload_device", "sela_hip_decode_whole_status_error",
+    "sela_hip_decode_whole",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
@@ -60,7 +62,7 @@ DEBUG_EXPORTS = [
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
-                   "encode_whole", "encode_split")
+                   "encode_whole", "encode_split", "decode_whole")
 
 
 class Trace(C.Structure):
@@ -214,6 +216,16 @@ def lib() -> C.CDLL:
     L.sela_hip_encode_whole_device.restype = C.c_int
     L.sela_hip_encode_whole.argtypes = [vp, u64, u32, vp, sz, vp, u32]
     L.sela_hip_encode_whole.restype = C.c_int
+    L.sela_hip_decode_whole_workspace_bytes.argtypes = [u32, u32]
+    L.sela_hip_decode_whole_workspace_bytes.restype = sz
+    L.sela_hip_decode_whole_device.argtypes = [vp, vp, u32, u32, vp, u64, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_whole_device.restype = C.c_int
+    L.sela_hip_decode_whole_payload_device.argtypes = [vp, sz, u32, u32, vp, u64, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_whole_payload_device.restype = C.c_int
+    L.sela_hip_decode_whole_status_error.argtypes = [vp]
+    L.sela_hip_decode_whole_status_error.restype = C.c_int
+    L.sela_hip_decode_whole.argtypes = [vp, vp, u32, u32, vp, u64, vp]
+    L.sela_hip_decode_whole.restype = C.c_int
     L.sela_hip_encode_status_error.argtypes = [vp]
     L.sela_hip_encode_status_error.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]

@@ -760,6 +760,96 @@ def encode_whole_host(pcm: np.ndarray, lossless: bool = False):
     return frames[: int(offs[n_frames])].copy(), offs
 
 
+class WholeDecoder:
+    """sela_hip_decode_whole_device: a full decode of a whole-track stream of up to max_frames frames -- frames of
+    2048 samples on the 2048-sample decoder and the long last frame (1 .. 4095 samples) beside them, behind them in the PCM.  Owns
+    its outputs and its workspace on the current device (or `device`); every call is asynchronous on the current stream,
+    overwrites them, and can be captured into a graph.  `capacity` (samples per channel) defaults to the most such a stream holds."""
+
+    def __init__(self, max_frames: int, channels: int, device=None, capacity=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels = max_frames, channels
+        self.capacity = max_frames * BLOCK + (BLOCK - 1 if max_frames else 0) if capacity is None else capacity
+        with torch.cuda.device(self.device):
+            self.pcm = torch.empty((max(self.capacity, 1), channels), dtype=torch.int16, device=self.device)
+            self.n_samples = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_decode_whole_workspace_bytes(max_frames, channels))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def decode(self, frames, offsets, n_frames: int, capacity=None):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> (pcm int16 [capacity, channels],
+        n_samples int64 [1]), the decoder's own buffers: the stream's samples are pcm[: n_samples[0]]."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        capacity = self.capacity if capacity is None else capacity
+        assert capacity <= self.capacity
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_whole_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.pcm.data_ptr(), capacity, self.n_samples.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.pcm, self.n_samples
+
+    def decode_payload(self, payload, max_frames=None, capacity=None):
+        """Index and decode a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count stays on
+        the device.  -> (pcm, n_samples int64 [1], frame_offsets int64 [max_frames + 1], count int32 [1]).  The workspace grows to
+        the largest payload seen (make one call before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        capacity = self.capacity if capacity is None else capacity
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames and capacity <= self.capacity
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_decode_whole_workspace_bytes(max_frames, self.channels))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_whole_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.pcm.data_ptr(), capacity, self.n_samples.data_ptr(),
+            self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
+            self.payload_workspace.numel(), stream))
+        return self.pcm, self.n_samples, self.frame_offsets[: max_frames + 1], self.count
+
+    def route(self) -> int:
+        """Waits for the last call -> 0 nothing decoded, 1 the 2048-sample decoder alone, 3 with the long last frame beside it."""
+        return int(self.status[3].item())
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with sela_hip_decode_whole_status_error's code."""
+        capi.check(decode_whole_status_error(self.status.cpu().numpy()))
+
+
+def decode_whole_status_error(status) -> int:
+    """sela_hip_decode_whole_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_decode_whole_status_error(st.ctypes.data))
+
+
+def decode_whole_host(frames: np.ndarray, offsets: np.ndarray, channels: int, capacity=None, check: bool = True):
+    """sela_hip_decode_whole on numpy arrays -> (pcm int16 [capacity, channels], n_samples, the call's code): the stream's samples
+    are pcm[:n_samples].  capacity (samples per channel) defaults to what a stream of that many frames can hold; check: raise
+    SelaHipError on a code other than 0."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    capacity = n_frames * BLOCK + (BLOCK - 1 if n_frames else 0) if capacity is None else capacity
+    pcm = np.zeros((max(capacity, 1), channels), np.int16)
+    n_samples = np.zeros(1, np.uint64)
+    rc = int(lib.sela_hip_decode_whole(fr.ctypes.data, offs.ctypes.data, n_frames, channels, pcm.ctypes.data, capacity, n_samples.ctypes.data))
+    if check:
+        capi.check(rc)
+    return pcm, int(n_samples[0]), rc
+
+
 def decode_host(frames: np.ndarray, offsets: np.ndarray, channels: int) -> np.ndarray:
     """-> int16 [n_frames, 2048, channels] for a stream of 2048-sample frames; for any other stream int16 [total samples,
     channels], frame f's samples from index_samples()[0][f] on."""

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sela_coalescer.h"
+#include "sela_decode_whole_plan.h"
 #include "sela_host.h"
 #include "sela_lease.h"
 
@@ -2109,6 +2110,7 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
             return -1;
         bytes = carve_encode_split(at, c, a32 - c, b).end;
         break;
+    case SELA_HIP_WORKSPACE_DECODE_WHOLE: bytes = sela::decode_whole_workspace_bytes(a32, b, &at); break;
     default: return -1;
     }
     return bytes == SIZE_MAX ? -1 : pieces.count;
@@ -2580,6 +2582,149 @@ int sela_hip_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (standard || largest == 0)
         return fail(rc, first_error); // (malformed in the ordinary sense)
     return sela::generic_decode(frames, frame_offsets, n_frames, channels, nullptr, largest, nullptr, pcm_out, sample_offsets.data());
+}
+
+// ---- a full decode of a whole-track stream (the plan: sela_decode_whole_plan.h, the kernels: sela_window_whole.hip) ----
+size_t sela_hip_decode_whole_workspace_bytes(uint32_t max_frames, uint32_t channels) { return sela::decode_whole_workspace_bytes(max_frames, channels); }
+
+extern "C++" {
+namespace {
+// sela_hip_decode_whole_device / sela_hip_decode_whole_payload_device: the forms of the any-length calls (FramesForm, PayloadForm),
+// the window calls' channels.  The launch: the plan on `stream`; the last frame's two kernels on WholeFork's side stream, forked
+// behind the plan; the 2048-sample decoder on `stream` beside them, on the plan's count; the join.
+template <typename Form>
+int decode_whole_call(const Form& form, uint32_t channels, int16_t* d_pcm_out, uint64_t pcm_capacity, uint64_t* d_n_samples, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    const auto formula = [](uint32_t max_frames, uint32_t ch, uint32_t) { return sela::decode_whole_workspace_bytes(max_frames, ch); };
+    const DeviceCallOf<decltype(formula)> c = { "decode_whole", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            if (channels == 0 || channels > 8)
+                return fail(SELA_HIP_EINVAL, "channels must be in 1..8: the last frame is decoded by the window calls' kernels (more channels: sela_hip_decode_n_device)");
+            int rc = need_pointers(d_status && d_n_samples && d_workspace && (!n_frames || d_pcm_out));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_pcm_out & 1) || ((uintptr_t)d_n_samples & 7) || ((uintptr_t)d_status & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_pcm_out must be 2-byte aligned, d_n_samples 8-byte aligned and d_status 4-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            sela::Carve carve(d_ws);
+            const sela::DecodeWholeWs w = sela::carve_decode_whole(carve, max_frames, channels);
+            const hipStream_t st = c.stream;
+            int rc = launched(sela::launch_decode_whole_plan(d_frames, d_frame_offsets, max_frames, d_n_found, pcm_capacity, w, d_n_samples, d_status, st), "decode_whole plan");
+            if (rc != SELA_HIP_OK || max_frames == 0)
+                return rc;
+            int dev = -1;
+            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+                return fail(SELA_HIP_ENODEV, "decode_whole: no current device");
+            WholeFork& wf = whole_fork();
+            std::lock_guard<std::mutex> lock(wf.mu);
+            if (!wf.ready(dev))
+                return fail(SELA_HIP_ENODEV, "decode_whole: no side stream");
+            const hipStream_t side = wf.side[dev];
+            hipError_t e = hipEventRecord(wf.forked[dev], st);
+            if (e == hipSuccess)
+                e = hipStreamWaitEvent(side, wf.forked[dev], 0);
+            if (e != hipSuccess)
+                return fail_hip(e, "decode_whole: fork");
+            // the last frame on the side stream: memory disjoint from what the 2048-sample decoder writes ...
+            rc = launched(sela::launch_decode_whole_tail(d_frames, d_frame_offsets, channels, w, d_pcm_out, d_status, side), "decode_whole tail");
+            if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
+                rc = fail_hip(e, "decode_whole: join");
+            // ... beside it frames 0 .. n - 2 (or all n), on the plan's count; the status words are the plan's, so they are not zeroed
+            // (no priorities: the launch does not have the device to itself) ...
+            if (rc == SELA_HIP_OK)
+                rc = launched(sela::launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, w.fast_workspace, st, nullptr, nullptr, nullptr,
+                                  g_recurrence_form, 0, w.fast_frames, false),
+                    "decode_whole launch");
+            // ... and the join (also after a failure in between: a side stream that has joined a capture must leave it)
+            if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
+                rc = fail_hip(e, "decode_whole: join");
+            if (rc == SELA_HIP_OK && !stream_is_capturing(st))
+                flights().note(dev, st);
+            return rc;
+        });
+}
+
+// the codes of two halves of one stream, in sela_hip_decode_whole_status_error's order
+int first_in_order(int a, int b)
+{
+    for (const int code : { SELA_HIP_ECAPACITY, SELA_HIP_EFORMAT, SELA_HIP_ERANGE, SELA_HIP_ENODEV })
+        if (a == code || b == code)
+            return code;
+    return a != SELA_HIP_OK ? a : b;
+}
+} // namespace
+} // extern "C++"
+
+int sela_hip_decode_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* d_pcm_out, uint64_t pcm_capacity,
+    uint64_t* d_n_samples, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_whole_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, d_pcm_out, pcm_capacity, d_n_samples, d_status, d_workspace, workspace_bytes, stream);
+}
+
+int sela_hip_decode_whole_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, int16_t* d_pcm_out, uint64_t pcm_capacity,
+    uint64_t* d_n_samples, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return decode_whole_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, d_pcm_out, pcm_capacity, d_n_samples, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+// The order is the header's: capacity, format (a malformed frame or a dry Rice stream), range, internal.  The flags alone: status[1]
+// counts a last frame that was declined for its coefficients too, which is a matter of range.
+int sela_hip_decode_whole_status_error(const uint32_t* status)
+{
+    if (!status)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    return sela::judge_decode(status[0], SELA_HIP_FLAG_STRIDE | sela::kJudgeJob | SELA_HIP_FLAG_INTERNAL, status[3] == sela::kWholeRouteTail ? sela::kRouteDevice32 : sela::kRouteFast,
+        "decode_whole");
+}
+
+// Host pointers, synchronous: the plan on the caller's bytes; frames 0 .. n - 2 where sela_hip_decode sends 2048-sample frames, the
+// last frame through the any-length route's one-shot decode on its own leased context, past the coalescer.  A thread with a
+// streaming job open gets both from that route, which leaves the job alone.
+int sela_hip_decode_whole(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, int16_t* pcm_out, uint64_t pcm_capacity,
+    uint64_t* n_samples)
+{
+    if (channels == 0 || channels > 8)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..8 (more channels: sela_hip_decode)");
+    if (!n_samples || (n_frames && (!frames || !frame_offsets || !pcm_out)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    *n_samples = 0;
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const sela::DecodeWholePlan plan = sela::plan_decode_whole(frames, frame_offsets, n_frames, pcm_capacity);
+    *n_samples = plan.samples;
+    if (plan.flags & SELA_HIP_FLAG_STRIDE)
+        return fail(SELA_HIP_ECAPACITY, "pcm_capacity is smaller than the stream's samples per channel (*n_samples)");
+    int rc_front = SELA_HIP_OK;
+    if (plan.fast_frames) {
+        if (g_lease.held && g_lease.held->job_open) {
+            std::vector<uint64_t> sample_offsets((size_t)plan.fast_frames + 1);
+            for (uint32_t f = 0; f <= plan.fast_frames; f++)
+                sample_offsets[f] = (uint64_t)SELA_HIP_SAMPLES_PER_FRAME * f;
+            rc_front = sela::generic_decode(frames, frame_offsets, plan.fast_frames, channels, nullptr, SELA_HIP_SAMPLES_PER_FRAME, nullptr, pcm_out, sample_offsets.data());
+        } else {
+            rc_front = decode_standard(frames, frame_offsets, plan.fast_frames, channels, pcm_out);
+        }
+    }
+    if (plan.route != sela::kWholeRouteTail)
+        return rc_front;
+    const std::string front_error = rc_front != SELA_HIP_OK ? std::string(sela_hip_last_error()) : std::string();
+    const uint64_t at = frame_offsets[plan.tail.frame];
+    const uint64_t last_offsets[2] = { 0, frame_offsets[plan.tail.frame + 1] - at }, last_samples[2] = { 0, plan.tail.n };
+    // (the stride is the longest subframe's, as sela_hip_decode finds it: a frame whose channels disagree is the combine's to refuse)
+    const uint32_t largest = sela::generic_index_samples(frames + at, last_offsets, 1, channels, nullptr, nullptr);
+    const int rc_last = largest == 0 ? fail(SELA_HIP_EFORMAT, "malformed frame stream (the last frame's header walk breaks)")
+                                     : sela::generic_decode(frames + at, last_offsets, 1, channels, nullptr, largest, nullptr,
+                                           pcm_out + (size_t)SELA_HIP_SAMPLES_PER_FRAME * plan.tail.frame * channels, last_samples);
+    const int rc = first_in_order(rc_front, rc_last);
+    if (rc != SELA_HIP_OK && rc == rc_front && rc != rc_last)
+        return fail(rc, front_error);
+    return rc;
 }
 
 size_t sela_hip_encode_bound_bytes_n(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel)

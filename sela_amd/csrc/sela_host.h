@@ -60,6 +60,22 @@ hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
 
+// ---- sela_window_whole.hip: a full decode of a whole-track stream ------------------------------------------------
+struct WindowTail;
+struct DecodeWholeWs { // the workspace of sela_hip_decode_whole_device
+    void* fast_workspace;   // launch_decode's (decode_workspace_bytes)
+    WindowTail* tail;       // the long last frame as k_tailwin_decode is told of it, or an empty record
+    uint32_t* fast_frames;  // launch_decode's count of frames
+    void* subs;             // a record per subframe of the last frame ...
+    int32_t* dec;           // ... and its 4096 decoded 32-bit samples
+};
+DecodeWholeWs carve_decode_whole(Carve& c, uint32_t max_frames, uint32_t channels);
+size_t decode_whole_workspace_bytes(uint32_t max_frames, uint32_t channels, Carve* at = nullptr);
+hipError_t launch_decode_whole_plan(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint64_t pcm_capacity,
+    const DecodeWholeWs& w, uint64_t* d_n_samples, uint32_t* d_status, hipStream_t stream);
+hipError_t launch_decode_whole_tail(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t channels, const DecodeWholeWs& w, int16_t* d_pcm_out,
+    uint32_t* d_status, hipStream_t stream);
+
 // ---- sela_whole.hip: a whole track with its tail ---------------------------------------------------------------
 struct WholeWs { // the workspace of sela_hip_encode_whole_device
     void* main_workspace;   // the 2048-sample frames' workspace (encode_workspace_bytes), and its bytes

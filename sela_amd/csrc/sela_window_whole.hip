@@ -1,4 +1,5 @@
-// sela_window_whole.hip -- sample windows that reach the long last frame of a whole-track stream (gfx950).
+// sela_window_whole.hip -- sample windows that reach the long last frame of a whole-track stream (gfx950), and, at
+// the end of the file, the full decode of such a stream on the same last-frame kernel.
 //
 // A whole-track stream (5.19) is 2048-sample frames and ONE last frame of 1 .. 4095 samples.  Frame f still starts at sample
 // 2048 f, so k_window_frames (sela_window.hip) keeps its arithmetic and its frames; the last frame is the any-length decoder's
@@ -28,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sela_host.h"
+#include "sela_decode_whole_plan.h"
 #include "sela_window_tail.h"
 
 #include "sela_synth.h"
@@ -123,49 +125,72 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     }
 }
 
+// What thread 0 of a store makes of a frame's records: k_interleave16's list of writes (src/frame/frame_decoder.cpp:17-69) --
+// independent subframes first, then dependent ones in subframe order -- under its rules: the channel and the parent exist, the
+// parent is long enough, every channel ends at the length n_frame that the frame's first subframe says.  Returns the frame's flags;
+// ok == 0: the decode declined a subframe or the rules refuse the layout, and nothing is to be stored.
+struct TailStoreList {
+    uint32_t sub[kTailChannels], n[kTailChannels], dst[kTailChannels], parent[kTailChannels], cnt[kTailChannels];
+    uint32_t ops, ok;
+};
+__device__ inline uint32_t tail_store_list(const TailSub* __restrict__ inf, uint32_t channels /* <= kTailChannels */, uint32_t n_frame, TailStoreList& l)
+{
+    uint32_t flags = 0;
+    bool declined = false;
+    for (uint32_t c = 0; c < channels; c++) {
+        l.cnt[c] = 0;
+        declined |= !inf[c].ok;
+        flags |= inf[c].flags;
+    }
+    bool bad = false;
+    uint32_t k = 0;
+    for (uint32_t type = 0; type < 2 && !declined; type++)
+        for (uint32_t c = 0; c < channels; c++) {
+            const TailSub si = inf[c];
+            if (si.type != type)
+                continue;
+            if (si.channel >= channels || (type == 1 && (si.parent >= channels || l.cnt[si.parent] < si.n))) {
+                bad = true;
+                continue;
+            }
+            l.sub[k] = c, l.n[k] = si.n, l.dst[k] = si.channel, l.parent[k] = type == 1 ? si.parent : kTailNoParent;
+            k++;
+            l.cnt[si.channel] = si.n;
+        }
+    for (uint32_t c = 0; c < channels && !declined; c++)
+        bad |= l.cnt[c] != n_frame;
+    if (bad)
+        flags |= SELA_HIP_FLAG_BAD_FRAME;
+    l.ops = k, l.ok = declined || bad ? 0u : 1u;
+    return flags;
+}
+
+// Sample i of every channel of the frame, by the list, into column t of the table (32-bit: narrowed where it is stored).
+__device__ inline void tail_store_sample(const int32_t* __restrict__ fd, const TailStoreList& l, uint32_t i, int32_t (*tab)[kTailStoreThreads], uint32_t t)
+{
+    for (uint32_t k = 0; k < l.ops; k++) {
+        if (i >= l.n[k])
+            continue;
+        int32_t v = fd[(size_t)l.sub[k] * kTailStride + i];
+        const uint32_t p = l.parent[k];
+        if (p != kTailNoParent)
+            v = (int32_t)((uint32_t)tab[p][t] - (uint32_t)v);
+        tab[l.dst[k]][t] = v;
+    }
+}
+
 __global__ __launch_bounds__(kTailStoreThreads) void k_tailwin_store(const int32_t* __restrict__ dec_ws, const TailSub* __restrict__ subs, const WindowTail* __restrict__ tails,
     uint32_t channels /* <= kTailChannels */, uint32_t window_samples, uint32_t format, void* __restrict__ out, uint32_t* __restrict__ window_flags, uint32_t* __restrict__ status)
 {
     __shared__ int32_t tab[kTailChannels][kTailStoreThreads];
-    __shared__ uint32_t op_sub[kTailChannels], op_n[kTailChannels], op_dst[kTailChannels], op_parent[kTailChannels];
-    __shared__ uint32_t cnt[kTailChannels];
-    __shared__ uint32_t s_ops, s_ok;
+    __shared__ TailStoreList list;
     const uint32_t w = blockIdx.x;
     const WindowTail tl = tails[w];
     if (tl.lo >= tl.hi)
         return;
     const uint32_t t = threadIdx.x;
     if (t == 0) {
-        const TailSub* const inf = subs + (size_t)w * channels;
-        uint32_t flags = 0;
-        bool declined = false;
-        for (uint32_t c = 0; c < channels; c++) {
-            cnt[c] = 0;
-            declined |= !inf[c].ok;
-            flags |= inf[c].flags;
-        }
-        // k_interleave16's list (src/frame/frame_decoder.cpp:17-69) and its rules: the channel and the parent exist, the parent is
-        // long enough, every channel ends at the length the frame's first subframe says
-        bool bad = false;
-        uint32_t k = 0;
-        for (uint32_t type = 0; type < 2 && !declined; type++)
-            for (uint32_t c = 0; c < channels; c++) {
-                const TailSub si = inf[c];
-                if (si.type != type)
-                    continue;
-                if (si.channel >= channels || (type == 1 && (si.parent >= channels || cnt[si.parent] < si.n))) {
-                    bad = true;
-                    continue;
-                }
-                op_sub[k] = c, op_n[k] = si.n, op_dst[k] = si.channel, op_parent[k] = type == 1 ? si.parent : kTailNoParent;
-                k++;
-                cnt[si.channel] = si.n;
-            }
-        for (uint32_t c = 0; c < channels && !declined; c++)
-            bad |= cnt[c] != tl.n;
-        if (bad)
-            flags |= SELA_HIP_FLAG_BAD_FRAME;
-        s_ops = k, s_ok = declined || bad ? 0u : 1u;
+        const uint32_t flags = tail_store_list(subs + (size_t)w * channels, channels, tl.n, list);
         if (flags) {
             atomicOr(&status[0], flags);
             if (flags & SELA_HIP_FLAG_BAD_FRAME)
@@ -175,9 +200,9 @@ __global__ __launch_bounds__(kTailStoreThreads) void k_tailwin_store(const int32
         }
     }
     __syncthreads();
-    if (!s_ok)
+    if (!list.ok)
         return;
-    const uint32_t ops = s_ops, n_share = tl.hi - tl.lo;
+    const uint32_t n_share = tl.hi - tl.lo;
     const int32_t* const fd = dec_ws + (size_t)w * channels * kTailStride;
     const bool planar = format == SELA_HIP_WINDOW_F32_PLANAR;
     int16_t* const out16 = static_cast<int16_t*>(out) + ((size_t)w * window_samples + tl.lo) * channels; // [window][sample][channel]
@@ -185,16 +210,7 @@ __global__ __launch_bounds__(kTailStoreThreads) void k_tailwin_store(const int32
     for (uint32_t base = 0; base < n_share; base += kTailStoreThreads) {
         const uint32_t j = base + t;
         if (j < n_share) {
-            const uint32_t i = tl.s0 + j; // (below tl.n: window_tail_share)
-            for (uint32_t k = 0; k < ops; k++) {
-                if (i >= op_n[k])
-                    continue;
-                int32_t v = fd[(size_t)op_sub[k] * kTailStride + i];
-                const uint32_t p = op_parent[k];
-                if (p != kTailNoParent)
-                    v = (int32_t)((uint32_t)tab[p][t] - (uint32_t)v);
-                tab[op_dst[k]][t] = v;
-            }
+            tail_store_sample(fd, list, tl.s0 + j /* (below tl.n: window_tail_share) */, tab, t);
             if (planar)
 #pragma clang loop vectorize(disable) interleave(disable) // (one dword per store: d_out has a float's alignment and no more)
                 for (uint32_t c = 0; c < channels; c++)
@@ -275,6 +291,106 @@ hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_
         return err;
     hipLaunchKernelGGL(k_tailwin_decode, dim3(n_windows, channels), dim3(64), 0, stream, d_frames, d_frame_offsets, channels, d_tails, d_dec, d_subs);
     hipLaunchKernelGGL(k_tailwin_store, dim3(n_windows), dim3(kTailStoreThreads), 0, stream, d_dec, d_subs, d_tails, channels, window_samples, format, d_out, flags, d_status);
+    return hipGetLastError();
+}
+
+// ---- a full decode of a whole-track stream: sela_hip_decode_whole_device ------------------------------------------
+// The 2048-sample decoder on frames 0 .. n - 2 and, beside it on a second stream, the long last frame: k_tailwin_decode as it is,
+// on one "window" whose share is the whole frame, and a store of all its samples behind the others'.
+//
+//   k_whole_plan    one thread.  plan_decode_whole (sela_decode_whole_plan.h) on the device's bytes and count: the fast decoder's
+//                   frame count, the WindowTail of L (or an empty one), *d_n_samples and all four status words.
+//   k_whole_store   kWholeStoreBlocks workgroups, each with 256 samples of the frame (k_tailwin_store's table is 256 columns: a
+//                   frame of 4095 samples in one workgroup would be sixteen rounds behind one another).  Every workgroup makes
+//                   the list for itself; the first one reports the flags.  A declined frame stores nothing.
+constexpr uint32_t kWholeStoreBlocks = kTailStride / kTailStoreThreads;
+
+__global__ __launch_bounds__(64) void k_whole_plan(const uint8_t* __restrict__ frames, const uint64_t* __restrict__ frame_offsets, uint32_t n_frames,
+    const uint32_t* __restrict__ n_found /* or null: n_frames is the count */, uint64_t pcm_capacity, WindowTail* __restrict__ tail, uint32_t* __restrict__ fast_frames,
+    uint64_t* __restrict__ n_samples, uint32_t* __restrict__ status)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0)
+        return;
+    const uint32_t n = n_found ? min(*n_found, n_frames) : n_frames;
+    const DecodeWholePlan p = plan_decode_whole(frames, frame_offsets, n, pcm_capacity);
+    *tail = p.tail;
+    *fast_frames = p.fast_frames;
+    *n_samples = p.samples;
+    status[0] = p.flags, status[1] = 0, status[2] = 0, status[3] = p.route;
+}
+
+__global__ __launch_bounds__(kTailStoreThreads) void k_whole_store(const int32_t* __restrict__ dec_ws, const TailSub* __restrict__ subs, const WindowTail* __restrict__ tail,
+    uint32_t channels /* <= kTailChannels */, int16_t* __restrict__ pcm_out, uint32_t* __restrict__ status)
+{
+    __shared__ int32_t tab[kTailChannels][kTailStoreThreads];
+    __shared__ TailStoreList list;
+    const WindowTail tl = *tail;
+    const uint32_t base = blockIdx.x * kTailStoreThreads;
+    if (tl.lo >= tl.hi || base >= tl.n) // no long last frame, or none of its samples here (the first workgroup always has some)
+        return;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) {
+        const uint32_t flags = tail_store_list(subs, channels, tl.n, list);
+        if (flags && blockIdx.x == 0) { // status[1] counts L whatever it is declined for: none of it is decoded
+            atomicOr(&status[0], flags);
+            atomicAdd(&status[1], 1u);
+        }
+    }
+    __syncthreads();
+    if (!list.ok)
+        return;
+    const uint32_t here = min(kTailStoreThreads, tl.n - base);
+    int16_t* const ob = pcm_out + ((size_t)SELA_HIP_SAMPLES_PER_FRAME * tl.frame + base) * channels; // frame L starts at sample 2048 L
+    if (t < here)
+        tail_store_sample(dec_ws, list, base + t, tab, t);
+    __syncthreads();
+    for (uint32_t e = t; e < here * channels; e += kTailStoreThreads) { // consecutive threads store consecutive int16
+        const uint32_t s = e / channels, c = e - s * channels;
+        ob[e] = (int16_t)(uint16_t)tab[c][s];
+    }
+}
+
+// The fast decoder's workspace | the WindowTail of L | the fast decoder's frame count | the subframe records | the decoded subframes.
+DecodeWholeWs carve_decode_whole(Carve& c, uint32_t max_frames, uint32_t channels)
+{
+    DecodeWholeWs w;
+    Carve fast = c.sub(decode_workspace_bytes(max_frames, channels));
+    w.fast_workspace = fast.base();
+    if (c.listing()) // (the decoder's own piece, where it lies)
+        decode_workspace_bytes(max_frames, channels, &fast);
+    w.tail = c.take<WindowTail>(1);
+    w.fast_frames = c.take<uint32_t>(1);
+    w.subs = c.take<TailSub>(channels);
+    w.dec = c.take<int32_t>((uint64_t)channels * kTailStride);
+    return w;
+}
+
+// The header's formula: the fast decoder's bytes, a record and 4096 samples per channel, and kDecodeWholeSlack -- the four roundings
+// that put each piece on a multiple of 256 with the two small pieces themselves (tests/test_decode_whole_cpu.py holds the carve
+// of every shape to this size).
+constexpr size_t kDecodeWholeSlack = 1024;
+size_t decode_whole_workspace_bytes(uint32_t max_frames, uint32_t channels, Carve* at)
+{
+    if (at)
+        carve_decode_whole(*at, max_frames, channels);
+    return decode_workspace_bytes(max_frames, channels) + (size_t)channels * (sizeof(TailSub) + kTailStride * sizeof(int32_t)) + kDecodeWholeSlack;
+}
+
+hipError_t launch_decode_whole_plan(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint64_t pcm_capacity,
+    const DecodeWholeWs& w, uint64_t* d_n_samples, uint32_t* d_status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_whole_plan, dim3(1), dim3(64), 0, stream, d_frames, d_frame_offsets, max_frames, d_n_found, pcm_capacity, w.tail, w.fast_frames, d_n_samples,
+        d_status);
+    return hipGetLastError();
+}
+
+// (channels in 1 .. kTailChannels: the caller has checked)
+hipError_t launch_decode_whole_tail(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t channels, const DecodeWholeWs& w, int16_t* d_pcm_out,
+    uint32_t* d_status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_tailwin_decode, dim3(1, channels), dim3(64), 0, stream, d_frames, d_frame_offsets, channels, w.tail, w.dec, static_cast<TailSub*>(w.subs));
+    hipLaunchKernelGGL(k_whole_store, dim3(kWholeStoreBlocks), dim3(kTailStoreThreads), 0, stream, w.dec, static_cast<const TailSub*>(w.subs), w.tail, channels, d_pcm_out,
+        d_status);
     return hipGetLastError();
 }
 
