@@ -1,0 +1,51 @@
+// wide.hpp -- 24- and 32-bit WAV files to and from .sela, beside file::WavFile and sela::encodeFile / decodeFile,
+// which stay the 16-bit path they are (file::WavFile::readFromFile refuses every other container, as the reference's reader does).
+//
+//   * file::probeWav walks a WAV file's chunk headers as WavFile::readHeader does -- a 'fmt ' chunk counts wherever it stands
+//     (behind the data too), the LAST 'data' chunk is the audio -- and says what the file holds, refusing nothing a 16-bit reader
+//     would take: the CLI asks it which path a file goes.
+//   * sela::encodeWideFile / decodeWideFile move the packed data chunk through page-locked memory and ONE call to
+//     sela_hip_encode_pcm / sela_hip_decode_pcm: 3 bytes per sample of a 24-bit file travel to the device, and the layout
+//     conversion is the device's.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "sela_host/data.hpp"
+
+namespace file {
+
+struct WavProbe {
+    uint32_t sampleRate = 0;
+    uint16_t channels = 0;
+    uint16_t bitsPerSample = 0; // the container: 16, 24 or 32
+    uint16_t validBits = 0;     // an extensible header's wValidBitsPerSample (20 in 24, say); else bitsPerSample
+    bool extensible = false;
+    uint64_t dataOffset = 0, dataBytes = 0; // the last 'data' chunk's payload, clipped to the file
+};
+
+// Throws data::Exception: the reader's messages for what is no WAV file at all or lacks a chunk; "Only 16, 24 and 32bits per sample
+// wav is supported." for another container; "Only PCM wav is supported ..." for float and every other format tag (0xFFFE,
+// extensible, needs 40 bytes of 'fmt ' body and the PCM subformat).
+WavProbe probeWav(const std::string& path);
+
+} // namespace file
+
+namespace sela {
+
+struct WideReport {
+    uint32_t frames = 0;         // 2048-sample frames coded / decoded
+    uint64_t droppedSamples = 0; // encode: samples per channel behind the last whole frame (dropped, as plain -e drops them)
+    uint32_t wideSamples = 0;    // decode: samples that did not fit a 3-byte container (their low bytes were written)
+};
+
+// in: a 24- or 32-bit PCM WAV (probeWav) -> out: a .sela file whose header carries the file's bitsPerSample; frames of 2048 samples.
+WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless = false);
+// in: a .sela file whose header says 24 or 32 -> out: a WAV with the canonical 44-byte PCM header of that width.
+WideReport decodeWideFile(const std::string& in, const std::string& out);
+// what the .sela header at `path` says its samples' width is; 0 where there is no such header (the caller's path then reports it)
+uint16_t selaFileBits(const std::string& path);
+
+} // namespace sela

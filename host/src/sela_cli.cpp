@@ -10,6 +10,8 @@
 //                                      frame are folded into a long last frame instead of dropped (with --lossless, -v then exits 0);
 //                                      not with --pair-channels, not with -E
 //   sela_mi355x -d in.sela out.wav     decode
+//   (-e, -e --lossless and -d take 24- and 32-bit files too, routed by what the WAV's or the .sela's header says: the packed samples
+//   go to the device as they lie in the file; every other verb and flag keeps to 16-bit files)
 //   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
 //                                      the frames the range touches are decoded and no others
 //   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
@@ -36,6 +38,7 @@
 
 #include "sela_host/codec.hpp"
 #include "sela_host/player.hpp"
+#include "sela_host/wide.hpp"
 
 namespace {
 
@@ -108,6 +111,27 @@ int batch(const std::string& verb, int argc, char** argv)
     return 0;
 }
 
+// Does `path` hold a 24- or 32-bit PCM WAV?  (Anything else -- no file, no WAV, another format -- is today's path's to take
+// or to refuse in its own words.)
+bool wideWav(const std::string& path)
+{
+    try {
+        const file::WavProbe p = file::probeWav(path);
+        return p.bitsPerSample == 24 || p.bitsPerSample == 32;
+    } catch (const data::Exception&) {
+        return false;
+    }
+}
+
+// plain -e and -e --lossless of a 24- or 32-bit file
+int encodeWide(const std::string& in, const std::string& out, bool lossless)
+{
+    std::cout << "Encoding (" << file::probeWav(in).bitsPerSample << "-bit" << (lossless ? ", lossless" : "") << "): " << in << std::endl;
+    const sela::WideReport r = sela::encodeWideFile(in, out, lossless);
+    std::cout << r.frames << " frames, " << r.droppedSamples << " samples per channel behind the last whole frame dropped" << std::endl;
+    return 0;
+}
+
 // all of `text` as an unsigned decimal number
 bool parseCount(const std::string& text, uint64_t* value)
 {
@@ -168,6 +192,8 @@ int run(int argc, char** argv)
         return 0;
     }
     if (verb == "-e" && argc == 5 && std::string(argv[2]) == "--lossless") {
+        if (wideWav(argv[3]))
+            return encodeWide(argv[3], argv[4], true);
         std::cout << "Encoding (lossless): " << argv[3] << std::endl;
         sela::encodeFile(std::string(argv[3]), std::string(argv[4]), true);
         return 0;
@@ -211,6 +237,17 @@ int run(int argc, char** argv)
     }
     if (argc != 4 || (verb != "-e" && verb != "-d"))
         return usage(program);
+    if (verb == "-e" && wideWav(argv[2]))
+        return encodeWide(argv[2], argv[3], false);
+    if (verb == "-d" && (sela::selaFileBits(argv[2]) == 24 || sela::selaFileBits(argv[2]) == 32)) {
+        std::cout << "Decoding (" << sela::selaFileBits(argv[2]) << "-bit): " << argv[2] << std::endl;
+        const sela::WideReport r = sela::decodeWideFile(std::string(argv[2]), std::string(argv[3]));
+        std::cout << r.frames << " frames";
+        if (r.wideSamples)
+            std::cout << ", " << r.wideSamples << " samples beyond 24 bits (their low bytes written)";
+        std::cout << std::endl;
+        return 0;
+    }
     if (verb == "-e") {
         std::cout << "Encoding: " << argv[2] << std::endl;
         sela::encodeFile(std::string(argv[2]), std::string(argv[3])); // read, GPU and write overlap; only the byte stream is produced

@@ -1,0 +1,231 @@
+// wide.cpp -- 24- and 32-bit WAV files to and from .sela (see wide.hpp).  The containers are written here as files.cpp writes
+// them (the canonical 44-byte PCM header of src/file/wav_file.cpp:224-243, the 15-byte .sela header of src/file/sela_file.cpp:
+// 40-50 with the file's own bitsPerSample); the samples never leave their packed form on the host.
+#include "sela_host/wide.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <vector>
+
+#include "sela_hip.h"
+#include "sela_host/buffer.hpp"
+
+namespace {
+
+uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
+uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+void put16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v, p[1] = (uint8_t)(v >> 8); }
+void put32(uint8_t* p, uint32_t v) { put16(p, v), put16(p + 2, v >> 16); }
+
+bool readExact(std::ifstream& in, void* dst, size_t n)
+{
+    in.read(static_cast<char*>(dst), (std::streamsize)n);
+    return (size_t)in.gcount() == n;
+}
+
+// KSDATAFORMAT_SUBTYPE_PCM: 00000001-0000-0010-8000-00AA00389B71
+const uint8_t kPcmSubformat[16] = { 0x01, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71 };
+constexpr uint32_t kFrameSamples = 2048;
+
+[[noreturn]] void failHip(const char* what) { throw data::Exception(std::string(what) + ": " + sela_hip_last_error()); }
+
+} // namespace
+
+namespace file {
+
+WavProbe probeWav(const std::string& path)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in)
+        throw data::Exception("cannot open " + path);
+    in.seekg(0, std::ios::end);
+    const std::streamoff end = in.tellg();
+    const uint64_t size = end > 0 ? (uint64_t)end : 0;
+    in.seekg(0, std::ios::beg);
+    if (size < 44)
+        throw data::Exception("File is too small, probably not a wav file.");
+    uint8_t riff[12];
+    if (!readExact(in, riff, 12) || std::memcmp(riff, "RIFF", 4) != 0)
+        throw data::Exception("chunkId is not RIFF, probably not a wav file.");
+    if ((uint64_t)le32(riff + 4) > size)
+        throw data::Exception("chunkSize exceeds file size, probably a corrupted file");
+    if (std::memcmp(riff + 8, "WAVE", 4) != 0)
+        throw data::Exception("format is not WAVE, probably not a wav file.");
+    WavProbe p;
+    bool haveFmt = false, haveData = false;
+    uint64_t pos = 12;
+    while (pos + 8 <= size) {
+        uint8_t head[8];
+        in.seekg((std::streamoff)pos, std::ios::beg);
+        if (!readExact(in, head, 8))
+            break;
+        uint64_t chunk = le32(head + 4);
+        if (pos + 8 + chunk > size)
+            chunk = size - pos - 8; // tolerate a short last chunk
+        if (std::memcmp(head, "fmt ", 4) == 0 && chunk >= 16) {
+            uint8_t body[40] = {};
+            const size_t have = (size_t)std::min<uint64_t>(chunk, 40);
+            if (!readExact(in, body, have))
+                break;
+            const uint16_t tag = le16(body);
+            p.channels = le16(body + 2);
+            p.sampleRate = le32(body + 4);
+            p.bitsPerSample = p.validBits = le16(body + 14);
+            p.extensible = tag == 0xFFFE;
+            if (tag == 3)
+                throw data::Exception("Only PCM wav is supported (audioFormat 3 is float).");
+            if (p.extensible) {
+                if (have < 40)
+                    throw data::Exception("Only PCM wav is supported (an extensible fmt subChunk needs 40 bytes).");
+                if (std::memcmp(body + 24, kPcmSubformat, 16) != 0)
+                    throw data::Exception("Only PCM wav is supported (the extensible subformat is not PCM).");
+                p.validBits = le16(body + 18);
+            } else if (tag != 1) {
+                throw data::Exception("Only PCM wav is supported.");
+            }
+            if (p.bitsPerSample != 16 && p.bitsPerSample != 24 && p.bitsPerSample != 32)
+                throw data::Exception("Only 16, 24 and 32bits per sample wav is supported.");
+            haveFmt = true;
+        } else if (std::memcmp(head, "data", 4) == 0) {
+            haveData = true; // ('fmt ' may stand behind it: the format is asked for only once the walk is over)
+            p.dataOffset = pos + 8;
+            p.dataBytes = chunk;
+        }
+        pos += 8 + chunk;
+    }
+    if (!haveFmt)
+        throw data::Exception("fmt subChunk is missing from file");
+    if (!haveData)
+        throw data::Exception("data subChunk is missing from file");
+    return p;
+}
+
+} // namespace file
+
+namespace sela {
+
+WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless)
+{
+    const file::WavProbe p = file::probeWav(in);
+    if (p.bitsPerSample != 24 && p.bitsPerSample != 32)
+        throw data::Exception("encodeWideFile takes 24- and 32-bit wav (16-bit: encodeFile)");
+    if (p.channels == 0 || p.channels > 255)
+        throw data::Exception("a .sela file holds 1 to 255 channels");
+    const uint32_t bytes = p.bitsPerSample / 8u;
+    const uint64_t samples = p.dataBytes / ((uint64_t)p.channels * bytes), frames64 = samples / kFrameSamples;
+    if (frames64 >= (1ull << 31))
+        throw data::Exception("the file holds too many frames");
+    WideReport report;
+    report.frames = (uint32_t)frames64;
+    report.droppedSamples = samples - frames64 * kFrameSamples;
+    const size_t frameBytes = (size_t)kFrameSamples * p.channels * bytes;
+    sela_host::PinnedBuffer<uint8_t> pcm((size_t)report.frames * frameBytes);
+    std::ifstream file(in, std::ios::binary);
+    file.seekg((std::streamoff)p.dataOffset, std::ios::beg);
+    if (!pcm.empty() && !readExact(file, pcm.data(), pcm.size()))
+        throw data::Exception("data subChunk is shorter than its header says");
+    std::vector<uint64_t> offsets((size_t)report.frames + 1, 0);
+    sela_host::PinnedBuffer<uint8_t> stream;
+    // room by the estimate the library's own chunks use (4.5 bytes a sample); the certain bound only for a file that needs it
+    const size_t estimate = (size_t)report.frames * (((size_t)kFrameSamples * p.channels * 9) / 2 + (size_t)p.channels * 192 + 64);
+    const size_t rooms[2] = { estimate, sela_hip_encode_pcm_bound_bytes(report.frames, p.channels, kFrameSamples, bytes) };
+    for (size_t room : rooms) {
+        stream.resize(std::max<size_t>(room, 4));
+        const int rc = sela_hip_encode_pcm(pcm.data(), bytes, report.frames, p.channels, kFrameSamples, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u, stream.data(),
+            stream.size(), offsets.data());
+        if (rc == SELA_HIP_OK)
+            break;
+        if (rc != SELA_HIP_ECAPACITY || room == rooms[1])
+            failHip("Encoder");
+    }
+    uint8_t header[15];
+    std::memcpy(header, "SeLa", 4);
+    put32(header + 4, p.sampleRate);
+    put16(header + 8, p.bitsPerSample);
+    header[10] = (uint8_t)p.channels;
+    put32(header + 11, report.frames);
+    std::ofstream o(out, std::ios::binary | std::ios::trunc);
+    if (!o)
+        throw data::Exception("cannot open " + out + " for writing");
+    o.write(reinterpret_cast<const char*>(header), 15);
+    o.write(reinterpret_cast<const char*>(stream.data()), (std::streamsize)offsets[report.frames]);
+    if (!o)
+        throw data::Exception("cannot write " + out);
+    return report;
+}
+
+uint16_t selaFileBits(const std::string& path)
+{
+    std::ifstream in(path, std::ios::binary);
+    uint8_t head[15];
+    if (!in || !readExact(in, head, 15) || std::memcmp(head, "SeLa", 4) != 0)
+        return 0;
+    return le16(head + 8);
+}
+
+WideReport decodeWideFile(const std::string& in, const std::string& out)
+{
+    std::ifstream file(in, std::ios::binary);
+    if (!file)
+        throw data::Exception("cannot open " + in);
+    file.seekg(0, std::ios::end);
+    const std::streamoff end = file.tellg();
+    file.seekg(0, std::ios::beg);
+    uint8_t head[15];
+    if (end < 15 || !readExact(file, head, 15))
+        throw data::Exception("File is too small, probably not a sela file.");
+    if (std::memcmp(head, "SeLa", 4) != 0)
+        throw data::Exception("Magic number is incorrect, probably not a sela file.");
+    const uint32_t rate = le32(head + 4), bits = le16(head + 8), channels = head[10], numFrames = le32(head + 11);
+    if (bits != 24 && bits != 32)
+        throw data::Exception("decodeWideFile takes .sela files of 24- and 32-bit samples (16-bit: decodeFile)");
+    if (channels == 0)
+        throw data::Exception("the .sela header says no channels");
+    const uint32_t bytes = bits / 8u;
+    sela_host::PinnedBuffer<uint8_t> stream((size_t)(end - 15));
+    if (!stream.empty() && !readExact(file, stream.data(), stream.size()))
+        throw data::Exception("File is too small, probably not a sela file.");
+    // the frames as SelaFile::readFromFile finds them: the header's count is not trusted for sizing, the walk stops at the first
+    // frame without a sync word
+    const size_t least = 4 + 12 * (size_t)channels;
+    const uint32_t plausible = (uint32_t)std::min<size_t>(numFrames, stream.size() / least);
+    std::vector<uint64_t> offsets((size_t)plausible + 1, 0);
+    const uint32_t found = sela_hip_index_frames(stream.data(), stream.size(), plausible, channels, offsets.data());
+    offsets.resize((size_t)found + 1);
+    std::vector<uint64_t> sampleOffsets((size_t)found + 1, 0);
+    if (found && sela_hip_index_samples(stream.data(), offsets.data(), found, channels, sampleOffsets.data()) == 0)
+        throw data::Exception("Decoder: malformed frame stream");
+    const uint64_t dataBytes = sampleOffsets[found] * channels * bytes;
+    if (dataBytes > 0xFFFFFFFFull - 36)
+        throw data::Exception("the samples do not fit a wav file");
+    WideReport report;
+    report.frames = found;
+    sela_host::PinnedBuffer<uint8_t> pcm((size_t)std::max<uint64_t>(dataBytes, 4));
+    if (found && sela_hip_decode_pcm(stream.data(), offsets.data(), found, channels, bytes, pcm.data(), (size_t)dataBytes, &report.wideSamples) != SELA_HIP_OK)
+        failHip("Decoder");
+    uint8_t wav[44];
+    std::memcpy(wav, "RIFF", 4);
+    put32(wav + 4, 36 + (uint32_t)dataBytes);
+    std::memcpy(wav + 8, "WAVEfmt ", 8);
+    put32(wav + 16, 16);
+    put16(wav + 20, 1); // PCM
+    put16(wav + 22, channels);
+    put32(wav + 24, rate);
+    put32(wav + 28, rate * channels * bytes);
+    put16(wav + 32, channels * bytes);
+    put16(wav + 34, bits);
+    std::memcpy(wav + 36, "data", 4);
+    put32(wav + 40, (uint32_t)dataBytes);
+    std::ofstream o(out, std::ios::binary | std::ios::trunc);
+    if (!o)
+        throw data::Exception("cannot open " + out + " for writing");
+    o.write(reinterpret_cast<const char*>(wav), 44);
+    o.write(reinterpret_cast<const char*>(pcm.data()), (std::streamsize)dataBytes);
+    if (!o)
+        throw data::Exception("cannot write " + out);
+    return report;
+}
+
+} // namespace sela

@@ -707,6 +707,75 @@ int sela_hip_decode_whole_status_error(const uint32_t* status /* [4], host copy 
 int sela_hip_decode_whole(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames + 1] */, uint32_t n_frames, uint32_t channels, int16_t* pcm_out,
     uint64_t pcm_capacity /* samples per channel */, uint64_t* n_samples);
 
+/* ---- 24- and 32-bit PCM: packed interleaved samples to and from .sela on the device ---------------------------
+ * What a WAV file's data chunk or a capture buffer holds: little-endian interleaved samples of bytes_per_sample = 3 or 4 bytes,
+ * [n_frames][samples_per_channel][channels].  (2-byte samples have had their calls all along: sela_hip_encode_n_device,
+ * sela_hip_decode_n_device and the int16 host calls.)  Two kernels convert between that and the planar int32 of the i32 calls:
+ *   sela_hip_pcm_unpack_device   packed -> d_samples int32 [n_frames][channels][samples_per_channel], sign-extended: what
+ *     sela_hip_encode_i32_device, the paired calls and sela_hip_verify_i32_device take.
+ *   sela_hip_pcm_pack_device     what sela_hip_decode_i32_device writes -- d_samples [n_frames][channels][stride], d_counts
+ *     [n_frames * channels], d_sample_offsets [n_frames + 1] -- -> frame f interleaved at byte d_sample_offsets[f] * channels *
+ *     bytes_per_sample of d_pcm_out, each sample its low bytes_per_sample bytes (the reference's writer, src/file/wav_file.cpp:262).
+ *     A frame whose channels disagree about its length (a count other than d_sample_offsets[f + 1] - d_sample_offsets[f]), or
+ *     that would end behind n_frames * stride samples, is not written: SELA_HIP_FLAG_BAD_FRAME into d_status[0] and one more in
+ *     d_status[1].  With 3 bytes d_status[3] grows by the number of samples outside [-2^23, 2^23).  d_status[0] is read first:
+ *     with SELA_HIP_FLAG_STRIDE in it nothing is written.  The call only ORs and adds: zero the words, or let a decode write them.
+ * Every base pointer is 4-byte aligned (a 3-byte frame may still start at any byte of its buffer: frames are packed back to
+ * back).  The kernels read only aligned dwords that hold at least one byte of their input -- never a byte beyond the page the
+ * input ends in -- and write each byte of their output once and no other byte.
+ *
+ * The composed calls, asynchronous on `stream` like every device-pointer call (no allocation, no host synchronisation, no
+ * host-side read of device data: a stream being captured into a HIP graph may take them):
+ *   sela_hip_encode_pcm_device   the unpack into the workspace, then sela_hip_encode_i32_device_opt's launches on it: d_frames,
+ *     d_frame_offsets and d_status are exactly that call's on the unpacked samples, sela_hip_encode_status_error() judges them.
+ *     options: 0 or SELA_HIP_ENCODE_LOSSLESS.  d_workspace: sela_hip_encode_pcm_workspace_bytes(n_frames, channels,
+ *     samples_per_channel) bytes -- the i32 call's and the samples'.
+ *   sela_hip_decode_pcm_device   sela_hip_decode_i32_device's launches into the workspace, then the pack: the contract of
+ *     sela_hip_decode_n_device's any-length route with a 3- or 4-byte container.  d_pcm_out has room for n_frames * stride * channels
+ *     * bytes_per_sample bytes; nothing at or past that is written on any input, on success nothing at or past d_sample_offsets
+ *     [n_frames] * channels * bytes_per_sample.  d_status [0..2] as sela_hip_decode_i32_device writes them -- SELA_HIP_FLAG_STRIDE
+ *     exactly where that call raises it, and nothing is written then -- with the frames the pack refuses added; [3] the samples
+ *     that did not fit a 3-byte container (their low bytes are written; 0 for 4 bytes).  d_workspace:
+ *     sela_hip_decode_pcm_workspace_bytes(n_frames, channels, stride).
+ *   sela_hip_decode_pcm_status_error   host only: sela_hip_decode_status_error()'s verdict on [0..2]; [3] is informational.
+ *
+ * sela_hip_encode_pcm_bound_bytes: room for every frame of such samples that the encoder does not refuse.  Nothing about a frame's
+ * size follows from the container -- a residue is a sample minus a prediction, and a predictor of order up to 100 on quantised
+ * coefficients may predict anything -- so the bound is the format's: the encoder refuses (SELA_HIP_ERANGE) a residue whose
+ * zig-zag value u reaches 2^31 and a subframe of more than 65535 Rice words, and its Rice parameter is the minimum of bits(k),
+ * convex in k = 0 .. 19, so never worse than k = 19: (u >> 19) + 20 <= 4115 bits a sample.  Per subframe that is the 12-byte
+ * header, 32 coefficient words and min(65535, ceil(samples_per_channel * 4115 / 32)) residue words; per frame 4 bytes more.
+ * (sela_hip_encode_bound_bytes_n promises 17-bit samples only; this is never smaller, and grows with each argument.)
+ *
+ * sela_hip_encode_pcm / sela_hip_decode_pcm: host pointers, synchronous.  The packed bytes travel -- 3 per sample of a 24-bit
+ * container over the link, not 4 -- in chunks of whole frames that keep the device scratch bounded (as sela_hip_encode_i32's), on
+ * the calling thread's leased context, past the coalescer; an open streaming job is left alone.  sela_hip_decode_pcm walks the
+ * stream as sela_hip_decode does (sela_hip_index_samples); pcm_out holds pcm_cap bytes, of which sample_offsets[n_frames] *
+ * channels * bytes_per_sample are written (fewer: SELA_HIP_ECAPACITY); *wide_samples (or NULL) receives status[3] of all chunks.
+ *
+ * SELA_HIP_EINVAL: a null pointer (d_sample_offsets of the decode may be NULL), bytes_per_sample other than 3 or 4, channels
+ * outside 1..255, samples_per_channel outside 1..65535, stride 0, a base pointer that is not 4-byte aligned, n_frames x signals
+ * per frame at 2^31 or more, an unknown option; SELA_HIP_ECAPACITY: a smaller workspace.  Nothing is enqueued then. */
+size_t sela_hip_encode_pcm_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel);
+size_t sela_hip_encode_pcm_bound_bytes(uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint32_t bytes_per_sample);
+size_t sela_hip_decode_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_pcm_unpack_device(const void* d_pcm, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel,
+    int32_t* d_samples /* [n_frames][channels][samples_per_channel] */, void* stream);
+int sela_hip_pcm_pack_device(const int32_t* d_samples /* [n_frames][channels][stride] */, const uint32_t* d_counts /* [n_frames * channels] */,
+    const uint64_t* d_sample_offsets /* [n_frames + 1] */, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample, void* d_pcm_out,
+    uint32_t* d_status /* [4] */, void* stream);
+int sela_hip_encode_pcm_device(const void* d_pcm, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint32_t options,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [n_frames + 1] */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+int sela_hip_decode_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, void* d_pcm_out, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+int sela_hip_decode_pcm_status_error(const uint32_t* status /* [4], host copy */);
+int sela_hip_encode_pcm(const void* pcm, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t channels, uint32_t samples_per_channel, uint32_t options,
+    uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out /* [n_frames + 1] */);
+int sela_hip_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, void* pcm_out,
+    size_t pcm_cap /* bytes */, uint32_t* wide_samples /* or NULL */);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

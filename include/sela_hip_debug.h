@@ -140,6 +140,9 @@ enum {
     SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT, SELA_HIP_WORKSPACE_DECODE_WHOLE
 };
 int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
+/* Debug hook (tests; process-wide): sela_hip_encode_pcm and sela_hip_decode_pcm work in chunks of this many whole frames; 0
+ * restores the chunks sized by the device scratch they keep bounded.  Same bytes either way, which is what the tests check. */
+void sela_hip_debug_pcm_chunk_frames(uint32_t frames);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,9 @@ EXPORTS = [
     "sela_hip_encode_whole_device", "sela_hip_encode_whole",
     "sela_hip_decode_whole_workspace_bytes", "sela_hip_decode_whole_device", "sela_hip_decode_whole_payload_device", "sela_hip_decode_whole_status_error",
     "sela_hip_decode_whole",
+    "sela_hip_pcm_unpack_device", "sela_hip_pcm_pack_device", "sela_hip_encode_pcm_workspace_bytes", "sela_hip_encode_pcm_bound_bytes",
+    "sela_hip_encode_pcm_device", "sela_hip_decode_pcm_workspace_bytes", "sela_hip_decode_pcm_device", "sela_hip_decode_pcm_status_error",
+    "sela_hip_encode_pcm", "sela_hip_decode_pcm",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
@@ -58,7 +61,7 @@ DEBUG_EXPORTS = [
     "sela_hip_debug_phase_buffer", "sela_hip_debug_force_plain_fir", "sela_hip_debug_mean_workers", "sela_hip_debug_encode_teams", "sela_hip_debug_encode_kernel", "sela_hip_debug_encode_fused", "sela_hip_debug_priorities", "sela_hip_debug_priorities_adaptive", "sela_hip_debug_launches_alone", "sela_hip_debug_block_forms", "sela_hip_debug_encode_hashes", "sela_hip_debug_standard_first", "sela_hip_debug_standard_chunks", "sela_hip_debug_segment_subframes", "sela_hip_debug_generic_wrap_taps", "sela_hip_debug_encode_split", "sela_hip_debug_launches_split", "sela_hip_debug_keep_both_candidates", "sela_hip_debug_stage_wait",
     "sela_hip_debug_reissued_feeds", "sela_hip_debug_contexts_created", "sela_hip_debug_decode_recurrence", "sela_hip_debug_coalesced", "sela_hip_debug_verify_lds_bytes",
     "sela_hip_debug_verify_i32_fallback_frames", "sela_hip_debug_window_lds_bytes", "sela_hip_debug_windows_staged_bytes",
-    "sela_hip_debug_workspace_pieces",
+    "sela_hip_debug_workspace_pieces", "sela_hip_debug_pcm_chunk_frames",
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
@@ -226,6 +229,24 @@ def lib() -> C.CDLL:
     L.sela_hip_decode_whole_status_error.restype = C.c_int
     L.sela_hip_decode_whole.argtypes = [vp, vp, u32, u32, vp, u64, vp]
     L.sela_hip_decode_whole.restype = C.c_int
+    # packed 3- / 4-byte PCM
+    L.sela_hip_encode_pcm_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_encode_pcm_bound_bytes.argtypes = [u32, u32, u32, u32]
+    L.sela_hip_decode_pcm_workspace_bytes.argtypes = [u32, u32, u32]
+    for name in ("sela_hip_encode_pcm_workspace_bytes", "sela_hip_encode_pcm_bound_bytes", "sela_hip_decode_pcm_workspace_bytes"):
+        getattr(L, name).restype = sz
+    L.sela_hip_pcm_unpack_device.argtypes = [vp, u32, u32, u32, u32, vp, vp]
+    L.sela_hip_pcm_pack_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
+    L.sela_hip_encode_pcm_device.argtypes = [vp, u32, u32, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_pcm_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_pcm_status_error.argtypes = [vp]
+    L.sela_hip_encode_pcm.argtypes = [vp, u32, u32, u32, u32, u32, vp, sz, vp]
+    L.sela_hip_decode_pcm.argtypes = [vp, vp, u32, u32, u32, vp, sz, vp]
+    for name in ("sela_hip_pcm_unpack_device", "sela_hip_pcm_pack_device", "sela_hip_encode_pcm_device", "sela_hip_decode_pcm_device",
+                 "sela_hip_decode_pcm_status_error", "sela_hip_encode_pcm", "sela_hip_decode_pcm"):
+        getattr(L, name).restype = C.c_int
+    L.sela_hip_debug_pcm_chunk_frames.argtypes = [u32]
+    L.sela_hip_debug_pcm_chunk_frames.restype = None
     L.sela_hip_encode_status_error.argtypes = [vp]
     L.sela_hip_encode_status_error.restype = C.c_int
     L.sela_hip_enable_kernel_timing.argtypes = [C.c_int]

@@ -1075,3 +1075,168 @@ def rice_decode(streams):
     capi.check(lib.sela_hip_rice_decode(C.c_void_p(flat.ctypes.data), C.c_void_p(woff.ctypes.data), C.c_void_p(k.ctypes.data), C.c_void_p(voff.ctypes.data), n,
                                         C.c_void_p(out.ctypes.data)))
     return [out[int(voff[i]): int(voff[i + 1])].copy() for i in range(n)]
+
+
+# ---- packed 3- / 4-byte PCM: what a 24- or 32-bit WAV's data chunk holds ------------------------------------------
+def _pcm_args_ok(torch, t) -> bool:
+    return t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous()
+
+
+def pcm_unpack(pcm, n_frames: int, channels: int, samples_per_channel: int, bytes_per_sample: int, out=None):
+    """sela_hip_pcm_unpack_device on the current stream: pcm uint8 cuda tensor, little-endian interleaved
+    [n_frames][samples_per_channel][channels] of bytes_per_sample (3 or 4) bytes -> int32 [n_frames, channels, samples_per_channel]
+    (`out`, or a new tensor), sign-extended: what Encoder32 and Verifier32 take."""
+    import torch
+
+    assert _pcm_args_ok(torch, pcm)
+    if out is None:
+        out = torch.empty((n_frames, channels, samples_per_channel), dtype=torch.int32, device=pcm.device)
+    assert out.dtype == torch.int32 and out.is_cuda and out.is_contiguous()
+    capi.check(capi.lib().sela_hip_pcm_unpack_device(pcm.data_ptr(), bytes_per_sample, n_frames, channels, samples_per_channel, out.data_ptr(),
+                                                     torch.cuda.current_stream(pcm.device).cuda_stream))
+    return out
+
+
+def pcm_pack(samples, counts, sample_offsets, bytes_per_sample: int, out, status):
+    """sela_hip_pcm_pack_device on the current stream: Decoder32's outputs (samples int32 [n_frames, channels, stride], counts int32
+    [n_frames, channels], sample_offsets int64 [n_frames + 1]) -> frame f interleaved at byte sample_offsets[f] * channels *
+    bytes_per_sample of `out` (uint8 cuda tensor).  status (int32 [4] cuda tensor; zeroed, or a decode's) takes the frames not
+    written ([0], [1]) and the samples beyond a 3-byte container ([3])."""
+    import torch
+
+    n_frames, channels, stride = samples.shape
+    assert samples.dtype == torch.int32 and samples.is_cuda and samples.is_contiguous() and _pcm_args_ok(torch, out)
+    assert counts.is_cuda and counts.is_contiguous() and counts.numel() == n_frames * channels and sample_offsets.numel() == n_frames + 1
+    capi.check(capi.lib().sela_hip_pcm_pack_device(samples.data_ptr(), counts.data_ptr(), sample_offsets.data_ptr(), n_frames, channels, stride, bytes_per_sample,
+                                                   out.data_ptr(), status.data_ptr(), torch.cuda.current_stream(samples.device).cuda_stream))
+    return out
+
+
+class EncoderPcm:
+    """sela_hip_encode_pcm_device: frames of packed 3- or 4-byte interleaved PCM (any samples_per_channel in 1 .. 65535) to .sela
+    frames on the device -- the unpack kernel, then Encoder32's launches.  Owns its workspace, frames, offsets and status, as
+    Encoder32 does (`capacity` as there: an estimate, check() and needed_bytes() say when it was too small)."""
+
+    def __init__(self, max_frames: int, channels: int, samples_per_channel: int, bytes_per_sample: int, capacity=None, lossless: bool = False, device=None):
+        import torch
+
+        self.options = capi.ENCODE_LOSSLESS if lossless else 0
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.n, self.bytes_per_sample = max_frames, channels, samples_per_channel, bytes_per_sample
+        if capacity is None:
+            capacity = max_frames * ((samples_per_channel * channels * 9) // 2 + channels * 192 + 64)
+        self.capacity = max(int(capacity), 4)
+        ws = int(self.lib.sela_hip_encode_pcm_workspace_bytes(max_frames, channels, samples_per_channel))
+        with torch.cuda.device(self.device):
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+            self.offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.n_frames = 0
+
+    def encode(self, pcm, n_frames=None):
+        """pcm: uint8 cuda tensor of n_frames * samples_per_channel * channels * bytes_per_sample bytes (n_frames: from its size)
+        -> (frames uint8 [capacity], offsets int64 [n_frames + 1], status int32 [4]), the encoder's own buffers."""
+        torch = self.torch
+        assert _pcm_args_ok(torch, pcm)
+        frame_bytes = self.n * self.channels * self.bytes_per_sample
+        if n_frames is None:
+            assert pcm.numel() % frame_bytes == 0
+            n_frames = pcm.numel() // frame_bytes
+        assert n_frames <= self.max_frames and pcm.numel() >= n_frames * frame_bytes
+        capi.check(self.lib.sela_hip_encode_pcm_device(
+            pcm.data_ptr(), self.bytes_per_sample, n_frames, self.channels, self.n, self.options, self.frames.data_ptr(), self.capacity,
+            self.offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        self.n_frames = n_frames
+        return self.frames, self.offsets[: n_frames + 1], self.status
+
+    needed_bytes = Encoder32.needed_bytes
+    check = Encoder32.check
+    to_host = Encoder32.to_host
+
+
+class DecoderPcm:
+    """sela_hip_decode_pcm_device: a stream of any samplesPerChannel to packed 3- or 4-byte interleaved PCM on the device --
+    Decoder32's launches, then the pack kernel.  Owns its output (max_frames * stride * channels * bytes_per_sample bytes), its
+    sample offsets, status and workspace; every call is asynchronous on the current stream and overwrites them."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, bytes_per_sample: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride, self.bytes_per_sample = max_frames, channels, stride, bytes_per_sample
+        with torch.cuda.device(self.device):
+            self.pcm = torch.empty(max_frames * stride * channels * bytes_per_sample, dtype=torch.uint8, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_decode_pcm_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def decode(self, frames, offsets, n_frames: int, out=None):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> (pcm uint8, sample_offsets int64
+        [n_frames + 1]): frame f at byte sample_offsets[f] * channels * bytes_per_sample of pcm (the decoder's own buffer, or `out`
+        with room for n_frames * stride * channels * bytes_per_sample bytes)."""
+        torch = self.torch
+        assert _pcm_args_ok(torch, frames)
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        pcm = self.pcm if out is None else out
+        assert _pcm_args_ok(torch, pcm) and pcm.numel() >= n_frames * self.stride * self.channels * self.bytes_per_sample
+        capi.check(self.lib.sela_hip_decode_pcm_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.bytes_per_sample, pcm.data_ptr(),
+            self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        return pcm, self.sample_offsets[: n_frames + 1]
+
+    def wide_samples(self) -> int:
+        """Waits for the last call -> how many samples did not fit a 3-byte container (their low bytes were written)."""
+        return int(self.status[3].item()) & 0xFFFFFFFF
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_pcm gives for the same input."""
+        capi.check(decode_pcm_status_error(self.status.cpu().numpy()))
+
+
+def decode_pcm_status_error(status) -> int:
+    """sela_hip_decode_pcm_status_error on a host copy of four status words -> the host call's code ([3] is informational)."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_decode_pcm_status_error(st.ctypes.data))
+
+
+def encode_pcm_host(pcm: np.ndarray, channels: int, samples_per_channel: int, bytes_per_sample: int, lossless: bool = False):
+    """sela_hip_encode_pcm: packed bytes (uint8, whole frames of samples_per_channel * channels * bytes_per_sample) on the host
+    -> (frames uint8, offsets uint64 [n_frames + 1])."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.uint8).reshape(-1)
+    frame_bytes = samples_per_channel * channels * bytes_per_sample
+    assert frame_bytes and pcm.size % frame_bytes == 0
+    n_frames = pcm.size // frame_bytes
+    lib = capi.lib()
+    cap = n_frames * ((samples_per_channel * channels * 9) // 2 + channels * 192 + 64)
+    for capacity in (cap, int(lib.sela_hip_encode_pcm_bound_bytes(n_frames, channels, samples_per_channel, bytes_per_sample))):
+        frames = np.empty(max(capacity, 4), dtype=np.uint8)
+        offsets = np.zeros(n_frames + 1, dtype=np.uint64)
+        rc = lib.sela_hip_encode_pcm(pcm.ctypes.data, bytes_per_sample, n_frames, channels, samples_per_channel, capi.ENCODE_LOSSLESS if lossless else 0,
+                                     frames.ctypes.data, frames.size, offsets.ctypes.data)
+        if rc != -4:
+            break
+    capi.check(rc)
+    return frames[: int(offsets[-1])].copy(), offsets
+
+
+def decode_pcm_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bytes_per_sample: int):
+    """sela_hip_decode_pcm -> (pcm uint8: the stream's samples interleaved, bytes_per_sample bytes each; wide: the samples that
+    did not fit a 3-byte container)."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = offsets.size - 1
+    total = int(index_samples(frames, offsets, channels)[0][-1]) if n_frames else 0
+    pcm = np.empty(max(total * channels * bytes_per_sample, 1), dtype=np.uint8)
+    wide = C.c_uint32(0)
+    capi.check(capi.lib().sela_hip_decode_pcm(frames.ctypes.data, offsets.ctypes.data, n_frames, channels, bytes_per_sample, pcm.ctypes.data,
+                                              total * channels * bytes_per_sample, C.addressof(wide)))
+    return pcm[: total * channels * bytes_per_sample], int(wide.value)

@@ -19,6 +19,7 @@
 
 #include "sela_host.h"
 #include "sela_lease.h"
+#include "sela_pcm.h"
 #include "sela_window_plan.h"
 
 namespace {
@@ -806,7 +807,149 @@ int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* re
     return SELA_HIP_OK;
 }
 
+// sela_hip_encode_pcm / sela_hip_decode_pcm: the device calls' launches (sela_capi_pcm.hip) on chunks of whole
+// frames, on the calling thread's context and stream, past the coalescer.  What travels is the packed bytes: 3 per sample of a
+// 24-bit container, not 4.  The chunks are sized as generic_encode's and generic_decode's (kChunkBudget of scratch), or by
+// sela_hip_debug_pcm_chunk_frames.
+namespace {
+std::atomic<uint32_t> g_pcm_chunk_frames{0};
+uint32_t pcm_chunk(uint32_t n_frames, size_t per_frame)
+{
+    const uint32_t forced = g_pcm_chunk_frames.load(std::memory_order_relaxed);
+    const size_t chunk = forced ? forced : kChunkBudget / per_frame;
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, chunk));
+}
+} // namespace
+
+// Per chunk ONE wait where the frames fit the estimate generic_encode sizes its own by (4.5 bytes a sample); a chunk that codes
+// to more is encoded again into room of the size its offsets ask for.
+int generic_encode_pcm(const uint8_t* pcm, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t channels, uint32_t n, bool lossless, uint8_t* frames_out,
+    size_t frames_cap, uint64_t* frame_offsets_out)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& arena = call.arena();
+    const hipStream_t st = call.stream();
+    const size_t in_frame_bytes = (size_t)n * channels * bytes_per_sample;
+    const size_t est_frame_bytes = ((size_t)n * channels * 9) / 2 + (size_t)channels * 192 + 64;
+    const size_t per_frame = encode_pcm_workspace_bytes(1, channels, n) + in_frame_bytes + est_frame_bytes + 8;
+    const uint32_t chunk = pcm_chunk(n_frames, per_frame);
+    uint64_t base_bytes = 0;
+    frame_offsets_out[0] = 0;
+    std::vector<uint64_t> head;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const size_t ws_bytes = encode_pcm_workspace_bytes(cf, channels, n);
+        const size_t head_words = 2 + (size_t)cf + 1; // status (4 x u32) | frame offsets
+        head.assign(head_words, 0);
+        size_t cap = (size_t)cf * est_frame_bytes;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            hipError_t e = arena.reserve(cf * in_frame_bytes + head_words * 8 + cap + ws_bytes + 8 * kPiece);
+            if (e != hipSuccess)
+                return report_hip_error(e, "encode_pcm: scratch");
+            uint8_t* d_in = arena.take<uint8_t>(cf * in_frame_bytes);
+            uint64_t* d_head = arena.take<uint64_t>(head_words);
+            uint8_t* d_frames = arena.take<uint8_t>(cap);
+            uint8_t* d_ws = arena.take<uint8_t>(ws_bytes);
+            if (!arena.fits())
+                return report_error(SELA_HIP_ENOMEM, "encode_pcm: internal scratch estimate too small");
+            e = hipMemcpyAsync(d_in, pcm + (size_t)f0 * in_frame_bytes, cf * in_frame_bytes, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess)
+                e = launch_encode_pcm_device(d_in, bytes_per_sample, cf, channels, n, lossless, d_frames, cap, d_head + 2, reinterpret_cast<uint32_t*>(d_head), d_ws, st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(head.data(), d_head, head_words * 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(st);
+            if (e != hipSuccess)
+                return report_hip_error(e, "encode_pcm");
+            uint32_t status[4];
+            std::memcpy(status, head.data(), 16);
+            const int rc = judge_encode(status[0], kJudgeEncode, "encode_pcm");
+            if (rc != SELA_HIP_OK)
+                return rc;
+            const uint64_t chunk_bytes = head[2 + cf];
+            if (base_bytes + chunk_bytes > frames_cap)
+                return report_error(SELA_HIP_ECAPACITY, "frames_out too small (see sela_hip_encode_pcm_bound_bytes)");
+            if (status[1] == 0) {
+                e = hipMemcpyAsync(frames_out + base_bytes, d_frames, (size_t)chunk_bytes, hipMemcpyDeviceToHost, st);
+                if (e == hipSuccess)
+                    e = hipStreamSynchronize(st);
+                if (e != hipSuccess)
+                    return report_hip_error(e, "encode_pcm: copy out");
+                for (uint32_t i = 1; i <= cf; i++)
+                    frame_offsets_out[f0 + i] = base_bytes + head[2 + i];
+                base_bytes += chunk_bytes;
+                break;
+            }
+            if (attempt == 1)
+                return report_error(SELA_HIP_ENODEV, "encode_pcm: a chunk did not fit the room its own offsets asked for");
+            cap = (size_t)chunk_bytes; // (rare: more than 4.5 bytes a sample)
+        }
+    }
+    return SELA_HIP_OK;
+}
+
+// The caller has walked the stream: the offsets never decrease, stride is the largest samplesPerChannel, sample_offsets the walk's.
+int generic_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, const uint64_t* sample_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, uint8_t* pcm_out, uint32_t* wide_samples)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    Arena& arena = call.arena();
+    const hipStream_t st = call.stream();
+    const size_t value_bytes = (size_t)channels * bytes_per_sample;
+    const size_t per_frame = decode_pcm_workspace_bytes(1, channels, stride) + (size_t)stride * value_bytes + 16;
+    const uint32_t chunk = pcm_chunk(n_frames, per_frame);
+    std::vector<uint64_t> local;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants a 4-byte aligned base)
+        const size_t ws_bytes = decode_pcm_workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, "decode_pcm: the chunk is too large");
+        const size_t out_room = (size_t)cf * stride * value_bytes, out_bytes = (size_t)(sample_offsets[f0 + cf] - sample_offsets[f0]) * value_bytes;
+        hipError_t e = arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + out_room + 16 + ws_bytes + 10 * kPiece);
+        if (e != hipSuccess)
+            return report_hip_error(e, "decode_pcm: scratch");
+        uint8_t* d_frames = arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = arena.take<uint64_t>((size_t)cf + 1);
+        uint8_t* d_out = arena.take<uint8_t>(out_room);
+        uint32_t* d_status = arena.take<uint32_t>(4);
+        uint8_t* d_ws = arena.take<uint8_t>(ws_bytes);
+        if (!arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "decode_pcm: internal scratch estimate too small");
+        local.resize((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        uint32_t status[4] = {};
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_decode_pcm_device(d_frames, d_offsets, cf, channels, stride, bytes_per_sample, d_out, nullptr, d_status, d_ws,
+                g_standard_first_mode.load(std::memory_order_relaxed), st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out_bytes)
+            e = hipMemcpyAsync(pcm_out + (size_t)sample_offsets[f0] * value_bytes, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "decode_pcm");
+        const int rc = sela_hip_decode_pcm_status_error(status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        if (wide_samples)
+            *wide_samples += status[3];
+    }
+    return SELA_HIP_OK;
+}
+
 } // namespace sela
+
+extern "C" void sela_hip_debug_pcm_chunk_frames(uint32_t frames) { sela::g_pcm_chunk_frames.store(frames, std::memory_order_relaxed); }
 
 extern "C" {
 void sela_hip_debug_standard_first(int mode) { g_standard_first_mode.store(mode, std::memory_order_relaxed); }
