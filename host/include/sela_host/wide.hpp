@@ -7,6 +7,7 @@
 //   * sela::encodeWideFile / decodeWideFile move the packed data chunk through page-locked memory and ONE call to
 //     sela_hip_encode_pcm / sela_hip_decode_pcm: 3 bytes per sample of a 24-bit file travel to the device, and the layout
 //     conversion is the device's.
+//   * sela::decodeWideFileRange is decodeFileRange for such files: one window of the stream through sela_hip_decode_windows_i32.
 #pragma once
 
 #include <cstddef>
@@ -45,6 +46,11 @@ struct WideReport {
 WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless = false);
 // in: a .sela file whose header says 24 or 32 -> out: a WAV with the canonical 44-byte PCM header of that width.
 WideReport decodeWideFile(const std::string& in, const std::string& out);
+// in: such a .sela file -> out: a WAV of that width holding samples startSample .. startSample + sampleCount - 1 per channel, cut at
+// the stream's end (only the frames the range touches are decoded).  Returns the samples per channel written;
+// throws decodeFileRange's message where startSample is at or past the end.  (Samples of a 24-bit file that lie outside 24 bits
+// go out as their low three bytes, as from decodeWideFile, but are not counted here: the host window call returns no status words.)
+size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64_t startSample, uint64_t sampleCount);
 // what the .sela header at `path` says its samples' width is; 0 where there is no such header (the caller's path then reports it)
 uint16_t selaFileBits(const std::string& path);
 

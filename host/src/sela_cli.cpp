@@ -10,8 +10,8 @@
 //                                      frame are folded into a long last frame instead of dropped (with --lossless, -v then exits 0);
 //                                      not with --pair-channels, not with -E
 //   sela_mi355x -d in.sela out.wav     decode
-//   (-e, -e --lossless and -d take 24- and 32-bit files too, routed by what the WAV's or the .sela's header says: the packed samples
-//   go to the device as they lie in the file; every other verb and flag keeps to 16-bit files)
+//   (-e, -e --lossless, -d and -d --start S --count N take 24- and 32-bit files too, routed by what the WAV's or the .sela's header
+//   says: the packed samples go to the device and come back as they lie in the file; every other verb and flag keeps to 16-bit files)
 //   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
 //                                      the frames the range touches are decoded and no others
 //   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
@@ -51,7 +51,7 @@ int usage(const std::string& program)
               << program << " -e --pair-channels [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Encoding a whole file (the samples beyond the last whole frame are kept, in a long last frame):\n"
               << program << " -e --keep-tail [--lossless] path/to/input.wav path/to/output.sela\n\n"
-              << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only):\n"
+              << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only; 16-, 24- and 32-bit files alike):\n"
               << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
@@ -181,8 +181,11 @@ int run(int argc, char** argv)
         uint64_t start = 0, count = 0;
         if (!parseCount(argv[3], &start) || !parseCount(argv[5], &count))
             return usage(program);
-        std::cout << "Decoding: " << argv[6] << ", samples " << start << " + " << count << std::endl;
-        const size_t written = sela::decodeFileRange(std::string(argv[6]), std::string(argv[7]), start, count);
+        const uint16_t bits = sela::selaFileBits(argv[6]);
+        const bool wide = bits == 24 || bits == 32;
+        std::cout << "Decoding" << (wide ? (bits == 24 ? " (24-bit)" : " (32-bit)") : "") << ": " << argv[6] << ", samples " << start << " + " << count << std::endl;
+        const size_t written = wide ? sela::decodeWideFileRange(std::string(argv[6]), std::string(argv[7]), start, count)
+                                    : sela::decodeFileRange(std::string(argv[6]), std::string(argv[7]), start, count);
         std::cout << written << " samples per channel" << std::endl;
         return 0;
     }

@@ -165,7 +165,18 @@ uint16_t selaFileBits(const std::string& path)
     return le16(head + 8);
 }
 
-WideReport decodeWideFile(const std::string& in, const std::string& out)
+namespace {
+
+// A .sela file of 24- or 32-bit samples as decodeWideFile and decodeWideFileRange read it: the header's fields, the payload in
+// page-locked memory and the frames as SelaFile::readFromFile finds them -- the header's count is not trusted for sizing, the walk
+// stops at the first frame without a sync word.
+struct WideSela {
+    uint32_t rate = 0, bits = 0, channels = 0, found = 0;
+    sela_host::PinnedBuffer<uint8_t> stream;
+    std::vector<uint64_t> offsets;
+};
+
+void readWideSela(const std::string& in, const char* who, WideSela& s)
 {
     std::ifstream file(in, std::ios::binary);
     if (!file)
@@ -178,24 +189,57 @@ WideReport decodeWideFile(const std::string& in, const std::string& out)
         throw data::Exception("File is too small, probably not a sela file.");
     if (std::memcmp(head, "SeLa", 4) != 0)
         throw data::Exception("Magic number is incorrect, probably not a sela file.");
-    const uint32_t rate = le32(head + 4), bits = le16(head + 8), channels = head[10], numFrames = le32(head + 11);
-    if (bits != 24 && bits != 32)
-        throw data::Exception("decodeWideFile takes .sela files of 24- and 32-bit samples (16-bit: decodeFile)");
-    if (channels == 0)
+    s.rate = le32(head + 4), s.bits = le16(head + 8), s.channels = head[10];
+    const uint32_t numFrames = le32(head + 11);
+    if (s.bits != 24 && s.bits != 32)
+        throw data::Exception(std::string(who) + " takes .sela files of 24- and 32-bit samples (16-bit: decodeFile)");
+    if (s.channels == 0)
         throw data::Exception("the .sela header says no channels");
-    const uint32_t bytes = bits / 8u;
-    sela_host::PinnedBuffer<uint8_t> stream((size_t)(end - 15));
-    if (!stream.empty() && !readExact(file, stream.data(), stream.size()))
+    s.stream.resize((size_t)(end - 15));
+    if (!s.stream.empty() && !readExact(file, s.stream.data(), s.stream.size()))
         throw data::Exception("File is too small, probably not a sela file.");
-    // the frames as SelaFile::readFromFile finds them: the header's count is not trusted for sizing, the walk stops at the first
-    // frame without a sync word
-    const size_t least = 4 + 12 * (size_t)channels;
-    const uint32_t plausible = (uint32_t)std::min<size_t>(numFrames, stream.size() / least);
-    std::vector<uint64_t> offsets((size_t)plausible + 1, 0);
-    const uint32_t found = sela_hip_index_frames(stream.data(), stream.size(), plausible, channels, offsets.data());
-    offsets.resize((size_t)found + 1);
+    const size_t least = 4 + 12 * (size_t)s.channels;
+    const uint32_t plausible = (uint32_t)std::min<size_t>(numFrames, s.stream.size() / least);
+    s.offsets.assign((size_t)plausible + 1, 0);
+    s.found = sela_hip_index_frames(s.stream.data(), s.stream.size(), plausible, s.channels, s.offsets.data());
+    s.offsets.resize((size_t)s.found + 1);
+}
+
+// the canonical 44-byte PCM header and the data chunk
+void writeWideWav(const std::string& out, const WideSela& s, const uint8_t* pcm, uint64_t dataBytes)
+{
+    const uint32_t bytes = s.bits / 8u;
+    uint8_t wav[44];
+    std::memcpy(wav, "RIFF", 4);
+    put32(wav + 4, 36 + (uint32_t)dataBytes);
+    std::memcpy(wav + 8, "WAVEfmt ", 8);
+    put32(wav + 16, 16);
+    put16(wav + 20, 1); // PCM
+    put16(wav + 22, s.channels);
+    put32(wav + 24, s.rate);
+    put32(wav + 28, s.rate * s.channels * bytes);
+    put16(wav + 32, s.channels * bytes);
+    put16(wav + 34, s.bits);
+    std::memcpy(wav + 36, "data", 4);
+    put32(wav + 40, (uint32_t)dataBytes);
+    std::ofstream o(out, std::ios::binary | std::ios::trunc);
+    if (!o)
+        throw data::Exception("cannot open " + out + " for writing");
+    o.write(reinterpret_cast<const char*>(wav), 44);
+    o.write(reinterpret_cast<const char*>(pcm), (std::streamsize)dataBytes);
+    if (!o)
+        throw data::Exception("cannot write " + out);
+}
+
+} // namespace
+
+WideReport decodeWideFile(const std::string& in, const std::string& out)
+{
+    WideSela s;
+    readWideSela(in, "decodeWideFile", s);
+    const uint32_t channels = s.channels, bytes = s.bits / 8u, found = s.found;
     std::vector<uint64_t> sampleOffsets((size_t)found + 1, 0);
-    if (found && sela_hip_index_samples(stream.data(), offsets.data(), found, channels, sampleOffsets.data()) == 0)
+    if (found && sela_hip_index_samples(s.stream.data(), s.offsets.data(), found, channels, sampleOffsets.data()) == 0)
         throw data::Exception("Decoder: malformed frame stream");
     const uint64_t dataBytes = sampleOffsets[found] * channels * bytes;
     if (dataBytes > 0xFFFFFFFFull - 36)
@@ -203,29 +247,39 @@ WideReport decodeWideFile(const std::string& in, const std::string& out)
     WideReport report;
     report.frames = found;
     sela_host::PinnedBuffer<uint8_t> pcm((size_t)std::max<uint64_t>(dataBytes, 4));
-    if (found && sela_hip_decode_pcm(stream.data(), offsets.data(), found, channels, bytes, pcm.data(), (size_t)dataBytes, &report.wideSamples) != SELA_HIP_OK)
+    if (found && sela_hip_decode_pcm(s.stream.data(), s.offsets.data(), found, channels, bytes, pcm.data(), (size_t)dataBytes, &report.wideSamples) != SELA_HIP_OK)
         failHip("Decoder");
-    uint8_t wav[44];
-    std::memcpy(wav, "RIFF", 4);
-    put32(wav + 4, 36 + (uint32_t)dataBytes);
-    std::memcpy(wav + 8, "WAVEfmt ", 8);
-    put32(wav + 16, 16);
-    put16(wav + 20, 1); // PCM
-    put16(wav + 22, channels);
-    put32(wav + 24, rate);
-    put32(wav + 28, rate * channels * bytes);
-    put16(wav + 32, channels * bytes);
-    put16(wav + 34, bits);
-    std::memcpy(wav + 36, "data", 4);
-    put32(wav + 40, (uint32_t)dataBytes);
-    std::ofstream o(out, std::ios::binary | std::ios::trunc);
-    if (!o)
-        throw data::Exception("cannot open " + out + " for writing");
-    o.write(reinterpret_cast<const char*>(wav), 44);
-    o.write(reinterpret_cast<const char*>(pcm.data()), (std::streamsize)dataBytes);
-    if (!o)
-        throw data::Exception("cannot write " + out);
+    writeWideWav(out, s, pcm.data(), dataBytes);
     return report;
+}
+
+// A range of a wide file's samples: the range is one window of the whole stream (sela_hip_decode_windows_i32 copies and decodes the
+// frames it touches and no others; a range longer than the call's 2^24 samples goes in pieces of that length), in the file's
+// own packed layout.  Nothing is created before the samples are there.
+size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64_t startSample, uint64_t sampleCount)
+{
+    WideSela s;
+    readWideSela(in, "decodeWideFileRange", s);
+    const uint32_t channels = s.channels, bytes = s.bits / 8u;
+    const uint64_t streamSamples = (uint64_t)s.found * kFrameSamples;
+    if (startSample >= streamSamples)
+        throw data::Exception("Decode: --start " + std::to_string(startSample) + " is at or past the end of the stream (" + std::to_string(streamSamples)
+            + " samples per channel)");
+    const uint64_t count = std::min(sampleCount, streamSamples - startSample);
+    const uint64_t dataBytes = count * channels * bytes;
+    if (dataBytes > 0xFFFFFFFFull - 36)
+        throw data::Exception("the samples do not fit a wav file");
+    std::vector<uint8_t> pcm((size_t)std::max<uint64_t>(dataBytes, 4));
+    const uint64_t piece = (uint64_t)1 << 24;
+    for (uint64_t done = 0; done < count; done += piece) {
+        const sela_hip_window window = { startSample + done, 0, s.found };
+        if (sela_hip_decode_windows_i32(s.stream.data(), s.offsets.data(), s.found, channels, &window, 1, (uint32_t)std::min(piece, count - done),
+                bytes == 3 ? SELA_HIP_WINDOW_PCM24_INTERLEAVED : SELA_HIP_WINDOW_PCM32_INTERLEAVED, s.bits, pcm.data() + (size_t)(done * channels * bytes), nullptr)
+            != SELA_HIP_OK)
+            failHip("Decode");
+    }
+    writeWideWav(out, s, pcm.data(), dataBytes);
+    return (size_t)count;
 }
 
 } // namespace sela

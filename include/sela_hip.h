@@ -464,8 +464,9 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
  *                  frame) decodes that met a malformed frame; [2] the number of windows with a non-zero flag word; [3] zero.
  *                  n_windows = 0 writes zero status words and nothing else.
  * Scope: frames of 2048 samples, 1 .. 8 channels, 16-bit samples.  More than 8 channels is SELA_HIP_EINVAL (decode the frames
- * with sela_hip_decode_device and crop); frames of other lengths are SELA_HIP_FLAG_BAD_FRAME, as from sela_hip_decode_device; 32-bit
- * output and streams of any other frame length have no window call (random access there needs a search of sample_offsets).
+ * with sela_hip_decode_device and crop); frames of other lengths are SELA_HIP_FLAG_BAD_FRAME, as from sela_hip_decode_device; samples
+ * of more than 16 bits: sela_hip_decode_windows_i32_device, below; streams of any other frame length have no window call (random
+ * access there needs a search of sample_offsets).
  * The device call is asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of device data (the
  * descriptors stay on the device; the launch is shaped by window_samples alone), so a stream being captured into a HIP graph may
  * take it, and a replay reads whatever d_windows holds then.  d_workspace: sela_hip_decode_windows_workspace_bytes() bytes, no
@@ -530,6 +531,61 @@ int sela_hip_decode_windows_whole_device(const uint8_t* d_frames, const uint64_t
     uint32_t* d_window_flags /* [n_windows] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
 int sela_hip_decode_windows_whole(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
     uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out,
+    uint32_t* window_flags /* [n_windows] or NULL */);
+
+/* ---- sample windows of 24- and 32-bit streams -------------------------------------------------------------------
+ * The window calls above hand out 16-bit samples.  These take the same descriptor (in device memory for the device call) and the
+ * same table and stream semantics -- a stream is cut at the table's end, start may be any uint64, windows may overlap, repeat and
+ * come in any order -- and hand out samples of up to 32 bits:
+ *   format         SELA_HIP_WINDOW_I32_PLANAR: d_out is int32 [n_windows][channels][window_samples];
+ *                  SELA_HIP_WINDOW_PCM24_INTERLEAVED: 3-byte little-endian [n_windows][window_samples][channels], each sample's low
+ *                  three bytes -- window w starts at byte w * window_samples * channels * 3, at any byte phase;
+ *                  SELA_HIP_WINDOW_PCM32_INTERLEAVED: int32 little-endian [n_windows][window_samples][channels];
+ *                  SELA_HIP_WINDOW_F32_PLANAR: float [n_windows][channels][window_samples] holding (float)value * 2^-(sample_bits - 1),
+ *                  the conversion rounding to nearest-even (exact for 24-bit audio); sample_bits in 1 .. 32.
+ *                  SELA_HIP_WINDOW_I16_INTERLEAVED is SELA_HIP_EINVAL here (the calls above).  sample_bits is ignored for the
+ *                  other formats.
+ * Output sample i of window w refers to table frame f = first_frame + (start + i) / 2048 where that lies inside the window's
+ * stream.  Frame f is TAKEN when it sits at a 4-byte-aligned offset, the header walk accepts all `channels` subframes, each says
+ * 2048 samples, is longer than its order and is sela_subframe_decodable, no Rice stream runs dry, no coefficient leaves the tables
+ * or int64, and the layout passes the combine's rules (channel and parent exist, the parent is written before and is long enough,
+ * every channel ends at 2048).  For a taken frame the value is exactly what sela_hip_decode_i32_device writes for
+ * (f, channel, (start + i) % 2048) at stride 2048.  For any other frame the whole share of that frame is zero and its flags are
+ * SELA_HIP_FLAG_RICE_OVERRUN, _Q_RANGE or _COEF_OVERFLOW where one was met, SELA_HIP_FLAG_BAD_FRAME otherwise (a frame that does
+ * not say 2048 among them).  Samples behind the stream's end are zero, without a flag.
+ *   d_window_flags uint32 [n_windows] or NULL: the OR over the frames that window touched.
+ *   d_status uint32[4]: [0] the OR over all (window, frame) decodes; [1] the number of (window, frame) decodes that raised
+ *                  SELA_HIP_FLAG_BAD_FRAME; [2] the number of windows with a non-zero flag word; [3] PCM24 only: the number of
+ *                  output samples outside [-2^23, 2^23), whose low three bytes are written all the same; 0 for the other formats.
+ *                  n_windows = 0 writes zero status words and nothing else.
+ * Every byte of d_out is written exactly once by the call's launches (there is no pre-clear), and no other byte: a PCM24 share
+ * goes out as aligned dwords with single bytes only at its two ragged ends.  Scope: frames of 2048 samples, 1 .. 8 channels.
+ * The device call is asynchronous and capturable as sela_hip_decode_windows_device is: one serial chain on `stream`, launches
+ * shaped by n_windows, window_samples and channels alone, no allocation, no host wait, no host read of device data.
+ *   workspace = n_windows * cover * channels * (16 + 4 * 2048) + 4 * n_windows + 1024,   cover = (window_samples + 2046) / 2048 + 1
+ * (per window, covering frame and channel a record and 2048 decoded 32-bit samples; a flag word per window for a call that
+ * passes no d_window_flags; alignment).  It does not depend on the data.
+ * Errors, found before a device is asked for (nothing is enqueued then): those of sela_hip_decode_windows_device in its order
+ * and with its codes, where "another format" is anything but the four above or sample_bits outside 1 .. 32 with F32, the product
+ * refused at 2^31 is n_windows * cover * channels, n_windows at or above 2^24 is refused behind it (a launch holds fewer than 2^32
+ * work-items per dimension), and d_out must be 4-byte aligned in every format; SELA_HIP_ECAPACITY: a smaller workspace.
+ * The host call stages only the distinct covering frames, runs where sela_hip_decode_windows runs and returns what it returns:
+ * SELA_HIP_EFORMAT for a malformed or dry frame, SELA_HIP_ERANGE for coefficient trouble, `out` and `window_flags` filled in both
+ * cases.  It has no status words: the PCM24 count of d_status[3] is the device call's alone.  ALIGNMENT IN THE HOST CALL: the
+ * covering frames are staged back to back, so the rule "at a 4-byte-aligned offset" is applied to a frame's offset in the STAGED
+ * table, not in the caller's.  Every frame the library's encoders write is whole words, and a table of such frames behaves alike
+ * in both calls; a frame of whole words that the caller's table holds at an offset of 4k + 1 .. 3 (behind a frame that is not whole
+ * words) is refused by the device call always, and by the host call only when the frames staged in front of it leave it at such an
+ * offset again -- alone in its batch it lands on offset 0 and is decoded. */
+#define SELA_HIP_WINDOW_I32_PLANAR 2u
+#define SELA_HIP_WINDOW_PCM24_INTERLEAVED 3u
+#define SELA_HIP_WINDOW_PCM32_INTERLEAVED 4u
+size_t sela_hip_decode_windows_i32_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+int sela_hip_decode_windows_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out,
+    uint32_t* d_window_flags /* [n_windows] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out,
     uint32_t* window_flags /* [n_windows] or NULL */);
 
 /* ---- encode options: the lossless mode ----------------------------------------------------------------------

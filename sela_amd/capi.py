@@ -41,6 +41,7 @@ EXPORTS = [
     "sela_hip_encode_ragged_i32_opt", "sela_hip_encode_begin_opt",
     "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
     "sela_hip_decode_windows_whole_workspace_bytes", "sela_hip_decode_windows_whole_device", "sela_hip_decode_windows_whole",
+    "sela_hip_decode_windows_i32_workspace_bytes", "sela_hip_decode_windows_i32_device", "sela_hip_decode_windows_i32",
     "sela_hip_paired_signals_per_frame", "sela_hip_encode_paired_workspace_bytes", "sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device",
     "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
     "sela_hip_whole_frames", "sela_hip_whole_frame", "sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes",
@@ -52,6 +53,7 @@ EXPORTS = [
     "sela_hip_encode_pcm", "sela_hip_decode_pcm",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
+WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED, WINDOW_PCM32_INTERLEAVED = 2, 3, 4  # (sela_hip_decode_windows_i32*: these and F32_PLANAR)
 ENCODE_LOSSLESS = 1  # SELA_HIP_ENCODE_LOSSLESS
 
 
@@ -65,7 +67,7 @@ DEBUG_EXPORTS = [
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
-                   "encode_whole", "encode_split", "decode_whole")
+                   "encode_whole", "encode_split", "decode_whole", "windows_i32")
 
 
 class Trace(C.Structure):
@@ -178,6 +180,12 @@ def lib() -> C.CDLL:
     L.sela_hip_decode_windows_whole_device.restype = C.c_int
     L.sela_hip_decode_windows_whole.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, vp, vp]
     L.sela_hip_decode_windows_whole.restype = C.c_int
+    L.sela_hip_decode_windows_i32_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_windows_i32_workspace_bytes.restype = sz
+    L.sela_hip_decode_windows_i32_device.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_windows_i32_device.restype = C.c_int
+    L.sela_hip_decode_windows_i32.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, vp]
+    L.sela_hip_decode_windows_i32.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]

@@ -462,6 +462,95 @@ def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, 
     return out, flags, rc
 
 
+def _window32_shape(n: int, window_samples: int, channels: int, format: int):
+    """(shape, numpy dtype name) of n windows in one of sela_hip_decode_windows_i32's formats."""
+    if format == capi.WINDOW_I32_PLANAR:
+        return (n, channels, window_samples), "int32"
+    if format == capi.WINDOW_F32_PLANAR:
+        return (n, channels, window_samples), "float32"
+    if format == capi.WINDOW_PCM32_INTERLEAVED:
+        return (n, window_samples, channels), "int32"
+    if format == capi.WINDOW_PCM24_INTERLEAVED:
+        return (n, window_samples, channels, 3), "uint8"
+    raise ValueError("format must be capi.WINDOW_F32_PLANAR, WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED or WINDOW_PCM32_INTERLEAVED")
+
+
+class WindowDecoder32:
+    """sela_hip_decode_windows_i32_device: windows of `window_samples` samples of up to 32 bits cut from streams of 2048-sample
+    frames that lie in device memory.  Owns its output, flags, status and workspace on the current device (or
+    `device`); every call is asynchronous on the current stream and overwrites them.  format (capi.WINDOW_*): I32_PLANAR int32
+    [n, channels, window_samples]; F32_PLANAR float32 of that shape holding value * 2^-(sample_bits - 1); PCM32_INTERLEAVED int32
+    [n, window_samples, channels]; PCM24_INTERLEAVED uint8 [n, window_samples, channels, 3], each sample's low three bytes."""
+
+    pack = staticmethod(WindowDecoder.pack)
+
+    def __init__(self, max_windows: int, window_samples: int, channels: int, format: int, sample_bits: int = 24, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_windows, self.window_samples, self.channels, self.format, self.sample_bits = max_windows, window_samples, channels, format, sample_bits
+        shape, dtype = _window32_shape(max_windows, window_samples, channels, format)
+        with torch.cuda.device(self.device):
+            self.out = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+            self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_decode_windows_i32_workspace_bytes(max_windows, window_samples, channels))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.n_windows = 0
+
+    def decode(self, frames, offsets, n_frames_total: int, windows):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames_total + 1], windows: int64 cuda tensor
+        [n, 2] (pack()) -> the first n windows of the decoder's own output buffer."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= n_frames_total + 1
+        assert windows.dtype == torch.int64 and windows.is_cuda and windows.is_contiguous() and windows.dim() == 2 and windows.shape[1] == 2
+        n = int(windows.shape[0])
+        assert n <= self.max_windows
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_decode_windows_i32_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format, self.sample_bits,
+            self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        self.n_windows = n
+        return self.out[:n]
+
+    @property
+    def flags(self):
+        """int32 cuda tensor [n]: the OR of the flag bits of the frames each window of the last call touched."""
+        return self.window_flags[: self.n_windows]
+
+    def wide_samples(self) -> int:
+        """Waits for the last call: PCM24's count of samples outside [-2^23, 2^23) (their low bytes were written); else 0."""
+        return int(self.status.cpu().numpy().view(np.uint32)[3])
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_windows_i32 returns for the same batch."""
+        st = self.status.cpu().numpy().copy()
+        st[2], st[3] = 0, 1  # (WindowDecoder.check: the fast route's mapping of [0] and [1]; [3] is this call's wide count)
+        capi.check(decode_n_status_error(st))
+
+
+def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, format: int, sample_bits: int = 24):
+    """sela_hip_decode_windows_i32 on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
+    in `format` (WindowDecoder32's shapes), the per-window flags (uint32 [n]) and the call's return code -- 0, or EFORMAT / ERANGE
+    (capi.ERRORS) for a batch with a bad frame, whose other windows are good all the same; any other code raises."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
+    n = len(win)
+    shape, dtype = _window32_shape(n, window_samples, channels, format)
+    out = np.zeros(shape, dtype)
+    flags = np.zeros(n, np.uint32)
+    rc = lib.sela_hip_decode_windows_i32(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, format, sample_bits,
+                                         out.ctypes.data, flags.ctypes.data)
+    if rc not in (capi.OK, -5, -6):
+        capi.check(rc)
+    return out, flags, rc
+
+
 def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.ndarray):
     """sela_hip_verify on numpy arrays; pcm: int16 in the layout decode_host returns.  Returns three values:
     diff_counts (uint32 [n_frames]), first_diff (uint32 [n_frames]; 0xFFFFFFFF where nothing differs) and the number of

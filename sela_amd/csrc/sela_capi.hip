@@ -1739,6 +1739,47 @@ int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_windo
         });
 }
 
+// sela_hip_decode_windows_i32_device (5.23): windows_call's checks in its order and with its codes -- the format's place holds the
+// wider formats and F32's sample_bits, the product counts the channels too (a wave per subframe) and is followed by a bound on
+// n_windows alone (the store's grid), d_out is a dword's.
+bool window32_format_ok(uint32_t format) { return format >= SELA_HIP_WINDOW_F32_PLANAR && format <= SELA_HIP_WINDOW_PCM32_INTERLEAVED; }
+constexpr const char* kWindow32Channels = "channels must be in 1..8: a frame's subframes are combined in one workgroup's table (more channels: sela_hip_decode_i32_device, then crop)";
+constexpr const char* kWindow32Format = "format must be SELA_HIP_WINDOW_F32_PLANAR, _I32_PLANAR, _PCM24_INTERLEAVED or _PCM32_INTERLEAVED (int16: sela_hip_decode_windows_device)";
+constexpr const char* kWindow32Bits = "sample_bits must be in 1..32 with SELA_HIP_WINDOW_F32_PLANAR";
+constexpr const char* kWindow32Product = "n_windows * cover * channels must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)";
+constexpr const char* kWindow32Windows = "n_windows must stay below 2^24 (a workgroup of 256 per window and covering frame: a launch holds fewer than 2^32 work-items per dimension)";
+int windows_i32_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
+    uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) { return sela::window32_workspace_bytes(n_windows, window_samples, channels); };
+    const DeviceCallOf<decltype(formula)> c = { "decode_windows_i32", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t) {
+            if (channels == 0 || channels > 8)
+                return fail(SELA_HIP_EINVAL, kWindow32Channels);
+            if (window_samples == 0 || window_samples > (1u << 24))
+                return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+            if (!window32_format_ok(format))
+                return fail(SELA_HIP_EINVAL, kWindow32Format);
+            if (format == SELA_HIP_WINDOW_F32_PLANAR && (sample_bits == 0 || sample_bits > 32))
+                return fail(SELA_HIP_EINVAL, kWindow32Bits);
+            if ((uint64_t)n_windows * sela::window_cover(window_samples) * channels >= (1ull << 31))
+                return fail(SELA_HIP_EINVAL, kWindow32Product);
+            if (n_windows >= (1u << 24))
+                return fail(SELA_HIP_EINVAL, kWindow32Windows);
+            int rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_windows & 7) || ((uintptr_t)d_out & 3) || ((uintptr_t)d_window_flags & 3) || ((uintptr_t)d_status & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_windows must be 8-byte aligned, d_out, d_window_flags and d_status 4-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const uint32_t*, void* d_ws) {
+            return launched(sela::launch_window32(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out,
+                                d_window_flags, d_status, d_ws, sela::generic_standard_first_mode() != 2, c.stream),
+                "decode_windows_i32 launch");
+        });
+}
+
 // sela_hip_verify_i32_device / sela_hip_verify_payload_i32_device (5.15): the decode_i32 call with the compare's arrays
 template <typename Form>
 int verify_i32_call(const Form& form, uint32_t channels, uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts,
@@ -2029,6 +2070,46 @@ int sela_hip_decode_windows_whole(const uint8_t* frames, const uint64_t* frame_o
     return windows_host_call(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags, true);
 }
 
+// Sample windows of 24- and 32-bit streams (5.23).
+size_t sela_hip_decode_windows_i32_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+{
+    return sela::window32_workspace_bytes(n_windows, window_samples, channels);
+}
+
+int sela_hip_decode_windows_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels,
+    const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out, uint32_t* d_window_flags,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return windows_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out,
+        d_window_flags, d_status, d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows on the any-length route's leased
+// context and stream, as sela_hip_decode_windows runs.
+int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags)
+{
+    sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
+    if (channels == 0 || channels > 8)
+        return fail(SELA_HIP_EINVAL, kWindow32Channels);
+    if (window_samples == 0 || window_samples > (1u << 24))
+        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+    if (!window32_format_ok(format))
+        return fail(SELA_HIP_EINVAL, kWindow32Format);
+    if (format == SELA_HIP_WINDOW_F32_PLANAR && (sample_bits == 0 || sample_bits > 32))
+        return fail(SELA_HIP_EINVAL, kWindow32Bits);
+    if ((uint64_t)n_windows * sela::window_cover(window_samples) * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, kWindow32Product);
+    if (n_windows >= (1u << 24))
+        return fail(SELA_HIP_EINVAL, kWindow32Windows);
+    if ((n_windows && (!windows || !out)) || !frame_offsets || (n_frames_total && !frames))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_windows == 0)
+        return SELA_HIP_OK;
+    return sela::generic_decode_windows(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags,
+        g_recurrence_form, false, true, sample_bits);
+}
+
 size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return sela::verify_i32_workspace_bytes(max_frames, channels, stride);
@@ -2111,6 +2192,7 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
         bytes = carve_encode_split(at, c, a32 - c, b).end;
         break;
     case SELA_HIP_WORKSPACE_DECODE_WHOLE: bytes = sela::decode_whole_workspace_bytes(a32, b, &at); break;
+    case SELA_HIP_WORKSPACE_WINDOWS_I32: bytes = sela::window32_workspace_bytes(a32, b, c, &at); break;
     default: return -1;
     }
     return bytes == SIZE_MAX ? -1 : pieces.count;

@@ -633,7 +633,7 @@ thread_local uint64_t g_windows_staged_bytes = 0; // sela_hip_debug_windows_stag
 void windows_staged_bytes_reset() { g_windows_staged_bytes = 0; }
 
 int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
-    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form, bool whole)
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form, bool whole, bool wide, uint32_t sample_bits)
 {
     const Call call;
     if (call.rc != SELA_HIP_OK)
@@ -642,7 +642,8 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
         return SELA_HIP_EFORMAT;
     Arena& g_arena = call.arena();
     const hipStream_t st = call.stream();
-    const size_t out_per_window = (size_t)window_samples * channels * (format == SELA_HIP_WINDOW_F32_PLANAR ? 4 : 2);
+    // (wide, DESIGN.md 5.23: sela_hip_decode_windows_i32 -- the same plan and staging, launch_window32 and its formats behind)
+    const size_t out_per_window = (size_t)window_samples * channels * (wide ? (format == SELA_HIP_WINDOW_PCM24_INTERLEAVED ? 3 : 4) : format == SELA_HIP_WINDOW_F32_PLANAR ? 4 : 2);
     // (an estimate for the chunk's size only -- what a chunk needs is reserved exactly below: a 16-bit frame is about 5 bytes a sample at most)
     const size_t per_window = out_per_window + (size_t)(window_cover(window_samples) + (whole ? 2 : 0)) * channels * kBlock * (sizeof(int32_t) + 5) + 64;
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_windows, kChunkBudget / per_window));
@@ -657,7 +658,9 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
         else
             plan_windows(frame_offsets, n_frames_total, windows + w0, cw, window_samples, &plan);
         const size_t in_bytes = (size_t)plan.staged_bytes(), n_staged = plan.frames.size(), out_bytes = (size_t)cw * out_per_window;
-        const size_t ws_bytes = whole ? window_whole_workspace_bytes(cw, window_samples, channels) : window_workspace_bytes(cw, window_samples, channels);
+        const size_t ws_bytes = wide ? window32_workspace_bytes(cw, window_samples, channels)
+            : whole                   ? window_whole_workspace_bytes(cw, window_samples, channels)
+                                      : window_workspace_bytes(cw, window_samples, channels);
         hipError_t e = g_arena.reserve(in_bytes + 8 + (n_staged + 1) * 8 + (size_t)cw * sizeof(sela_hip_window) + out_bytes + (4 + (size_t)cw) * 4 + ws_bytes + 8 * kPiece);
         if (e != hipSuccess)
             return report_hip_error(e, "decode_windows: scratch");
@@ -687,7 +690,10 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
             e = hipMemcpyAsync(d_offsets, plan.offsets.data(), (n_staged + 1) * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
             e = hipMemcpyAsync(d_windows, plan.windows.data(), (size_t)cw * sizeof(sela_hip_window), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
+        if (e == hipSuccess && wide)
+            e = launch_window32(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, sample_bits, d_out, d_tail + 4, d_tail, d_ws,
+                g_standard_first_mode.load(std::memory_order_relaxed) != 2, st);
+        else if (e == hipSuccess)
             e = (whole ? launch_window_whole : launch_window_frames)(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, d_out,
                 d_tail + 4, d_tail, d_ws, st, recurrence_form, 0);
         if (e == hipSuccess)

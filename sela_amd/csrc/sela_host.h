@@ -54,6 +54,14 @@ struct WindowWs { // launch_window_frames' pieces; launch_window_whole's workspa
 };
 WindowWs carve_windows(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels);
 
+hipError_t launch_window_clear(uint32_t* d_status, uint32_t* d_window_flags /* or null */, uint32_t n_windows, hipStream_t stream); // k_window_clear alone
+
+// ---- sela_window32.hip: sample windows of 24- and 32-bit streams -------------------------------------------------
+size_t window32_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
+hipError_t launch_window32(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace,
+    bool standard_path /* false: every subframe by segments (sela_hip_debug_standard_first(2)) */, hipStream_t stream);
+
 // ---- sela_window_whole.hip: windows that reach a whole-track stream's long last frame --------------------------
 size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
 hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
@@ -145,7 +153,8 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form,
-    bool whole = false /* plan_windows_whole and launch_window_whole */);
+    bool whole = false /* plan_windows_whole and launch_window_whole */,
+    bool wide = false /* launch_window32 and its formats */, uint32_t sample_bits = 0);
 void windows_staged_bytes_reset(); // sela_hip_debug_windows_staged_bytes of the calling thread back to 0: the entry point's first act
 int generic_lpc_encode(const int32_t* samples, uint32_t n_blocks, uint32_t n, int32_t* order_out, int32_t* q_out, int32_t* residues_out);
 int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* residues, uint32_t n_blocks, uint32_t n, int32_t* samples_out, int64_t* coefs_out);

@@ -137,6 +137,14 @@ __global__ __launch_bounds__(kWindowClearThreads) void k_window_clear(uint32_t* 
         window_flags[w] = 0;
 }
 
+// k_window_clear for the window calls of other files (sela_window32.hip): a word per window, or none where window_flags is null.
+hipError_t launch_window_clear(uint32_t* d_status, uint32_t* d_window_flags, uint32_t n_windows, hipStream_t stream)
+{
+    const uint32_t groups = d_window_flags && n_windows ? (n_windows + kWindowClearThreads - 1) / kWindowClearThreads : 1u;
+    hipLaunchKernelGGL(k_window_clear, dim3(groups), dim3(kWindowClearThreads), 0, stream, d_status, d_window_flags, d_window_flags ? n_windows : 0u);
+    return hipGetLastError();
+}
+
 uint32_t window_cover(uint32_t window_samples) { return (uint32_t)(((uint64_t)window_samples + 2046) / (uint32_t)kBlock + 1); }
 
 // The dynamic LDS a launch of k_window_frames asks for (sela_hip_debug_window_lds_bytes: tests hold it against the decoder's).
