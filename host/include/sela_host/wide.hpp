@@ -7,6 +7,8 @@
 //   * sela::encodeWideFile / decodeWideFile move the packed data chunk through page-locked memory and ONE call to
 //     sela_hip_encode_pcm / sela_hip_decode_pcm: 3 bytes per sample of a 24-bit file travel to the device, and the layout
 //     conversion is the device's.
+//   * sela::verifyWideFile is verifyFile for such a pair: ONE call to sela_hip_verify_pcm holds the stream against the WAV's packed
+//     data chunk.
 //   * sela::decodeWideFileRange is decodeFileRange for such files: one window of the stream through sela_hip_decode_windows_i32.
 #pragma once
 
@@ -14,6 +16,7 @@
 #include <cstdint>
 #include <string>
 
+#include "sela_host/codec.hpp"
 #include "sela_host/data.hpp"
 
 namespace file {
@@ -51,6 +54,10 @@ WideReport decodeWideFile(const std::string& in, const std::string& out);
 // throws decodeFileRange's message where startSample is at or past the end.  (Samples of a 24-bit file that lie outside 24 bits
 // go out as their low three bytes, as from decodeWideFile, but are not counted here: the host window call returns no status words.)
 size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64_t startSample, uint64_t sampleCount);
+// wavPath: a 24- or 32-bit PCM WAV, selaPath: a .sela file of the same width -> verifyFile's report (formatVerifyReport and
+// verifyExitCode apply unchanged): the frames that come back different, the WAV's tail, the samples the .sela holds beyond the WAV.
+// Throws data::Exception, naming both widths, where the two files' widths disagree.
+VerifyReport verifyWideFile(const std::string& wavPath, const std::string& selaPath);
 // what the .sela header at `path` says its samples' width is; 0 where there is no such header (the caller's path then reports it)
 uint16_t selaFileBits(const std::string& path);
 

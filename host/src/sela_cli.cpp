@@ -10,13 +10,14 @@
 //                                      frame are folded into a long last frame instead of dropped (with --lossless, -v then exits 0);
 //                                      not with --pair-channels, not with -E
 //   sela_mi355x -d in.sela out.wav     decode
-//   (-e, -e --lossless, -d and -d --start S --count N take 24- and 32-bit files too, routed by what the WAV's or the .sela's header
+//   (-e, -e --lossless, -d, -d --start S --count N and -v take 24- and 32-bit files too, routed by what the WAV's or the .sela's header
 //   says: the packed samples go to the device and come back as they lie in the file; every other verb and flag keeps to 16-bit files)
 //   sela_mi355x -d --start S --count N in.sela out.wav   decode samples S .. S + N - 1 per channel only (cut at the stream's end):
 //                                      the frames the range touches are decoded and no others
 //   sela_mi355x -v in.wav in.sela      verify: which frames of in.sela come back different from in.wav (compared on the GPU), and
 //                                      what of in.wav it never held; exit 0: all of it comes back exactly, 3: a frame differs or
-//                                      the headers disagree, 4: only tail samples are missing, 1: an error
+//                                      the headers disagree, 4: only tail samples are missing, 1: an error (a .wav and a .sela
+//                                      of different sample widths among them)
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -234,7 +235,14 @@ int run(int argc, char** argv)
     }
     if (verb == "-v" && argc == 4) {
         std::cout << "Verifying: " << argv[3] << " against " << argv[2] << std::endl;
-        const sela::VerifyReport report = sela::verifyFile(std::string(argv[2]), std::string(argv[3]));
+        // (by the WAV's header, as -e: a 24- or 32-bit file goes to sela_hip_verify_pcm; a 16-bit WAV held against a
+        // wider .sela is refused in the same words)
+        const uint16_t selaBits = sela::selaFileBits(argv[3]);
+        if (!wideWav(argv[2]) && (selaBits == 24 || selaBits == 32) && file::probeWav(argv[2]).bitsPerSample == 16)
+            throw data::Exception("Verify: the .wav holds 16-bit samples, the .sela " + std::to_string(selaBits)
+                + "-bit samples: files of different widths are not held against each other");
+        const sela::VerifyReport report = wideWav(argv[2]) ? sela::verifyWideFile(std::string(argv[2]), std::string(argv[3]))
+                                                           : sela::verifyFile(std::string(argv[2]), std::string(argv[3]));
         std::cout << sela::formatVerifyReport(report) << std::flush;
         return sela::verifyExitCode(report);
     }

@@ -282,4 +282,63 @@ size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64
     return (size_t)count;
 }
 
+// verifyFile for a 24- or 32-bit pair: the headers held against each other as verifyFile holds them, the frames the .sela really
+// holds against the WAV's packed data chunk in ONE sela_hip_verify_pcm call -- pcm_samples is what the WAV holds, so samples the
+// .sela has beyond it count as differences of their frames, and the WAV's tail is reported as now.
+VerifyReport verifyWideFile(const std::string& wavPath, const std::string& selaPath)
+{
+    const file::WavProbe wav = file::probeWav(wavPath);
+    const uint16_t selaBits = selaFileBits(selaPath);
+    if (selaBits != 0 && selaBits != wav.bitsPerSample)
+        throw data::Exception("Verify: the .wav holds " + std::to_string(wav.bitsPerSample) + "-bit samples, the .sela " + std::to_string(selaBits)
+            + "-bit samples: files of different widths are not held against each other");
+    if (wav.bitsPerSample != 24 && wav.bitsPerSample != 32)
+        throw data::Exception("verifyWideFile takes 24- and 32-bit wav (16-bit: verifyFile)");
+    WideSela s;
+    readWideSela(selaPath, "verifyWideFile", s);
+    std::ifstream head(selaPath, std::ios::binary);
+    uint8_t header[15] = {};
+    (void)readExact(head, header, 15);
+    const uint32_t channels = s.channels, bytes = s.bits / 8u, found = s.found;
+    VerifyReport r;
+    r.channels = channels;
+    r.wavRate = wav.sampleRate, r.selaRate = s.rate;
+    r.wavChannels = wav.channels, r.selaChannels = channels;
+    r.rateDiffers = r.wavRate != r.selaRate;
+    r.channelsDiffer = r.wavChannels != r.selaChannels;
+    r.selaHeaderFrames = le32(header + 11);
+    std::vector<uint64_t> sampleOffsets((size_t)found + 1, 0);
+    if (found && sela_hip_index_samples(s.stream.data(), s.offsets.data(), found, channels, sampleOffsets.data()) == 0)
+        throw data::Exception("Verify: malformed frame stream");
+    const uint64_t selaSamples = sampleOffsets[found];
+    bool ordinary = true;
+    for (uint32_t f = 0; ordinary && f <= found; f++)
+        ordinary = sampleOffsets[f] == (uint64_t)f * kFrameSamples;
+    const uint64_t wavSamples = wav.channels ? wav.dataBytes / ((uint64_t)wav.channels * bytes) : 0;
+    r.selaFrames = found;
+    r.wavFrames = wavSamples / kFrameSamples;
+    r.frameCountDiffers = r.selaHeaderFrames != found || (ordinary && !r.channelsDiffer && found != r.wavFrames);
+    if (r.channelsDiffer)
+        return r; // (nothing to hold against each other)
+    r.tailSamplesPerChannel = wavSamples > selaSamples ? wavSamples - selaSamples : 0;
+    r.missingSamplesPerChannel = selaSamples > wavSamples ? selaSamples - wavSamples : 0;
+    const uint64_t held = std::min(wavSamples, selaSamples);
+    sela_host::PinnedBuffer<uint8_t> pcm((size_t)std::max<uint64_t>(held * channels * bytes, 4));
+    std::ifstream file(wavPath, std::ios::binary);
+    file.seekg((std::streamoff)wav.dataOffset, std::ios::beg);
+    if (held && !readExact(file, pcm.data(), (size_t)(held * channels * bytes)))
+        throw data::Exception("data subChunk is shorter than its header says");
+    std::vector<uint32_t> counts((size_t)found + 1), first((size_t)found + 1);
+    uint32_t lossy = 0;
+    if (sela_hip_verify_pcm(s.stream.data(), s.offsets.data(), found, channels, bytes, pcm.data(), wavSamples, counts.data(), first.data(),
+            &lossy)
+        != SELA_HIP_OK)
+        failHip("Verify");
+    r.framesCompared = found;
+    for (uint32_t f = 0; f < found; f++)
+        if (counts[f])
+            r.lossy.push_back({ f, counts[f], first[f] });
+    return r;
+}
+
 } // namespace sela

@@ -832,6 +832,60 @@ int sela_hip_encode_pcm(const void* pcm, uint32_t bytes_per_sample, uint32_t n_f
 int sela_hip_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, void* pcm_out,
     size_t pcm_cap /* bytes */, uint32_t* wide_samples /* or NULL */);
 
+/* ---- verification against packed PCM: a 24- or 32-bit stream against the WAV's own bytes ---------------------------
+ * sela_hip_verify_i32_device with the original read where a WAV or a capture buffer has it: little-endian interleaved samples of
+ * bytes_per_sample = 3 or 4, the layout sela_hip_decode_pcm_device writes.  One compare kernel takes the packed bytes through
+ * LDS; no unpacked copy of the original is made, and frames of different lengths (a whole-track tail, any-length frames) are
+ * taken as they come.
+ *   d_pcm          pcm_samples samples per channel; frame f starts at byte so[f] * channels * bytes_per_sample, so being
+ *                  sela_hip_index_samples' sample offsets (a frame's first subframe says how long the frame is).  The base is
+ *                  4-byte aligned; a frame may start at any byte phase.  Read only, and only as aligned dwords that hold at least
+ *                  one byte of [0, pcm_samples * channels * bytes_per_sample) -- whatever the stream says: n_f is clamped to
+ *                  stride and so[f] to pcm_samples before anything is addressed.
+ *   With n_f = so[f + 1] - so[f], L_f = min(n_f, max(pcm_samples - so[f], 0)), m_c the count sela_hip_decode_i32_device reports
+ *   for (f, c) and dec its samples:
+ *   d_diff_counts  [n_frames]: the sum over the channels of #{ i < min(m_c, L_f) : dec[c][i] != the sign-extended original }
+ *                  + |m_c - L_f|.  A decoded value outside 24 bits never equals a 3-byte original, even if its low bytes do.
+ *   d_first_diff   [n_frames]: the smallest i * channels + c -- interleaved order relative to the frame, as
+ *                  sela_hip_verify_device counts -- i being channel c's first differing index, or min(m_c, L_f) where only the
+ *                  lengths differ; 0xFFFFFFFF where nothing differs.
+ *   (Apart from the order of d_first_diff: sela_hip_verify_i32_device on the unpacked samples with d_lengths[f][c] = L_f.)
+ *   d_sample_offsets [n_frames + 1] or NULL: the sample offsets, as sela_hip_decode_pcm_device leaves them.
+ *   d_status uint32[4]: [0] and [1] exactly sela_hip_decode_i32_device's (SELA_HIP_FLAG_STRIDE included: nothing is compared
+ *                  then); [2] the number of frames whose count is not 0; [3] zero.  sela_hip_decode_status_error() applies
+ *                  unchanged; n_frames = 0 writes zero status words.
+ * Asynchronous on `stream`: no allocation, no host synchronisation, no host-side read of device data -- capturable into a HIP
+ * graph.  Nothing but the outputs named here and the workspace is written.
+ * d_workspace: sela_hip_verify_pcm_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more).  With up(b) = b rounded up to a multiple of 256 and
+ * tile = max((4096 / channels) & ~3, 4) samples it is
+ *     sela_hip_decode_i32_workspace_bytes(max_frames, channels, stride)      the subframes as decoded, their records, the index
+ *   + up(max_frames * channels * stride * 4)                                 the samples by channel, for frames of any other layout
+ *   + up(max_frames * channels * 4)                                          ... and their counts
+ *   + up(max(max_frames, 1) * 4)                                             a mark per frame: which way it went
+ *   + up(max(max_frames * ceil(stride / tile), 1) * 8)                       two words per (frame, tile)
+ *   + 256                                                                    the two control words
+ *   + up((max_frames + 1) * 8)                                               the sample offsets of a caller that passes none
+ * and SIZE_MAX where sela_hip_verify_i32_workspace_bytes() is, or for channels = 0.
+ * Errors: sela_hip_verify_i32_device's, in its order; then SELA_HIP_EINVAL for bytes_per_sample other than 3 or 4, then for a
+ * d_pcm that is not 4-byte aligned (d_sample_offsets: 8-byte).  Nothing is enqueued then; an argument error is found before a
+ * device is asked for. */
+size_t sela_hip_verify_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts /* [n_frames] */, uint32_t* d_first_diff /* [n_frames] */,
+    uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their entries in the two arrays are not written). */
+int sela_hip_verify_payload_pcm_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of whole frames (3 bytes a sample travel for a 3-byte original): sela_hip_decode_i32's
+ * checks in its order, the stride being the stream's own largest frame; 0: the arrays are valid.  *lossy_frames (or NULL): the
+ * frames with a difference.  pcm needs no alignment.  Runs where sela_hip_verify_i32 runs: the calling thread's any-length context
+ * and its own stream, past the coalescer; an open streaming job of the thread is left alone. */
+int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample,
+    const void* pcm, uint64_t pcm_samples, uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
+
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and
  * returns at once -- from page-locked buffers nothing in it waits for the device (an encode feed is one kernel

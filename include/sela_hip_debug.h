@@ -82,6 +82,9 @@ size_t sela_hip_debug_verify_lds_bytes(uint32_t channels);
  * call pass the workspace behind its index part (d_workspace + sela_hip_index_workspace_bytes()).  Synchronises the device.
  * -1 on an error. */
 long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);
+/* The same of the LAST sela_hip_verify_pcm_device call that used this workspace: the frames that went through
+ * k_generic_combine<false> and k_verify_pcm's rest form -- 0: every frame was compared from the subframes as decoded. */
+long long sela_hip_debug_verify_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);
 
 /* Debug hook (tests; process-wide): while on, a device-pointer encode with a d_trace pointer runs the PRODUCT kernels plus a few
  * instructions (their kMode 3 instantiations, not the trace builds) and leaves, instead of traces, two 64-bit words per block at
@@ -140,7 +143,7 @@ enum {
     SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT, SELA_HIP_WORKSPACE_DECODE_WHOLE, SELA_HIP_WORKSPACE_WINDOWS_I32
 };
 int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
-/* Debug hook (tests; process-wide): sela_hip_encode_pcm and sela_hip_decode_pcm work in chunks of this many whole frames; 0
+/* Debug hook (tests; process-wide): sela_hip_encode_pcm, sela_hip_decode_pcm and sela_hip_verify_pcm work in chunks of this many whole frames; 0
  * restores the chunks sized by the device scratch they keep bounded.  Same bytes either way, which is what the tests check. */
 void sela_hip_debug_pcm_chunk_frames(uint32_t frames);
 

@@ -672,6 +672,110 @@ def verify_i32(frames: np.ndarray, offsets: np.ndarray, channels: int, samples: 
     return counts, first, int(lossy.value)
 
 
+class VerifierPcm:
+    """sela_hip_verify_pcm_device: a stream held against the packed interleaved PCM it was made from -- 3 or 4
+    bytes a sample, little-endian, frame f at sample_offsets[f] (the layout DecoderPcm writes and a WAV's data chunk has), frames
+    of any lengths -- frame by frame, on the device, without an unpacked copy of the original.  Owns its outputs and its
+    workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites them."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, bytes_per_sample: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride, self.bytes_per_sample = max_frames, channels, stride, bytes_per_sample
+        with torch.cuda.device(self.device):
+            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_verify_pcm_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def _samples(self, pcm, pcm_samples) -> int:
+        torch = self.torch
+        assert pcm.dtype == torch.uint8 and pcm.is_cuda and pcm.is_contiguous()
+        per = self.channels * self.bytes_per_sample
+        if pcm_samples is None:
+            pcm_samples = pcm.numel() // per
+        assert pcm_samples * per <= pcm.numel()
+        return pcm_samples
+
+    def verify(self, frames, offsets, n_frames: int, pcm, pcm_samples=None):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1], pcm: uint8 cuda tensor (4-byte
+        aligned) of pcm_samples samples per channel (None: all it holds)
+        -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]: sample * channels + channel in the frame; -1: nothing
+        differs), views of the verifier's own buffers."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        pcm_samples = self._samples(pcm, pcm_samples)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_pcm_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, pcm.data_ptr(), self.bytes_per_sample, pcm_samples,
+            self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(),
+            self.workspace.numel(), stream))
+        return self.diff_counts[:n_frames], self.first_diff[:n_frames]
+
+    def verify_payload(self, payload, pcm, pcm_samples=None, max_frames=None):
+        """Index and verify a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device.  -> (diff_counts [max_frames], first_diff [max_frames], count int32 [1]): entries up to count[0] are the
+        stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        pcm_samples = self._samples(pcm, pcm_samples)
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_verify_pcm_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_verify_payload_pcm_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, pcm.data_ptr(), self.bytes_per_sample, pcm_samples,
+            self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(),
+            self.status.data_ptr(), self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
+
+    def lossy_frames(self) -> int:
+        """Waits for the last call -> the number of frames with a difference (status[2])."""
+        return int(self.status[2].item())
+
+    def fallback_frames(self, n_frames=None) -> int:
+        """Waits for the last verify() call (not verify_payload) -> the frames whose layout was not direct (test hook)."""
+        return int(self.lib.sela_hip_debug_verify_pcm_fallback_frames(
+            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        st[2] = 0
+        capi.check(decode_status_error(st))
+
+
+def verify_pcm_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bytes_per_sample: int, pcm, pcm_samples=None):
+    """sela_hip_verify_pcm on numpy arrays; pcm: the packed interleaved bytes (uint8, or anything with a buffer), pcm_samples: the
+    samples per channel it holds (None: all of it).  Returns three values: diff_counts (uint32 [n_frames]), first_diff (uint32
+    [n_frames]: sample * channels + channel in the frame; 0xFFFFFFFF where nothing differs) and the number of frames with a difference."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    p = np.ascontiguousarray(np.frombuffer(pcm, dtype=np.uint8) if not isinstance(pcm, np.ndarray) else pcm.view(np.uint8).reshape(-1))
+    if pcm_samples is None:
+        pcm_samples = p.size // (channels * bytes_per_sample) if channels and bytes_per_sample else 0
+    assert pcm_samples * channels * bytes_per_sample <= p.size
+    counts = np.zeros(n_frames, np.uint32)
+    first = np.zeros(n_frames, np.uint32)
+    lossy = C.c_uint32(0)
+    capi.check(lib.sela_hip_verify_pcm(fr.ctypes.data, offs.ctypes.data, n_frames, channels, bytes_per_sample, p.ctypes.data, pcm_samples, counts.ctypes.data,
+                                       first.ctypes.data, C.byref(lossy)))
+    return counts, first, int(lossy.value)
+
+
 class Encoder32:
     """sela_hip_encode_i32 -- and sela_hip_encode of any length -- on the device: frames of any samples_per_channel (1 .. 65535),
     32-bit samples.  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is

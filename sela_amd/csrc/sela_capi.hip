@@ -1802,6 +1802,36 @@ int verify_i32_call(const Form& form, uint32_t channels, uint32_t stride, const 
                 "verify_i32 launch");
         });
 }
+
+// sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device (5.24): the verify_i32 call's checks in its order, then the
+// container's and the original's alignment
+template <typename Form>
+int verify_pcm_call(const Form& form, uint32_t channels, uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts,
+    uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "verify_pcm", sela::verify_pcm_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || (d_pcm && d_diff_counts && d_first_diff)));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_diff_counts & 3) || ((uintptr_t)d_first_diff & 3)))
+                rc = fail(SELA_HIP_EINVAL, "d_diff_counts and d_first_diff must be 4-byte aligned");
+            if (rc == SELA_HIP_OK && bytes_per_sample != 3 && bytes_per_sample != 4)
+                rc = fail(SELA_HIP_EINVAL, "bytes_per_sample must be 3 or 4 (16-bit samples: sela_hip_verify_device)");
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_pcm & 3))
+                rc = fail(SELA_HIP_EINVAL, "d_pcm must be 4-byte aligned");
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_sample_offsets & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_sample_offsets must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_verify_pcm_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_pcm, bytes_per_sample, pcm_samples,
+                                d_diff_counts, d_first_diff, d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), c.stream),
+                "verify_pcm launch");
+        });
+}
 } // namespace
 } // extern "C++"
 
@@ -2160,6 +2190,62 @@ long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uin
     uint32_t left = 0;
     if (hipDeviceSynchronize() != hipSuccess
         || hipMemcpy(&left, sela::verify_i32_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return (long long)left;
+}
+
+// ---- verification against packed PCM -----------------------------------------------------------------------
+size_t sela_hip_verify_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::verify_pcm_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const void* d_pcm,
+    uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return verify_pcm_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_diff_counts, d_first_diff,
+        d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
+}
+
+int sela_hip_verify_payload_pcm_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, const void* d_pcm,
+    uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return verify_pcm_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_pcm, bytes_per_sample, pcm_samples,
+        d_diff_counts, d_first_diff, d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: sela_hip_decode_i32's checks in its order (the stride is the stream's own largest frame), then chunks
+// of whole frames on the any-length route's leased context and stream (generic_verify_pcm), past the coalescer; an open streaming
+// job of the thread is left alone.
+int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const void* pcm,
+    uint64_t pcm_samples, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    if (lossy_frames)
+        *lossy_frames = 0;
+    if (channels == 0 || channels > 255 || (n_frames && (!frames || !frame_offsets || !diff_counts || !first_diff)) || (n_frames && pcm_samples && !pcm))
+        return fail(SELA_HIP_EINVAL, "bad argument");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (bytes_per_sample != 3 && bytes_per_sample != 4)
+        return fail(SELA_HIP_EINVAL, "bytes_per_sample must be 3 or 4 (16-bit samples: sela_hip_verify)");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    return sela::generic_verify_pcm(frames, frame_offsets, n_frames, channels, bytes_per_sample, static_cast<const uint8_t*>(pcm), pcm_samples, diff_counts, first_diff,
+        lossy_frames);
+}
+
+// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
+long long sela_hip_debug_verify_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    if (!d_workspace || sela::verify_pcm_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return -1;
+    uint32_t left = 0;
+    if (hipDeviceSynchronize() != hipSuccess
+        || hipMemcpy(&left, sela::verify_pcm_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
     return (long long)left;
 }

@@ -531,14 +531,42 @@ struct VerifySamples { // int32 [frame][channel][stride], lengths or null; judge
         return sela_hip_decode_status_error(decode_status);
     }
 };
+struct VerifyPacked { // packed interleaved PCM of 3 or 4 bytes a sample, where sela_hip_decode_pcm writes it (sample_offsets); judged as VerifySamples
+    const uint8_t* pcm;
+    uint64_t pcm_samples;
+    const uint64_t* sample_offsets;
+    uint32_t channels, stride, bytes_per_sample;
+    uint8_t* d_pcm;
+    uint32_t chunk_f0; // the first frame of the chunk d_pcm holds
+    uint64_t held(uint32_t f0) const { return pcm_samples - std::min(sample_offsets[f0], pcm_samples); } // samples the original holds from the chunk's first frame on
+    uint64_t samples(uint32_t f0, uint32_t cf) const { return std::min(sample_offsets[f0 + cf] - sample_offsets[f0], held(f0)); }
+    size_t bytes(uint32_t f0, uint32_t cf) const { return (size_t)samples(f0, cf) * channels * bytes_per_sample + 4; }
+    void take(Arena& arena, uint32_t f0, uint32_t cf) { d_pcm = arena.take<uint8_t>(bytes(f0, cf)), chunk_f0 = f0; }
+    hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
+    {
+        const size_t n = (size_t)samples(f0, cf) * channels * bytes_per_sample;
+        return n ? hipMemcpyAsync(d_pcm, pcm + sample_offsets[f0] * channels * bytes_per_sample, n, hipMemcpyHostToDevice, st) : hipSuccess;
+    }
+    hipError_t launch(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, uint32_t* d_tail, void* d_ws, int mode, hipStream_t st) const
+    {
+        return launch_verify_pcm_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, bytes_per_sample, held(chunk_f0), d_tail + 4, d_tail + 4 + cf, nullptr,
+            d_tail, d_ws, mode, st);
+    }
+    int judge(const uint32_t* tail) const
+    {
+        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
+        return sela_hip_decode_status_error(decode_status);
+    }
+};
 
 template <typename Ref>
 int verify_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
-    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), Ref ref, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), Ref ref, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames,
+    uint32_t forced_chunk = 0 /* tests: this many frames a chunk */)
 {
     Arena& g_arena = call.arena();
     const std::string name(who);
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, forced_chunk ? forced_chunk : kChunkBudget / per_frame));
     const hipStream_t st = call.stream();
     const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
     uint32_t lossy = 0;
@@ -951,6 +979,21 @@ int generic_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, con
             *wide_samples += status[3];
     }
     return SELA_HIP_OK;
+}
+
+// sela_hip_verify_pcm: verify_chunks on the packed original; the chunks as above, or by sela_hip_debug_pcm_chunk_frames.
+int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const uint8_t* pcm,
+    uint64_t pcm_samples, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
+    const uint32_t stride = std::max(generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), nullptr), 1u);
+    const size_t per_frame = (size_t)channels * stride * (8 + bytes_per_sample) + (size_t)channels * (sizeof(GenericSubInfo) + 8) + (size_t)verify_pcm_tiles(stride, channels) * 8 + 64;
+    return verify_chunks(call, "verify_pcm", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_pcm_workspace_bytes,
+        VerifyPacked{ pcm, pcm_samples, sample_offsets.data(), channels, stride, bytes_per_sample, nullptr, 0 }, diff_counts, first_diff, lossy_frames,
+        g_pcm_chunk_frames.load(std::memory_order_relaxed));
 }
 
 } // namespace sela

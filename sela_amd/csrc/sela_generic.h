@@ -88,11 +88,31 @@ hipError_t launch_verify32_direct(const int32_t* d_dec, const GenericSubInfo* d_
 hipError_t launch_verify32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
     const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, void* d_parts,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, hipStream_t stream);
+// the gate and the sum alone, for a compare with kernels of its own in between (sela_verify_pcm.hip)
+hipError_t launch_verify32_gate(uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_ctl, hipStream_t stream);
+hipError_t launch_verify32_sum(const void* d_parts, uint32_t n_slices, uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_diff_counts, uint32_t* d_first_diff,
+    uint32_t* d_status, hipStream_t stream);
 size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
 inline size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return verify_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
 const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
 hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device: launch_verify_i32_device's shape with the
+// original read as packed interleaved PCM of 3 or 4 bytes a sample, frame f at d_sample_offsets[f] (the caller's, or the
+// workspace's copy) -- sela_verify_pcm.hip's kernels on the tiles of sela_pcm_layout.h, no unpacked copy.
+uint32_t verify_pcm_tiles(uint32_t stride, uint32_t channels); // pcm_tiles(stride, channels)
+hipError_t launch_verify_pcm_direct(const int32_t* d_dec, const GenericSubInfo* d_info, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, const uint64_t* d_sample_offsets, const uint32_t* d_status, uint32_t* d_ctl,
+    uint32_t* d_marks /* [max_frames] */, void* d_parts /* [max_frames][verify_pcm_tiles()] x 8 bytes */, hipStream_t stream);
+hipError_t launch_verify_pcm_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride, const void* d_pcm,
+    uint32_t bytes_per_sample, uint64_t pcm_samples, const uint64_t* d_sample_offsets, const uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks, void* d_parts,
+    hipStream_t stream);
+size_t verify_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t verify_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return verify_pcm_workspace_bytes(max_frames, channels, stride, nullptr); }
+const uint32_t* verify_pcm_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
+hipError_t launch_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.

@@ -1838,7 +1838,7 @@ struct VerifyI32Ws {
     uint64_t* parts;
     uint32_t* ctl;
 };
-static VerifyI32Ws carve_verify_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+static VerifyI32Ws carve_verify_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t slices /* of a frame: two words each */)
 {
     const uint64_t subs = (uint64_t)max_frames * channels;
     VerifyI32Ws w;
@@ -1846,7 +1846,7 @@ static VerifyI32Ws carve_verify_i32(Carve& c, uint32_t max_frames, uint32_t chan
     w.all = c.take<int32_t>(subs * stride);
     w.counts = c.take<uint32_t>(subs);
     w.marks = c.take<uint32_t>(std::max<uint64_t>(max_frames, 1));
-    w.parts = c.take<uint64_t>(std::max<uint64_t>((uint64_t)max_frames * verify32_slices(stride), 1));
+    w.parts = c.take<uint64_t>(std::max<uint64_t>((uint64_t)max_frames * slices, 1));
     w.ctl = c.take<uint32_t>(2);
     return w;
 }
@@ -1856,13 +1856,13 @@ size_t verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32
     // (frames x channels first: the product of all three can wrap 64 bits; the launch calls keep it below 2^31)
     if ((uint64_t)max_frames * channels >= (1ull << 31) || (uint64_t)max_frames * channels * stride >= (1ull << 60))
         return SIZE_MAX;
-    return measured(at, [&](Carve& c) { carve_verify_i32(c, max_frames, channels, stride); });
+    return measured(at, [&](Carve& c) { carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride)); });
 }
 
 const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     Carve c(d_workspace);
-    return carve_verify_i32(c, max_frames, channels, stride).ctl;
+    return carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride)).ctl;
 }
 
 // launch_decode_i32_device with a compare in place of the combine: the sample index, k_verify32_begin (status[2], the largest
@@ -1877,7 +1877,7 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
     Carve c(d_workspace);
-    const VerifyI32Ws w = carve_verify_i32(c, max_frames, channels, stride);
+    const VerifyI32Ws w = carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride));
     launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.d.counters, w.d.tiles, stream);
     hipError_t e = launch_verify32_begin(d_status, w.ctl, stream);
     if (e != hipSuccess || max_frames * channels == 0)
@@ -1892,6 +1892,66 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
         w.all, w.counts, nullptr, nullptr, d_status, w.ctl + 1);
     return launch_verify32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, d_diff_counts,
         d_first_diff, stream);
+}
+
+// ---- verification against packed PCM on the device (sela_hip_verify_pcm_device) -------------------------------
+// Workspace: launch_verify_i32_device's pieces, the words per (frame, slice) sized by the tiles of sela_pcm_layout.h | the sample
+// offsets of a caller that asks for none.
+struct VerifyPcmWs {
+    VerifyI32Ws v;
+    uint64_t* offsets;
+};
+static VerifyPcmWs carve_verify_pcm(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    VerifyPcmWs w;
+    w.v = carve_verify_i32(c, max_frames, channels, stride, verify_pcm_tiles(stride, channels));
+    w.offsets = c.take<uint64_t>((uint64_t)max_frames + 1);
+    return w;
+}
+
+size_t verify_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (channels == 0 || verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_verify_pcm(c, max_frames, channels, stride); });
+}
+
+const uint32_t* verify_pcm_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    Carve c(d_workspace);
+    return carve_verify_pcm(c, max_frames, channels, stride).v.ctl;
+}
+
+// launch_verify_i32_device with the compare's kernels exchanged for sela_verify_pcm.hip's: the sample index (into the caller's
+// offsets or the workspace's: the compare reads them), k_verify32_begin, the subframes by position, the direct compare, the gate,
+// the combine on its count, the rest, the sum over the tiles.
+hipError_t launch_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const VerifyPcmWs w = carve_verify_pcm(c, max_frames, channels, stride);
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.offsets;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, w.v.d.counters, w.v.d.tiles, stream);
+    hipError_t e = launch_verify32_begin(d_status, w.v.ctl, stream);
+    if (e != hipSuccess || max_frames * channels == 0)
+        return e;
+    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.v.d, d_status, mode, d_n_found, stream);
+    if (e != hipSuccess)
+        return e;
+    e = launch_verify_pcm_direct(w.v.d.dec, w.v.d.info, max_frames, d_n_found, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.v.ctl,
+        w.v.marks, w.v.parts, stream);
+    if (e == hipSuccess)
+        e = launch_verify32_gate(max_frames, d_n_found, w.v.ctl, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.v.d.dec, w.v.d.info, max_frames, channels, stride,
+        w.v.all, w.v.counts, nullptr, nullptr, d_status, w.v.ctl + 1);
+    e = launch_verify_pcm_rest(w.v.all, w.v.counts, max_frames, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.v.ctl, w.v.marks, w.v.parts,
+        stream);
+    if (e != hipSuccess)
+        return e;
+    return launch_verify32_sum(w.v.parts, verify_pcm_tiles(stride, channels), max_frames, d_n_found, d_diff_counts, d_first_diff, d_status, stream);
 }
 
 // Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total.  No

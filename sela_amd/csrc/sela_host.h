@@ -151,6 +151,10 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     uint32_t* first_diff, uint32_t* lossy_frames, int recurrence_form);
 int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
+// sela_hip_verify_pcm: the stride is the stream's largest samplesPerChannel (the host's walk); each chunk's packed bytes are staged
+// from the chunk's first frame, so the device's base is aligned and the chunk's own sample offsets start at 0.
+int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const uint8_t* pcm,
+    uint64_t pcm_samples, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, int recurrence_form,
     bool whole = false /* plan_windows_whole and launch_window_whole */,

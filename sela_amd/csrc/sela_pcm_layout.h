@@ -131,5 +131,23 @@ SELA_PCM_HD int32_t pcm_extract(uint32_t lo, uint32_t hi, uint32_t shift, uint32
     return bytes_per_sample == 3 ? (int32_t)(v << 8) >> 8 : (int32_t)v;
 }
 
+// k_verify_pcm's view of an original frame (sela_verify_pcm.hip): a buffer of pcm_samples samples per channel, a
+// frame said to run from sample so0 to so1 -- by a header walk that may have broken: anything, so1 < so0 too.  The frame's
+// length is clamped to stride and its start to pcm_samples before anything is addressed: [so, so + n) lies inside the buffer.
+struct PcmHeld {
+    uint64_t so; // the frame's first sample, at most pcm_samples
+    uint32_t n;  // the samples of each channel the buffer holds of it: min(so1 - so0, stride, pcm_samples - so)
+};
+SELA_PCM_HD PcmHeld pcm_held_frame(uint64_t so0, uint64_t so1, uint32_t stride, uint64_t pcm_samples)
+{
+    PcmHeld h;
+    h.so = so0 < pcm_samples ? so0 : pcm_samples;
+    uint64_t n = so1 - so0; // (mod 2^64)
+    n = n < stride ? n : stride;
+    const uint64_t left = pcm_samples - h.so;
+    h.n = (uint32_t)(n < left ? n : left);
+    return h;
+}
+
 } // namespace sela
 #endif

@@ -18,22 +18,11 @@
 // Per frame: diff_count[f] = sum over the channels of #{ i < min(m, L) : decoded != original } + |m - L| (m: the decoder's
 // count, L: the original's length), first_diff[f] = the smallest c * stride + i (0xFFFFFFFF: nothing differs).
 #include "sela_host.h"
+#include "sela_verify32_rule.h"
 
 namespace sela {
 
 namespace {
-
-constexpr uint32_t kNoDiff = 0xFFFFFFFFu;
-constexpr uint32_t kV32Threads = 256, kV32Waves = kV32Threads / 64;
-constexpr uint32_t kV32NoParent = 0xFFFFu;
-
-// Minimum of one unsigned 32-bit value per lane (wave_max_u32 on the complements; the result is wave-uniform).
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) { return ~wave_max_u32(~v); }
-
-__device__ __forceinline__ uint32_t frames_in_call(const uint32_t* __restrict__ n_frames_found, uint32_t max_frames)
-{
-    return n_frames_found ? min(*n_frames_found, max_frames) : max_frames;
-}
 
 // Samples [lo, end) of one channel: dec (minus: par - dec mod 2^32 where par is not null) against org; a difference at i counts
 // as index_base + i.  kVec: all three rows are 16-byte aligned and whole int4s long (stride % 4 == 0), so a thread takes four
@@ -86,27 +75,6 @@ __device__ __forceinline__ void compare_lengths(uint32_t m, uint32_t L, uint32_t
     }
 }
 
-// The workgroup's count and smallest index: DPP rows inside a wave, LDS across the waves; thread 0 leaves the slice's two words
-// (parts: the counts of every (frame, slice), then the smallest indices: n_slots of each).
-__device__ __forceinline__ void leave_slice_words(uint32_t n_diff, uint32_t first, uint32_t* s_count, uint32_t* s_first, uint32_t* __restrict__ parts,
-    size_t slot, size_t n_slots)
-{
-    n_diff = wave_sum_small(n_diff);
-    first = wave_min32(first);
-    if (threadIdx.x % 64 == 0)
-        s_count[threadIdx.x / 64] = n_diff, s_first[threadIdx.x / 64] = first;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0, least = kNoDiff;
-        for (uint32_t w = 0; w < kV32Waves; w++) {
-            total += s_count[w];
-            least = min(least, s_first[w]);
-        }
-        parts[slot] = total;
-        parts[n_slots + slot] = least;
-    }
-}
-
 // ctl[0]: the frames k_verify32_direct leaves alone; ctl[1]: the frames the fallback takes (k_verify32_gate)
 __global__ __launch_bounds__(64) void k_verify32_begin(uint32_t* __restrict__ status, uint32_t* __restrict__ ctl)
 {
@@ -128,39 +96,7 @@ __global__ __launch_bounds__(kV32Threads) void k_verify32_direct(const int32_t* 
         return;
     const size_t row = (size_t)f * channels;
     const GenericSubInfo* const inf = info + row;
-    s_named[t] = 0, s_pos[t] = 0;
-    if (t == 0)
-        s_other = 0;
-    __syncthreads();
-    GenericSubInfo si;
-    si.channel = si.type = si.parent = si.ok = 0, si.n = 0;
-    bool good = false;
-    if (t < channels) {
-        si = inf[t];
-        good = si.ok && si.type <= 1 && si.channel < channels;
-        if (good) {
-            atomicAdd(&s_named[si.channel], 1u);
-            s_pos[si.channel] = (uint16_t)t, s_n[si.channel] = si.n; // (a channel named twice: either one, the frame is not direct)
-        }
-    }
-    __syncthreads();
-    if (t < channels) {
-        bool ok = good && s_named[t] == 1;
-        uint32_t ppos = kV32NoParent;
-        if (ok && si.type == 1) {
-            ok = si.parent < channels && s_named[si.parent] == 1;
-            if (ok) {
-                ppos = s_pos[si.parent];
-                const GenericSubInfo ps = inf[ppos];
-                ok = ps.type == 0 && ps.n >= si.n;
-            }
-        }
-        if (good)
-            s_ppos[si.channel] = (uint16_t)ppos;
-        if (!ok)
-            s_other = 1;
-    }
-    __syncthreads();
+    verify32_judge_layout(inf, channels, t, s_named, s_n, s_pos, s_ppos, s_other);
     const bool first_slice = blockIdx.y == 0;
     if (s_other) { // the fallback's: marked and counted once
         if (first_slice && t == 0) {
@@ -251,6 +187,20 @@ uint32_t verify32_slices(uint32_t stride) { return (stride + kVerify32Slice - 1)
 hipError_t launch_verify32_begin(uint32_t* d_status, uint32_t* d_ctl, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_verify32_begin, dim3(1), dim3(64), 0, stream, d_status, d_ctl);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify32_gate(uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_ctl, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_verify32_gate, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, d_ctl);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify32_sum(const void* d_parts, uint32_t n_slices, uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_diff_counts, uint32_t* d_first_diff,
+    uint32_t* d_status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_verify32_sum, dim3((max_frames + kV32Threads - 1) / kV32Threads), dim3(kV32Threads), 0, stream, static_cast<const uint32_t*>(d_parts), n_slices,
+        max_frames, d_n_found, d_diff_counts, d_first_diff, d_status);
     return hipGetLastError();
 }
 
