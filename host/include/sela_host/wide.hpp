@@ -40,13 +40,15 @@ WavProbe probeWav(const std::string& path);
 namespace sela {
 
 struct WideReport {
-    uint32_t frames = 0;         // 2048-sample frames coded / decoded
+    uint32_t frames = 0;         // frames coded / decoded
     uint64_t droppedSamples = 0; // encode: samples per channel behind the last whole frame (dropped, as plain -e drops them)
     uint32_t wideSamples = 0;    // decode: samples that did not fit a 3-byte container (their low bytes were written)
 };
 
 // in: a 24- or 32-bit PCM WAV (probeWav) -> out: a .sela file whose header carries the file's bitsPerSample; frames of 2048 samples.
-WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless = false);
+// keepTail: the whole data chunk through sela_hip_encode_whole_pcm -- the samples behind the last whole frame are
+// folded into a long last frame, numFrames is sela_hip_whole_frames' and droppedSamples 0.
+WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless = false, bool keepTail = false);
 // in: a .sela file whose header says 24 or 32 -> out: a WAV with the canonical 44-byte PCM header of that width.
 WideReport decodeWideFile(const std::string& in, const std::string& out);
 // in: such a .sela file -> out: a WAV of that width holding samples startSample .. startSample + sampleCount - 1 per channel, cut at

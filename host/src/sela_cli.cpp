@@ -9,6 +9,9 @@
 //   sela_mi355x -e --keep-tail [--lossless] in.wav out.sela   encode the whole file: the samples beyond the last whole 2048-sample
 //                                      frame are folded into a long last frame instead of dropped (with --lossless, -v then exits 0);
 //                                      not with --pair-channels, not with -E
+//   sela_mi355x -e --whole [--lossless] in.wav out.sela   the same by the file's own header: a 16-bit file exactly as --keep-tail, a
+//                                      24- or 32-bit file through sela_hip_encode_whole_pcm (--keep-tail itself keeps to 16-bit files);
+//                                      -d, -d --start S --count N and -v read such files without a flag
 //   sela_mi355x -d in.sela out.wav     decode
 //   (-e, -e --lossless, -d, -d --start S --count N and -v take 24- and 32-bit files too, routed by what the WAV's or the .sela's header
 //   says: the packed samples go to the device and come back as they lie in the file; every other verb and flag keeps to 16-bit files)
@@ -52,6 +55,8 @@ int usage(const std::string& program)
               << program << " -e --pair-channels [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Encoding a whole file (the samples beyond the last whole frame are kept, in a long last frame):\n"
               << program << " -e --keep-tail [--lossless] path/to/input.wav path/to/output.sela\n\n"
+              << "Encoding a whole 16-, 24- or 32-bit file (as --keep-tail, by the file's own header):\n"
+              << program << " -e --whole [--lossless] path/to/input.wav path/to/output.sela\n\n"
               << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only; 16-, 24- and 32-bit files alike):\n"
               << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
@@ -124,11 +129,11 @@ bool wideWav(const std::string& path)
     }
 }
 
-// plain -e and -e --lossless of a 24- or 32-bit file
-int encodeWide(const std::string& in, const std::string& out, bool lossless)
+// plain -e and -e --lossless of a 24- or 32-bit file; keepTail: -e --whole (5.25)
+int encodeWide(const std::string& in, const std::string& out, bool lossless, bool keepTail = false)
 {
-    std::cout << "Encoding (" << file::probeWav(in).bitsPerSample << "-bit" << (lossless ? ", lossless" : "") << "): " << in << std::endl;
-    const sela::WideReport r = sela::encodeWideFile(in, out, lossless);
+    std::cout << "Encoding (" << file::probeWav(in).bitsPerSample << "-bit" << (keepTail ? ", whole file" : "") << (lossless ? ", lossless" : "") << "): " << in << std::endl;
+    const sela::WideReport r = sela::encodeWideFile(in, out, lossless, keepTail);
     std::cout << r.frames << " frames, " << r.droppedSamples << " samples per channel behind the last whole frame dropped" << std::endl;
     return 0;
 }
@@ -147,9 +152,11 @@ int run(int argc, char** argv)
     const std::string program = argv[0];
     const std::string verb = argc > 1 ? argv[1] : "";
     // (--keep-tail is -e's alone, right behind it, with --lossless behind it or nothing: with --pair-channels, with -E and anywhere
-    // else it is refused, not ignored)
+    // else it is refused, not ignored; so is --whole, which sends a 24- or 32-bit file to encodeWideFile and any other down
+    // --keep-tail's path)
     for (int i = 2; i < argc; i++) {
-        if (std::string(argv[i]) != "--keep-tail")
+        const bool whole = std::string(argv[i]) == "--whole";
+        if (std::string(argv[i]) != "--keep-tail" && !whole)
             continue;
         const bool keepLossless = argc == 6 && std::string(argv[3]) == "--lossless";
         if (!(verb == "-e" && i == 2 && (argc == 5 || keepLossless)))
@@ -157,6 +164,8 @@ int run(int argc, char** argv)
         for (int k = 3; k < argc; k++)
             if (std::string(argv[k]).rfind("--", 0) == 0 && !(keepLossless && k == 3))
                 return usage(program);
+        if (whole && wideWav(argv[argc - 2]))
+            return encodeWide(argv[argc - 2], argv[argc - 1], keepLossless, true);
         std::cout << "Encoding (whole file" << (keepLossless ? ", lossless" : "") << "): " << argv[argc - 2] << std::endl;
         sela::encodeFile(std::string(argv[argc - 2]), std::string(argv[argc - 1]), keepLossless, false, true);
         return 0;

@@ -106,7 +106,7 @@ WavProbe probeWav(const std::string& path)
 
 namespace sela {
 
-WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless)
+WideReport encodeWideFile(const std::string& in, const std::string& out, bool lossless, bool keepTail)
 {
     const file::WavProbe p = file::probeWav(in);
     if (p.bitsPerSample != 24 && p.bitsPerSample != 32)
@@ -114,14 +114,15 @@ WideReport encodeWideFile(const std::string& in, const std::string& out, bool lo
     if (p.channels == 0 || p.channels > 255)
         throw data::Exception("a .sela file holds 1 to 255 channels");
     const uint32_t bytes = p.bitsPerSample / 8u;
-    const uint64_t samples = p.dataBytes / ((uint64_t)p.channels * bytes), frames64 = samples / kFrameSamples;
+    // keepTail: the whole data chunk, the layout sela_hip_whole_frames gives it
+    const uint64_t samples = p.dataBytes / ((uint64_t)p.channels * bytes), frames64 = keepTail ? sela_hip_whole_frames(samples) : samples / kFrameSamples;
     if (frames64 >= (1ull << 31))
         throw data::Exception("the file holds too many frames");
     WideReport report;
     report.frames = (uint32_t)frames64;
-    report.droppedSamples = samples - frames64 * kFrameSamples;
-    const size_t frameBytes = (size_t)kFrameSamples * p.channels * bytes;
-    sela_host::PinnedBuffer<uint8_t> pcm((size_t)report.frames * frameBytes);
+    const uint64_t coded = keepTail ? samples : frames64 * kFrameSamples; // samples per channel that go into the stream
+    report.droppedSamples = samples - coded;
+    sela_host::PinnedBuffer<uint8_t> pcm((size_t)(coded * p.channels * bytes));
     std::ifstream file(in, std::ios::binary);
     file.seekg((std::streamoff)p.dataOffset, std::ios::beg);
     if (!pcm.empty() && !readExact(file, pcm.data(), pcm.size()))
@@ -129,12 +130,14 @@ WideReport encodeWideFile(const std::string& in, const std::string& out, bool lo
     std::vector<uint64_t> offsets((size_t)report.frames + 1, 0);
     sela_host::PinnedBuffer<uint8_t> stream;
     // room by the estimate the library's own chunks use (4.5 bytes a sample); the certain bound only for a file that needs it
-    const size_t estimate = (size_t)report.frames * (((size_t)kFrameSamples * p.channels * 9) / 2 + (size_t)p.channels * 192 + 64);
-    const size_t rooms[2] = { estimate, sela_hip_encode_pcm_bound_bytes(report.frames, p.channels, kFrameSamples, bytes) };
+    const size_t estimate = ((size_t)coded * p.channels * 9) / 2 + (size_t)report.frames * ((size_t)p.channels * 192 + 64);
+    const size_t rooms[2] = { estimate, keepTail ? sela_hip_encode_whole_pcm_bound_bytes(samples, p.channels, bytes)
+                                                 : sela_hip_encode_pcm_bound_bytes(report.frames, p.channels, kFrameSamples, bytes) };
+    const uint32_t options = lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u;
     for (size_t room : rooms) {
         stream.resize(std::max<size_t>(room, 4));
-        const int rc = sela_hip_encode_pcm(pcm.data(), bytes, report.frames, p.channels, kFrameSamples, lossless ? SELA_HIP_ENCODE_LOSSLESS : 0u, stream.data(),
-            stream.size(), offsets.data());
+        const int rc = keepTail ? sela_hip_encode_whole_pcm(pcm.data(), bytes, samples, p.channels, options, stream.data(), stream.size(), offsets.data())
+                                : sela_hip_encode_pcm(pcm.data(), bytes, report.frames, p.channels, kFrameSamples, options, stream.data(), stream.size(), offsets.data());
         if (rc == SELA_HIP_OK)
             break;
         if (rc != SELA_HIP_ECAPACITY || room == rooms[1])
@@ -253,7 +256,7 @@ WideReport decodeWideFile(const std::string& in, const std::string& out)
     return report;
 }
 
-// A range of a wide file's samples: the range is one window of the whole stream (sela_hip_decode_windows_i32 copies and decodes the
+// A range of a wide file's samples: the range is one window of the whole stream (sela_hip_decode_windows_i32_whole copies and decodes the
 // frames it touches and no others; a range longer than the call's 2^24 samples goes in pieces of that length), in the file's
 // own packed layout.  Nothing is created before the samples are there.
 size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64_t startSample, uint64_t sampleCount)
@@ -261,7 +264,11 @@ size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64
     WideSela s;
     readWideSela(in, "decodeWideFileRange", s);
     const uint32_t channels = s.channels, bytes = s.bits / 8u;
-    const uint64_t streamSamples = (uint64_t)s.found * kFrameSamples;
+    // the stream's length by what its frames say (a whole-track stream ends in a frame of 1 .. 4095 samples)
+    std::vector<uint64_t> sampleOffsets((size_t)s.found + 1, 0);
+    if (s.found && sela_hip_index_samples(s.stream.data(), s.offsets.data(), s.found, channels, sampleOffsets.data()) == 0)
+        throw data::Exception("Decode: malformed frame stream");
+    const uint64_t streamSamples = sampleOffsets[s.found];
     if (startSample >= streamSamples)
         throw data::Exception("Decode: --start " + std::to_string(startSample) + " is at or past the end of the stream (" + std::to_string(streamSamples)
             + " samples per channel)");
@@ -273,7 +280,7 @@ size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64
     const uint64_t piece = (uint64_t)1 << 24;
     for (uint64_t done = 0; done < count; done += piece) {
         const sela_hip_window window = { startSample + done, 0, s.found };
-        if (sela_hip_decode_windows_i32(s.stream.data(), s.offsets.data(), s.found, channels, &window, 1, (uint32_t)std::min(piece, count - done),
+        if (sela_hip_decode_windows_i32_whole(s.stream.data(), s.offsets.data(), s.found, channels, &window, 1, (uint32_t)std::min(piece, count - done),
                 bytes == 3 ? SELA_HIP_WINDOW_PCM24_INTERLEAVED : SELA_HIP_WINDOW_PCM32_INTERLEAVED, s.bits, pcm.data() + (size_t)(done * channels * bytes), nullptr)
             != SELA_HIP_OK)
             failHip("Decode");

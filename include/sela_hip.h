@@ -588,6 +588,42 @@ int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_off
     uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out,
     uint32_t* window_flags /* [n_windows] or NULL */);
 
+/* ---- sample windows of 24- and 32-bit whole-track streams: the long last frame too ------------------------------
+ * These are to sela_hip_decode_windows_i32* what sela_hip_decode_windows_whole* are to sela_hip_decode_windows*: the same
+ * arguments and descriptor, the same argument checks in the same order with the same codes (nothing is enqueued on a refusal), the
+ * same four formats, and a window's stream read as a WHOLE-TRACK stream.  Let n be the stream's frames inside the table, L the
+ * last of them and n_L what L says its length is by sela_hip_index_samples' rule.  Where n_L is in 1 .. 4095 and not 2048 the
+ * stream holds S = 2048 (n - 1) + n_L samples per channel, and output sample i of window w is
+ *   start + i < 2048 (n - 1):   what sela_hip_decode_windows_i32_device writes, for every input, malformed frames included;
+ *   2048 (n - 1) <= start + i < S:   exactly the value sela_hip_decode_i32_device writes for sample start + i - 2048 (n - 1) of frame L
+ *                  decoded alone at stride 4095, where the last frame's kernel takes the frame and the combine's rules accept
+ *                  its layout -- in the call's format: int32 planar, (float)value * 2^-(sample_bits - 1), interleaved int32, or
+ *                  the low three bytes;
+ *   otherwise:     zero.
+ * A frame L that is declined -- the cases sela_hip_decode_windows_whole_device lists -- leaves its share zero and raises the flags
+ * that call lists, in the window's word and in d_status[0..2], by the same counting.  SELA_HIP_WINDOW_PCM24_INTERLEAVED adds the
+ * tail share's samples outside [-2^23, 2^23) to d_status[3].  Where n_L is 2048, 0 or above 4095 every word written (d_out,
+ * d_window_flags, d_status) is what sela_hip_decode_windows_i32_device writes; so is everything for a frame in front of L that does
+ * not say 2048.  Scope: 1 .. 8 channels, a last frame of at most 4095 samples.
+ * The device call is one serial chain on `stream`, asynchronous and capturable as the plain call is.  The plain call's launches
+ * write every byte of d_out, the share of L as the zeros of a stream that has ended there; one more store launch then writes
+ * every byte of a taken share and NO byte outside it (a PCM24 share as aligned dwords with single bytes only at its two ragged
+ * ends).  So where the plain call promises "exactly once", here the bytes of a taken share of L are written TWICE by the call, by
+ * two launches in series; every other byte of d_out once; no other byte.
+ *   workspace = sela_hip_decode_windows_i32_workspace_bytes(n_windows, window_samples, channels)
+ *             + n_windows * (48 + channels * (16 + 4 * 4096)) + 1024
+ * (a copy of each descriptor and a record of its share of L; per channel a record and 4096 decoded 32-bit samples; alignment).
+ * It does not depend on the data or the device.
+ * The host call stages the covering frames only, L among them for every window that reaches 2048 (n - 1), and returns what
+ * sela_hip_decode_windows_i32 returns, `out` and `window_flags` filled in the SELA_HIP_EFORMAT and SELA_HIP_ERANGE cases too. */
+size_t sela_hip_decode_windows_i32_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels);
+int sela_hip_decode_windows_i32_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out,
+    uint32_t* d_window_flags /* [n_windows] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_decode_windows_i32_whole(const uint8_t* frames, const uint64_t* frame_offsets /* [n_frames_total + 1] */, uint32_t n_frames_total,
+    uint32_t channels, const sela_hip_window* windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out,
+    uint32_t* window_flags /* [n_windows] or NULL */);
+
 /* ---- encode options: the lossless mode ----------------------------------------------------------------------
  * The reference's encoder predicts with (2^34 + sum) >> 35 and its decoder with -((2^34 - sum) >> 35): where 2^34 + sum is a
  * multiple of 2^35 the two differ by one, and the frame does not come back as it went in.  With SELA_HIP_ENCODE_LOSSLESS the
@@ -885,6 +921,51 @@ int sela_hip_verify_payload_pcm_device(const uint8_t* d_payload, size_t payload_
  * and its own stream, past the coalescer; an open streaming job of the thread is left alone. */
 int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample,
     const void* pcm, uint64_t pcm_samples, uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
+
+/* ---- a whole track from packed 3- or 4-byte PCM: the tail of a 24- or 32-bit file kept ----------------------------
+ * sela_hip_encode_whole* ("a whole track", above) for the containers of sela_hip_encode_pcm*: d_pcm is little-endian interleaved
+ * [N][channels] samples of bytes_per_sample = 3 or 4 bytes.  The layout rule is the one sela_hip_whole_frames / sela_hip_whole_frame
+ * define.  With F = N / 2048 and t = N % 2048: frames 0 .. F - 2 are byte for byte what sela_hip_encode_pcm_device writes for them at
+ * samples_per_channel = 2048 with the same options; the last frame is byte for byte what that call writes for one frame of 2048 + t
+ * samples (frame::FrameEncoder's for a frame of that length, the per-frame stereo decision included); N < 2048 gives one frame of
+ * N samples; t == 0 the plain call's stream; N == 0 writes d_frame_offsets[0] = 0 and zero status words.
+ *   sela_hip_encode_whole_pcm_bound_bytes      (F - 1) * sela_hip_encode_pcm_bound_bytes(1, channels, 2048, bytes_per_sample)
+ *                                              + sela_hip_encode_pcm_bound_bytes(1, channels, the last frame's length,
+ *                                              bytes_per_sample); SIZE_MAX beyond size_t, 0 for what the call refuses or N == 0.
+ *   sela_hip_encode_whole_pcm_workspace_bytes  the device call's workspace for every track of at most max_samples samples per
+ *                                              channel; it does not depend on the data or the device.  With F = the frames of
+ *                                              max_samples, last = min(max(max_samples, 1), 4095) and up(b) = b rounded up to a
+ *                                              multiple of 256 it is
+ *                                                up(4 * F * 2048 * channels) + sela_hip_encode_i32_workspace_bytes(F, channels, 2048)
+ *                                              + up(4 * last * channels) + sela_hip_encode_i32_workspace_bytes(1, channels, last)
+ *                                              + up(sela_hip_encode_pcm_bound_bytes(1, channels, last, 4)) + 256 + 256
+ *                                              (the 2048-sample frames unpacked and their encoder's workspace, the same for the
+ *                                              last frame, that frame as coded, its offsets and status words, alignment);
+ *                                              SIZE_MAX for what the call refuses.
+ * sela_hip_encode_whole_pcm_device: d_pcm and d_frames 4-byte aligned; d_frame_offsets [frames + 1]; d_status uint32[4]; options: 0
+ *   or SELA_HIP_ENCODE_LOSSLESS.  Offsets, status words and the capacity rule are sela_hip_encode_whole_device's: the offsets are
+ *   always written in full; a frame that ends beyond frames_cap is counted in d_status[1] and not written, and nothing at or past
+ *   frames_cap is; sela_hip_encode_status_error() judges the status words.  Asynchronous on `stream` and capturable: no allocation,
+ *   no host wait, no host read of device data.  Launches: the unpack and the any-length encoder's three on frames 0 .. F - 2, into
+ *   and out of the workspace, on `stream`; the last frame's own unpack -- its packed bytes start at byte (F - 1) * 2048 * channels *
+ *   bytes_per_sample, a multiple of 4 -- and three encode launches on a stream of the library's own between two events (forked from
+ *   `stream` before the main launches, joined behind them; inside a capture the side stream joins the capture and leaves it at the
+ *   join), coded into the workspace; then the splice of sela_hip_encode_whole_device on `stream`.  With t == 0, or a single frame,
+ *   only the one call it is, on `stream`.
+ *   SELA_HIP_EINVAL, in this order: bytes_per_sample other than 3 or 4, channels outside 1..255, frames x signals per frame at 2^31
+ *   or more, an unknown option, a null pointer (d_pcm and d_frames only where N > 0), a misaligned d_pcm or d_frames;
+ *   SELA_HIP_ECAPACITY: a smaller workspace.  They are found before a device is asked for, and nothing is enqueued.
+ * sela_hip_encode_whole_pcm: the same stream from HOST pointers, synchronous.  Frames 0 .. F - 2 go where sela_hip_encode_pcm codes
+ *   them, in chunks of whole frames with the packed bytes travelling; the last frame is one more chunk of its own length on the
+ *   same leased context.  Errors are sela_hip_encode_pcm's (SELA_HIP_ECAPACITY: frames_out too small; frame_offsets_out is not
+ *   defined then).  A thread's open streaming job is left alone. */
+size_t sela_hip_encode_whole_pcm_bound_bytes(uint64_t n_samples, uint32_t channels, uint32_t bytes_per_sample);
+size_t sela_hip_encode_whole_pcm_workspace_bytes(uint64_t max_samples, uint32_t channels);
+int sela_hip_encode_whole_pcm_device(const void* d_pcm, uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options,
+    uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets /* [frames + 1] */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+int sela_hip_encode_whole_pcm(const void* pcm, uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options,
+    uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out /* [frames + 1] */);
 
 /* ---- streaming jobs (host pointers) -------------------------------------------------------------------
  * For callers that produce their input piece by piece (a file being read): feed() enqueues a piece and

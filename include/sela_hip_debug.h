@@ -140,7 +140,8 @@ uint64_t sela_hip_debug_windows_staged_bytes(void);
 enum {
     SELA_HIP_WORKSPACE_ENCODE = 0, SELA_HIP_WORKSPACE_DECODE, SELA_HIP_WORKSPACE_INDEX, SELA_HIP_WORKSPACE_DECODE_I32, SELA_HIP_WORKSPACE_DECODE_N,
     SELA_HIP_WORKSPACE_VERIFY, SELA_HIP_WORKSPACE_VERIFY_I32, SELA_HIP_WORKSPACE_ENCODE_I32, SELA_HIP_WORKSPACE_ENCODE_PAIRED, SELA_HIP_WORKSPACE_WINDOWS,
-    SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT, SELA_HIP_WORKSPACE_DECODE_WHOLE, SELA_HIP_WORKSPACE_WINDOWS_I32
+    SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT, SELA_HIP_WORKSPACE_DECODE_WHOLE, SELA_HIP_WORKSPACE_WINDOWS_I32,
+    SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM
 };
 int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
 /* Debug hook (tests; process-wide): sela_hip_encode_pcm, sela_hip_decode_pcm and sela_hip_verify_pcm work in chunks of this many whole frames; 0

@@ -42,6 +42,8 @@ EXPORTS = [
     "sela_hip_decode_windows_workspace_bytes", "sela_hip_decode_windows_device", "sela_hip_decode_windows",
     "sela_hip_decode_windows_whole_workspace_bytes", "sela_hip_decode_windows_whole_device", "sela_hip_decode_windows_whole",
     "sela_hip_decode_windows_i32_workspace_bytes", "sela_hip_decode_windows_i32_device", "sela_hip_decode_windows_i32",
+    "sela_hip_decode_windows_i32_whole_workspace_bytes", "sela_hip_decode_windows_i32_whole_device", "sela_hip_decode_windows_i32_whole",
+    "sela_hip_encode_whole_pcm_bound_bytes", "sela_hip_encode_whole_pcm_workspace_bytes", "sela_hip_encode_whole_pcm_device", "sela_hip_encode_whole_pcm",
     "sela_hip_paired_signals_per_frame", "sela_hip_encode_paired_workspace_bytes", "sela_hip_encode_paired_i32_device", "sela_hip_encode_paired_n_device",
     "sela_hip_encode_paired_i32", "sela_hip_encode_paired",
     "sela_hip_whole_frames", "sela_hip_whole_frame", "sela_hip_encode_whole_bound_bytes", "sela_hip_encode_whole_workspace_bytes",
@@ -68,7 +70,7 @@ DEBUG_EXPORTS = [
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
-                   "encode_whole", "encode_split", "decode_whole", "windows_i32")
+                   "encode_whole", "encode_split", "decode_whole", "windows_i32", "windows_i32_whole", "encode_whole_pcm")
 
 
 class Trace(C.Structure):
@@ -187,6 +189,12 @@ def lib() -> C.CDLL:
     L.sela_hip_decode_windows_i32_device.restype = C.c_int
     L.sela_hip_decode_windows_i32.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, vp]
     L.sela_hip_decode_windows_i32.restype = C.c_int
+    L.sela_hip_decode_windows_i32_whole_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_decode_windows_i32_whole_workspace_bytes.restype = sz
+    L.sela_hip_decode_windows_i32_whole_device.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_decode_windows_i32_whole_device.restype = C.c_int
+    L.sela_hip_decode_windows_i32_whole.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp, vp]
+    L.sela_hip_decode_windows_i32_whole.restype = C.c_int
     L.sela_hip_encode_i32_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_encode_i32_workspace_bytes.restype = sz
     L.sela_hip_encode_i32_device.argtypes = [vp, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp]
@@ -228,6 +236,14 @@ def lib() -> C.CDLL:
     L.sela_hip_encode_whole_device.restype = C.c_int
     L.sela_hip_encode_whole.argtypes = [vp, u64, u32, vp, sz, vp, u32]
     L.sela_hip_encode_whole.restype = C.c_int
+    L.sela_hip_encode_whole_pcm_bound_bytes.argtypes = [u64, u32, u32]
+    L.sela_hip_encode_whole_pcm_bound_bytes.restype = sz
+    L.sela_hip_encode_whole_pcm_workspace_bytes.argtypes = [u64, u32]
+    L.sela_hip_encode_whole_pcm_workspace_bytes.restype = sz
+    L.sela_hip_encode_whole_pcm_device.argtypes = [vp, u32, u64, u32, u32, vp, sz, vp, vp, vp, sz, vp]
+    L.sela_hip_encode_whole_pcm_device.restype = C.c_int
+    L.sela_hip_encode_whole_pcm.argtypes = [vp, u32, u64, u32, u32, vp, sz, vp]
+    L.sela_hip_encode_whole_pcm.restype = C.c_int
     L.sela_hip_decode_whole_workspace_bytes.argtypes = [u32, u32]
     L.sela_hip_decode_whole_workspace_bytes.restype = sz
     L.sela_hip_decode_whole_device.argtypes = [vp, vp, u32, u32, vp, u64, vp, vp, vp, sz, vp]

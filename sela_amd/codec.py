@@ -484,19 +484,22 @@ class WindowDecoder32:
 
     pack = staticmethod(WindowDecoder.pack)
 
-    def __init__(self, max_windows: int, window_samples: int, channels: int, format: int, sample_bits: int = 24, device=None):
+    def __init__(self, max_windows: int, window_samples: int, channels: int, format: int, sample_bits: int = 24, device=None, whole: bool = False):
         import torch
 
         self.torch = torch
         self.lib = capi.lib()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_windows, self.window_samples, self.channels, self.format, self.sample_bits = max_windows, window_samples, channels, format, sample_bits
+        # whole: sela_hip_decode_windows_i32_whole_device -- a stream's long last frame is decoded too
+        self._call = self.lib.sela_hip_decode_windows_i32_whole_device if whole else self.lib.sela_hip_decode_windows_i32_device
+        sizing = self.lib.sela_hip_decode_windows_i32_whole_workspace_bytes if whole else self.lib.sela_hip_decode_windows_i32_workspace_bytes
         shape, dtype = _window32_shape(max_windows, window_samples, channels, format)
         with torch.cuda.device(self.device):
             self.out = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
             self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
             self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_decode_windows_i32_workspace_bytes(max_windows, window_samples, channels))
+            ws = int(sizing(max_windows, window_samples, channels))
             self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.n_windows = 0
 
@@ -510,7 +513,7 @@ class WindowDecoder32:
         n = int(windows.shape[0])
         assert n <= self.max_windows
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(self.lib.sela_hip_decode_windows_i32_device(
+        capi.check(self._call(
             frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format, self.sample_bits,
             self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
         self.n_windows = n
@@ -532,8 +535,9 @@ class WindowDecoder32:
         capi.check(decode_n_status_error(st))
 
 
-def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, format: int, sample_bits: int = 24):
-    """sela_hip_decode_windows_i32 on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
+def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, format: int, sample_bits: int = 24,
+                            whole: bool = False):
+    """sela_hip_decode_windows_i32 (whole: sela_hip_decode_windows_i32_whole) on numpy arrays; windows: int64 [n, 2] (WindowDecoder.pack).  Returns three values: the windows
     in `format` (WindowDecoder32's shapes), the per-window flags (uint32 [n]) and the call's return code -- 0, or EFORMAT / ERANGE
     (capi.ERRORS) for a batch with a bad frame, whose other windows are good all the same; any other code raises."""
     lib = capi.lib()
@@ -544,8 +548,8 @@ def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: i
     shape, dtype = _window32_shape(n, window_samples, channels, format)
     out = np.zeros(shape, dtype)
     flags = np.zeros(n, np.uint32)
-    rc = lib.sela_hip_decode_windows_i32(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, format, sample_bits,
-                                         out.ctypes.data, flags.ctypes.data)
+    call = lib.sela_hip_decode_windows_i32_whole if whole else lib.sela_hip_decode_windows_i32
+    rc = call(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, format, sample_bits, out.ctypes.data, flags.ctypes.data)
     if rc not in (capi.OK, -5, -6):
         capi.check(rc)
     return out, flags, rc
@@ -1415,6 +1419,73 @@ def encode_pcm_host(pcm: np.ndarray, channels: int, samples_per_channel: int, by
         offsets = np.zeros(n_frames + 1, dtype=np.uint64)
         rc = lib.sela_hip_encode_pcm(pcm.ctypes.data, bytes_per_sample, n_frames, channels, samples_per_channel, capi.ENCODE_LOSSLESS if lossless else 0,
                                      frames.ctypes.data, frames.size, offsets.ctypes.data)
+        if rc != -4:
+            break
+    capi.check(rc)
+    return frames[: int(offsets[-1])].copy(), offsets
+
+
+class WholeEncoderPcm:
+    """sela_hip_encode_whole_pcm_device: a whole track of up to max_samples samples per channel from packed 3- or 4-byte interleaved
+    PCM, its tail kept in a long last frame.  Owns its workspace, frames, offsets and status, as WholeEncoder
+    does; `capacity` (bytes of frames) defaults to EncoderPcm's estimate -- check() and needed_bytes() say when it was too small."""
+
+    def __init__(self, max_samples: int, channels: int, bytes_per_sample: int, lossless: bool = False, capacity=None, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.options = capi.ENCODE_LOSSLESS if lossless else 0
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_samples, self.channels, self.bytes_per_sample = int(max_samples), int(channels), int(bytes_per_sample)
+        self.max_frames = int(self.lib.sela_hip_whole_frames(self.max_samples))
+        if capacity is None:
+            capacity = (self.max_samples * channels * 9) // 2 + self.max_frames * (channels * 192 + 64)
+        self.capacity = max(int(capacity), 4)
+        ws = int(self.lib.sela_hip_encode_whole_pcm_workspace_bytes(self.max_samples, channels))
+        with torch.cuda.device(self.device):
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+            self.offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.n_frames = 0
+
+    def encode(self, pcm, n_samples=None):
+        """pcm: uint8 cuda tensor of n_samples * channels * bytes_per_sample bytes (n_samples: from its size) -> (frames uint8
+        [capacity], offsets int64 [frames + 1], status int32 [4]), the encoder's own buffers."""
+        torch = self.torch
+        assert _pcm_args_ok(torch, pcm)
+        value_bytes = self.channels * self.bytes_per_sample
+        if n_samples is None:
+            assert pcm.numel() % value_bytes == 0
+            n_samples = pcm.numel() // value_bytes
+        assert n_samples <= self.max_samples and pcm.numel() >= n_samples * value_bytes
+        capi.check(self.lib.sela_hip_encode_whole_pcm_device(
+            pcm.data_ptr(), self.bytes_per_sample, n_samples, self.channels, self.options, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), torch.cuda.current_stream(self.device).cuda_stream))
+        self.n_frames = int(self.lib.sela_hip_whole_frames(n_samples))
+        return self.frames, self.offsets[: self.n_frames + 1], self.status
+
+    needed_bytes = Encoder32.needed_bytes
+    check = Encoder32.check
+    to_host = Encoder32.to_host
+
+
+def encode_whole_pcm_host(pcm: np.ndarray, channels: int, bytes_per_sample: int, lossless: bool = False):
+    """sela_hip_encode_whole_pcm: a whole track's packed bytes (uint8, n_samples * channels * bytes_per_sample of them) on the host
+    -> (frames uint8, offsets uint64 [frames + 1]); the tail is kept in a long last frame."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.uint8).reshape(-1)
+    value_bytes = channels * bytes_per_sample
+    assert value_bytes and pcm.size % value_bytes == 0
+    n_samples = pcm.size // value_bytes
+    lib = capi.lib()
+    n_frames = int(lib.sela_hip_whole_frames(n_samples))
+    estimate = (n_samples * channels * 9) // 2 + n_frames * (channels * 192 + 64)
+    for capacity in (estimate, int(lib.sela_hip_encode_whole_pcm_bound_bytes(n_samples, channels, bytes_per_sample))):
+        frames = np.empty(max(capacity, 4), dtype=np.uint8)
+        offsets = np.zeros(n_frames + 1, dtype=np.uint64)
+        rc = lib.sela_hip_encode_whole_pcm(pcm.ctypes.data, bytes_per_sample, n_samples, channels, capi.ENCODE_LOSSLESS if lossless else 0, frames.ctypes.data,
+                                           frames.size, offsets.ctypes.data)
         if rc != -4:
             break
     capi.check(rc)

@@ -25,6 +25,7 @@
 #include "sela_decode_whole_plan.h"
 #include "sela_host.h"
 #include "sela_lease.h"
+#include "sela_pcm.h"
 
 namespace {
 
@@ -1749,10 +1750,13 @@ constexpr const char* kWindow32Bits = "sample_bits must be in 1..32 with SELA_HI
 constexpr const char* kWindow32Product = "n_windows * cover * channels must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)";
 constexpr const char* kWindow32Windows = "n_windows must stay below 2^24 (a workgroup of 256 per window and covering frame: a launch holds fewer than 2^32 work-items per dimension)";
 int windows_i32_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
-    uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+    uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream,
+    bool whole /* 5.25: the same checks, the long last frame's kernels behind */)
 {
-    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) { return sela::window32_workspace_bytes(n_windows, window_samples, channels); };
-    const DeviceCallOf<decltype(formula)> c = { "decode_windows_i32", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) {
+        return whole ? sela::window32_whole_workspace_bytes(n_windows, window_samples, channels) : sela::window32_workspace_bytes(n_windows, window_samples, channels);
+    };
+    const DeviceCallOf<decltype(formula)> c = { whole ? "decode_windows_i32_whole" : "decode_windows_i32", formula, channels, 0, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
     return form(
         c,
         [&](uint32_t) {
@@ -1774,8 +1778,9 @@ int windows_i32_call(const FramesForm& form, uint32_t channels, const sela_hip_w
             return rc;
         },
         [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const uint32_t*, void* d_ws) {
-            return launched(sela::launch_window32(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out,
-                                d_window_flags, d_status, d_ws, sela::generic_standard_first_mode() != 2, c.stream),
+            const auto launch = whole ? sela::launch_window32_whole : sela::launch_window32;
+            return launched(launch(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out, d_window_flags,
+                                d_status, d_ws, sela::generic_standard_first_mode() != 2, c.stream),
                 "decode_windows_i32 launch");
         });
 }
@@ -2111,13 +2116,28 @@ int sela_hip_decode_windows_i32_device(const uint8_t* d_frames, const uint64_t* 
     uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
     return windows_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out,
-        d_window_flags, d_status, d_workspace, workspace_bytes, stream);
+        d_window_flags, d_status, d_workspace, workspace_bytes, stream, false);
+}
+
+// The same call for whole-track streams (5.25): a last frame of 1 .. 4095 samples is decoded by k_tailwin_decode and stored by
+// k_tail32_store (sela_window32_whole.hip).
+size_t sela_hip_decode_windows_i32_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+{
+    return sela::window32_whole_workspace_bytes(n_windows, window_samples, channels);
+}
+
+int sela_hip_decode_windows_i32_whole_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels,
+    const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out, uint32_t* d_window_flags,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return windows_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames_total }, channels, d_windows, n_windows, window_samples, format, sample_bits, d_out,
+        d_window_flags, d_status, d_workspace, workspace_bytes, stream, true);
 }
 
 // Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows on the any-length route's leased
 // context and stream, as sela_hip_decode_windows runs.
-int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
-    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags)
+static int windows_i32_host_call(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags, bool whole)
 {
     sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
     if (channels == 0 || channels > 8)
@@ -2137,7 +2157,19 @@ int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_off
     if (n_windows == 0)
         return SELA_HIP_OK;
     return sela::generic_decode_windows(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, out, window_flags,
-        g_recurrence_form, false, true, sample_bits);
+        g_recurrence_form, whole, true, sample_bits);
+}
+
+int sela_hip_decode_windows_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags)
+{
+    return windows_i32_host_call(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, sample_bits, out, window_flags, false);
+}
+
+int sela_hip_decode_windows_i32_whole(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags)
+{
+    return windows_i32_host_call(frames, frame_offsets, n_frames_total, channels, windows, n_windows, window_samples, format, sample_bits, out, window_flags, true);
 }
 
 size_t sela_hip_verify_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
@@ -2257,7 +2289,7 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
     sela::Carve at(&pieces);
     const uint32_t a32 = (uint32_t)a;
     size_t bytes = SIZE_MAX;
-    if (call != SELA_HIP_WORKSPACE_INDEX && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE && a > 0xFFFFFFFFull)
+    if (call != SELA_HIP_WORKSPACE_INDEX && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM && a > 0xFFFFFFFFull)
         return -1;
     switch (call) {
     case SELA_HIP_WORKSPACE_ENCODE: bytes = sela::encode_workspace_bytes(a32, b, &at); break;
@@ -2279,6 +2311,8 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
         break;
     case SELA_HIP_WORKSPACE_DECODE_WHOLE: bytes = sela::decode_whole_workspace_bytes(a32, b, &at); break;
     case SELA_HIP_WORKSPACE_WINDOWS_I32: bytes = sela::window32_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE: bytes = sela::window32_whole_workspace_bytes(a32, b, c, &at); break;
+    case SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM: bytes = sela::whole_pcm_workspace_bytes(a, b, &at); break;
     default: return -1;
     }
     return bytes == SIZE_MAX ? -1 : pieces.count;
@@ -2697,6 +2731,122 @@ int sela_hip_encode_whole(const int16_t* pcm, uint64_t n_samples, uint32_t chann
     uint64_t last_offsets[2] = { 0, 0 };
     rc = sela::generic_encode(pcm + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels, true, 1, channels, (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME),
         frames_out + before, frames_cap - (size_t)before, last_offsets, lossless);
+    frame_offsets_out[whole + 1] = before + last_offsets[1];
+    return rc;
+}
+
+// ---- the same track from packed 3- or 4-byte PCM (the workspace: sela_whole.hip) ------------------------------------
+namespace {
+// sela_hip_encode_pcm_device's checks of the shape and the options in its order, on sela_hip_encode_whole_device's frames
+int whole_pcm_arguments(uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options, bool* lossless, const void* pcm, const void* frames,
+    const void* frame_offsets)
+{
+    if (bytes_per_sample != 3 && bytes_per_sample != 4)
+        return fail(SELA_HIP_EINVAL, "bytes_per_sample must be 3 or 4 (16-bit samples: sela_hip_encode_whole_device and sela_hip_encode_whole)");
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (sela_hip_whole_frames(n_samples) * sela::generic_signals(channels, false) >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "frames * signals per frame must stay below 2^31");
+    const int rc = encode_options(options, lossless);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (!frame_offsets || (n_samples && (!pcm || !frames)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    return SELA_HIP_OK;
+}
+} // namespace
+
+// The launches: k_pcm_unpack and the any-length encoder's three on frames 0 .. F - 2, on `stream`; the last frame's own unpack and
+// three launches on WholeFork's side stream, forked before the main launches and joined behind them; the splice.  The last
+// frame's packed bytes start at byte (F - 1) * 2048 * channels * bytes_per_sample: a multiple of 4, as the unpack asks.
+int sela_hip_encode_whole_pcm_device(const void* d_pcm, uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options, uint8_t* d_frames,
+    size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    bool lossless = false;
+    const int rc0 = whole_pcm_arguments(bytes_per_sample, n_samples, channels, options, &lossless, d_pcm, d_frames, d_frame_offsets);
+    if (rc0 != SELA_HIP_OK)
+        return rc0;
+    if (!d_status || !d_workspace)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
+        return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
+    if (workspace_bytes < sela::whole_pcm_workspace_bytes(n_samples, channels))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_whole_pcm_workspace_bytes()");
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
+    sela::Carve carve(d_workspace);
+    const sela::WholePcmWs w = sela::carve_whole_pcm(carve, n_samples, channels);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    // frames [first, first + count) of `length` samples each, unpacked into `samples` and coded by the any-length encoder's launches
+    const auto encode = [&](uint32_t first, uint32_t count, uint32_t length, int32_t* samples, void* workspace, uint8_t* out, size_t cap, uint64_t* offsets,
+                            uint32_t* status, hipStream_t on) {
+        const uint8_t* const from = static_cast<const uint8_t*>(d_pcm) + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample;
+        hipError_t e = sela::launch_pcm_unpack(from, bytes_per_sample, count, channels, length, samples, on);
+        if (e == hipSuccess)
+            e = sela::launch_encode_i32_device(samples, false, count, channels, length, out, cap, offsets, status, workspace, on, lossless);
+        return launched(e, "encode_whole_pcm launch");
+    };
+    if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
+        return encode(0, 0, 1, w.last_samples, w.last_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    if (tail == 0) // whole frames only: sela_hip_encode_pcm_device's stream
+        return encode(0, frames, SELA_HIP_SAMPLES_PER_FRAME, w.main_samples, w.main_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
+    if (last == 0) // one frame, of up to 4095 samples
+        return encode(0, 1, last_samples, w.last_samples, w.last_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+        return fail(SELA_HIP_ENODEV, "encode_whole_pcm: no current device");
+    WholeFork& wf = whole_fork();
+    std::lock_guard<std::mutex> lock(wf.mu);
+    if (!wf.ready(dev))
+        return fail(SELA_HIP_ENODEV, "encode_whole_pcm: no side stream");
+    const hipStream_t side = wf.side[dev];
+    // fork: the side stream follows whatever produced d_pcm, and the workspace's previous user, on the caller's stream
+    hipError_t e = hipEventRecord(wf.forked[dev], st);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(side, wf.forked[dev], 0);
+    if (e != hipSuccess)
+        return fail_hip(e, "encode_whole_pcm: fork");
+    // the last frame, coded into the workspace, on the side stream ...
+    int rc = encode(last, 1, last_samples, w.last_samples, w.last_workspace, w.last_frame, w.last_cap, w.last_offsets, w.last_status, side);
+    if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
+        rc = fail_hip(e, "encode_whole_pcm: join");
+    // ... beside it the 2048-sample frames on the caller's ...
+    if (rc == SELA_HIP_OK)
+        rc = encode(0, last, SELA_HIP_SAMPLES_PER_FRAME, w.main_samples, w.main_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    // ... the join (also after a failure in between: a side stream that has joined a capture must leave it) ...
+    if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
+        rc = fail_hip(e, "encode_whole_pcm: join");
+    if (rc != SELA_HIP_OK)
+        return rc;
+    // ... and the last frame behind them
+    return launched(sela::launch_whole_splice(w.last_frame, w.last_offsets, w.last_status, channels, d_frames, frames_cap, d_frame_offsets, last, d_status, st),
+        "encode_whole_pcm splice");
+}
+
+// Host pointers: frames 0 .. F - 2 in sela_hip_encode_pcm's chunks, the last frame as one more chunk of its own length, on the
+// calling thread's leased context, past the coalescer; an open streaming job is left alone.
+int sela_hip_encode_whole_pcm(const void* pcm, uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options, uint8_t* frames_out,
+    size_t frames_cap, uint64_t* frame_offsets_out)
+{
+    bool lossless = false;
+    int rc = whole_pcm_arguments(bytes_per_sample, n_samples, channels, options, &lossless, pcm, frames_out, frame_offsets_out);
+    if (rc != SELA_HIP_OK)
+        return rc;
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples);
+    frame_offsets_out[0] = 0;
+    if (frames == 0)
+        return SELA_HIP_OK;
+    const uint32_t whole = frames - 1; // the frames of 2048 samples in front of the last one
+    const uint8_t* const bytes = static_cast<const uint8_t*>(pcm);
+    if (whole) {
+        rc = sela::generic_encode_pcm(bytes, bytes_per_sample, whole, channels, SELA_HIP_SAMPLES_PER_FRAME, lossless, frames_out, frames_cap, frame_offsets_out);
+        if (rc != SELA_HIP_OK)
+            return rc;
+    }
+    const uint64_t before = frame_offsets_out[whole];
+    uint64_t last_offsets[2] = { 0, 0 };
+    rc = sela::generic_encode_pcm(bytes + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample, bytes_per_sample, 1, channels,
+        (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME), lossless, frames_out + before, frames_cap - (size_t)before, last_offsets);
     frame_offsets_out[whole + 1] = before + last_offsets[1];
     return rc;
 }

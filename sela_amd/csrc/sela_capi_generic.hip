@@ -670,7 +670,8 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
         return SELA_HIP_EFORMAT;
     Arena& g_arena = call.arena();
     const hipStream_t st = call.stream();
-    // (wide, DESIGN.md 5.23: sela_hip_decode_windows_i32 -- the same plan and staging, launch_window32 and its formats behind)
+    // (wide, DESIGN.md 5.23: sela_hip_decode_windows_i32 -- the same plan and staging, launch_window32 and its formats behind; wide and
+    // whole, 5.25: launch_window32_whole)
     const size_t out_per_window = (size_t)window_samples * channels * (wide ? (format == SELA_HIP_WINDOW_PCM24_INTERLEAVED ? 3 : 4) : format == SELA_HIP_WINDOW_F32_PLANAR ? 4 : 2);
     // (an estimate for the chunk's size only -- what a chunk needs is reserved exactly below: a 16-bit frame is about 5 bytes a sample at most)
     const size_t per_window = out_per_window + (size_t)(window_cover(window_samples) + (whole ? 2 : 0)) * channels * kBlock * (sizeof(int32_t) + 5) + 64;
@@ -686,7 +687,7 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
         else
             plan_windows(frame_offsets, n_frames_total, windows + w0, cw, window_samples, &plan);
         const size_t in_bytes = (size_t)plan.staged_bytes(), n_staged = plan.frames.size(), out_bytes = (size_t)cw * out_per_window;
-        const size_t ws_bytes = wide ? window32_workspace_bytes(cw, window_samples, channels)
+        const size_t ws_bytes = wide ? (whole ? window32_whole_workspace_bytes : window32_workspace_bytes)(cw, window_samples, channels, nullptr)
             : whole                   ? window_whole_workspace_bytes(cw, window_samples, channels)
                                       : window_workspace_bytes(cw, window_samples, channels);
         hipError_t e = g_arena.reserve(in_bytes + 8 + (n_staged + 1) * 8 + (size_t)cw * sizeof(sela_hip_window) + out_bytes + (4 + (size_t)cw) * 4 + ws_bytes + 8 * kPiece);
@@ -719,8 +720,8 @@ int generic_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets,
         if (e == hipSuccess)
             e = hipMemcpyAsync(d_windows, plan.windows.data(), (size_t)cw * sizeof(sela_hip_window), hipMemcpyHostToDevice, st);
         if (e == hipSuccess && wide)
-            e = launch_window32(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, sample_bits, d_out, d_tail + 4, d_tail, d_ws,
-                g_standard_first_mode.load(std::memory_order_relaxed) != 2, st);
+            e = (whole ? launch_window32_whole : launch_window32)(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, sample_bits,
+                d_out, d_tail + 4, d_tail, d_ws, g_standard_first_mode.load(std::memory_order_relaxed) != 2, st);
         else if (e == hipSuccess)
             e = (whole ? launch_window_whole : launch_window_frames)(d_frames, d_offsets, (uint32_t)n_staged, channels, d_windows, cw, window_samples, format, d_out,
                 d_tail + 4, d_tail, d_ws, st, recurrence_form, 0);

@@ -61,12 +61,32 @@ size_t window32_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uin
 hipError_t launch_window32(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace,
     bool standard_path /* false: every subframe by segments (sela_hip_debug_standard_first(2)) */, hipStream_t stream);
+struct TailSub;
+struct Window32Ws { // launch_window32's pieces; launch_window32_whole's workspace opens with them
+    TailSub* subs;        // a record per (window, covering frame, subframe position) ...
+    int32_t* dec;         // ... and its 2048 decoded 32-bit samples
+    uint32_t* flag_words; // a word per window, for a call that passes no d_window_flags
+};
+Window32Ws carve_window32(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels);
 
 // ---- sela_window_whole.hip: windows that reach a whole-track stream's long last frame --------------------------
 size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
 hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, hipStream_t stream,
     int recurrence_form, uint32_t synth_priorities);
+// k_tailwin_plan and k_tailwin_decode alone, for the window calls of other files (sela_window32_whole.hip): d_subs is TailSub
+// [n_windows][channels], d_dec int32 [n_windows][channels][kTailStride]
+struct WindowTail;
+hipError_t launch_tailwin_plan(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const sela_hip_window* d_windows, uint32_t n_windows,
+    uint32_t window_samples, sela_hip_window* d_copies, WindowTail* d_tails, hipStream_t stream);
+hipError_t launch_tailwin_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t channels, const WindowTail* d_tails, uint32_t n_windows, int32_t* d_dec,
+    void* d_subs, hipStream_t stream);
+
+// ---- sela_window32_whole.hip: 32-bit windows that reach a whole-track stream's long last frame ------------------
+size_t window32_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels, Carve* at = nullptr);
+hipError_t launch_window32_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
+    uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace,
+    bool standard_path, hipStream_t stream);
 
 // ---- sela_window_whole.hip: a full decode of a whole-track stream ------------------------------------------------
 struct WindowTail;
@@ -96,6 +116,18 @@ struct WholeWs { // the workspace of sela_hip_encode_whole_device
 };
 WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels); // (arguments that whole_workspace_bytes does not refuse)
 size_t whole_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at = nullptr); // SIZE_MAX for what the call refuses
+struct WholePcmWs { // the workspace of sela_hip_encode_whole_pcm_device
+    int32_t* main_samples;  // the 2048-sample frames unpacked, and sela_hip_encode_i32_device's workspace for them
+    void* main_workspace;
+    int32_t* last_samples;  // the last frame unpacked, and its any-length workspace
+    void* last_workspace;
+    uint8_t* last_frame;    // the last frame's bytes as coded, and their room
+    size_t last_cap;
+    uint64_t* last_offsets; // its two offsets ...
+    uint32_t* last_status;  // ... and its four status words
+};
+WholePcmWs carve_whole_pcm(Carve& c, uint64_t max_samples, uint32_t channels); // (arguments that whole_pcm_workspace_bytes does not refuse)
+size_t whole_pcm_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at = nullptr); // SIZE_MAX for what the call refuses
 hipError_t launch_whole_splice(const uint8_t* d_last_frame, const uint64_t* d_last_offsets, const uint32_t* d_last_status, uint32_t channels, uint8_t* d_frames,
     uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last, uint32_t* d_status, hipStream_t stream);
 

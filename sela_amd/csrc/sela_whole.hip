@@ -1,5 +1,6 @@
-// sela_whole.hip -- a whole track with its tail (gfx950): the layout rule, the workspace of
-// sela_hip_encode_whole_device, and the splice that puts the long last frame behind the 2048-sample frames.
+// sela_whole.hip -- a whole track with its tail (gfx950): the layout rule, the workspaces of
+// sela_hip_encode_whole_device and sela_hip_encode_whole_pcm_device (5.25), and the splice that puts the long last frame behind
+// the 2048-sample frames.
 //
 // The rule (include/sela_hip.h "a whole track"): N samples per channel are F = N / 2048 frames when F >= 1 -- the last of them
 // 2048 + N % 2048 samples long -- and one frame of N samples below 2048.  It is written here once; the entry points
@@ -46,6 +47,38 @@ size_t whole_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at)
     if (channels == 0 || channels > 255 || sela_hip_whole_frames(max_samples) * sela_hip_signals_per_frame(channels) >= (1ull << 31))
         return SIZE_MAX;
     return measured(at, [&](Carve& c) { carve_whole(c, max_samples, channels); });
+}
+
+// ---- the same track from packed 3- or 4-byte PCM: sela_hip_encode_whole_pcm_device ---------------------------------
+// The 2048-sample frames' unpacked samples | sela_hip_encode_i32_device's workspace for them | the last frame's samples | its
+// any-length workspace | the last frame as coded | its head.  (A track of whole frames only, or of one frame, uses the first or
+// the second pair alone.)
+WholePcmWs carve_whole_pcm(Carve& c, uint64_t max_samples, uint32_t channels)
+{
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(max_samples), last = std::max(longest_last_frame(max_samples), 1u);
+    WholePcmWs w;
+    w.main_samples = c.take<int32_t>((uint64_t)frames * channels * kFrame);
+    Carve main_ws = c.sub(encode_i32_device_workspace_bytes(frames, channels, (uint32_t)kFrame));
+    w.main_workspace = main_ws.base();
+    if (c.listing()) // (the call's own pieces, where they lie)
+        encode_i32_device_workspace_bytes(frames, channels, (uint32_t)kFrame, false, &main_ws);
+    w.last_samples = c.take<int32_t>((uint64_t)channels * last);
+    Carve last_ws = c.sub(encode_i32_device_workspace_bytes(1, channels, last));
+    w.last_workspace = last_ws.base();
+    if (c.listing())
+        encode_i32_device_workspace_bytes(1, channels, last, false, &last_ws);
+    w.last_cap = (size_t)workspace_up(sela_hip_encode_pcm_bound_bytes(1, channels, last, 4));
+    w.last_frame = c.take<uint8_t>(w.last_cap);
+    w.last_offsets = c.take<uint64_t>(2 + 2); // (the head: the offsets, and the status words behind them)
+    w.last_status = reinterpret_cast<uint32_t*>(w.last_offsets + 2);
+    return w;
+}
+
+size_t whole_pcm_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at)
+{
+    if (channels == 0 || channels > 255 || sela_hip_whole_frames(max_samples) * generic_signals(channels, false) >= (1ull << 31))
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_whole_pcm(c, max_samples, channels); });
 }
 
 // ---- the splice ---------------------------------------------------------------------------------------------------------------
@@ -113,5 +146,20 @@ size_t sela_hip_encode_whole_bound_bytes(uint64_t n_samples, uint32_t channels)
 }
 
 size_t sela_hip_encode_whole_workspace_bytes(uint64_t max_samples, uint32_t channels) { return sela::whole_workspace_bytes(max_samples, channels); }
+
+size_t sela_hip_encode_whole_pcm_bound_bytes(uint64_t n_samples, uint32_t channels, uint32_t bytes_per_sample)
+{
+    const uint64_t frames = sela_hip_whole_frames(n_samples);
+    if (frames == 0 || channels == 0 || channels > 255 || (bytes_per_sample != 3 && bytes_per_sample != 4))
+        return 0;
+    const uint32_t last = (uint32_t)(n_samples - (frames - 1) * sela::kFrame);
+    const size_t per_frame = sela_hip_encode_pcm_bound_bytes(1, channels, SELA_HIP_SAMPLES_PER_FRAME, bytes_per_sample),
+                 last_frame = sela_hip_encode_pcm_bound_bytes(1, channels, last, bytes_per_sample);
+    if (frames - 1 > (SIZE_MAX - last_frame) / per_frame)
+        return SIZE_MAX;
+    return (size_t)((frames - 1) * per_frame) + last_frame;
+}
+
+size_t sela_hip_encode_whole_pcm_workspace_bytes(uint64_t max_samples, uint32_t channels) { return sela::whole_pcm_workspace_bytes(max_samples, channels); }
 
 } // extern "C"

@@ -238,13 +238,9 @@ __global__ __launch_bounds__(kWin32Threads) void k_window32_store(const int32_t*
     }
 }
 
-// The subframe records | the decoded subframes, 2048 samples each | a flag word per window for a call that passes no d_window_flags.
-struct Window32Ws {
-    TailSub* subs;
-    int32_t* dec;
-    uint32_t* flag_words;
-};
-static Window32Ws carve_window32(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
+// The subframe records | the decoded subframes, 2048 samples each | a flag word per window for a call that passes no d_window_flags
+// (Window32Ws: sela_host.h).
+Window32Ws carve_window32(Carve& c, uint32_t n_windows, uint32_t window_samples, uint32_t channels)
 {
     const uint64_t slots = (uint64_t)n_windows * window_cover(window_samples) * channels;
     Window32Ws w;

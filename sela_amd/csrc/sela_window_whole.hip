@@ -201,6 +201,21 @@ size_t window_whole_workspace_bytes(uint32_t n_windows, uint32_t window_samples,
         + (size_t)n_windows * (sizeof(sela_hip_window) + sizeof(WindowTail) + (size_t)channels * (sizeof(TailSub) + kTailStride * sizeof(int32_t))) + kWindowWholeSlack;
 }
 
+hipError_t launch_tailwin_plan(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const sela_hip_window* d_windows, uint32_t n_windows,
+    uint32_t window_samples, sela_hip_window* d_copies, WindowTail* d_tails, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_tailwin_plan, dim3((n_windows + kTailPlanThreads - 1) / kTailPlanThreads), dim3(kTailPlanThreads), 0, stream, d_frames, d_frame_offsets, n_frames_total,
+        d_windows, n_windows, window_samples, d_copies, d_tails);
+    return hipGetLastError();
+}
+
+hipError_t launch_tailwin_decode(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t channels, const WindowTail* d_tails, uint32_t n_windows, int32_t* d_dec,
+    void* d_subs, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_tailwin_decode, dim3(n_windows, channels), dim3(64), 0, stream, d_frames, d_frame_offsets, channels, d_tails, d_dec, static_cast<TailSub*>(d_subs));
+    return hipGetLastError();
+}
+
 // Plan, the 2048-sample frames, the tails: one serial chain on the caller's stream, capturable.  The arguments have been checked
 // (sela_capi.hip), as for launch_window_frames.
 hipError_t launch_window_whole(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* d_windows,
