@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "sela_host/files.hpp"
+#include "sela_host/levels.hpp"
 
 namespace sela {
 
@@ -109,6 +110,21 @@ VerifyReport verifyFile(const std::string& wavPath, const std::string& selaPath)
 std::string formatVerifyReport(const VerifyReport& report);
 // 0: everything in the WAV comes back exactly; 3: a frame differs or the headers disagree; 4: only tail samples are missing.
 int verifyExitCode(const VerifyReport& report);
+
+// ---- levels: how loud is this .sela? ------------------------------------------------------------------
+// measureFile() reads the file the way verifyFile does (the frames it really holds; a --keep-tail file's long last frame as it
+// stands) and asks sela_hip_levels for every frame's records: measured on the GPU, nothing decoded into host memory.  A 24- or
+// 32-bit .sela is refused by name: the records are those of 16-bit samples.
+struct LevelReport {
+    uint32_t channels = 0, sampleRate = 0;
+    uint64_t frames = 0, silentFrames = 0; // frames held; those of them in which every channel is digital silence
+    std::vector<ChannelLevel> perChannel;  // [channels]
+    ChannelLevel track;                    // all channels folded into one
+};
+LevelReport measureFile(const std::string& selaPath);
+// One line per channel -- the exact integers (peak= samples= sum= sum_squares=), then dBFS peak, dBFS RMS and DC -- and a last
+// line for the track; no GPU needed.
+std::string formatLevelReport(const LevelReport& report);
 
 // ---- many files, all GPUs of the node ------------------------------------------------------------------
 // BASELINE.json configs[3]: an album's tracks are one index space of frames, cut into contiguous balanced

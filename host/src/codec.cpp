@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <cstddef>
+#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -1045,6 +1047,62 @@ int verifyExitCode(const VerifyReport& r)
     if (!r.lossy.empty() || r.headersDisagree() || r.missingSamplesPerChannel)
         return 3;
     return r.tailSamplesPerChannel ? 4 : 0;
+}
+
+// ---- levels ----------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(LevelRecord) == sizeof(sela_hip_level) && offsetof(LevelRecord, samples) == offsetof(sela_hip_level, samples)
+        && offsetof(LevelRecord, sum) == offsetof(sela_hip_level, sum) && offsetof(LevelRecord, sumSquares) == offsetof(sela_hip_level, sum_squares),
+    "levels.hpp restates the device's record");
+
+LevelReport measureFile(const std::string& selaPath)
+{
+    const SelaInfo info = probeSela(selaPath);
+    if (info.header.bitsPerSample == 24 || info.header.bitsPerSample == 32)
+        throw data::Exception("Measure: " + selaPath + " holds " + std::to_string(info.header.bitsPerSample)
+            + "-bit samples: levels are measured on 16-bit streams only");
+    const uint32_t channels = info.header.channels;
+    LevelReport r;
+    r.channels = channels;
+    r.sampleRate = info.header.sampleRate;
+    // the frames the file really holds (as verifyFile finds them)
+    std::vector<uint8_t> payload(info.payload + 8);
+    if (info.payload)
+        sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
+    std::vector<uint64_t> offsets(info.announced + 1, 0);
+    const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
+    std::vector<sela_hip_level> levels((size_t)found * channels + 1);
+    if (sela_hip_levels(payload.data(), offsets.data(), found, channels, levels.data()) != SELA_HIP_OK)
+        gpuFailure("Measure");
+    r.frames = found;
+    r.perChannel = foldChannels(reinterpret_cast<const LevelRecord*>(levels.data()), found, channels);
+    for (uint32_t f = 0; f < found; f++) {
+        bool silent = true;
+        for (uint32_t c = 0; c < channels; c++)
+            silent = silent && levels[(size_t)f * channels + c].peak == 0;
+        r.silentFrames += silent ? 1 : 0;
+    }
+    for (const ChannelLevel& c : r.perChannel)
+        fold(r.track, c);
+    return r;
+}
+
+namespace {
+std::string levelFigures(const ChannelLevel& l)
+{
+    char figures[128];
+    std::snprintf(figures, sizeof(figures), " peak_dbfs=%.2f rms_dbfs=%.2f dc=%.4f", peakDbfs(l), rmsDbfs(l), dcOffset(l));
+    return "peak=" + std::to_string(l.peak) + " samples=" + std::to_string(l.samples) + " sum=" + std::to_string(l.sum) + " sum_squares="
+        + std::to_string(l.sumSquares) + figures;
+}
+} // namespace
+
+std::string formatLevelReport(const LevelReport& r)
+{
+    std::string out;
+    for (size_t c = 0; c < r.perChannel.size(); c++)
+        out += "channel " + std::to_string(c) + ": " + levelFigures(r.perChannel[c]) + "\n";
+    out += "track: " + levelFigures(r.track) + " (" + std::to_string(r.frames) + " frames, " + std::to_string(r.silentFrames) + " silent)\n";
+    return out;
 }
 
 // ---- many files by path: every GPU worker reads, codes and writes its own pieces ----------------------------------

@@ -21,6 +21,10 @@
 //                                      what of in.wav it never held; exit 0: all of it comes back exactly, 3: a frame differs or
 //                                      the headers disagree, 4: only tail samples are missing, 1: an error (a .wav and a .sela
 //                                      of different sample widths among them)
+//   sela_mi355x -m in.sela             measure: per channel the exact peak, sample count, sum and sum of squares of the decoded
+//                                      int16 samples (reduced on the GPU, nothing decoded into memory), then dBFS peak, dBFS RMS and
+//                                      DC offset; a last line for the track.  A --keep-tail file is read as it stands; a 24- or
+//                                      32-bit .sela is refused by name (exit 1)
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -60,6 +64,8 @@ int usage(const std::string& program)
               << "Decoding a file (--start S --count N: samples S .. S + N - 1 per channel only; 16-, 24- and 32-bit files alike):\n"
               << program << " -d [--start S --count N] path/to/input.sela path/to/output.wav\n\n"
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
+              << "Measuring a 16-bit file (per channel and for the track: peak, sum and sum of squares, then dBFS peak, dBFS RMS and DC):\n"
+              << program << " -m path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -254,6 +260,13 @@ int run(int argc, char** argv)
                                                            : sela::verifyFile(std::string(argv[2]), std::string(argv[3]));
         std::cout << sela::formatVerifyReport(report) << std::flush;
         return sela::verifyExitCode(report);
+    }
+    if (verb == "-m") {
+        if (argc != 3)
+            return usage(program);
+        std::cout << "Measuring: " << argv[2] << std::endl;
+        std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
+        return 0;
     }
     if (argc != 4 || (verb != "-e" && verb != "-d"))
         return usage(program);

@@ -922,6 +922,54 @@ int sela_hip_verify_payload_pcm_device(const uint8_t* d_payload, size_t payload_
 int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample,
     const void* pcm, uint64_t pcm_samples, uint32_t* diff_counts /* [n_frames] */, uint32_t* first_diff /* [n_frames] */, uint32_t* lossy_frames /* or NULL */);
 
+/* ---- levels: how loud a stream is, per frame and channel -------------------------------------------------------
+ * A track's peak, RMS and DC offset, and which of its frames are digital silence, without decoding it into memory: what
+ * sela_hip_decode_n_device does, with a reduction where it stores -- on the 2048-sample route (up to eight channels) in one kernel
+ * that writes no PCM at all.  Record [f][c] is taken over exactly the int16 values v that sela_hip_decode_n_device writes for
+ * (frame f, channel c) with the same d_frames, d_frame_offsets, n_frames, channels and stride: its narrowing of wider samples, its
+ * combine of difference subframes, its route, its zeros for a channel that ends early.  All four fields are integers and exact,
+ * whatever the order of the additions: peak <= 32768 (|-32768|), |sum| <= 65535 * 32768 < 2^31, sum_squares <= 65535 * 2^30 < 2^46.
+ * Scope: the domain of sela_hip_decode_n_device (16-bit output, frames of 0 .. 65535 samples, 1 .. 255 channels, the long last frame
+ * of a whole-track stream included).  Samples of more than 16 bits are measured as that call narrows them, not as they are.
+ *   d_levels       [n_frames][channels], 8-byte aligned.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_n_device leaves them for the same frames;
+ *                  [2] the number of frames in which some channel has peak != 0 (the largest samplesPerChannel is not reported
+ *                  here: sela_hip_index_samples() or d_sample_offsets say it).
+ *   sela_hip_decode_n_status_error() applies to [0], [1] and [3] unchanged; where it gives non-zero, or SELA_HIP_FLAG_STRIDE is
+ *   set, d_levels is not defined.  n_frames = 0 writes zero status words (and d_sample_offsets[0] = 0 where given) and nothing else.
+ * d_workspace: sela_hip_levels_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at a time may use it.  With up(b) = b rounded up to a
+ * multiple of 256 the size is
+ *     sela_hip_decode_n_workspace_bytes(max_frames, channels, stride)       the decode call's pieces, its alignment included
+ *   + up(2 * max_frames * channels * stride)                                the int16 PCM of the routes that are not fused
+ * and SIZE_MAX where sela_hip_verify_workspace_bytes() is, or for channels = 0.
+ * Arguments, errors and their order are sela_hip_verify_device's (SELA_HIP_EINVAL: channels outside 1..255, stride 0, n_frames *
+ * channels at 2^31 or more, a null pointer -- d_sample_offsets may be NULL, d_levels only where there are frames -- a d_levels
+ * that is not 8-byte aligned, a null or misaligned d_frames / d_payload; SELA_HIP_ECAPACITY: a smaller workspace), found before any
+ * device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no allocation, no host wait, no
+ * host read of device data, so a stream being captured into a HIP graph may take either call.  Apart from d_levels,
+ * d_sample_offsets, d_status and the workspace (the payload call: its two index outputs too) nothing is written.
+ * sela_hip_debug_standard_first routes the any-length kernels as it does for the decode call. */
+typedef struct sela_hip_level { /* 24 bytes, 8-byte aligned */
+    uint32_t peak;        /* max |v| over the frame's samples of this channel: 0 .. 32768 */
+    uint32_t samples;     /* samples per channel of the frame: sample_offsets[f + 1] - sample_offsets[f] */
+    int64_t sum;          /* sum of v */
+    uint64_t sum_squares; /* sum of v * v */
+} sela_hip_level;
+size_t sela_hip_levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_levels_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level* d_levels /* [n_frames][channels] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written). */
+int sela_hip_levels_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames: returns what sela_hip_decode returns for the stream (0: the records are
+ * valid).  Runs where sela_hip_verify runs: the calling thread's any-length context and its own stream, past the coalescer; an
+ * open streaming job of the thread is left alone.  n_frames = 0 returns 0 and asks for no device. */
+int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels /* [n_frames][channels] */);
+
 /* ---- a whole track from packed 3- or 4-byte PCM: the tail of a 24- or 32-bit file kept ----------------------------
  * sela_hip_encode_whole* ("a whole track", above) for the containers of sela_hip_encode_pcm*: d_pcm is little-endian interleaved
  * [N][channels] samples of bytes_per_sample = 3 or 4 bytes.  The layout rule is the one sela_hip_whole_frames / sela_hip_whole_frame

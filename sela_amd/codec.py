@@ -368,6 +368,110 @@ class Verifier:
         capi.check(decode_n_status_error(st))
 
 
+# sela_hip_level (include/sela_hip.h): 24 bytes per (frame, channel)
+LEVEL_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u4"), ("sum", "<i8"), ("sum_squares", "<u8")])
+TRACK_LEVEL_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u8"), ("sum", "<i8"), ("sum_squares", "<u8")])
+
+
+class Leveler:
+    """sela_hip_levels_device: how loud a stream is, frame by frame and channel by channel, on the device -- the peak |v|, the sum
+    and the sum of squares of the int16 samples DecoderN.decode would write.  All integers, so exact.  Owns its
+    records and its workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites
+    them.  No PCM is written: on the 2048-sample route of up to eight channels not even into the workspace."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        with torch.cuda.device(self.device):
+            # the records as int64 [max_frames, channels, 3]: word 0 peak | samples << 32, word 1 sum, word 2 sum_squares
+            self.levels = torch.zeros((max_frames, channels, 3), dtype=torch.int64, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_levels_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def measure(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
+        n_frames frames, int64 cuda tensor [n_frames, channels, 3], a view of the leveler's own buffer (records(): as LEVEL_DTYPE)."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_levels_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.levels[:n_frames]
+
+    def measure_payload(self, payload, max_frames=None):
+        """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (records [max_frames, channels, 3], count int32 [1]):
+        records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_levels_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_levels_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
+            self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
+            self.payload_workspace.numel(), stream))
+        return self.levels[:max_frames], self.count
+
+    @staticmethod
+    def records(levels) -> np.ndarray:
+        """Waits for the last call -> a host copy of records as LEVEL_DTYPE [n_frames, channels]."""
+        host = np.ascontiguousarray(levels.cpu().numpy())
+        return host.view(LEVEL_DTYPE).reshape(host.shape[:-1])
+
+    def loud_frames(self) -> int:
+        """Waits for the last call -> the number of frames in which some channel is not digital silence (status[2])."""
+        return int(self.status[2].item())
+
+    def route(self) -> int:
+        """Waits for the last call -> the route it took: 0 nothing measured, 1 the 2048-sample decoder, 2 the any-length kernels."""
+        return int(self.status[3].item())
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        st[2] = 0
+        capi.check(decode_n_status_error(st))
+
+
+def levels_host(frames: np.ndarray, offsets: np.ndarray, channels: int) -> np.ndarray:
+    """sela_hip_levels on numpy arrays -> the records, LEVEL_DTYPE [n_frames, channels]."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    out = np.zeros((n_frames, channels), LEVEL_DTYPE)
+    capi.check(lib.sela_hip_levels(fr.ctypes.data, offs.ctypes.data, n_frames, channels, out.ctypes.data))
+    return out
+
+
+def track_levels(levels: np.ndarray) -> np.ndarray:
+    """Folds records (LEVEL_DTYPE [n_frames, channels]) into one row per channel (TRACK_LEVEL_DTYPE [channels]): the largest peak
+    and the sums of samples, sum and sum_squares, in Python's integers -- a sum that leaves its field's range raises OverflowError."""
+    rec = np.asarray(levels, dtype=LEVEL_DTYPE)
+    assert rec.ndim == 2
+    out = np.zeros(rec.shape[1], TRACK_LEVEL_DTYPE)
+    for c in range(rec.shape[1]):
+        col = rec[:, c]
+        out[c] = (max((int(p) for p in col["peak"]), default=0), sum(int(s) for s in col["samples"]), sum(int(s) for s in col["sum"]),
+                  sum(int(s) for s in col["sum_squares"]))
+    return out
+
+
 class WindowDecoder:
     """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
     device memory -- only the frames a window touches are decoded.  Owns its output, flags, status and workspace

@@ -1703,6 +1703,30 @@ int verify_call(const Form& form, uint32_t channels, uint32_t stride, const int1
         });
 }
 
+// sela_hip_levels_device / sela_hip_levels_payload_device (5.26): the verify call with the records for the compare's arrays
+template <typename Form>
+int levels_call(const Form& form, uint32_t channels, uint32_t stride, sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "levels", sela::levels_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || d_levels));
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_levels & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_levels must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launch_with_priorities(max_frames, stream, "levels launch", [&](uint32_t synth_priorities) {
+                return sela::launch_levels_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_levels, d_sample_offsets, d_status, d_ws,
+                    sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
 // sela_hip_decode_windows_device (5.17), in the frames form: the table is the form's, the windows are the call's.  Its workspace
 // is sized by the windows and not by the table, so its formula is sela_hip_decode_windows_workspace_bytes itself, closed over
 // the call's own arguments (the form asks it only after the check has passed them); the call has no stride.
@@ -2042,6 +2066,38 @@ int sela_hip_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (!frame_offsets || (n_frames && (!frames || !pcm || !diff_counts || !first_diff)))
         return fail(SELA_HIP_EINVAL, "null pointer");
     return sela::generic_verify(frames, frame_offsets, n_frames, channels, pcm, diff_counts, first_diff, lossy_frames, g_recurrence_form);
+}
+
+size_t sela_hip_levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::levels_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_levels_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level* d_levels,
+    uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return levels_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_levels, d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
+}
+
+int sela_hip_levels_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, sela_hip_level* d_levels,
+    uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return levels_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_levels, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: where sela_hip_verify runs (generic_levels); no frames need no device.
+int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!frame_offsets || (n_frames && (!frames || !levels)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    return sela::generic_levels(frames, frame_offsets, n_frames, channels, levels, g_recurrence_form);
 }
 
 size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)

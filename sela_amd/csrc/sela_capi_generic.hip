@@ -638,6 +638,67 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
         VerifyPcm{ pcm, sample_offsets.data(), channels, stride, recurrence_form, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
+// sela_hip_levels: generic_verify without a reference.  Per chunk the frames and their offsets go in; status
+// (4 x u32, padded to 8 bytes' alignment by the arena) and the chunk's records come back behind the chunk's ONE wait; the first
+// chunk whose status words fail ends the call with that code.
+int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels, int recurrence_form)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    if (check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const uint32_t largest = generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (n_frames && largest == 0)
+        return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    const uint32_t stride = std::max(largest, 1u);
+    const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2) + (size_t)channels * (sizeof(GenericSubInfo) + sizeof(sela_hip_level)) + 64;
+    Arena& g_arena = call.arena();
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const hipStream_t st = call.stream();
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
+        const size_t ws_bytes = levels_workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, "levels: the chunk is too large");
+        const size_t records = (size_t)cf * channels;
+        hipError_t e = g_arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + 16 + records * sizeof(sela_hip_level) + ws_bytes + 12 * kPiece);
+        if (e != hipSuccess)
+            return report_hip_error(e, "levels: scratch");
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
+        uint32_t* d_status = g_arena.take<uint32_t>(4);
+        sela_hip_level* d_levels = g_arena.take<sela_hip_level>(records);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "levels: internal scratch estimate too small");
+        std::vector<uint64_t> local((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        uint32_t status[4] = { 0, 0, 0, 0 };
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_levels_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, records * sizeof(sela_hip_level), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "levels");
+        const uint32_t route_status[4] = { status[0], status[1], 0, status[3] };
+        const int rc = sela_hip_decode_n_status_error(route_status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+    }
+    return SELA_HIP_OK;
+}
+
 // The caller has walked the stream: the offsets never decrease, the largest samplesPerChannel fits the stride.
 int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, const int32_t* samples,
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)

@@ -172,6 +172,15 @@ __device__ __forceinline__ uint64_t wave_sum_40(uint64_t v)
     const uint32_t hi = wave_sum_small((uint32_t)(v >> 20));
     return ((uint64_t)hi << 20) + lo;
 }
+// Exact wave sum of any per-lane 64-bit values whose total fits 64 bits: three 22-bit limbs (the top one 20 bits), each
+// summed without overflow (64 * 2^22 = 2^28).
+__device__ __forceinline__ uint64_t wave_sum_64(uint64_t v)
+{
+    const uint32_t lo = wave_sum_small((uint32_t)v & 0x3FFFFFu);
+    const uint32_t mid = wave_sum_small((uint32_t)(v >> 22) & 0x3FFFFFu);
+    const uint32_t hi = wave_sum_small((uint32_t)(v >> 44));
+    return ((uint64_t)hi << 44) + ((uint64_t)mid << 22) + lo;
+}
 
 // Exclusive prefix sum over the 64 lanes (totals must fit 32 bits): the same DPP ladder -- prefix sums
 // within each row of 16, then the totals of the rows before are broadcast in.
@@ -426,7 +435,7 @@ __device__ __forceinline__ void step_up_from_q(uint32_t order, int32_t q_lo, int
 // resident_frames: the workgroups of `kernel` the current device holds at once (0: the runtime would not say), asked once per
 // (kernel slot, device, waves per workgroup) -- the occupancy query is per kernel, so every kernel has a slot of its own.
 // vec_shift_from_for: which workgroups of a launch run their recurrence in the lonely-wave form (k_decode_frames).
-constexpr int kResidencyDecode = 0, kResidencyVerify = 1, kResidencyWindows = 2, kResidencySlots = 3;
+constexpr int kResidencyDecode = 0, kResidencyVerify = 1, kResidencyWindows = 2, kResidencyLevels = 3, kResidencySlots = 4;
 uint32_t resident_frames(const void* kernel, int n_waves, size_t lds, int slot = kResidencyDecode);
 uint32_t vec_shift_from_for(uint32_t n_frames, int n_waves, uint32_t resident);
 int decode_waves(uint32_t channels);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sela_hip.h"
 #include "sela_workspace.h"
 
 namespace sela {
@@ -75,6 +76,19 @@ inline size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uin
 hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
+// sela_hip_levels_device / sela_hip_levels_payload_device: launch_verify_n_device's shape with the compare
+// turned into a reduction -- peak, sum and sum of squares per (frame, channel).  Up to kVerifyFusedChannels channels the
+// 2048-sample route is one kernel (k_level_frames, sela_levels.hip); every other route decodes into the workspace and
+// k_level_channels takes it from there.
+hipError_t launch_level_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* d_levels,
+    uint32_t* d_status, void* d_workspace, hipStream_t stream, int recurrence_form, uint32_t synth_priorities, const uint32_t* d_n_found);
+hipError_t launch_level_channels(const int16_t* d_decoded, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, sela_hip_level* d_levels, uint32_t* d_status, hipStream_t stream);
+size_t levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return levels_workspace_bytes(max_frames, channels, stride, nullptr); }
+hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
+    uint32_t synth_priorities, hipStream_t stream);
 // sela_hip_verify_i32_device / sela_hip_verify_payload_i32_device: launch_decode_i32_device's shape with the
 // combine turned into a compare against d_samples ([frames][channels][stride] int32, d_lengths or null).  The kernels are
 // sela_verify32.hip's: frames of a direct layout are compared from the subframes as decoded, nothing stored; any other frame goes

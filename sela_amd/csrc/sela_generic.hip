@@ -1828,6 +1828,64 @@ hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_fra
         stream);
 }
 
+// ---- levels on the device (sela_hip_levels_device) -------------------------------------------------------------
+// Workspace: launch_decode_n_device's | the PCM of the routes that are not fused (as sela_hip_decode_n_device writes it).
+struct LevelsWs {
+    DecodeNWs n;
+    int16_t* pcm;
+};
+static LevelsWs carve_levels(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    LevelsWs w;
+    w.n = carve_decode_n(c, max_frames, channels, stride);
+    w.pcm = c.take<int16_t>((uint64_t)max_frames * channels * stride);
+    return w;
+}
+
+size_t levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (channels == 0 || verify_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_levels(c, max_frames, channels, stride); });
+}
+
+// launch_verify_n_device with a reduction in place of the compare: the sample index, k_route_n, k_verify_begin (status[2], the
+// largest samplesPerChannel while k_route_n reads it, becomes the count of frames that are not silent), then
+//   route 1, up to kVerifyFusedChannels channels: k_level_frames on the fast decoder's count -- nothing decoded reaches memory;
+//   route 1 above (k_decode_frames_wide) and route 2 (the any-length kernels and the int16 writer): decoded into the workspace as
+//   sela_hip_decode_n_device decodes into d_pcm_out, then k_level_channels / k_level_count on the count of the route that ran.
+hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
+    uint32_t synth_priorities, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const LevelsWs w = carve_levels(c, max_frames, channels, stride);
+    const DecodeHeadWs& head = w.n.head;
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.n.offsets;
+    const uint32_t* const n_fast = head.counters + 5;
+    const uint32_t* const n_any = head.counters + 6;
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, head.counters, head.tiles, stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, head.counters);
+    hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, stream, d_status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || max_frames * channels == 0)
+        return e;
+    // route 1 (its workspace: the decoded subframes' piece, as in launch_decode_n_device)
+    const bool fused = channels <= kVerifyFusedChannels;
+    if (fused)
+        e = launch_level_frames(d_frames, d_frame_offsets, max_frames, channels, d_levels, d_status, head.dec, stream, recurrence_form, synth_priorities, n_fast);
+    else
+        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, w.pcm, d_status, head.dec, stream, nullptr, nullptr, nullptr, recurrence_form,
+            synth_priorities, n_fast, false);
+    if (e != hipSuccess)
+        return e;
+    // route 2
+    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, w.n, d_so, w.pcm, d_status, mode, stream);
+    if (e != hipSuccess)
+        return e;
+    return launch_level_channels(w.pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, d_levels, d_status, stream);
+}
+
 // ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
 // Workspace: launch_decode_i32_device's | the fallback's samples by channel, [frames][channels][stride] | its counts | a mark per
 // frame | k_verify32_direct's / _rest's words per (frame, slice) | the two control words.
