@@ -125,6 +125,18 @@ LevelReport measureFile(const std::string& selaPath);
 // One line per channel -- the exact integers (peak= samples= sum= sum_squares=), then dBFS peak, dBFS RMS and DC -- and a last
 // line for the track; no GPU needed.
 std::string formatLevelReport(const LevelReport& report);
+// The same for a .sela of 24- or 32-bit samples (host/src/wide.cpp): the width and the channel count are the
+// header's, the frames are found as measureFile finds them, and sela_hip_levels_i32 gives every frame's records -- a --whole
+// file's long last frame as it stands.  The energy is 128 bits wide; dBFS is against the file's own full scale, 2^(bits - 1).
+struct WideLevelReport {
+    uint32_t channels = 0, sampleRate = 0, bitsPerSample = 0;
+    uint64_t frames = 0, silentFrames = 0;
+    std::vector<ChannelLevelWide> perChannel; // [channels]
+    ChannelLevelWide track;                   // all channels folded into one
+};
+WideLevelReport measureWideFile(const std::string& selaPath);
+// formatLevelReport's lines, with the integers of the wide records; no GPU needed.
+std::string formatLevelReport(const WideLevelReport& report);
 
 // ---- many files, all GPUs of the node ------------------------------------------------------------------
 // BASELINE.json configs[3]: an album's tracks are one index space of frames, cut into contiguous balanced

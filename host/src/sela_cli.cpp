@@ -25,6 +25,9 @@
 //                                      int16 samples (reduced on the GPU, nothing decoded into memory), then dBFS peak, dBFS RMS and
 //                                      DC offset; a last line for the track.  A --keep-tail file is read as it stands; a 24- or
 //                                      32-bit .sela is refused by name (exit 1)
+//   sela_mi355x -M in.sela             the same by the file's own header: a 16-bit file exactly as -m, a 24- or 32-bit file through
+//                                      sela_hip_levels_i32 -- the integers of its samples as they are (the sum of squares in 128
+//                                      bits, printed whole), dBFS against the file's own full scale; a --whole file as it stands
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -66,6 +69,8 @@ int usage(const std::string& program)
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Measuring a 16-bit file (per channel and for the track: peak, sum and sum of squares, then dBFS peak, dBFS RMS and DC):\n"
               << program << " -m path/to/input.sela\n\n"
+              << "Measuring a 16-, 24- or 32-bit file (as -m, by the file's own header; dBFS against the file's own full scale):\n"
+              << program << " -M path/to/input.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -266,6 +271,20 @@ int run(int argc, char** argv)
             return usage(program);
         std::cout << "Measuring: " << argv[2] << std::endl;
         std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
+        return 0;
+    }
+    if (verb == "-M") {
+        if (argc != 3)
+            return usage(program);
+        // (by the .sela's header: a 24- or 32-bit file goes to sela_hip_levels_i32; any other file down -m's path)
+        const uint16_t bits = sela::selaFileBits(argv[2]);
+        if (bits == 24 || bits == 32) {
+            std::cout << "Measuring (" << bits << "-bit): " << argv[2] << std::endl;
+            std::cout << sela::formatLevelReport(sela::measureWideFile(std::string(argv[2]))) << std::flush;
+        } else {
+            std::cout << "Measuring: " << argv[2] << std::endl;
+            std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
+        }
         return 0;
     }
     if (argc != 4 || (verb != "-e" && verb != "-d"))

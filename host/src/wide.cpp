@@ -4,6 +4,8 @@
 #include "sela_host/wide.hpp"
 
 #include <algorithm>
+#include <cstddef>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -287,6 +289,53 @@ size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64
     }
     writeWideWav(out, s, pcm.data(), dataBytes);
     return (size_t)count;
+}
+
+// ---- levels --------------------------------------------------------------------------------------------------
+static_assert(sizeof(LevelRecord32) == sizeof(sela_hip_level32) && offsetof(LevelRecord32, samples) == offsetof(sela_hip_level32, samples)
+        && offsetof(LevelRecord32, sum) == offsetof(sela_hip_level32, sum) && offsetof(LevelRecord32, sumSquaresLo) == offsetof(sela_hip_level32, sum_squares_lo)
+        && offsetof(LevelRecord32, sumSquaresHi) == offsetof(sela_hip_level32, sum_squares_hi),
+    "levels.hpp restates the device's record");
+
+WideLevelReport measureWideFile(const std::string& selaPath)
+{
+    WideSela s;
+    readWideSela(selaPath, "measureWideFile", s);
+    WideLevelReport r;
+    r.channels = s.channels, r.sampleRate = s.rate, r.bitsPerSample = s.bits;
+    std::vector<sela_hip_level32> levels((size_t)s.found * s.channels + 1);
+    if (sela_hip_levels_i32(s.stream.data(), s.offsets.data(), s.found, s.channels, levels.data()) != SELA_HIP_OK)
+        failHip("Measure");
+    r.frames = s.found;
+    r.perChannel = foldChannels(reinterpret_cast<const LevelRecord32*>(levels.data()), s.found, s.channels);
+    for (uint32_t f = 0; f < s.found; f++) {
+        bool silent = true;
+        for (uint32_t c = 0; c < s.channels; c++)
+            silent = silent && levels[(size_t)f * s.channels + c].peak == 0;
+        r.silentFrames += silent ? 1 : 0;
+    }
+    for (const ChannelLevelWide& c : r.perChannel)
+        fold(r.track, c);
+    return r;
+}
+
+namespace {
+std::string wideLevelFigures(const ChannelLevelWide& l, double scale)
+{
+    char figures[128];
+    std::snprintf(figures, sizeof(figures), " peak_dbfs=%.2f rms_dbfs=%.2f dc=%.4f", peakDbfs(l, scale), rmsDbfs(l, scale), dcOffset(l));
+    return "peak=" + std::to_string(l.peak) + " samples=" + std::to_string(l.samples) + " sum=" + std::to_string(l.sum) + " sum_squares=" + energyDecimal(l) + figures;
+}
+} // namespace
+
+std::string formatLevelReport(const WideLevelReport& r)
+{
+    const double scale = fullScale(r.bitsPerSample);
+    std::string out;
+    for (size_t c = 0; c < r.perChannel.size(); c++)
+        out += "channel " + std::to_string(c) + ": " + wideLevelFigures(r.perChannel[c], scale) + "\n";
+    out += "track: " + wideLevelFigures(r.track, scale) + " (" + std::to_string(r.frames) + " frames, " + std::to_string(r.silentFrames) + " silent)\n";
+    return out;
 }
 
 // verifyFile for a 24- or 32-bit pair: the headers held against each other as verifyFile holds them, the frames the .sela really

@@ -970,6 +970,63 @@ int sela_hip_levels_payload_device(const uint8_t* d_payload, size_t payload_byte
  * open streaming job of the thread is left alone.  n_frames = 0 returns 0 and asks for no device. */
 int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels /* [n_frames][channels] */);
 
+/* ---- levels of 24- and 32-bit streams --------------------------------------------------------------------------
+ * The calls above on the whole domain of sela_hip_decode_i32_device: samples of up to 32 bits, channels of different lengths,
+ * every subframe layout that call takes.  What sela_hip_decode_i32_device does, with a reduction where it stores: record [f][c] is
+ * taken over exactly samples_out[f][c][0 .. counts_out[f * channels + c]) as that call writes them for the same d_frames,
+ * d_frame_offsets, n_frames, channels and stride -- difference subframes combined mod 2^32, a channel that no subframe names with a
+ * count of 0 and so an all-zero record, a malformed frame with whatever counts that call writes.  Frames of the layouts this
+ * project's encoders write are reduced from the subframes as decoded and no sample is stored; any other frame goes through the
+ * decode call's combine into the workspace first.  All five fields are integers and exact, whatever the launch's shape:
+ * peak <= 2^31 (|INT32_MIN|), |sum| <= 65535 * 2^31 < 2^47, sum of squares <= 65535 * 2^62 < 2^78, hence two words.
+ *   d_levels       [n_frames][channels], 8-byte aligned.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_i32_device leaves them for the same
+ *                  frames; [2] the number of frames in which some channel has peak != 0 (the largest samplesPerChannel is not
+ *                  reported here: sela_hip_index_samples() or d_sample_offsets say it).
+ *   sela_hip_decode_status_error() applies to [0], [1] and [3] unchanged; with SELA_HIP_FLAG_STRIDE set d_levels is not defined.
+ *   n_frames = 0 writes the status words (and d_sample_offsets[0] = 0 where given) and nothing else.
+ * d_workspace: sela_hip_levels_i32_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at a time may use it.  The size is
+ * sela_hip_verify_i32_workspace_bytes()'s with 32 bytes per (frame, slice of 4096 samples, channel) where that call has 8 bytes per
+ * (frame, slice); it does not depend on the data, and is SIZE_MAX where sela_hip_verify_i32_workspace_bytes() is, or for channels = 0.
+ * Arguments, errors and their order are sela_hip_levels_device's (SELA_HIP_EINVAL: channels outside 1..255, stride 0, n_frames *
+ * channels at 2^31 or more, a null pointer -- d_sample_offsets may be NULL, d_levels only where there are frames -- a d_levels
+ * that is not 8-byte aligned, a null or misaligned d_frames / d_payload; SELA_HIP_ECAPACITY: a smaller workspace), found before any
+ * device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no allocation, no host wait, no
+ * host read of device data, so a stream being captured into a HIP graph may take any of these calls.  Apart from d_levels,
+ * d_sample_offsets, d_status and the workspace (the payload call: its two index outputs too) nothing is written, and no byte of
+ * d_levels beyond [n_frames][channels]. */
+typedef struct sela_hip_level32 { /* 32 bytes, 8-byte aligned */
+    uint32_t peak;           /* max |v| over the channel's samples of the frame: 0 .. 2^31 */
+    uint32_t samples;        /* the channel's samples in the frame: counts_out[f * channels + c] */
+    int64_t sum;             /* sum of v */
+    uint64_t sum_squares_lo; /* sum of v * v, bits 0 .. 63 */
+    uint64_t sum_squares_hi; /* sum of v * v, bits 64 .. 127 */
+} sela_hip_level32;
+size_t sela_hip_levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_levels_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels /* [n_frames][channels] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written). */
+int sela_hip_levels_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* The same records from planar int32 samples that already lie in device memory -- sela_hip_pcm_unpack_device's output ahead of an
+ * encode, or a decode's output: record [f][c] over d_samples[f][c][0 .. min(d_counts[f * channels + c], stride)), d_counts NULL:
+ * stride samples each.  d_samples and d_counts 4-byte aligned (rows at multiples of 16 bytes are read 16 bytes at a time).
+ * d_status: [2] as above, the other words zeroed.  d_workspace: sela_hip_levels_samples_i32_workspace_bytes(n_frames, channels,
+ * stride) bytes (the partial records alone).  Errors as above, without a stream of frames. */
+size_t sela_hip_levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_levels_samples_i32_device(const int32_t* d_samples /* [n_frames][channels][stride] */, const uint32_t* d_counts /* [n_frames * channels] or NULL */,
+    uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level32* d_levels, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+/* Host pointers, synchronous, in chunks of frames with the stream's largest samplesPerChannel for a stride: returns what
+ * sela_hip_decode_i32 returns for the stream (0: the records are valid).  Runs where sela_hip_verify_i32 runs: the calling thread's
+ * any-length context and its own stream, past the coalescer; an open streaming job of the thread is left alone.  n_frames = 0
+ * returns 0 and asks for no device. */
+int sela_hip_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level32* levels /* [n_frames][channels] */);
+
 /* ---- a whole track from packed 3- or 4-byte PCM: the tail of a 24- or 32-bit file kept ----------------------------
  * sela_hip_encode_whole* ("a whole track", above) for the containers of sela_hip_encode_pcm*: d_pcm is little-endian interleaved
  * [N][channels] samples of bytes_per_sample = 3 or 4 bytes.  The layout rule is the one sela_hip_whole_frames / sela_hip_whole_frame

@@ -472,6 +472,132 @@ def track_levels(levels: np.ndarray) -> np.ndarray:
     return out
 
 
+# sela_hip_level32 (include/sela_hip.h): 32 bytes per (frame, channel); the energy is sum_squares_lo + (sum_squares_hi << 64)
+LEVEL32_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u4"), ("sum", "<i8"), ("sum_squares_lo", "<u8"), ("sum_squares_hi", "<u8")])
+
+
+class Leveler32:
+    """sela_hip_levels_i32_device: Leveler on the whole domain of sela_hip_decode_i32_device -- samples of up to 32 bits, channels
+    of different lengths, every subframe layout.  Record [f][c] is taken over the samples that call writes for
+    channel c of frame f, with a 128-bit sum of squares.  Owns its records and its workspace on the current device (or `device`);
+    every call is asynchronous on the current stream and overwrites them.  No decoded sample is stored for the layouts this
+    project's encoders write."""
+
+    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
+        import torch
+
+        self.torch = torch
+        self.lib = capi.lib()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        with torch.cuda.device(self.device):
+            # the records as int64 [max_frames, channels, 4]: word 0 peak | samples << 32, word 1 sum, words 2 and 3 the energy
+            self.levels = torch.zeros((max_frames, channels, 4), dtype=torch.int64, device=self.device)
+            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            ws = int(self.lib.sela_hip_levels_i32_workspace_bytes(max_frames, channels, stride))
+            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+
+    def measure(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
+        n_frames frames, int64 cuda tensor [n_frames, channels, 4], a view of the leveler's own buffer (records(): as LEVEL32_DTYPE)."""
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_levels_i32_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
+            self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.levels[:n_frames]
+
+    def measure_payload(self, payload, max_frames=None):
+        """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (records [max_frames, channels, 4], count int32 [1]):
+        records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
+            self.lib.sela_hip_levels_i32_workspace_bytes(max_frames, self.channels, self.stride))
+        with torch.cuda.device(self.device):
+            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_levels_payload_i32_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
+            self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
+            self.payload_workspace.numel(), stream))
+        return self.levels[:max_frames], self.count
+
+    @staticmethod
+    def records(levels) -> np.ndarray:
+        """Waits for the last call -> a host copy of records as LEVEL32_DTYPE [n_frames, channels]."""
+        host = np.ascontiguousarray(levels.cpu().numpy())
+        return host.view(LEVEL32_DTYPE).reshape(host.shape[:-1])
+
+    def loud_frames(self) -> int:
+        """Waits for the last call -> the number of frames in which some channel is not digital silence (status[2])."""
+        return int(self.status[2].item())
+
+    def fallback_frames(self, n_frames=None) -> int:
+        """Waits for the last measure() -> the frames whose layout was not direct (sela_hip_debug_levels_i32_fallback_frames)."""
+        return int(self.lib.sela_hip_debug_levels_i32_fallback_frames(
+            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        st[2] = 0
+        capi.check(decode_status_error(st))
+
+
+def levels_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int) -> np.ndarray:
+    """sela_hip_levels_i32 on numpy arrays -> the records, LEVEL32_DTYPE [n_frames, channels]."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    out = np.zeros((n_frames, channels), LEVEL32_DTYPE)
+    capi.check(lib.sela_hip_levels_i32(fr.ctypes.data, offs.ctypes.data, n_frames, channels, out.ctypes.data))
+    return out
+
+
+def levels_samples_i32(samples, counts=None):
+    """sela_hip_levels_samples_i32_device: samples int32 cuda tensor [n_frames, channels, stride] (contiguous), counts int32 cuda
+    tensor [n_frames * channels] or None (stride samples each) -> (records int64 cuda tensor [n_frames, channels, 4], status int32
+    cuda tensor [4]); asynchronous on the current stream.  Leveler32.records() turns the records into LEVEL32_DTYPE."""
+    import torch
+
+    assert samples.dtype == torch.int32 and samples.is_cuda and samples.is_contiguous() and samples.dim() == 3
+    n_frames, channels, stride = samples.shape
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous() and counts.numel() == n_frames * channels)
+    lib = capi.lib()
+    levels = torch.zeros((n_frames, channels, 4), dtype=torch.int64, device=samples.device)
+    status = torch.zeros(4, dtype=torch.int32, device=samples.device)
+    workspace = torch.empty(int(lib.sela_hip_levels_samples_i32_workspace_bytes(n_frames, channels, stride)), dtype=torch.uint8, device=samples.device)
+    capi.check(lib.sela_hip_levels_samples_i32_device(
+        samples.data_ptr(), None if counts is None else counts.data_ptr(), n_frames, channels, stride, levels.data_ptr(), status.data_ptr(),
+        workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(samples.device).cuda_stream))
+    return levels, status
+
+
+def track_levels32(levels: np.ndarray) -> list:
+    """Folds records (LEVEL32_DTYPE [n_frames, channels]) into one dict per channel -- peak, samples, sum, sum_squares -- in
+    Python's integers: a track's sum of squares passes 2^64 within a few frames at full scale."""
+    rec = np.asarray(levels, dtype=LEVEL32_DTYPE)
+    assert rec.ndim == 2
+    out = []
+    for c in range(rec.shape[1]):
+        col = rec[:, c]
+        out.append({
+            "peak": max((int(p) for p in col["peak"]), default=0), "samples": sum(int(s) for s in col["samples"]), "sum": sum(int(s) for s in col["sum"]),
+            "sum_squares": sum(int(lo) + (int(hi) << 64) for lo, hi in zip(col["sum_squares_lo"], col["sum_squares_hi"])),
+        })
+    return out
+
+
 class WindowDecoder:
     """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
     device memory -- only the frames a window touches are decoded.  Owns its output, flags, status and workspace

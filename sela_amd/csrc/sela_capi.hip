@@ -1832,6 +1832,29 @@ int verify_i32_call(const Form& form, uint32_t channels, uint32_t stride, const 
         });
 }
 
+// sela_hip_levels_i32_device / sela_hip_levels_payload_i32_device (5.27): levels_call's checks in its order, the decode_i32 call's launch shape
+template <typename Form>
+int levels_i32_call(const Form& form, uint32_t channels, uint32_t stride, sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "levels_i32", sela::levels_i32_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || d_levels));
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_levels & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_levels must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_levels_i32_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_levels, d_sample_offsets, d_status, d_ws,
+                                sela::generic_standard_first_mode(), c.stream),
+                "levels_i32 launch");
+        });
+}
+
 // sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device (5.24): the verify_i32 call's checks in its order, then the
 // container's and the original's alignment
 template <typename Form>
@@ -2098,6 +2121,85 @@ int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (n_frames == 0)
         return SELA_HIP_OK;
     return sela::generic_levels(frames, frame_offsets, n_frames, channels, levels, g_recurrence_form);
+}
+
+// ---- levels of 24- and 32-bit streams ------------------------------------------------------------------------
+size_t sela_hip_levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::levels_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_levels_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return levels_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_levels, d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
+}
+
+int sela_hip_levels_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return levels_i32_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_levels, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+size_t sela_hip_levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::levels_samples_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+// levels_call's checks in its order, with the samples where the frames are
+int sela_hip_levels_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int rc = check_frames_shape(n_frames, channels, stride);
+    if (rc == SELA_HIP_OK)
+        rc = need_pointers(d_status && d_workspace && (!n_frames || d_levels));
+    if (rc == SELA_HIP_OK && ((uintptr_t)d_levels & 7))
+        rc = fail(SELA_HIP_EINVAL, "d_levels must be 8-byte aligned");
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (n_frames && !d_samples)
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if (((uintptr_t)d_samples & 3) || ((uintptr_t)d_counts & 3))
+        return fail(SELA_HIP_EINVAL, "d_samples and d_counts must be 4-byte aligned");
+    const size_t need = sela::levels_samples_i32_workspace_bytes(n_frames, channels, stride);
+    if (need == SIZE_MAX || workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_levels_samples_i32_workspace_bytes()");
+    return launched(sela::launch_levels_samples_i32_device(d_samples, d_counts, n_frames, channels, stride, d_levels, d_status, d_workspace, static_cast<hipStream_t>(stream)),
+        "levels_samples_i32 launch");
+}
+
+// Host pointers, synchronous: sela_hip_verify_i32's walk, then chunks of frames where that call runs (generic_levels_i32); no
+// frames need no device.
+int sela_hip_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level32* levels)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!frame_offsets || (n_frames && (!frames || !levels)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (largest == 0)
+        return fail(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    return sela::generic_levels_i32(frames, frame_offsets, n_frames, channels, largest, levels);
+}
+
+// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
+long long sela_hip_debug_levels_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    if (!d_workspace || sela::levels_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return -1;
+    uint32_t left = 0;
+    if (hipDeviceSynchronize() != hipSuccess
+        || hipMemcpy(&left, sela::levels_i32_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return (long long)left;
 }
 
 size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)

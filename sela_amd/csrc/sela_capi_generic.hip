@@ -711,6 +711,61 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
         VerifySamples{ samples, lengths, channels, stride, nullptr, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
+// sela_hip_levels_i32: generic_verify_i32's chunks without a reference.  Per chunk the frames and their offsets go
+// in; status (4 x u32, padded to 8 bytes' alignment by the arena) and the chunk's records come back behind the chunk's ONE wait;
+// the first chunk whose status words fail ends the call with that code.  The caller has walked the stream, as for generic_verify_i32.
+int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level32* levels)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 8 + sizeof(sela_hip_level32) * (1 + verify32_slices(stride))) + 64;
+    Arena& g_arena = call.arena();
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
+    const hipStream_t st = call.stream();
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
+        const size_t ws_bytes = levels_i32_workspace_bytes(cf, channels, stride);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, "levels_i32: the chunk is too large");
+        const size_t records = (size_t)cf * channels;
+        hipError_t e = g_arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + 16 + records * sizeof(sela_hip_level32) + ws_bytes + 12 * kPiece);
+        if (e != hipSuccess)
+            return report_hip_error(e, "levels_i32: scratch");
+        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
+        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
+        uint32_t* d_status = g_arena.take<uint32_t>(4);
+        sela_hip_level32* d_levels = g_arena.take<sela_hip_level32>(records);
+        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
+        if (!g_arena.fits())
+            return report_error(SELA_HIP_ENOMEM, "levels_i32: internal scratch estimate too small");
+        std::vector<uint64_t> local((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        uint32_t status[4] = { 0, 0, 0, 0 };
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_levels_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, records * sizeof(sela_hip_level32), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, "levels_i32");
+        const uint32_t decode_status[4] = { status[0], status[1], 0, 0 };
+        const int rc = sela_hip_decode_status_error(decode_status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+    }
+    return SELA_HIP_OK;
+}
+
 // sela_hip_decode_windows: the *_device launch on chunks of WINDOWS, on the calling thread's context and stream.
 // Per chunk only the frames its windows touch go in (plan_windows: the distinct covering frames back to back, the descriptors
 // on that compacted table; runs of neighbouring frames are gathered with one memcpy each, the whole with one copy); status

@@ -181,6 +181,26 @@ __device__ __forceinline__ uint64_t wave_sum_64(uint64_t v)
     const uint32_t hi = wave_sum_small((uint32_t)(v >> 44));
     return ((uint64_t)hi << 44) + ((uint64_t)mid << 22) + lo;
 }
+// Exact wave sum, mod 2^96, of one 96-bit value per lane (low: bits 0 .. 63, high: bits 64 .. 95): five limbs of at most 22 bits
+// (the top one 8), each summed without overflow (64 * 2^22 = 2^28), then put together with their carries.
+struct Sum96 {
+    uint64_t low;
+    uint32_t high;
+};
+__device__ __forceinline__ Sum96 wave_sum_96(uint64_t low, uint32_t high)
+{
+    const uint64_t l0 = wave_sum_small((uint32_t)low & 0x3FFFFFu);
+    const uint64_t l1 = wave_sum_small((uint32_t)(low >> 22) & 0x3FFFFFu);
+    const uint64_t l2 = wave_sum_small(((uint32_t)(low >> 44) | (high << 20)) & 0x3FFFFFu); // bits 44 .. 65
+    const uint32_t l3 = wave_sum_small((high >> 2) & 0x3FFFFFu);                             // bits 66 .. 87
+    const uint32_t l4 = wave_sum_small(high >> 24);                                          // bits 88 .. 95
+    Sum96 s;
+    s.low = l0 + (l1 << 22); // (below 2^51)
+    const uint64_t l2_low = l2 << 44;
+    s.low += l2_low;
+    s.high = (uint32_t)(l2 >> 20) + (s.low < l2_low ? 1u : 0u) + (l3 << 2) + (l4 << 24);
+    return s;
+}
 
 // Exclusive prefix sum over the 64 lanes (totals must fit 32 bits): the same DPP ladder -- prefix sums
 // within each row of 16, then the totals of the rows before are broadcast in.

@@ -112,6 +112,26 @@ const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_f
 hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_levels_i32_device / sela_hip_levels_payload_i32_device: launch_verify_i32_device's shape with the
+// compare turned into a reduction -- peak, sum and the 128-bit sum of squares per (frame, channel).  The kernels are
+// sela_levels32.hip's; between the slices a partial record per (frame, slice, channel) lies in the workspace.
+hipError_t launch_level32_begin(uint32_t* d_status, uint32_t* d_ctl /* [2] or null */, bool whole /* every status word, not [2] alone */, hipStream_t stream);
+hipError_t launch_level32_direct(const int32_t* d_dec, const GenericSubInfo* d_info, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, const uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks /* [max_frames] */,
+    uint64_t* d_parts /* [max_frames][verify32_slices()][channels] x 32 bytes */, hipStream_t stream);
+// d_ctl and d_marks null: every frame of d_all (the caller's samples; d_counts or null: stride); then the records and status[2]
+hipError_t launch_level32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
+    uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, uint64_t* d_parts, sela_hip_level32* d_levels, hipStream_t stream);
+size_t levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return levels_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
+const uint32_t* levels_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
+hipError_t launch_levels_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_levels_samples_i32_device: the fallback's reduction on its own, over samples that already lie in device memory
+size_t levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return levels_samples_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
+hipError_t launch_levels_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint32_t* d_status, void* d_workspace, hipStream_t stream);
 // sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device: launch_verify_i32_device's shape with the
 // original read as packed interleaved PCM of 3 or 4 bytes a sample, frame f at d_sample_offsets[f] (the caller's, or the
 // workspace's copy) -- sela_verify_pcm.hip's kernels on the tiles of sela_pcm_layout.h, no unpacked copy.

@@ -1952,6 +1952,77 @@ hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_f
         d_first_diff, stream);
 }
 
+// ---- levels of 32-bit and ragged streams on the device (sela_hip_levels_i32_device) --------------------------
+// Workspace: launch_verify_i32_device's pieces, with a partial record (four 8-byte words) per (frame, slice, channel) where that
+// call has two words per (frame, slice).
+constexpr uint32_t kLevel32PartWords = 4;
+static VerifyI32Ws carve_levels_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride) * channels * kLevel32PartWords);
+}
+
+size_t levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (channels == 0 || verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_levels_i32(c, max_frames, channels, stride); });
+}
+
+const uint32_t* levels_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    Carve c(d_workspace);
+    return carve_levels_i32(c, max_frames, channels, stride).ctl;
+}
+
+// launch_verify_i32_device with a reduction in place of the compare: the sample index, k_level32_begin (status[2], the largest
+// samplesPerChannel, becomes the count of frames that are not silent), k_decode_subframes32 and the judge into the workspace by
+// position, then k_level32_direct on the subframes as decoded.  The frames it leaves alone send the whole call through
+// k_generic_combine<false> -- gated on the device by k_verify32_gate's count -- and k_level32_rest reduces those frames from the
+// combine's output; k_level32_sum adds the slices up.
+hipError_t launch_levels_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const VerifyI32Ws w = carve_levels_i32(c, max_frames, channels, stride);
+    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.d.counters, w.d.tiles, stream);
+    hipError_t e = launch_level32_begin(d_status, w.ctl, false, stream);
+    if (e != hipSuccess || max_frames * channels == 0)
+        return e;
+    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.d, d_status, mode, d_n_found, stream);
+    if (e != hipSuccess)
+        return e;
+    e = launch_level32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.d.dec, w.d.info, max_frames, channels, stride,
+        w.all, w.counts, nullptr, nullptr, d_status, w.ctl + 1);
+    return launch_level32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, d_levels, stream);
+}
+
+// The partial records alone.
+static uint64_t* carve_levels_samples_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return c.take<uint64_t>(std::max<uint64_t>((uint64_t)max_frames * verify32_slices(stride) * channels * kLevel32PartWords, 1));
+}
+
+size_t levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (channels == 0 || verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_levels_samples_i32(c, max_frames, channels, stride); });
+}
+
+hipError_t launch_levels_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    sela_hip_level32* d_levels, uint32_t* d_status, void* d_workspace, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    uint64_t* const parts = carve_levels_samples_i32(c, max_frames, channels, stride);
+    const hipError_t e = launch_level32_begin(d_status, nullptr, true, stream);
+    if (e != hipSuccess || max_frames * channels == 0)
+        return e;
+    return launch_level32_rest(d_samples, d_counts, max_frames, nullptr, channels, stride, d_status, nullptr, nullptr, parts, d_levels, stream);
+}
+
 // ---- verification against packed PCM on the device (sela_hip_verify_pcm_device) -------------------------------
 // Workspace: launch_verify_i32_device's pieces, the words per (frame, slice) sized by the tiles of sela_pcm_layout.h | the sample
 // offsets of a caller that asks for none.
