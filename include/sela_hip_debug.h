@@ -149,8 +149,9 @@ enum {
     SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM
 };
 int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
-/* Debug hook (tests; process-wide): sela_hip_encode_pcm, sela_hip_decode_pcm and sela_hip_verify_pcm work in chunks of this many whole frames; 0
- * restores the chunks sized by the device scratch they keep bounded.  Same bytes either way, which is what the tests check. */
+/* Debug hook (tests; process-wide): the host-pointer calls that work in chunks of whole frames on one loop -- sela_hip_verify, sela_hip_verify_i32,
+ * sela_hip_verify_pcm, sela_hip_levels, sela_hip_levels_i32, sela_hip_decode_pcm -- and sela_hip_encode_pcm take this many frames a chunk; 0, the
+ * default, restores the chunks sized by the device scratch they keep bounded.  Same results either way, which is what the tests check. */
 void sela_hip_debug_pcm_chunk_frames(uint32_t frames);
 
 #ifdef __cplusplus

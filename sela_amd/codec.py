@@ -150,10 +150,29 @@ class Decoder:
             raise capi.SelaHipError(-5, "a Rice stream ended before all its values were read")
 
 
-class Decoder32:
-    """sela_hip_decode_i32 on the device: streams of any samplesPerChannel (0 .. 65535), 32-bit samples, channels of
-    different lengths -- what frame::FrameDecoder returns, nothing narrowed.  Owns its outputs and its workspace on the current
-    device (or `device`); every call is asynchronous on the current stream and overwrites them."""
+def decode_status_error(status) -> int:
+    """sela_hip_decode_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_decode_status_error(st.ctypes.data))
+
+
+def decode_n_status_error(status) -> int:
+    """sela_hip_decode_n_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
+    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert st.shape == (4,)
+    return int(capi.lib().sela_hip_decode_n_status_error(st.ctypes.data))
+
+
+class _DeviceCall:
+    """What the classes over sela_hip_<_call>_device and its payload form share: the device, the offsets, the frame count and the
+    status words, the workspace of sela_hip_<_call>_workspace_bytes, the payload form's grow-only workspace, the argument asserts
+    and check().  A class names its call and its status judge, allocates its outputs in _allocate(), and lists the status
+    accessors it has (route = _DeviceCall._route, ...)."""
+
+    _call = None          # "verify_i32": sela_hip_verify_i32_workspace_bytes, sela_hip_debug_verify_i32_fallback_frames
+    _judge = None         # decode_status_error or decode_n_status_error
+    _own_count = True     # status[2] holds the call's own count of frames (lossy, loud), not the largest frame: zeroed for the judge
 
     def __init__(self, max_frames: int, channels: int, stride: int, device=None):
         import torch
@@ -162,24 +181,86 @@ class Decoder32:
         self.lib = capi.lib()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_frames, self.channels, self.stride = max_frames, channels, stride
+        self.payload_workspace = None
         with torch.cuda.device(self.device):
-            self.samples = torch.empty((max_frames, channels, stride), dtype=torch.int32, device=self.device)
-            self.counts = torch.zeros((max_frames, channels), dtype=torch.int32, device=self.device)
+            self._allocate(torch)
             self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
             self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
             self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
             self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_decode_i32_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.workspace = torch.empty(self._workspace_bytes(max_frames), dtype=torch.uint8, device=self.device)
+
+    def _workspace_bytes(self, max_frames: int) -> int:
+        return int(getattr(self.lib, f"sela_hip_{self._call}_workspace_bytes")(max_frames, self.channels, self.stride))
+
+    def _allocate_diffs(self, torch) -> None:
+        self.diff_counts = torch.zeros(self.max_frames, dtype=torch.int32, device=self.device)
+        self.first_diff = torch.zeros(self.max_frames, dtype=torch.int32, device=self.device)
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _frames_ok(self, frames, offsets, n_frames: int) -> None:
+        torch = self.torch
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+
+    def _payload_ok(self, payload, max_frames) -> int:
+        """The payload form's opening: max_frames (None: the class's own), the payload's asserts, and payload_workspace grown to
+        what the index and the call need for it."""
+        torch = self.torch
+        max_frames = self.max_frames if max_frames is None else max_frames
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + self._workspace_bytes(max_frames)
+        with torch.cuda.device(self.device):
+            if self.payload_workspace is None or self.payload_workspace.numel() < need:
+                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return max_frames
+
+    def _route(self) -> int:
+        """Waits for the last call -> the route it took: 0 nothing decoded, 1 the 2048-sample decoder, 2 the any-length kernels."""
+        return int(self.status[3].item())
+
+    def _lossy_frames(self) -> int:
+        """Waits for the last call -> the number of frames with a difference (status[2])."""
+        return int(self.status[2].item())
+
+    def _loud_frames(self) -> int:
+        """Waits for the last call -> the number of frames in which some channel is not digital silence (status[2])."""
+        return int(self.status[2].item())
+
+    def _fallback_frames(self, n_frames=None) -> int:
+        """Waits for the last call on frames and offsets (not the payload form) -> the frames whose layout was not direct
+        (sela_hip_debug_<call>_fallback_frames, a test hook)."""
+        return int(getattr(self.lib, f"sela_hip_debug_{self._call}_fallback_frames")(
+            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
+
+    def check(self) -> None:
+        """Waits for the last call and raises SelaHipError with the code the host call of the class's judge (sela_hip_decode for
+        decode_n_status_error, sela_hip_decode_i32 for decode_status_error) gives for the same stream."""
+        st = self.status.cpu().numpy().copy()
+        if self._own_count:
+            st[2] = 0
+        capi.check(type(self)._judge(st))
+
+
+class Decoder32(_DeviceCall):
+    """sela_hip_decode_i32 on the device: streams of any samplesPerChannel (0 .. 65535), 32-bit samples, channels of
+    different lengths -- what frame::FrameDecoder returns, nothing narrowed.  Owns its outputs and its workspace on the current
+    device (or `device`); every call is asynchronous on the current stream and overwrites them."""
+
+    _call, _judge, _own_count = "decode_i32", staticmethod(decode_status_error), False
+
+    def _allocate(self, torch) -> None:
+        self.samples = torch.empty((self.max_frames, self.channels, self.stride), dtype=torch.int32, device=self.device)
+        self.counts = torch.zeros((self.max_frames, self.channels), dtype=torch.int32, device=self.device)
 
     def decode(self, frames, offsets, n_frames: int):
         """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1]
         -> (samples int32 [n, channels, stride], counts int32 [n, channels], sample_offsets int64 [n + 1]), views of the
         decoder's own buffers (counts and offsets hold the library's uint32 / uint64 bit patterns)."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_decode_i32_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.samples.data_ptr(), self.counts.data_ptr(),
             self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
@@ -191,15 +272,8 @@ class Decoder32:
         counts [max_frames, channels], sample_offsets [max_frames + 1], frame_offsets int64 [max_frames + 1], count int32 [1]):
         entries up to count[0] (samples and counts: below it) are the stream's, the rest are not written.  The workspace grows
         to the largest payload seen (make one call before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_decode_i32_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_decode_payload_i32_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.samples.data_ptr(), self.counts.data_ptr(),
             self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
@@ -207,48 +281,26 @@ class Decoder32:
         return (self.samples[:max_frames], self.counts[:max_frames], self.sample_offsets[: max_frames + 1],
                 self.frame_offsets[: max_frames + 1], self.count)
 
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same input."""
-        capi.check(decode_status_error(self.status.cpu().numpy()))
 
-
-def decode_status_error(status) -> int:
-    """sela_hip_decode_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
-    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-    assert st.shape == (4,)
-    return int(capi.lib().sela_hip_decode_status_error(st.ctypes.data))
-
-
-class DecoderN:
+class DecoderN(_DeviceCall):
     """sela_hip_decode on the device: int16 interleaved PCM of streams of any samplesPerChannel (0 .. 65535), samples wider
     than 16 bits narrowed as the host call narrows them, the route (2048-sample decoder or any-length kernels) chosen on the
     device.  Owns its outputs and its workspace on the current device (or `device`); every call is asynchronous on the current
     stream and overwrites them."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
-        import torch
+    _call, _judge, _own_count = "decode_n", staticmethod(decode_n_status_error), False
 
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride = max_frames, channels, stride
-        with torch.cuda.device(self.device):
-            self.pcm = torch.empty((max_frames * stride, channels), dtype=torch.int16, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_decode_n_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    def _allocate(self, torch) -> None:
+        self.pcm = torch.empty((self.max_frames * self.stride, self.channels), dtype=torch.int16, device=self.device)
+
+    route = _DeviceCall._route
 
     def decode(self, frames, offsets, n_frames: int):
         """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1]
         -> (pcm int16 [max_frames * stride, channels], sample_offsets int64 [n + 1]), views of the decoder's own buffers: frame f
         at pcm[sample_offsets[f]], sample_offsets[n] samples in all (the library's uint64 bit patterns)."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_decode_n_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.pcm.data_ptr(), self.sample_offsets.data_ptr(),
             self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
@@ -260,59 +312,25 @@ class DecoderN:
         sample_offsets [max_frames + 1], frame_offsets int64 [max_frames + 1], count int32 [1]): offsets up to count[0] are the
         stream's, pcm up to sample_offsets[count[0]].  The workspace grows to the largest payload seen (make one call before
         capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_decode_n_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_decode_payload_n_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.pcm.data_ptr(), self.sample_offsets.data_ptr(),
             self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
             self.payload_workspace.numel(), stream))
         return self.pcm[: max_frames * self.stride], self.sample_offsets[: max_frames + 1], self.frame_offsets[: max_frames + 1], self.count
 
-    def route(self) -> int:
-        """Waits for the last call -> the route it took: 0 nothing decoded, 1 the 2048-sample decoder, 2 the any-length kernels."""
-        return int(self.status[3].item())
 
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same input."""
-        capi.check(decode_n_status_error(self.status.cpu().numpy()))
-
-
-def decode_n_status_error(status) -> int:
-    """sela_hip_decode_n_status_error on a host copy of four status words (any integer array of 4) -> the host call's code."""
-    st = np.ascontiguousarray(np.asarray(status).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-    assert st.shape == (4,)
-    return int(capi.lib().sela_hip_decode_n_status_error(st.ctypes.data))
-
-
-class Verifier:
+class Verifier(_DeviceCall):
     """sela_hip_verify_device: a stream held against the PCM it was made from, frame by frame, on the device -- which frames the
     decoder returns differently (the reference's rounding ties), how many values, and the first of them.  Owns its
     outputs and its workspace on the current device (or `device`); every call is asynchronous on the current stream and
     overwrites them.  No PCM is written: on the 2048-sample route of up to eight channels not even into the workspace."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
-        import torch
-
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride = max_frames, channels, stride
-        with torch.cuda.device(self.device):
-            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_verify_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    _call, _judge = "verify", staticmethod(decode_n_status_error)
+    _allocate = _DeviceCall._allocate_diffs
+    lossy_frames = _DeviceCall._lossy_frames
+    route = _DeviceCall._route
 
     def _pcm_ok(self, pcm) -> bool:
         return pcm.dtype == self.torch.int16 and pcm.is_cuda and pcm.is_contiguous()
@@ -321,11 +339,9 @@ class Verifier:
         """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1], pcm: int16 cuda tensor in the
         layout DecoderN.decode returns (frame f at sample_offsets[f]; [n_frames, 2048, channels] for a 2048 stream)
         -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]; -1: nothing differs), views of the verifier's own buffers."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        self._frames_ok(frames, offsets, n_frames)
         assert self._pcm_ok(pcm)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, pcm.data_ptr(), self.diff_counts.data_ptr(),
             self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
@@ -337,35 +353,14 @@ class Verifier:
         leaves the device, so the call can be captured into a graph.  -> (diff_counts [max_frames], first_diff [max_frames],
         count int32 [1]): entries up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call
         before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        max_frames = self._payload_ok(payload, max_frames)
         assert self._pcm_ok(pcm)
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_verify_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_payload_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, pcm.data_ptr(), self.diff_counts.data_ptr(),
             self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
             self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
         return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
-
-    def lossy_frames(self) -> int:
-        """Waits for the last call -> the number of frames with a difference (status[2])."""
-        return int(self.status[2].item())
-
-    def route(self) -> int:
-        """Waits for the last call -> the route it took: 0 nothing verified, 1 the 2048-sample decoder, 2 the any-length kernels."""
-        return int(self.status[3].item())
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same stream."""
-        st = self.status.cpu().numpy().copy()
-        st[2] = 0
-        capi.check(decode_n_status_error(st))
 
 
 # sela_hip_level (include/sela_hip.h): 24 bytes per (frame, channel)
@@ -373,36 +368,26 @@ LEVEL_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u4"), ("sum", "<i8"), ("s
 TRACK_LEVEL_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u8"), ("sum", "<i8"), ("sum_squares", "<u8")])
 
 
-class Leveler:
+class Leveler(_DeviceCall):
     """sela_hip_levels_device: how loud a stream is, frame by frame and channel by channel, on the device -- the peak |v|, the sum
     and the sum of squares of the int16 samples DecoderN.decode would write.  All integers, so exact.  Owns its
     records and its workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites
     them.  No PCM is written: on the 2048-sample route of up to eight channels not even into the workspace."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
-        import torch
+    _call, _judge = "levels", staticmethod(decode_n_status_error)
 
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride = max_frames, channels, stride
-        with torch.cuda.device(self.device):
-            # the records as int64 [max_frames, channels, 3]: word 0 peak | samples << 32, word 1 sum, word 2 sum_squares
-            self.levels = torch.zeros((max_frames, channels, 3), dtype=torch.int64, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_levels_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames, channels, 3]: word 0 peak | samples << 32, word 1 sum, word 2 sum_squares
+        self.levels = torch.zeros((self.max_frames, self.channels, 3), dtype=torch.int64, device=self.device)
+
+    loud_frames = _DeviceCall._loud_frames
+    route = _DeviceCall._route
 
     def measure(self, frames, offsets, n_frames: int):
         """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
         n_frames frames, int64 cuda tensor [n_frames, channels, 3], a view of the leveler's own buffer (records(): as LEVEL_DTYPE)."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_levels_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
             self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
@@ -412,15 +397,8 @@ class Leveler:
         """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
         leaves the device, so the call can be captured into a graph.  -> (records [max_frames, channels, 3], count int32 [1]):
         records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_levels_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_levels_payload_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
             self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
@@ -432,20 +410,6 @@ class Leveler:
         """Waits for the last call -> a host copy of records as LEVEL_DTYPE [n_frames, channels]."""
         host = np.ascontiguousarray(levels.cpu().numpy())
         return host.view(LEVEL_DTYPE).reshape(host.shape[:-1])
-
-    def loud_frames(self) -> int:
-        """Waits for the last call -> the number of frames in which some channel is not digital silence (status[2])."""
-        return int(self.status[2].item())
-
-    def route(self) -> int:
-        """Waits for the last call -> the route it took: 0 nothing measured, 1 the 2048-sample decoder, 2 the any-length kernels."""
-        return int(self.status[3].item())
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode gives for the same stream."""
-        st = self.status.cpu().numpy().copy()
-        st[2] = 0
-        capi.check(decode_n_status_error(st))
 
 
 def levels_host(frames: np.ndarray, offsets: np.ndarray, channels: int) -> np.ndarray:
@@ -476,37 +440,27 @@ def track_levels(levels: np.ndarray) -> np.ndarray:
 LEVEL32_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u4"), ("sum", "<i8"), ("sum_squares_lo", "<u8"), ("sum_squares_hi", "<u8")])
 
 
-class Leveler32:
+class Leveler32(_DeviceCall):
     """sela_hip_levels_i32_device: Leveler on the whole domain of sela_hip_decode_i32_device -- samples of up to 32 bits, channels
     of different lengths, every subframe layout.  Record [f][c] is taken over the samples that call writes for
     channel c of frame f, with a 128-bit sum of squares.  Owns its records and its workspace on the current device (or `device`);
     every call is asynchronous on the current stream and overwrites them.  No decoded sample is stored for the layouts this
     project's encoders write."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
-        import torch
+    _call, _judge = "levels_i32", staticmethod(decode_status_error)
 
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride = max_frames, channels, stride
-        with torch.cuda.device(self.device):
-            # the records as int64 [max_frames, channels, 4]: word 0 peak | samples << 32, word 1 sum, words 2 and 3 the energy
-            self.levels = torch.zeros((max_frames, channels, 4), dtype=torch.int64, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_levels_i32_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames, channels, 4]: word 0 peak | samples << 32, word 1 sum, words 2 and 3 the energy
+        self.levels = torch.zeros((self.max_frames, self.channels, 4), dtype=torch.int64, device=self.device)
+
+    loud_frames = _DeviceCall._loud_frames
+    fallback_frames = _DeviceCall._fallback_frames
 
     def measure(self, frames, offsets, n_frames: int):
         """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
         n_frames frames, int64 cuda tensor [n_frames, channels, 4], a view of the leveler's own buffer (records(): as LEVEL32_DTYPE)."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_levels_i32_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
             self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
@@ -516,15 +470,8 @@ class Leveler32:
         """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
         leaves the device, so the call can be captured into a graph.  -> (records [max_frames, channels, 4], count int32 [1]):
         records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_levels_i32_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
         capi.check(self.lib.sela_hip_levels_payload_i32_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.levels.data_ptr(), self.sample_offsets.data_ptr(),
             self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
@@ -536,21 +483,6 @@ class Leveler32:
         """Waits for the last call -> a host copy of records as LEVEL32_DTYPE [n_frames, channels]."""
         host = np.ascontiguousarray(levels.cpu().numpy())
         return host.view(LEVEL32_DTYPE).reshape(host.shape[:-1])
-
-    def loud_frames(self) -> int:
-        """Waits for the last call -> the number of frames in which some channel is not digital silence (status[2])."""
-        return int(self.status[2].item())
-
-    def fallback_frames(self, n_frames=None) -> int:
-        """Waits for the last measure() -> the frames whose layout was not direct (sela_hip_debug_levels_i32_fallback_frames)."""
-        return int(self.lib.sela_hip_debug_levels_i32_fallback_frames(
-            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
-        st = self.status.cpu().numpy().copy()
-        st[2] = 0
-        capi.check(decode_status_error(st))
 
 
 def levels_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int) -> np.ndarray:
@@ -801,28 +733,16 @@ def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.
     return counts, first, int(lossy.value)
 
 
-class Verifier32:
+class Verifier32(_DeviceCall):
     """sela_hip_verify_i32_device: a stream held against the int32 samples it was made from, frame by frame, on the device --
     the whole domain of Decoder32 (samples of up to 32 bits, planar frames, channels of different lengths).  Owns its outputs and
     its workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  For
     the layouts the encoders write no decoded sample is stored anywhere beyond the subframes as decoded."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, device=None):
-        import torch
-
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride = max_frames, channels, stride
-        with torch.cuda.device(self.device):
-            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_verify_i32_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    _call, _judge = "verify_i32", staticmethod(decode_status_error)
+    _allocate = _DeviceCall._allocate_diffs
+    lossy_frames = _DeviceCall._lossy_frames
+    fallback_frames = _DeviceCall._fallback_frames
 
     def _inputs_ok(self, samples, lengths, n_frames: int) -> bool:
         torch = self.torch
@@ -836,11 +756,9 @@ class Verifier32:
         [n_frames, channels, stride] (the layout Decoder32.decode returns), lengths: int32 cuda tensor [n_frames, channels] (the
         original's length of every channel) or None: every channel is stride long
         -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]; -1: nothing differs), views of the verifier's own buffers."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        self._frames_ok(frames, offsets, n_frames)
         assert self._inputs_ok(samples, lengths, n_frames)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_i32_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, samples.data_ptr(),
             None if lengths is None else lengths.data_ptr(), self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(),
@@ -852,37 +770,15 @@ class Verifier32:
         leaves the device, so the call can be captured into a graph.  -> (diff_counts [max_frames], first_diff [max_frames],
         count int32 [1]): entries up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call
         before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        max_frames = self._payload_ok(payload, max_frames)
         assert self._inputs_ok(samples, lengths, max_frames)
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_verify_i32_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_payload_i32_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, samples.data_ptr(),
             None if lengths is None else lengths.data_ptr(), self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(),
             self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(), self.payload_workspace.data_ptr(),
             self.payload_workspace.numel(), stream))
         return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
-
-    def lossy_frames(self) -> int:
-        """Waits for the last call -> the number of frames with a difference (status[2])."""
-        return int(self.status[2].item())
-
-    def fallback_frames(self, n_frames=None) -> int:
-        """Waits for the last verify() call (not verify_payload) -> the frames whose layout was not direct (test hook)."""
-        return int(self.lib.sela_hip_debug_verify_i32_fallback_frames(
-            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
-        st = self.status.cpu().numpy().copy()
-        st[2] = 0
-        capi.check(decode_status_error(st))
 
 
 def verify_i32(frames: np.ndarray, offsets: np.ndarray, channels: int, samples: np.ndarray, lengths=None):
@@ -906,28 +802,20 @@ def verify_i32(frames: np.ndarray, offsets: np.ndarray, channels: int, samples: 
     return counts, first, int(lossy.value)
 
 
-class VerifierPcm:
+class VerifierPcm(_DeviceCall):
     """sela_hip_verify_pcm_device: a stream held against the packed interleaved PCM it was made from -- 3 or 4
     bytes a sample, little-endian, frame f at sample_offsets[f] (the layout DecoderPcm writes and a WAV's data chunk has), frames
     of any lengths -- frame by frame, on the device, without an unpacked copy of the original.  Owns its outputs and its
     workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites them."""
 
-    def __init__(self, max_frames: int, channels: int, stride: int, bytes_per_sample: int, device=None):
-        import torch
+    _call, _judge = "verify_pcm", staticmethod(decode_status_error)
+    _allocate = _DeviceCall._allocate_diffs
+    lossy_frames = _DeviceCall._lossy_frames
+    fallback_frames = _DeviceCall._fallback_frames
 
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_frames, self.channels, self.stride, self.bytes_per_sample = max_frames, channels, stride, bytes_per_sample
-        with torch.cuda.device(self.device):
-            self.diff_counts = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.first_diff = torch.zeros(max_frames, dtype=torch.int32, device=self.device)
-            self.sample_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.frame_offsets = torch.zeros(max_frames + 1, dtype=torch.int64, device=self.device)
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(self.lib.sela_hip_verify_pcm_workspace_bytes(max_frames, channels, stride))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+    def __init__(self, max_frames: int, channels: int, stride: int, bytes_per_sample: int, device=None):
+        self.bytes_per_sample = bytes_per_sample
+        super().__init__(max_frames, channels, stride, device)
 
     def _samples(self, pcm, pcm_samples) -> int:
         torch = self.torch
@@ -943,11 +831,9 @@ class VerifierPcm:
         aligned) of pcm_samples samples per channel (None: all it holds)
         -> (diff_counts int32 [n_frames], first_diff int32 [n_frames]: sample * channels + channel in the frame; -1: nothing
         differs), views of the verifier's own buffers."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and n_frames <= self.max_frames
+        self._frames_ok(frames, offsets, n_frames)
         pcm_samples = self._samples(pcm, pcm_samples)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_pcm_device(
             frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, pcm.data_ptr(), self.bytes_per_sample, pcm_samples,
             self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(),
@@ -958,36 +844,14 @@ class VerifierPcm:
         """Index and verify a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
         leaves the device.  -> (diff_counts [max_frames], first_diff [max_frames], count int32 [1]): entries up to count[0] are the
         stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
-        torch = self.torch
-        max_frames = self.max_frames if max_frames is None else max_frames
-        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and max_frames <= self.max_frames
+        max_frames = self._payload_ok(payload, max_frames)
         pcm_samples = self._samples(pcm, pcm_samples)
-        need = int(self.lib.sela_hip_index_workspace_bytes(payload.numel(), max_frames)) + int(
-            self.lib.sela_hip_verify_pcm_workspace_bytes(max_frames, self.channels, self.stride))
-        with torch.cuda.device(self.device):
-            if getattr(self, "payload_workspace", None) is None or self.payload_workspace.numel() < need:
-                self.payload_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         capi.check(self.lib.sela_hip_verify_payload_pcm_device(
             payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, pcm.data_ptr(), self.bytes_per_sample, pcm_samples,
             self.diff_counts.data_ptr(), self.first_diff.data_ptr(), self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(),
             self.status.data_ptr(), self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
         return self.diff_counts[:max_frames], self.first_diff[:max_frames], self.count
-
-    def lossy_frames(self) -> int:
-        """Waits for the last call -> the number of frames with a difference (status[2])."""
-        return int(self.status[2].item())
-
-    def fallback_frames(self, n_frames=None) -> int:
-        """Waits for the last verify() call (not verify_payload) -> the frames whose layout was not direct (test hook)."""
-        return int(self.lib.sela_hip_debug_verify_pcm_fallback_frames(
-            self.workspace.data_ptr(), self.max_frames if n_frames is None else n_frames, self.channels, self.stride))
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_i32 gives for the same stream."""
-        st = self.status.cpu().numpy().copy()
-        st[2] = 0
-        capi.check(decode_status_error(st))
 
 
 def verify_pcm_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bytes_per_sample: int, pcm, pcm_samples=None):

@@ -2190,16 +2190,22 @@ int sela_hip_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
     return sela::generic_levels_i32(frames, frame_offsets, n_frames, channels, largest, levels);
 }
 
-// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
-long long sela_hip_debug_levels_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+// Test hooks (include/sela_hip_debug.h), one per call of the int32 family: the frames the last call on this workspace left to the
+// fallback, the first of the call's control words.  Waits for the device.
+static long long fallback_frames(size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), const uint32_t* (*control_words)(const void*, uint32_t, uint32_t, uint32_t),
+    const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
-    if (!d_workspace || sela::levels_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+    if (!d_workspace || workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
         return -1;
     uint32_t left = 0;
-    if (hipDeviceSynchronize() != hipSuccess
-        || hipMemcpy(&left, sela::levels_i32_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&left, control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
     return (long long)left;
+}
+
+long long sela_hip_debug_levels_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return fallback_frames(sela::levels_i32_workspace_bytes, sela::levels_i32_control_words, d_workspace, max_frames, channels, stride);
 }
 
 size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)
@@ -2372,16 +2378,9 @@ int sela_hip_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
     return sela::generic_verify_i32(frames, frame_offsets, n_frames, channels, stride, samples, lengths, diff_counts, first_diff, lossy_frames);
 }
 
-// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
 long long sela_hip_debug_verify_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
-    if (!d_workspace || sela::verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
-        return -1;
-    uint32_t left = 0;
-    if (hipDeviceSynchronize() != hipSuccess
-        || hipMemcpy(&left, sela::verify_i32_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
-    return (long long)left;
+    return fallback_frames(sela::verify_i32_workspace_bytes, sela::verify_i32_control_words, d_workspace, max_frames, channels, stride);
 }
 
 // ---- verification against packed PCM -----------------------------------------------------------------------
@@ -2428,16 +2427,9 @@ int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, ui
         lossy_frames);
 }
 
-// Test hook (include/sela_hip_debug.h): the frames the last call on this workspace left to the fallback.  Waits for the device.
 long long sela_hip_debug_verify_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
-    if (!d_workspace || sela::verify_pcm_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
-        return -1;
-    uint32_t left = 0;
-    if (hipDeviceSynchronize() != hipSuccess
-        || hipMemcpy(&left, sela::verify_pcm_control_words(d_workspace, max_frames, channels, stride), sizeof(left), hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
-    return (long long)left;
+    return fallback_frames(sela::verify_pcm_workspace_bytes, sela::verify_pcm_control_words, d_workspace, max_frames, channels, stride);
 }
 
 // Test hook (include/sela_hip_debug.h): the pieces of a call's workspace, from the description its launch runs.  No device.

@@ -470,21 +470,98 @@ int generic_decode(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
     return SELA_HIP_OK;
 }
 
-// sela_hip_verify and sela_hip_verify_i32: the *_device launch on chunks of frames, on the calling thread's
-// context and stream.  Per chunk the frames, their offsets and the reference data go in; status (4 x u32) | diff_counts [cf] |
-// first_diff [cf] come back in one piece behind the chunk's ONE wait; the first chunk whose status words fail ends the call with
-// that code.  What the two calls differ in is their `Ref`: the reference data (its bytes, its pieces of the arena, its upload),
-// the launch and the judge.
+// The host-pointer calls that decode a stream and keep something other than the samples -- sela_hip_verify, _verify_i32,
+// _verify_pcm, _levels, _levels_i32 -- and sela_hip_decode_pcm: their *_device launch
+// on chunks of whole frames, on the calling thread's context and stream (frame_chunks).  Per chunk the frames and their offsets
+// (relative to a 4-byte aligned base) go in, with what the call uploads beside them; what it reads back lands behind the chunk's ONE
+// wait; the first chunk whose status words fail ends the call with that code.  What a call brings is its `Op`:
+//   per_frame                       the scratch a frame costs, roughly: it picks the chunk size (kChunkBudget), nothing else
+//   workspace_bytes(cf)             its launch's workspace for cf frames
+//   pieces(c, f0, cf)               its pieces of the arena, between the frame offsets and the workspace.  Run on a measuring
+//                                   Carve to size the arena and on the arena's to take them, so the two cannot disagree
+//   submit(.., f0, cf, d_ws, ..)    its upload, its launch and its copies back, all on the stream
+//   finish(f0, cf)                  behind the wait: the status words judged, the results handed on
 namespace {
-struct VerifyPcm { // int16, interleaved, where sela_hip_decode writes it (sample_offsets); judged as sela_hip_decode_n_status_error judges
+std::atomic<uint32_t> g_pcm_chunk_frames{0}; // sela_hip_debug_pcm_chunk_frames: this many frames a chunk (0: the budget decides)
+uint32_t pcm_chunk(uint32_t n_frames, size_t per_frame)
+{
+    const uint32_t forced = g_pcm_chunk_frames.load(std::memory_order_relaxed);
+    const size_t chunk = forced ? forced : kChunkBudget / per_frame;
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, chunk));
+}
+
+template <typename T>
+T* piece(Carve& c, uint64_t count) { return c.take<T>(std::max<uint64_t>(count, 1)); }
+
+template <typename Op>
+int frame_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, Op& op)
+{
+    Arena& arena = call.arena();
+    const std::string name(who);
+    const uint32_t chunk = pcm_chunk(n_frames, op.per_frame);
+    const hipStream_t st = call.stream();
+    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+    std::vector<uint64_t> local;
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cf = std::min(chunk, n_frames - f0);
+        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes;
+        const size_t ws_bytes = op.workspace_bytes(cf);
+        if (ws_bytes == SIZE_MAX)
+            return report_error(SELA_HIP_EINVAL, name + ": the chunk is too large");
+        uint8_t *d_frames = nullptr, *d_ws = nullptr;
+        uint64_t* d_offsets = nullptr;
+        const auto pieces = [&](Carve& c) {
+            d_frames = piece<uint8_t>(c, in_bytes + 8);
+            d_offsets = piece<uint64_t>(c, (uint64_t)cf + 1);
+            op.pieces(c, f0, cf);
+            d_ws = piece<uint8_t>(c, ws_bytes);
+        };
+        hipError_t e = arena.reserve(measured(nullptr, pieces));
+        if (e != hipSuccess)
+            return report_hip_error(e, (name + ": scratch").c_str());
+        pieces(arena.carve);
+        local.resize((size_t)cf + 1);
+        for (uint32_t i = 0; i <= cf; i++)
+            local[i] = frame_offsets[f0 + i] - base_bytes;
+        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = op.submit(d_frames, d_offsets, f0, cf, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return report_hip_error(e, who);
+        const int rc = op.finish(f0, cf);
+        if (rc != SELA_HIP_OK)
+            return rc;
+    }
+    return SELA_HIP_OK;
+}
+
+// The two judges of a chunk's status words: as sela_hip_decode_n_status_error judges (the int16 calls), as
+// sela_hip_decode_status_error judges (the int32 ones).  status[2] is the call's own count there, not the largest frame.
+int judge_n(const uint32_t* status)
+{
+    const uint32_t route_status[4] = { status[0], status[1], 0, status[3] };
+    return sela_hip_decode_n_status_error(route_status);
+}
+int judge_i32(const uint32_t* status)
+{
+    const uint32_t decode_status[4] = { status[0], status[1], 0, 0 };
+    return sela_hip_decode_status_error(decode_status);
+}
+
+// The three verify calls: a `Ref` -- the reference data (its pieces of the arena, its upload), the launch and the judge -- and
+// behind it status (4 x u32) | diff_counts [cf] | first_diff [cf], read back in one piece.
+struct VerifyPcm { // int16, interleaved, where sela_hip_decode writes it (sample_offsets)
     const int16_t* pcm;
     const uint64_t* sample_offsets;
     uint32_t channels, stride;
     int recurrence_form;
     int16_t* d_pcm;
     uint64_t values(uint32_t f0, uint32_t cf) const { return (sample_offsets[f0 + cf] - sample_offsets[f0]) * channels; }
-    size_t bytes(uint32_t f0, uint32_t cf) const { return (size_t)values(f0, cf) * 2; }
-    void take(Arena& arena, uint32_t f0, uint32_t cf) { d_pcm = arena.take<int16_t>((size_t)values(f0, cf)); }
+    void take(Carve& c, uint32_t f0, uint32_t cf) { d_pcm = piece<int16_t>(c, values(f0, cf)); }
     hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
     {
         const uint64_t n = values(f0, cf);
@@ -495,23 +572,18 @@ struct VerifyPcm { // int16, interleaved, where sela_hip_decode writes it (sampl
         return launch_verify_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode, recurrence_form,
             0, st);
     }
-    int judge(const uint32_t* tail) const
-    {
-        const uint32_t route_status[4] = { tail[0], tail[1], 0, tail[3] };
-        return sela_hip_decode_n_status_error(route_status);
-    }
+    static constexpr auto judge = judge_n;
 };
-struct VerifySamples { // int32 [frame][channel][stride], lengths or null; judged as sela_hip_decode_status_error judges
+struct VerifySamples { // int32 [frame][channel][stride], lengths or null
     const int32_t* samples;
     const uint32_t* lengths;
     uint32_t channels, stride;
     int32_t* d_samples;
     uint32_t* d_lengths;
-    size_t bytes(uint32_t, uint32_t cf) const { return (size_t)cf * channels * stride * 4 + (size_t)cf * channels * 4; }
-    void take(Arena& arena, uint32_t, uint32_t cf)
+    void take(Carve& c, uint32_t, uint32_t cf)
     {
-        d_samples = arena.take<int32_t>((size_t)cf * channels * stride);
-        d_lengths = lengths ? arena.take<uint32_t>((size_t)cf * channels) : nullptr;
+        d_samples = piece<int32_t>(c, (uint64_t)cf * channels * stride);
+        d_lengths = lengths ? piece<uint32_t>(c, (uint64_t)cf * channels) : nullptr;
     }
     hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
     {
@@ -525,13 +597,9 @@ struct VerifySamples { // int32 [frame][channel][stride], lengths or null; judge
     {
         return launch_verify_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_samples, d_lengths, d_tail + 4, d_tail + 4 + cf, nullptr, d_tail, d_ws, mode, st);
     }
-    int judge(const uint32_t* tail) const
-    {
-        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
-        return sela_hip_decode_status_error(decode_status);
-    }
+    static constexpr auto judge = judge_i32;
 };
-struct VerifyPacked { // packed interleaved PCM of 3 or 4 bytes a sample, where sela_hip_decode_pcm writes it (sample_offsets); judged as VerifySamples
+struct VerifyPacked { // packed interleaved PCM of 3 or 4 bytes a sample, where sela_hip_decode_pcm writes it (sample_offsets)
     const uint8_t* pcm;
     uint64_t pcm_samples;
     const uint64_t* sample_offsets;
@@ -540,11 +608,11 @@ struct VerifyPacked { // packed interleaved PCM of 3 or 4 bytes a sample, where 
     uint32_t chunk_f0; // the first frame of the chunk d_pcm holds
     uint64_t held(uint32_t f0) const { return pcm_samples - std::min(sample_offsets[f0], pcm_samples); } // samples the original holds from the chunk's first frame on
     uint64_t samples(uint32_t f0, uint32_t cf) const { return std::min(sample_offsets[f0 + cf] - sample_offsets[f0], held(f0)); }
-    size_t bytes(uint32_t f0, uint32_t cf) const { return (size_t)samples(f0, cf) * channels * bytes_per_sample + 4; }
-    void take(Arena& arena, uint32_t f0, uint32_t cf) { d_pcm = arena.take<uint8_t>(bytes(f0, cf)), chunk_f0 = f0; }
+    size_t bytes(uint32_t f0, uint32_t cf) const { return (size_t)samples(f0, cf) * channels * bytes_per_sample; }
+    void take(Carve& c, uint32_t f0, uint32_t cf) { d_pcm = piece<uint8_t>(c, bytes(f0, cf) + 4), chunk_f0 = f0; }
     hipError_t upload(uint32_t f0, uint32_t cf, hipStream_t st) const
     {
-        const size_t n = (size_t)samples(f0, cf) * channels * bytes_per_sample;
+        const size_t n = bytes(f0, cf);
         return n ? hipMemcpyAsync(d_pcm, pcm + sample_offsets[f0] * channels * bytes_per_sample, n, hipMemcpyHostToDevice, st) : hipSuccess;
     }
     hipError_t launch(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, uint32_t* d_tail, void* d_ws, int mode, hipStream_t st) const
@@ -552,68 +620,93 @@ struct VerifyPacked { // packed interleaved PCM of 3 or 4 bytes a sample, where 
         return launch_verify_pcm_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_pcm, bytes_per_sample, held(chunk_f0), d_tail + 4, d_tail + 4 + cf, nullptr,
             d_tail, d_ws, mode, st);
     }
-    int judge(const uint32_t* tail) const
-    {
-        const uint32_t decode_status[4] = { tail[0], tail[1], 0, 0 };
-        return sela_hip_decode_status_error(decode_status);
-    }
+    static constexpr auto judge = judge_i32;
 };
 
 template <typename Ref>
-int verify_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
-    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), Ref ref, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames,
-    uint32_t forced_chunk = 0 /* tests: this many frames a chunk */)
-{
-    Arena& g_arena = call.arena();
-    const std::string name(who);
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, forced_chunk ? forced_chunk : kChunkBudget / per_frame));
-    const hipStream_t st = call.stream();
-    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
+struct VerifyOp {
+    size_t per_frame;
+    size_t (*workspace)(uint32_t, uint32_t, uint32_t);
+    Ref ref;
+    uint32_t *diff_counts, *first_diff;
     uint32_t lossy = 0;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
-        const size_t ws_bytes = workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, name + ": the chunk is too large");
-        const size_t need = in_bytes + 8 + ((size_t)cf + 1) * 8 + ref.bytes(f0, cf) + (size_t)cf * 8 + 16 + ws_bytes + 12 * kPiece;
-        hipError_t e = g_arena.reserve(need);
-        if (e != hipSuccess)
-            return report_hip_error(e, (name + ": scratch").c_str());
-        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
-        ref.take(g_arena, f0, cf);
-        uint32_t* d_tail = g_arena.take<uint32_t>(4 + 2 * (size_t)cf);
-        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
-        if (!g_arena.fits())
-            return report_error(SELA_HIP_ENOMEM, name + ": internal scratch estimate too small");
-        std::vector<uint64_t> local((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        std::vector<uint32_t> tail(4 + 2 * (size_t)cf);
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = ref.upload(f0, cf, st);
+    uint32_t* d_tail = nullptr;
+    std::vector<uint32_t> tail;
+    size_t workspace_bytes(uint32_t cf) const { return workspace(cf, ref.channels, ref.stride); }
+    void pieces(Carve& c, uint32_t f0, uint32_t cf)
+    {
+        ref.take(c, f0, cf);
+        d_tail = piece<uint32_t>(c, 4 + 2 * (uint64_t)cf);
+    }
+    hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
+    {
+        tail.resize(4 + 2 * (size_t)cf);
+        hipError_t e = ref.upload(f0, cf, st);
         if (e == hipSuccess)
             e = ref.launch(d_frames, d_offsets, cf, d_tail, d_ws, mode, st);
         if (e == hipSuccess)
             e = hipMemcpyAsync(tail.data(), d_tail, tail.size() * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, who);
-        const int rc = ref.judge(tail.data());
+        return e;
+    }
+    int finish(uint32_t f0, uint32_t cf)
+    {
+        const int rc = Ref::judge(tail.data());
         if (rc != SELA_HIP_OK)
             return rc;
         std::memcpy(diff_counts + f0, tail.data() + 4, (size_t)cf * 4);
         std::memcpy(first_diff + f0, tail.data() + 4 + cf, (size_t)cf * 4);
         lossy += tail[2];
+        return SELA_HIP_OK;
     }
-    if (lossy_frames)
-        *lossy_frames = lossy;
-    return SELA_HIP_OK;
+};
+
+template <typename Ref>
+int verify_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, size_t per_frame,
+    size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), Ref ref, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
+{
+    VerifyOp<Ref> op{ per_frame, workspace_bytes, ref, diff_counts, first_diff };
+    const int rc = frame_chunks(call, who, frames, frame_offsets, n_frames, op);
+    if (rc == SELA_HIP_OK && lossy_frames)
+        *lossy_frames = op.lossy;
+    return rc;
+}
+
+// The two levels calls: no reference; status (4 x u32) | the chunk's records, read back in two pieces, the records straight into
+// the caller's.  `Launch`: the call's *_device launch on (d_frames, d_offsets, cf, d_levels, d_status, d_ws, mode, stream).
+template <typename Record, typename Launch>
+struct LevelsOp {
+    size_t per_frame;
+    size_t (*workspace)(uint32_t, uint32_t, uint32_t);
+    int (*judge)(const uint32_t*);
+    uint32_t channels, stride;
+    Record* levels;
+    Launch launch;
+    uint32_t* d_status = nullptr;
+    Record* d_levels = nullptr;
+    uint32_t status[4] = { 0, 0, 0, 0 };
+    size_t workspace_bytes(uint32_t cf) const { return workspace(cf, channels, stride); }
+    void pieces(Carve& c, uint32_t, uint32_t cf)
+    {
+        d_status = piece<uint32_t>(c, 4);
+        d_levels = piece<Record>(c, (uint64_t)cf * channels);
+    }
+    hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
+    {
+        hipError_t e = launch(d_frames, d_offsets, cf, d_levels, d_status, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, (size_t)cf * channels * sizeof(Record), hipMemcpyDeviceToHost, st);
+        return e;
+    }
+    int finish(uint32_t, uint32_t) const { return judge(status); }
+};
+template <typename Record, typename Launch>
+int levels_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), int (*judge)(const uint32_t*), Record* levels, Launch launch)
+{
+    LevelsOp<Record, Launch> op{ per_frame, workspace_bytes, judge, channels, stride, levels, launch };
+    return frame_chunks(call, who, frames, frame_offsets, n_frames, op);
 }
 } // namespace
 
@@ -634,13 +727,11 @@ int generic_verify(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
         return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
     const uint32_t stride = std::max(largest, 1u);
     const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2 + 2) + (size_t)channels * sizeof(GenericSubInfo) + 64;
-    return verify_chunks(call, "verify", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_workspace_bytes,
+    return verify_chunks(call, "verify", frames, frame_offsets, n_frames, per_frame, verify_workspace_bytes,
         VerifyPcm{ pcm, sample_offsets.data(), channels, stride, recurrence_form, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
-// sela_hip_levels: generic_verify without a reference.  Per chunk the frames and their offsets go in; status
-// (4 x u32, padded to 8 bytes' alignment by the arena) and the chunk's records come back behind the chunk's ONE wait; the first
-// chunk whose status words fail ends the call with that code.
+// sela_hip_levels.  The stride is the stream's largest samplesPerChannel (the host's walk).
 int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels, int recurrence_form)
 {
     const Call call;
@@ -653,50 +744,10 @@ int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
         return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
     const uint32_t stride = std::max(largest, 1u);
     const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2) + (size_t)channels * (sizeof(GenericSubInfo) + sizeof(sela_hip_level)) + 64;
-    Arena& g_arena = call.arena();
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
-    const hipStream_t st = call.stream();
-    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
-        const size_t ws_bytes = levels_workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, "levels: the chunk is too large");
-        const size_t records = (size_t)cf * channels;
-        hipError_t e = g_arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + 16 + records * sizeof(sela_hip_level) + ws_bytes + 12 * kPiece);
-        if (e != hipSuccess)
-            return report_hip_error(e, "levels: scratch");
-        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
-        uint32_t* d_status = g_arena.take<uint32_t>(4);
-        sela_hip_level* d_levels = g_arena.take<sela_hip_level>(records);
-        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
-        if (!g_arena.fits())
-            return report_error(SELA_HIP_ENOMEM, "levels: internal scratch estimate too small");
-        std::vector<uint64_t> local((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        uint32_t status[4] = { 0, 0, 0, 0 };
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_levels_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, records * sizeof(sela_hip_level), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, "levels");
-        const uint32_t route_status[4] = { status[0], status[1], 0, status[3] };
-        const int rc = sela_hip_decode_n_status_error(route_status);
-        if (rc != SELA_HIP_OK)
-            return rc;
-    }
-    return SELA_HIP_OK;
+    return levels_chunks(call, "levels", frames, frame_offsets, n_frames, channels, stride, per_frame, levels_workspace_bytes, judge_n, levels,
+        [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, sela_hip_level* d_levels, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
+            return launch_levels_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
+        });
 }
 
 // The caller has walked the stream: the offsets never decrease, the largest samplesPerChannel fits the stride.
@@ -707,63 +758,21 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
     if (call.rc != SELA_HIP_OK)
         return call.rc;
     const size_t per_frame = (size_t)channels * stride * 12 + (size_t)channels * (sizeof(GenericSubInfo) + 8) + 64;
-    return verify_chunks(call, "verify_i32", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_i32_workspace_bytes,
+    return verify_chunks(call, "verify_i32", frames, frame_offsets, n_frames, per_frame, verify_i32_workspace_bytes,
         VerifySamples{ samples, lengths, channels, stride, nullptr, nullptr }, diff_counts, first_diff, lossy_frames);
 }
 
-// sela_hip_levels_i32: generic_verify_i32's chunks without a reference.  Per chunk the frames and their offsets go
-// in; status (4 x u32, padded to 8 bytes' alignment by the arena) and the chunk's records come back behind the chunk's ONE wait;
-// the first chunk whose status words fail ends the call with that code.  The caller has walked the stream, as for generic_verify_i32.
+// sela_hip_levels_i32.  The caller has walked the stream, as for generic_verify_i32.
 int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level32* levels)
 {
     const Call call;
     if (call.rc != SELA_HIP_OK)
         return call.rc;
     const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 8 + sizeof(sela_hip_level32) * (1 + verify32_slices(stride))) + 64;
-    Arena& g_arena = call.arena();
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, kChunkBudget / per_frame));
-    const hipStream_t st = call.stream();
-    const int mode = g_standard_first_mode.load(std::memory_order_relaxed);
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants offsets relative to a 4-byte aligned base)
-        const size_t ws_bytes = levels_i32_workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, "levels_i32: the chunk is too large");
-        const size_t records = (size_t)cf * channels;
-        hipError_t e = g_arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + 16 + records * sizeof(sela_hip_level32) + ws_bytes + 12 * kPiece);
-        if (e != hipSuccess)
-            return report_hip_error(e, "levels_i32: scratch");
-        uint8_t* d_frames = g_arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = g_arena.take<uint64_t>((size_t)cf + 1);
-        uint32_t* d_status = g_arena.take<uint32_t>(4);
-        sela_hip_level32* d_levels = g_arena.take<sela_hip_level32>(records);
-        uint8_t* d_ws = g_arena.take<uint8_t>(ws_bytes);
-        if (!g_arena.fits())
-            return report_error(SELA_HIP_ENOMEM, "levels_i32: internal scratch estimate too small");
-        std::vector<uint64_t> local((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        uint32_t status[4] = { 0, 0, 0, 0 };
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_levels_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, records * sizeof(sela_hip_level32), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, "levels_i32");
-        const uint32_t decode_status[4] = { status[0], status[1], 0, 0 };
-        const int rc = sela_hip_decode_status_error(decode_status);
-        if (rc != SELA_HIP_OK)
-            return rc;
-    }
-    return SELA_HIP_OK;
+    return levels_chunks(call, "levels_i32", frames, frame_offsets, n_frames, channels, stride, per_frame, levels_i32_workspace_bytes, judge_i32, levels,
+        [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, sela_hip_level32* d_levels, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
+            return launch_levels_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, st);
+        });
 }
 
 // sela_hip_decode_windows: the *_device launch on chunks of WINDOWS, on the calling thread's context and stream.
@@ -960,18 +969,9 @@ int generic_lpc_decode(const int32_t* order, const int32_t* q, const int32_t* re
 
 // sela_hip_encode_pcm / sela_hip_decode_pcm: the device calls' launches (sela_capi_pcm.hip) on chunks of whole
 // frames, on the calling thread's context and stream, past the coalescer.  What travels is the packed bytes: 3 per sample of a
-// 24-bit container, not 4.  The chunks are sized as generic_encode's and generic_decode's (kChunkBudget of scratch), or by
-// sela_hip_debug_pcm_chunk_frames.
-namespace {
-std::atomic<uint32_t> g_pcm_chunk_frames{0};
-uint32_t pcm_chunk(uint32_t n_frames, size_t per_frame)
-{
-    const uint32_t forced = g_pcm_chunk_frames.load(std::memory_order_relaxed);
-    const size_t chunk = forced ? forced : kChunkBudget / per_frame;
-    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, chunk));
-}
-} // namespace
-
+// 24-bit container, not 4.  The chunks are sized by pcm_chunk (kChunkBudget of scratch, or sela_hip_debug_pcm_chunk_frames); the
+// decode runs on frame_chunks (above).
+//
 // Per chunk ONE wait where the frames fit the estimate generic_encode sizes its own by (4.5 bytes a sample); a chunk that codes
 // to more is encoded again into room of the size its offsets ask for.
 int generic_encode_pcm(const uint8_t* pcm, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t channels, uint32_t n, bool lossless, uint8_t* frames_out,
@@ -1041,6 +1041,45 @@ int generic_encode_pcm(const uint8_t* pcm, uint32_t bytes_per_sample, uint32_t n
     return SELA_HIP_OK;
 }
 
+// sela_hip_decode_pcm on frame_chunks: nothing uploaded beside the frames; the chunk's packed PCM | status (4 x u32), read back in
+// two pieces, the PCM straight into the caller's at the chunk's sample offset.
+namespace {
+struct DecodePcmOp {
+    size_t per_frame;
+    const uint64_t* sample_offsets;
+    uint32_t channels, stride, bytes_per_sample;
+    uint8_t* pcm_out;
+    uint32_t* wide_samples;
+    uint8_t* d_out = nullptr;
+    uint32_t* d_status = nullptr;
+    uint32_t status[4] = {};
+    size_t value_bytes() const { return (size_t)channels * bytes_per_sample; }
+    size_t workspace_bytes(uint32_t cf) const { return decode_pcm_workspace_bytes(cf, channels, stride); }
+    void pieces(Carve& c, uint32_t, uint32_t cf)
+    {
+        d_out = piece<uint8_t>(c, (uint64_t)cf * stride * value_bytes());
+        d_status = piece<uint32_t>(c, 4);
+    }
+    hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
+    {
+        const size_t out_bytes = (size_t)(sample_offsets[f0 + cf] - sample_offsets[f0]) * value_bytes();
+        hipError_t e = launch_decode_pcm_device(d_frames, d_offsets, cf, channels, stride, bytes_per_sample, d_out, nullptr, d_status, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out_bytes)
+            e = hipMemcpyAsync(pcm_out + (size_t)sample_offsets[f0] * value_bytes(), d_out, out_bytes, hipMemcpyDeviceToHost, st);
+        return e;
+    }
+    int finish(uint32_t, uint32_t) const
+    {
+        const int rc = sela_hip_decode_pcm_status_error(status);
+        if (rc == SELA_HIP_OK && wide_samples)
+            *wide_samples += status[3];
+        return rc;
+    }
+};
+} // namespace
+
 // The caller has walked the stream: the offsets never decrease, stride is the largest samplesPerChannel, sample_offsets the walk's.
 int generic_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, const uint64_t* sample_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
     uint32_t bytes_per_sample, uint8_t* pcm_out, uint32_t* wide_samples)
@@ -1048,57 +1087,12 @@ int generic_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, con
     const Call call;
     if (call.rc != SELA_HIP_OK)
         return call.rc;
-    Arena& arena = call.arena();
-    const hipStream_t st = call.stream();
-    const size_t value_bytes = (size_t)channels * bytes_per_sample;
-    const size_t per_frame = decode_pcm_workspace_bytes(1, channels, stride) + (size_t)stride * value_bytes + 16;
-    const uint32_t chunk = pcm_chunk(n_frames, per_frame);
-    std::vector<uint64_t> local;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-        const uint32_t cf = std::min(chunk, n_frames - f0);
-        const uint64_t base_bytes = frame_offsets[f0] & ~(uint64_t)3, in_bytes = frame_offsets[f0 + cf] - base_bytes; // (the device wants a 4-byte aligned base)
-        const size_t ws_bytes = decode_pcm_workspace_bytes(cf, channels, stride);
-        if (ws_bytes == SIZE_MAX)
-            return report_error(SELA_HIP_EINVAL, "decode_pcm: the chunk is too large");
-        const size_t out_room = (size_t)cf * stride * value_bytes, out_bytes = (size_t)(sample_offsets[f0 + cf] - sample_offsets[f0]) * value_bytes;
-        hipError_t e = arena.reserve(in_bytes + 8 + ((size_t)cf + 1) * 8 + out_room + 16 + ws_bytes + 10 * kPiece);
-        if (e != hipSuccess)
-            return report_hip_error(e, "decode_pcm: scratch");
-        uint8_t* d_frames = arena.take<uint8_t>(in_bytes + 8);
-        uint64_t* d_offsets = arena.take<uint64_t>((size_t)cf + 1);
-        uint8_t* d_out = arena.take<uint8_t>(out_room);
-        uint32_t* d_status = arena.take<uint32_t>(4);
-        uint8_t* d_ws = arena.take<uint8_t>(ws_bytes);
-        if (!arena.fits())
-            return report_error(SELA_HIP_ENOMEM, "decode_pcm: internal scratch estimate too small");
-        local.resize((size_t)cf + 1);
-        for (uint32_t i = 0; i <= cf; i++)
-            local[i] = frame_offsets[f0 + i] - base_bytes;
-        uint32_t status[4] = {};
-        e = hipMemcpyAsync(d_frames, frames + base_bytes, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_offsets, local.data(), local.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_decode_pcm_device(d_frames, d_offsets, cf, channels, stride, bytes_per_sample, d_out, nullptr, d_status, d_ws,
-                g_standard_first_mode.load(std::memory_order_relaxed), st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && out_bytes)
-            e = hipMemcpyAsync(pcm_out + (size_t)sample_offsets[f0] * value_bytes, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return report_hip_error(e, "decode_pcm");
-        const int rc = sela_hip_decode_pcm_status_error(status);
-        if (rc != SELA_HIP_OK)
-            return rc;
-        if (wide_samples)
-            *wide_samples += status[3];
-    }
-    return SELA_HIP_OK;
+    const size_t per_frame = decode_pcm_workspace_bytes(1, channels, stride) + (size_t)stride * channels * bytes_per_sample + 16;
+    DecodePcmOp op{ per_frame, sample_offsets, channels, stride, bytes_per_sample, pcm_out, wide_samples };
+    return frame_chunks(call, "decode_pcm", frames, frame_offsets, n_frames, op);
 }
 
-// sela_hip_verify_pcm: verify_chunks on the packed original; the chunks as above, or by sela_hip_debug_pcm_chunk_frames.
+// sela_hip_verify_pcm: verify_chunks on the packed original.
 int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const uint8_t* pcm,
     uint64_t pcm_samples, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)
 {
@@ -1108,9 +1102,8 @@ int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uin
     std::vector<uint64_t> sample_offsets((size_t)n_frames + 1);
     const uint32_t stride = std::max(generic_index_samples(frames, frame_offsets, n_frames, channels, sample_offsets.data(), nullptr), 1u);
     const size_t per_frame = (size_t)channels * stride * (8 + bytes_per_sample) + (size_t)channels * (sizeof(GenericSubInfo) + 8) + (size_t)verify_pcm_tiles(stride, channels) * 8 + 64;
-    return verify_chunks(call, "verify_pcm", frames, frame_offsets, n_frames, channels, stride, per_frame, verify_pcm_workspace_bytes,
-        VerifyPacked{ pcm, pcm_samples, sample_offsets.data(), channels, stride, bytes_per_sample, nullptr, 0 }, diff_counts, first_diff, lossy_frames,
-        g_pcm_chunk_frames.load(std::memory_order_relaxed));
+    return verify_chunks(call, "verify_pcm", frames, frame_offsets, n_frames, per_frame, verify_pcm_workspace_bytes,
+        VerifyPacked{ pcm, pcm_samples, sample_offsets.data(), channels, stride, bytes_per_sample, nullptr, 0 }, diff_counts, first_diff, lossy_frames);
 }
 
 } // namespace sela

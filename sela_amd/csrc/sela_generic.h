@@ -102,7 +102,8 @@ hipError_t launch_verify32_direct(const int32_t* d_dec, const GenericSubInfo* d_
 hipError_t launch_verify32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
     const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, void* d_parts,
     uint32_t* d_diff_counts, uint32_t* d_first_diff, hipStream_t stream);
-// the gate and the sum alone, for a compare with kernels of its own in between (sela_verify_pcm.hip)
+// the gate (launched behind every direct kernel by the family's sequence, sela_generic.hip), and the sum alone for a compare
+// whose rest kernel does not launch it (sela_verify_pcm.hip)
 hipError_t launch_verify32_gate(uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_ctl, hipStream_t stream);
 hipError_t launch_verify32_sum(const void* d_parts, uint32_t n_slices, uint32_t max_frames, const uint32_t* d_n_found, uint32_t* d_diff_counts, uint32_t* d_first_diff,
     uint32_t* d_status, hipStream_t stream);

@@ -1782,50 +1782,79 @@ size_t verify_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t s
     return measured(at, [&](Carve& c) { carve_verify(c, max_frames, channels, stride); });
 }
 
-// launch_decode_n_device with a compare in place of the PCM: the sample index, k_route_n, then
-//   route 1, up to kVerifyFusedChannels channels: k_verify_frames on the fast decoder's count -- nothing decoded reaches memory;
-//   route 1 above (k_decode_frames_wide) and route 2 (the any-length kernels and the int16 writer): decoded into the workspace as
-//   sela_hip_decode_n_device decodes into d_pcm_out, then k_verify_compare / k_verify_combine on the count of the route that ran.
+// The int16 family's sequence (verify, levels): launch_decode_n_device with a consumer in place of the PCM.  The sample index,
+// k_route_n, k_verify_begin, then
+//   route 1, up to kVerifyFusedChannels channels: the consumer's fused kernel on the fast decoder's count -- nothing decoded
+//   reaches memory;
+//   route 1 above (k_decode_frames_wide) and route 2 (the any-length kernels and the int16 writer): decoded into `pcm` as
+//   sela_hip_decode_n_device decodes into d_pcm_out, then the consumer's kernels on the count of the route that ran.
 // status[2], the largest samplesPerChannel while k_route_n reads it, is zeroed behind it by k_verify_begin (one thread): the
-// kernels count the frames with a difference there.
+// consumer's kernels count their frames there.
 __global__ __launch_bounds__(64) void k_verify_begin(uint32_t* __restrict__ status)
 {
     if (threadIdx.x == 0)
         status[2] = 0;
 }
 
+// What every call of either family is given: the stream, where its status goes, and how to launch.
+struct StreamCall {
+    const uint8_t* d_frames;
+    const uint64_t* d_frame_offsets;
+    uint32_t max_frames;
+    const uint32_t* d_n_found;
+    uint32_t channels, stride;
+    uint32_t* d_status;
+    int mode;
+    hipStream_t stream;
+};
+
+// fused(dec, n_fast): the consumer's kernel over route 1's frames; consume(d_so, n_any, n_fast or null): the consumer over `pcm`.
+template <typename Fused, typename Consume>
+static hipError_t launch_n_sequence(const StreamCall& s, const DecodeNWs& n, int16_t* pcm, uint64_t* d_sample_offsets, int recurrence_form, uint32_t synth_priorities,
+    Fused fused_step, Consume consume)
+{
+    const DecodeHeadWs& head = n.head;
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : n.offsets;
+    const uint32_t* const n_fast = head.counters + 5;
+    const uint32_t* const n_any = head.counters + 6;
+    launch_sample_index(s.d_frames, s.d_frame_offsets, s.max_frames, s.d_n_found, s.channels, s.stride, d_so, s.d_status, head.counters, head.tiles, s.stream);
+    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, s.stream, s.max_frames, s.d_n_found, s.stride, s.d_status, head.counters);
+    hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, s.stream, s.d_status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || s.max_frames * s.channels == 0)
+        return e;
+    // route 1 (its workspace: the decoded subframes' piece, as in launch_decode_n_device)
+    const bool fused = s.channels <= kVerifyFusedChannels;
+    if (fused)
+        e = fused_step(head.dec, n_fast);
+    else
+        e = launch_decode(s.d_frames, s.d_frame_offsets, s.max_frames, s.channels, pcm, s.d_status, head.dec, s.stream, nullptr, nullptr, nullptr, recurrence_form,
+            synth_priorities, n_fast, false);
+    if (e != hipSuccess)
+        return e;
+    // route 2
+    e = launch_any_length_n(s.d_frames, s.d_frame_offsets, s.max_frames, s.channels, s.stride, n, d_so, pcm, s.d_status, s.mode, s.stream);
+    if (e != hipSuccess)
+        return e;
+    return consume(d_so, n_any, fused ? nullptr : n_fast);
+}
+
+// Verify plugs in k_verify_frames, and k_verify_compare / k_verify_combine.
 hipError_t launch_verify_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int16_t* d_pcm, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
     int mode, int recurrence_form, uint32_t synth_priorities, hipStream_t stream)
 {
     Carve c(d_workspace);
     const VerifyWs w = carve_verify(c, max_frames, channels, stride);
-    const DecodeHeadWs& head = w.n.head;
-    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.n.offsets;
-    const uint32_t* const n_fast = head.counters + 5;
-    const uint32_t* const n_any = head.counters + 6;
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, head.counters, head.tiles, stream);
-    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, head.counters);
-    hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, stream, d_status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || max_frames * channels == 0)
-        return e;
-    // route 1 (its workspace: the decoded subframes' piece, as in launch_decode_n_device)
-    const bool fused = channels <= kVerifyFusedChannels;
-    if (fused)
-        e = launch_verify_frames(d_frames, d_frame_offsets, max_frames, channels, d_pcm, d_diff_counts, d_first_diff, d_status, head.dec, stream, recurrence_form,
-            synth_priorities, n_fast);
-    else
-        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, w.pcm, d_status, head.dec, stream, nullptr, nullptr, nullptr, recurrence_form,
-            synth_priorities, n_fast, false);
-    if (e != hipSuccess)
-        return e;
-    // route 2
-    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, w.n, d_so, w.pcm, d_status, mode, stream);
-    if (e != hipSuccess)
-        return e;
-    return launch_verify_compare(w.pcm, d_pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, w.parts, d_diff_counts, d_first_diff, d_status,
-        stream);
+    return launch_n_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w.n, w.pcm, d_sample_offsets, recurrence_form,
+        synth_priorities,
+        [&](int32_t* dec, const uint32_t* n_fast) {
+            return launch_verify_frames(d_frames, d_frame_offsets, max_frames, channels, d_pcm, d_diff_counts, d_first_diff, d_status, dec, stream, recurrence_form,
+                synth_priorities, n_fast);
+        },
+        [&](const uint64_t* d_so, const uint32_t* n_any, const uint32_t* n_fast) {
+            return launch_verify_compare(w.pcm, d_pcm, d_so, max_frames, channels, stride, n_any, n_fast, w.parts, d_diff_counts, d_first_diff, d_status, stream);
+        });
 }
 
 // ---- levels on the device (sela_hip_levels_device) -------------------------------------------------------------
@@ -1849,41 +1878,22 @@ size_t levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t s
     return measured(at, [&](Carve& c) { carve_levels(c, max_frames, channels, stride); });
 }
 
-// launch_verify_n_device with a reduction in place of the compare: the sample index, k_route_n, k_verify_begin (status[2], the
-// largest samplesPerChannel while k_route_n reads it, becomes the count of frames that are not silent), then
-//   route 1, up to kVerifyFusedChannels channels: k_level_frames on the fast decoder's count -- nothing decoded reaches memory;
-//   route 1 above (k_decode_frames_wide) and route 2 (the any-length kernels and the int16 writer): decoded into the workspace as
-//   sela_hip_decode_n_device decodes into d_pcm_out, then k_level_channels / k_level_count on the count of the route that ran.
+// Levels plug k_level_frames, and k_level_channels / k_level_count, into launch_n_sequence: status[2] becomes the count of frames
+// that are not silent.
 hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
     uint32_t synth_priorities, hipStream_t stream)
 {
     Carve c(d_workspace);
     const LevelsWs w = carve_levels(c, max_frames, channels, stride);
-    const DecodeHeadWs& head = w.n.head;
-    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.n.offsets;
-    const uint32_t* const n_fast = head.counters + 5;
-    const uint32_t* const n_any = head.counters + 6;
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, head.counters, head.tiles, stream);
-    hipLaunchKernelGGL(k_route_n, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, stride, d_status, head.counters);
-    hipLaunchKernelGGL(k_verify_begin, dim3(1), dim3(64), 0, stream, d_status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || max_frames * channels == 0)
-        return e;
-    // route 1 (its workspace: the decoded subframes' piece, as in launch_decode_n_device)
-    const bool fused = channels <= kVerifyFusedChannels;
-    if (fused)
-        e = launch_level_frames(d_frames, d_frame_offsets, max_frames, channels, d_levels, d_status, head.dec, stream, recurrence_form, synth_priorities, n_fast);
-    else
-        e = launch_decode(d_frames, d_frame_offsets, max_frames, channels, w.pcm, d_status, head.dec, stream, nullptr, nullptr, nullptr, recurrence_form,
-            synth_priorities, n_fast, false);
-    if (e != hipSuccess)
-        return e;
-    // route 2
-    e = launch_any_length_n(d_frames, d_frame_offsets, max_frames, channels, stride, w.n, d_so, w.pcm, d_status, mode, stream);
-    if (e != hipSuccess)
-        return e;
-    return launch_level_channels(w.pcm, d_so, max_frames, channels, stride, n_any, fused ? nullptr : n_fast, d_levels, d_status, stream);
+    return launch_n_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w.n, w.pcm, d_sample_offsets, recurrence_form,
+        synth_priorities,
+        [&](int32_t* dec, const uint32_t* n_fast) {
+            return launch_level_frames(d_frames, d_frame_offsets, max_frames, channels, d_levels, d_status, dec, stream, recurrence_form, synth_priorities, n_fast);
+        },
+        [&](const uint64_t* d_so, const uint32_t* n_any, const uint32_t* n_fast) {
+            return launch_level_channels(w.pcm, d_so, max_frames, channels, stride, n_any, n_fast, d_levels, d_status, stream);
+        });
 }
 
 // ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
@@ -1923,33 +1933,50 @@ const uint32_t* verify_i32_control_words(const void* d_workspace, uint32_t max_f
     return carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride)).ctl;
 }
 
-// launch_decode_i32_device with a compare in place of the combine: the sample index, k_verify32_begin (status[2], the largest
-// samplesPerChannel, becomes the count of frames with a difference; nothing on this route reads it behind the index),
-// k_decode_subframes32 and the judge into the workspace by position, then k_verify32_direct on the subframes as decoded.  The
-// frames it leaves alone (any layout that is not direct) send the whole call through k_generic_combine<false> -- gated on the
-// device by k_verify32_gate's count, 0 when no frame was left: every workgroup returns at once -- and k_verify32_rest compares
-// those frames from the combine's output.  SELA_HIP_FLAG_BAD_FRAME and status[1] come from the combine as in the decode call:
-// a direct frame is never malformed there.
+// The int32 family's sequence (verify against int32 and against packed PCM, levels): launch_decode_i32_device with a consumer in
+// place of the combine.  The sample index (into d_so), the consumer's begin (status[2], the largest samplesPerChannel, becomes the
+// consumer's count of frames; nothing on this route reads it behind the index; the two control words), k_decode_subframes32 and the
+// judge into the workspace by position, then the consumer's direct kernel on the subframes as decoded.  The frames it leaves alone
+// (any layout that is not direct) send the whole call through k_generic_combine<false> -- gated on the device by k_verify32_gate's
+// count, 0 when no frame was left: every workgroup returns at once -- and the consumer's rest kernels take those frames from the
+// combine's output and add the slices up.  SELA_HIP_FLAG_BAD_FRAME and status[1] come from the combine as in the decode call: a
+// direct frame is never malformed there.
+template <typename Begin, typename Direct, typename Rest>
+static hipError_t launch_i32_sequence(const StreamCall& s, const VerifyI32Ws& w, uint64_t* d_so, Begin begin, Direct direct, Rest rest)
+{
+    launch_sample_index(s.d_frames, s.d_frame_offsets, s.max_frames, s.d_n_found, s.channels, s.stride, d_so, s.d_status, w.d.counters, w.d.tiles, s.stream);
+    hipError_t e = begin();
+    if (e != hipSuccess || s.max_frames * s.channels == 0)
+        return e;
+    e = launch_any_length_subframes(s.d_frames, s.d_frame_offsets, s.max_frames, s.channels, s.stride, w.d, s.d_status, s.mode, s.d_n_found, s.stream);
+    if (e != hipSuccess)
+        return e;
+    e = direct();
+    if (e == hipSuccess)
+        e = launch_verify32_gate(s.max_frames, s.d_n_found, w.ctl, s.stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(s.max_frames, s.stride), dim3(kCombineThreads), 0, s.stream, w.d.dec, w.d.info, s.max_frames, s.channels,
+        s.stride, w.all, w.counts, nullptr, nullptr, s.d_status, w.ctl + 1);
+    return rest();
+}
+
+// Verify against int32 plugs in k_verify32_begin, k_verify32_direct, and k_verify32_rest with k_verify32_sum.
 hipError_t launch_verify_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const int32_t* d_samples, const uint32_t* d_lengths, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
     Carve c(d_workspace);
     const VerifyI32Ws w = carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride));
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.d.counters, w.d.tiles, stream);
-    hipError_t e = launch_verify32_begin(d_status, w.ctl, stream);
-    if (e != hipSuccess || max_frames * channels == 0)
-        return e;
-    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.d, d_status, mode, d_n_found, stream);
-    if (e != hipSuccess)
-        return e;
-    e = launch_verify32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, stream);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.d.dec, w.d.info, max_frames, channels, stride,
-        w.all, w.counts, nullptr, nullptr, d_status, w.ctl + 1);
-    return launch_verify32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, d_diff_counts,
-        d_first_diff, stream);
+    return launch_i32_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w, d_sample_offsets,
+        [&] { return launch_verify32_begin(d_status, w.ctl, stream); },
+        [&] {
+            return launch_verify32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, stream);
+        },
+        [&] {
+            return launch_verify32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_samples, d_lengths, d_status, w.ctl, w.marks, w.parts, d_diff_counts,
+                d_first_diff, stream);
+        });
 }
 
 // ---- levels of 32-bit and ragged streams on the device (sela_hip_levels_i32_device) --------------------------
@@ -1974,29 +2001,17 @@ const uint32_t* levels_i32_control_words(const void* d_workspace, uint32_t max_f
     return carve_levels_i32(c, max_frames, channels, stride).ctl;
 }
 
-// launch_verify_i32_device with a reduction in place of the compare: the sample index, k_level32_begin (status[2], the largest
-// samplesPerChannel, becomes the count of frames that are not silent), k_decode_subframes32 and the judge into the workspace by
-// position, then k_level32_direct on the subframes as decoded.  The frames it leaves alone send the whole call through
-// k_generic_combine<false> -- gated on the device by k_verify32_gate's count -- and k_level32_rest reduces those frames from the
-// combine's output; k_level32_sum adds the slices up.
+// Levels plug k_level32_begin, k_level32_direct, and k_level32_rest with k_level32_sum into launch_i32_sequence: status[2] becomes
+// the count of frames that are not silent.
 hipError_t launch_levels_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, sela_hip_level32* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
     Carve c(d_workspace);
     const VerifyI32Ws w = carve_levels_i32(c, max_frames, channels, stride);
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_sample_offsets, d_status, w.d.counters, w.d.tiles, stream);
-    hipError_t e = launch_level32_begin(d_status, w.ctl, false, stream);
-    if (e != hipSuccess || max_frames * channels == 0)
-        return e;
-    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.d, d_status, mode, d_n_found, stream);
-    if (e != hipSuccess)
-        return e;
-    e = launch_level32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, stream);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.d.dec, w.d.info, max_frames, channels, stride,
-        w.all, w.counts, nullptr, nullptr, d_status, w.ctl + 1);
-    return launch_level32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, d_levels, stream);
+    return launch_i32_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w, d_sample_offsets,
+        [&] { return launch_level32_begin(d_status, w.ctl, false, stream); },
+        [&] { return launch_level32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, stream); },
+        [&] { return launch_level32_rest(w.all, w.counts, max_frames, d_n_found, channels, stride, d_status, w.ctl, w.marks, w.parts, d_levels, stream); });
 }
 
 // The partial records alone.
@@ -2051,36 +2066,30 @@ const uint32_t* verify_pcm_control_words(const void* d_workspace, uint32_t max_f
     return carve_verify_pcm(c, max_frames, channels, stride).v.ctl;
 }
 
-// launch_verify_i32_device with the compare's kernels exchanged for sela_verify_pcm.hip's: the sample index (into the caller's
-// offsets or the workspace's: the compare reads them), k_verify32_begin, the subframes by position, the direct compare, the gate,
-// the combine on its count, the rest, the sum over the tiles.
+// Verify against packed PCM plugs sela_verify_pcm.hip's kernels into launch_i32_sequence: k_verify32_begin, k_verify_pcm<., false>,
+// and k_verify_pcm<., true> with k_verify32_sum over the tiles.  The sample index goes into the caller's offsets or the workspace's:
+// the compare reads them.
 hipError_t launch_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
 {
     Carve c(d_workspace);
-    const VerifyPcmWs w = carve_verify_pcm(c, max_frames, channels, stride);
-    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : w.offsets;
-    launch_sample_index(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_so, d_status, w.v.d.counters, w.v.d.tiles, stream);
-    hipError_t e = launch_verify32_begin(d_status, w.v.ctl, stream);
-    if (e != hipSuccess || max_frames * channels == 0)
-        return e;
-    e = launch_any_length_subframes(d_frames, d_frame_offsets, max_frames, channels, stride, w.v.d, d_status, mode, d_n_found, stream);
-    if (e != hipSuccess)
-        return e;
-    e = launch_verify_pcm_direct(w.v.d.dec, w.v.d.info, max_frames, d_n_found, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.v.ctl,
-        w.v.marks, w.v.parts, stream);
-    if (e == hipSuccess)
-        e = launch_verify32_gate(max_frames, d_n_found, w.v.ctl, stream);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k_generic_combine<false>, combine_grid(max_frames, stride), dim3(kCombineThreads), 0, stream, w.v.d.dec, w.v.d.info, max_frames, channels, stride,
-        w.v.all, w.v.counts, nullptr, nullptr, d_status, w.v.ctl + 1);
-    e = launch_verify_pcm_rest(w.v.all, w.v.counts, max_frames, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.v.ctl, w.v.marks, w.v.parts,
-        stream);
-    if (e != hipSuccess)
-        return e;
-    return launch_verify32_sum(w.v.parts, verify_pcm_tiles(stride, channels), max_frames, d_n_found, d_diff_counts, d_first_diff, d_status, stream);
+    const VerifyPcmWs pw = carve_verify_pcm(c, max_frames, channels, stride);
+    const VerifyI32Ws& w = pw.v;
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : pw.offsets;
+    return launch_i32_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w, d_so,
+        [&] { return launch_verify32_begin(d_status, w.ctl, stream); },
+        [&] {
+            return launch_verify_pcm_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.ctl,
+                w.marks, w.parts, stream);
+        },
+        [&] {
+            const hipError_t e = launch_verify_pcm_rest(w.all, w.counts, max_frames, channels, stride, d_pcm, bytes_per_sample, pcm_samples, d_so, d_status, w.ctl,
+                w.marks, w.parts, stream);
+            if (e != hipSuccess)
+                return e;
+            return launch_verify32_sum(w.parts, verify_pcm_tiles(stride, channels), max_frames, d_n_found, d_diff_counts, d_first_diff, d_status, stream);
+        });
 }
 
 // Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total.  No

@@ -1,7 +1,10 @@
 // sela_levels.hip -- how loud a .sela stream is, measured on the device: per frame and channel the peak, the sum and the sum of
-// squares of the int16 samples sela_hip_decode_n_device would write (gfx950).
+// squares of the int16 samples sela_hip_decode_n_device would write (gfx950).  The launches are the int16 family's
+// sequence (launch_n_sequence, sela_generic.hip: the sample index, k_route_n, k_verify_begin, a fused kernel for the 2048-sample
+// route of up to eight channels, every other route decoded into the workspace, a consumer of that PCM); launch_levels_n_device
+// plugs in
 //
-//   k_level_frames     the decoder with a reduction for a store: k_verify_frames (sela_verify.hip) with the compare taken out.  One
+//   k_level_frames     the fused kernel: the decoder with a reduction for a store: k_verify_frames (sela_verify.hip) with the compare taken out.  One
 //                      workgroup per frame, one wave per subframe: frame_prologue and decode_subframe of sela_decode_core.inc, the
 //                      barrier, then the shared second pass (parent - difference, mod 2^16) -- and where the decoder stores a
 //                      frame's interleaved int16 samples, this kernel folds them into max |v|, sum v and sum v * v per channel.

@@ -1,17 +1,16 @@
 // sela_levels32.hip -- how loud a 24- or 32-bit .sela stream is, measured on the device: per frame and channel the peak, the sum
 // and the 128-bit sum of squares of the int32 samples sela_hip_decode_i32_device would write (gfx950).
 //
-// sela_hip_levels_i32_device is sela_hip_verify_i32_device (sela_verify32.hip, 5.15) with a reduction where the compare is: the
-// sample index, the fast kernel and the judge decode every subframe into the workspace BY POSITION (launch_levels_i32_device,
-// sela_generic.hip), and then
+// sela_hip_levels_i32_device is sela_hip_verify_i32_device (sela_verify32.hip, 5.15) with a reduction where the compare is.  The
+// launches are the int32 family's sequence (launch_i32_sequence, sela_generic.hip; its steps: sela_verify32.hip's head);
+// launch_levels_i32_device plugs in
 //
 //   k_level32_begin    status[2] = 0 (it becomes the count of frames that are not silent) and the two control words.
 //   k_level32_direct   one workgroup per (frame, slice of kVerify32Slice samples).  verify32_judge_layout decides whether the
 //                      layout is DIRECT; for such a frame the value of channel c at i is dec[pos(c)][i], or dec[pos(parent)][i] -
 //                      dec[pos(c)][i] mod 2^32: formed in registers and folded into the channel's partial record of this slice.
 //                      No decoded sample is written.  Any other frame is marked and counted.
-//   (k_verify32_gate, then k_generic_combine<false> on its count, into the workspace: frame_decoder.cpp's order of writes)
-//   k_level32_rest     the marked frames, from the combine's samples and counts; with no marks, every frame of planar samples
+//   k_level32_rest     the rest step: the marked frames, from the combine's samples and counts; with no marks, every frame of planar samples
 //                      that already lie in device memory (sela_hip_levels_samples_i32_device).
 //   k_level32_sum      a thread per word of a record: the slices' partial records added up, status[2].
 //
@@ -251,8 +250,7 @@ hipError_t launch_level32_direct(const int32_t* d_dec, const GenericSubInfo* d_i
     else
         hipLaunchKernelGGL(k_level32_direct<false>, grid, dim3(kV32Threads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_status, d_n_found, d_ctl, d_marks,
             d_parts);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_verify32_gate(max_frames, d_n_found, d_ctl, stream);
+    return hipGetLastError();
 }
 
 hipError_t launch_level32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,

@@ -1,7 +1,9 @@
 // sela_verify32.hip -- a .sela stream checked against its int32 samples on the device, frame by frame (gfx950).
 //
-// sela_hip_verify_i32_device is sela_hip_decode_i32_device with a compare where the combine stores: the sample index, the fast
-// kernel and the judge decode every subframe into the workspace BY POSITION (launch_verify_i32_device, sela_generic.hip), and then
+// sela_hip_verify_i32_device is sela_hip_decode_i32_device with a compare where the combine stores.  The launches are the int32
+// family's sequence (launch_i32_sequence, sela_generic.hip): the sample index, a begin step, every subframe decoded into the
+// workspace BY POSITION, a direct step, k_verify32_gate, k_generic_combine<false> on its count, a rest step that ends with a sum
+// over the slices.  This file has the gate, and what launch_verify_i32_device plugs in:
 //
 //   k_verify32_begin   status[2] = 0 (it becomes the count of frames with a difference) and the two control words.
 //   k_verify32_direct  one workgroup per (frame, slice of kVerify32Slice samples).  It reads the frame's GenericSubInfos and
@@ -11,7 +13,8 @@
 //                      at i is dec[pos(c)][i], or dec[pos(parent)][i] - dec[pos(c)][i] mod 2^32: computed in registers and
 //                      compared with the original.  No decoded sample is written.  Any other frame is marked and counted.
 //   k_verify32_gate    one thread: the frames the fallback takes -- 0 when no frame was marked, else the call's own count.
-//   (k_generic_combine<false> on that count, into the workspace: frame_decoder.cpp's order of writes, its malformed frames)
+//                      (The sequence's, for every call of the family; then k_generic_combine<false> on that count, into the
+//                      workspace: frame_decoder.cpp's order of writes, its malformed frames.)
 //   k_verify32_rest    the marked frames against the original, from the combine's samples and counts.
 //   k_verify32_sum     a thread per frame: the slices' words added up, the frame's two words, status[2].
 //
@@ -216,7 +219,6 @@ hipError_t launch_verify32_direct(const int32_t* d_dec, const GenericSubInfo* d_
     else
         hipLaunchKernelGGL(k_verify32_direct<false>, grid, dim3(kV32Threads), 0, stream, d_dec, d_info, max_frames, channels, stride, d_samples, d_lengths, d_status,
             d_n_found, d_ctl, d_marks, parts);
-    hipLaunchKernelGGL(k_verify32_gate, dim3(1), dim3(64), 0, stream, max_frames, d_n_found, d_ctl);
     return hipGetLastError();
 }
 

@@ -3,17 +3,16 @@
 //
 // sela_hip_verify_pcm_device is sela_hip_verify_i32_device (sela_verify32.hip, 5.15) with the original read where it lies: little-
 // endian interleaved samples, frame f at sample_offsets[f] * channels * kBytes -- the layout sela_hip_decode_pcm_device writes.
-// No unpacked copy of it is made.  The launches are launch_verify_pcm_device's (sela_generic.hip): the sample index,
-// k_verify32_begin, the decode of every subframe into the workspace by position, and then
+// No unpacked copy of it is made.  The launches are the int32 family's sequence (launch_i32_sequence, sela_generic.hip; its steps:
+// sela_verify32.hip's head); launch_verify_pcm_device plugs in k_verify32_begin and
 //
-//   k_verify_pcm<kBytes, false>  one workgroup per (frame, tile of sela_pcm_layout.h), the tile clipped to the original's length
+//   k_verify_pcm<kBytes, false>  the direct step: one workgroup per (frame, tile of sela_pcm_layout.h), the tile clipped to the original's length
 //                      L_f.  The tile's packed bytes are loaded into the LDS image as k_pcm_unpack loads them (aligned dwords, a
 //                      run of kBytes per lane); the frame's layout is judged by k_verify32_direct's rule (sela_verify32_rule.h);
 //                      a lane takes four consecutive samples of one channel out of the image, an int4 of the subframe as
 //                      decoded (and of its parent for a type-1 subframe), and compares in registers.  Frames of any other
 //                      layout are marked and counted.
-//   k_verify32_gate, k_generic_combine<false> on its count (the marked frames by channel, into the workspace)
-//   k_verify_pcm<kBytes, true>   the marked frames, from the combine's samples and counts.
+//   k_verify_pcm<kBytes, true>   the rest step: the marked frames, from the combine's samples and counts; then
 //   k_verify32_sum     on pcm_tiles(stride, channels) slices: the frame's two words, status[2].
 //
 // Per frame, with n_f = so[f + 1] - so[f] (at most stride), L_f = min(n_f, the samples the buffer still holds from so[f] on) and
