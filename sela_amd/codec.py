@@ -530,32 +530,29 @@ def track_levels32(levels: np.ndarray) -> list:
     return out
 
 
-class WindowDecoder:
-    """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
-    device memory -- only the frames a window touches are decoded (DESIGN.md 5.17).  Owns its output, flags, status and workspace
-    on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  planar_float:
-    float32 [n, channels, window_samples] holding value / 32768 instead of int16 [n, window_samples, channels].  whole:
-    sela_hip_decode_windows_whole_device (DESIGN.md 5.20) -- the streams are whole-track streams, whose last frame of 1 .. 4095
-    samples is decoded too."""
+class _WindowCall:
+    """What WindowDecoder and WindowDecoder32 share: the buffers they own -- output, flags, status, and the workspace of
+    sela_hip_<_entry>[_whole]_workspace_bytes -- the asserted decode(), flags, pack() and check().  A class names its entry, gives
+    _allocate() its format and its output's shape and dtype, and lists in _extra what its call takes between the format and the
+    output."""
 
-    def __init__(self, max_windows: int, window_samples: int, channels: int, planar_float: bool = False, device=None, whole: bool = False):
+    _entry = None  # "decode_windows": sela_hip_decode_windows_device, or with whole sela_hip_decode_windows_whole_device
+    _extra = ()
+
+    def _allocate(self, max_windows: int, window_samples: int, channels: int, format: int, shape, dtype: str, device, whole: bool) -> None:
         import torch
 
         self.torch = torch
         self.lib = capi.lib()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_windows, self.window_samples, self.channels = max_windows, window_samples, channels
-        self.format = capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED
-        self.call = self.lib.sela_hip_decode_windows_whole_device if whole else self.lib.sela_hip_decode_windows_device
+        self.max_windows, self.window_samples, self.channels, self.format = max_windows, window_samples, channels, format
+        entry = f"sela_hip_{self._entry}_whole" if whole else f"sela_hip_{self._entry}"
+        self.call = getattr(self.lib, entry + "_device")
         with torch.cuda.device(self.device):
-            if planar_float:
-                self.out = torch.empty((max_windows, channels, window_samples), dtype=torch.float32, device=self.device)
-            else:
-                self.out = torch.empty((max_windows, window_samples, channels), dtype=torch.int16, device=self.device)
+            self.out = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
             self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
             self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            sizing = self.lib.sela_hip_decode_windows_whole_workspace_bytes if whole else self.lib.sela_hip_decode_windows_workspace_bytes
-            ws = int(sizing(max_windows, window_samples, channels))
+            ws = int(getattr(self.lib, entry + "_workspace_bytes")(max_windows, window_samples, channels))
             self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.n_windows = 0
 
@@ -583,7 +580,7 @@ class WindowDecoder:
         assert n <= self.max_windows
         stream = torch.cuda.current_stream(self.device).cuda_stream
         capi.check(self.call(
-            frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format,
+            frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format, *self._extra,
             self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
         self.n_windows = n
         return self.out[:n]
@@ -594,13 +591,46 @@ class WindowDecoder:
         return self.window_flags[: self.n_windows]
 
     def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_windows returns for the same batch."""
+        """Waits for the last call and raises SelaHipError with the code the class's host call (sela_hip_decode_windows,
+        sela_hip_decode_windows_i32) returns for the same batch."""
         st = self.status.cpu().numpy().copy()
         # sela_hip_decode_n_status_error judges [0] flag bits and [1] bad frames by the route named in [3]; 1 is the 2048-sample
         # decoder's, the mapping the host call uses (a malformed frame or a dry Rice stream: EFORMAT; a coefficient outside the
-        # tables or beyond int64: ERANGE).  This call's [2] counts flagged windows, which that function does not read.
+        # tables or beyond int64: ERANGE).  This call's [2] counts flagged windows, which that function does not read, and the
+        # 32-bit call's [3] is its wide count.
         st[2], st[3] = 0, 1
         capi.check(decode_n_status_error(st))
+
+
+def _windows_host(call, frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, format: int, extra, shape_of):
+    """The body of decode_windows_host and decode_windows_i32_host: `call` on contiguous copies, `extra` between the format and
+    the output, which is shape_of(n)'s (shape, dtype); any code but 0, EFORMAT and ERANGE raises."""
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros(*shape_of(len(win)))
+    flags = np.zeros(len(win), np.uint32)
+    rc = call(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, len(win), window_samples, format, *extra, out.ctypes.data, flags.ctypes.data)
+    if rc not in (capi.OK, -5, -6):
+        capi.check(rc)
+    return out, flags, rc
+
+
+class WindowDecoder(_WindowCall):
+    """sela_hip_decode_windows_device: windows of `window_samples` samples cut from streams of 2048-sample frames that lie in
+    device memory -- only the frames a window touches are decoded (DESIGN.md 5.17).  Owns its output, flags, status and workspace
+    on the current device (or `device`); every call is asynchronous on the current stream and overwrites them.  planar_float:
+    float32 [n, channels, window_samples] holding value / 32768 instead of int16 [n, window_samples, channels].  whole:
+    sela_hip_decode_windows_whole_device (DESIGN.md 5.20) -- the streams are whole-track streams, whose last frame of 1 .. 4095
+    samples is decoded too."""
+
+    _entry = "decode_windows"
+
+    def __init__(self, max_windows: int, window_samples: int, channels: int, planar_float: bool = False, device=None, whole: bool = False):
+        if planar_float:
+            self._allocate(max_windows, window_samples, channels, capi.WINDOW_F32_PLANAR, (max_windows, channels, window_samples), "float32", device, whole)
+        else:
+            self._allocate(max_windows, window_samples, channels, capi.WINDOW_I16_INTERLEAVED, (max_windows, window_samples, channels), "int16", device, whole)
 
 
 def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, planar_float: bool = False,
@@ -610,18 +640,10 @@ def decode_windows_host(frames: np.ndarray, offsets: np.ndarray, channels: int, 
     call's return code -- 0, or EFORMAT / ERANGE (capi.ERRORS) for a batch with a bad frame, whose other windows are good all
     the same; any other code raises."""
     lib = capi.lib()
-    fr = np.ascontiguousarray(frames, dtype=np.uint8)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
-    n = len(win)
-    out = np.zeros((n, channels, window_samples), np.float32) if planar_float else np.zeros((n, window_samples, channels), np.int16)
-    flags = np.zeros(n, np.uint32)
     call = lib.sela_hip_decode_windows_whole if whole else lib.sela_hip_decode_windows
-    rc = call(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, capi.WINDOW_F32_PLANAR if planar_float else capi.WINDOW_I16_INTERLEAVED,
-              out.ctypes.data, flags.ctypes.data)
-    if rc not in (capi.OK, -5, -6):
-        capi.check(rc)
-    return out, flags, rc
+    if planar_float:
+        return _windows_host(call, frames, offsets, channels, windows, window_samples, capi.WINDOW_F32_PLANAR, (), lambda n: ((n, channels, window_samples), np.float32))
+    return _windows_host(call, frames, offsets, channels, windows, window_samples, capi.WINDOW_I16_INTERLEAVED, (), lambda n: ((n, window_samples, channels), np.int16))
 
 
 def _window32_shape(n: int, window_samples: int, channels: int, format: int):
@@ -637,64 +659,24 @@ def _window32_shape(n: int, window_samples: int, channels: int, format: int):
     raise ValueError("format must be capi.WINDOW_F32_PLANAR, WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED or WINDOW_PCM32_INTERLEAVED")
 
 
-class WindowDecoder32:
+class WindowDecoder32(_WindowCall):
     """sela_hip_decode_windows_i32_device: windows of `window_samples` samples of up to 32 bits cut from streams of 2048-sample
     frames that lie in device memory.  Owns its output, flags, status and workspace on the current device (or
     `device`); every call is asynchronous on the current stream and overwrites them.  format (capi.WINDOW_*): I32_PLANAR int32
     [n, channels, window_samples]; F32_PLANAR float32 of that shape holding value * 2^-(sample_bits - 1); PCM32_INTERLEAVED int32
     [n, window_samples, channels]; PCM24_INTERLEAVED uint8 [n, window_samples, channels, 3], each sample's low three bytes."""
 
-    pack = staticmethod(WindowDecoder.pack)
+    _entry = "decode_windows_i32"
 
     def __init__(self, max_windows: int, window_samples: int, channels: int, format: int, sample_bits: int = 24, device=None, whole: bool = False):
-        import torch
-
-        self.torch = torch
-        self.lib = capi.lib()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_windows, self.window_samples, self.channels, self.format, self.sample_bits = max_windows, window_samples, channels, format, sample_bits
         # whole: sela_hip_decode_windows_i32_whole_device -- a stream's long last frame is decoded too (DESIGN.md 5.25)
-        self._call = self.lib.sela_hip_decode_windows_i32_whole_device if whole else self.lib.sela_hip_decode_windows_i32_device
-        sizing = self.lib.sela_hip_decode_windows_i32_whole_workspace_bytes if whole else self.lib.sela_hip_decode_windows_i32_workspace_bytes
-        shape, dtype = _window32_shape(max_windows, window_samples, channels, format)
-        with torch.cuda.device(self.device):
-            self.out = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
-            self.window_flags = torch.zeros(max(max_windows, 1), dtype=torch.int32, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-            ws = int(sizing(max_windows, window_samples, channels))
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
-        self.n_windows = 0
-
-    def decode(self, frames, offsets, n_frames_total: int, windows):
-        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames_total + 1], windows: int64 cuda tensor
-        [n, 2] (pack()) -> the first n windows of the decoder's own output buffer."""
-        torch = self.torch
-        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
-        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= n_frames_total + 1
-        assert windows.dtype == torch.int64 and windows.is_cuda and windows.is_contiguous() and windows.dim() == 2 and windows.shape[1] == 2
-        n = int(windows.shape[0])
-        assert n <= self.max_windows
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(self._call(
-            frames.data_ptr(), offsets.data_ptr(), n_frames_total, self.channels, windows.data_ptr(), n, self.window_samples, self.format, self.sample_bits,
-            self.out.data_ptr(), self.window_flags.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
-        self.n_windows = n
-        return self.out[:n]
-
-    @property
-    def flags(self):
-        """int32 cuda tensor [n]: the OR of the flag bits of the frames each window of the last call touched."""
-        return self.window_flags[: self.n_windows]
+        self.sample_bits = sample_bits
+        self._extra = (sample_bits,)
+        self._allocate(max_windows, window_samples, channels, format, *_window32_shape(max_windows, window_samples, channels, format), device, whole)
 
     def wide_samples(self) -> int:
         """Waits for the last call: PCM24's count of samples outside [-2^23, 2^23) (their low bytes were written); else 0."""
         return int(self.status.cpu().numpy().view(np.uint32)[3])
-
-    def check(self) -> None:
-        """Waits for the last call and raises SelaHipError with the code sela_hip_decode_windows_i32 returns for the same batch."""
-        st = self.status.cpu().numpy().copy()
-        st[2], st[3] = 0, 1  # (WindowDecoder.check: the fast route's mapping of [0] and [1]; [3] is this call's wide count)
-        capi.check(decode_n_status_error(st))
 
 
 def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int, windows: np.ndarray, window_samples: int, format: int, sample_bits: int = 24,
@@ -703,18 +685,8 @@ def decode_windows_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: i
     in `format` (WindowDecoder32's shapes), the per-window flags (uint32 [n]) and the call's return code -- 0, or EFORMAT / ERANGE
     (capi.ERRORS) for a batch with a bad frame, whose other windows are good all the same; any other code raises."""
     lib = capi.lib()
-    fr = np.ascontiguousarray(frames, dtype=np.uint8)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 2)
-    n = len(win)
-    shape, dtype = _window32_shape(n, window_samples, channels, format)
-    out = np.zeros(shape, dtype)
-    flags = np.zeros(n, np.uint32)
     call = lib.sela_hip_decode_windows_i32_whole if whole else lib.sela_hip_decode_windows_i32
-    rc = call(fr.ctypes.data, offs.ctypes.data, len(offs) - 1, channels, win.ctypes.data, n, window_samples, format, sample_bits, out.ctypes.data, flags.ctypes.data)
-    if rc not in (capi.OK, -5, -6):
-        capi.check(rc)
-    return out, flags, rc
+    return _windows_host(call, frames, offsets, channels, windows, window_samples, format, (sample_bits,), lambda n: _window32_shape(n, window_samples, channels, format))
 
 
 def verify_host(frames: np.ndarray, offsets: np.ndarray, channels: int, pcm: np.ndarray):
@@ -960,13 +932,11 @@ def whole_frames(n_samples: int):
     return out
 
 
-class WholeEncoder:
-    """sela_hip_encode_whole_device: a whole track of up to max_samples samples per channel, its tail kept in a long last frame
-    (DESIGN.md 5.19).  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
-    asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the certain bound.
-    lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder."""
+class _WholeEncode:
+    """What WholeEncoder and WholeEncoderPcm share: the track's bounds, the buffers they own, the end of encode(), check() and
+    to_host().  A class opens with _bounds(), which its default capacity may ask, then allocates."""
 
-    def __init__(self, max_samples: int, channels: int, lossless: bool = False, device=None, capacity=None):
+    def _bounds(self, max_samples: int, channels: int, lossless: bool, device) -> None:
         import torch
 
         self.torch = torch
@@ -975,27 +945,18 @@ class WholeEncoder:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_samples, self.channels = int(max_samples), int(channels)
         self.max_frames = int(self.lib.sela_hip_whole_frames(self.max_samples))
-        if capacity is None:
-            capacity = int(self.lib.sela_hip_encode_whole_bound_bytes(self.max_samples, channels))
+
+    def _allocate(self, capacity: int, workspace_bytes: int) -> None:
+        torch = self.torch
         self.capacity = max(int(capacity), 4)
-        ws = int(self.lib.sela_hip_encode_whole_workspace_bytes(self.max_samples, channels))
         with torch.cuda.device(self.device):
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            self.workspace = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
             self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
             self.offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
             self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
         self.n_frames = 0
 
-    def encode(self, pcm):
-        """pcm: int16 cuda tensor [n_samples, channels], contiguous -> (frames uint8 [capacity], offsets int64 [frames + 1],
-        status int32 [4]): the encoder's own buffers, the first offsets[-1] bytes of frames the stream's when check() passes."""
-        torch = self.torch
-        assert pcm.is_cuda and pcm.is_contiguous() and pcm.dtype == torch.int16 and pcm.dim() == 2 and pcm.shape[1] == self.channels
-        n_samples = pcm.shape[0]
-        assert n_samples <= self.max_samples
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(self.lib.sela_hip_encode_whole_device(pcm.data_ptr(), n_samples, self.channels, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
-                                                         self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream, self.options))
+    def _encoded(self, n_samples: int):
         self.n_frames = int(self.lib.sela_hip_whole_frames(n_samples))
         return self.frames, self.offsets[: self.n_frames + 1], self.status
 
@@ -1008,6 +969,31 @@ class WholeEncoder:
         self.check()
         offs = self.offsets[: self.n_frames + 1].cpu().numpy().view(np.uint64)
         return self.frames[: int(offs[-1])].cpu().numpy(), offs
+
+
+class WholeEncoder(_WholeEncode):
+    """sela_hip_encode_whole_device: a whole track of up to max_samples samples per channel, its tail kept in a long last frame
+    (DESIGN.md 5.19).  Owns its workspace, frames, offsets and status on the current device (or `device`); every call is
+    asynchronous on the current stream and overwrites them.  `capacity` (bytes of frames) defaults to the certain bound.
+    lossless: SELA_HIP_ENCODE_LOSSLESS, as Encoder."""
+
+    def __init__(self, max_samples: int, channels: int, lossless: bool = False, device=None, capacity=None):
+        self._bounds(max_samples, channels, lossless, device)
+        if capacity is None:
+            capacity = int(self.lib.sela_hip_encode_whole_bound_bytes(self.max_samples, channels))
+        self._allocate(capacity, self.lib.sela_hip_encode_whole_workspace_bytes(self.max_samples, channels))
+
+    def encode(self, pcm):
+        """pcm: int16 cuda tensor [n_samples, channels], contiguous -> (frames uint8 [capacity], offsets int64 [frames + 1],
+        status int32 [4]): the encoder's own buffers, the first offsets[-1] bytes of frames the stream's when check() passes."""
+        torch = self.torch
+        assert pcm.is_cuda and pcm.is_contiguous() and pcm.dtype == torch.int16 and pcm.dim() == 2 and pcm.shape[1] == self.channels
+        n_samples = pcm.shape[0]
+        assert n_samples <= self.max_samples
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.check(self.lib.sela_hip_encode_whole_device(pcm.data_ptr(), n_samples, self.channels, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
+                                                         self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream, self.options))
+        return self._encoded(n_samples)
 
 
 def encode_status_error(status) -> int:
@@ -1519,30 +1505,17 @@ def encode_pcm_host(pcm: np.ndarray, channels: int, samples_per_channel: int, by
     return frames[: int(offsets[-1])].copy(), offsets
 
 
-class WholeEncoderPcm:
+class WholeEncoderPcm(_WholeEncode):
     """sela_hip_encode_whole_pcm_device: a whole track of up to max_samples samples per channel from packed 3- or 4-byte interleaved
     PCM, its tail kept in a long last frame.  Owns its workspace, frames, offsets and status, as WholeEncoder
     does; `capacity` (bytes of frames) defaults to EncoderPcm's estimate -- check() and needed_bytes() say when it was too small."""
 
     def __init__(self, max_samples: int, channels: int, bytes_per_sample: int, lossless: bool = False, capacity=None, device=None):
-        import torch
-
-        self.torch = torch
-        self.lib = capi.lib()
-        self.options = capi.ENCODE_LOSSLESS if lossless else 0
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.max_samples, self.channels, self.bytes_per_sample = int(max_samples), int(channels), int(bytes_per_sample)
-        self.max_frames = int(self.lib.sela_hip_whole_frames(self.max_samples))
+        self._bounds(max_samples, channels, lossless, device)
+        self.bytes_per_sample = int(bytes_per_sample)
         if capacity is None:
             capacity = (self.max_samples * channels * 9) // 2 + self.max_frames * (channels * 192 + 64)
-        self.capacity = max(int(capacity), 4)
-        ws = int(self.lib.sela_hip_encode_whole_pcm_workspace_bytes(self.max_samples, channels))
-        with torch.cuda.device(self.device):
-            self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
-            self.frames = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
-            self.offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
-            self.status = torch.zeros(4, dtype=torch.int32, device=self.device)
-        self.n_frames = 0
+        self._allocate(capacity, self.lib.sela_hip_encode_whole_pcm_workspace_bytes(self.max_samples, channels))
 
     def encode(self, pcm, n_samples=None):
         """pcm: uint8 cuda tensor of n_samples * channels * bytes_per_sample bytes (n_samples: from its size) -> (frames uint8
@@ -1557,12 +1530,9 @@ class WholeEncoderPcm:
         capi.check(self.lib.sela_hip_encode_whole_pcm_device(
             pcm.data_ptr(), self.bytes_per_sample, n_samples, self.channels, self.options, self.frames.data_ptr(), self.capacity, self.offsets.data_ptr(),
             self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), torch.cuda.current_stream(self.device).cuda_stream))
-        self.n_frames = int(self.lib.sela_hip_whole_frames(n_samples))
-        return self.frames, self.offsets[: self.n_frames + 1], self.status
+        return self._encoded(n_samples)
 
     needed_bytes = Encoder32.needed_bytes
-    check = Encoder32.check
-    to_host = Encoder32.to_host
 
 
 def encode_whole_pcm_host(pcm: np.ndarray, channels: int, bytes_per_sample: int, lossless: bool = False):

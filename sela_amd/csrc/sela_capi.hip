@@ -1073,11 +1073,16 @@ uint32_t launch_priorities(hipStream_t stream, int& dev)
 // than the 15 us of plan + assemble they hide.  So the library never cuts by itself; the form stays behind
 // sela_hip_debug_encode_split (bench.py --encode-split N) for the comparison.  Never while kernel timing is on, with a trace or phase
 // buffer, with a kernel forced by a debug hook, or into a stream that is being captured.
-struct Splitter {
+//
+// A side lane: per device a stream of the library's own and the two events that cross to it and back -- `forked`, recorded on the
+// caller's stream for the side stream to wait on, and `side_done`, recorded on the side stream for the caller's to wait on.  (In a
+// stream that is being captured the side stream joins the capture at the first crossing and leaves it at the second.)  Whoever
+// holds `mu` enqueues through it; the work of successive holders still overlaps on the device.  The library has two, which never
+// wait on each other: the encode split's, taken with try_to_lock, and the whole-track calls' (fork_join below), taken blocking.
+struct SideLane {
     std::mutex mu;
     hipStream_t side[64] = {};
-    hipEvent_t begun[64] = {}, half_done[64] = {};
-    std::map<const void*, std::pair<uint32_t, uint32_t>> last; // workspace -> (frames of the launch, frames of its first half; 0: whole)
+    hipEvent_t forked[64] = {}, side_done[64] = {};
     bool ready(int dev)
     {
         if (side[dev])
@@ -1086,7 +1091,7 @@ struct Splitter {
             side[dev] = nullptr;
             return false;
         }
-        if (hipEventCreateWithFlags(&begun[dev], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&half_done[dev], hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&forked[dev], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&side_done[dev], hipEventDisableTiming) != hipSuccess) {
             (void)hipStreamDestroy(side[dev]);
             side[dev] = nullptr;
             return false;
@@ -1102,20 +1107,68 @@ struct Splitter {
             if (side[dev]) {
                 (void)hipSetDevice(dev);
                 (void)hipStreamSynchronize(side[dev]);
-                (void)hipEventDestroy(begun[dev]);
-                (void)hipEventDestroy(half_done[dev]);
+                (void)hipEventDestroy(forked[dev]);
+                (void)hipEventDestroy(side_done[dev]);
                 (void)hipStreamDestroy(side[dev]);
                 side[dev] = nullptr;
             }
-        last.clear();
         if (before >= 0)
             (void)hipSetDevice(before);
+    }
+};
+struct Splitter : SideLane {
+    std::map<const void*, std::pair<uint32_t, uint32_t>> last; // workspace -> (frames of the launch, frames of its first half; 0: whole)
+    void release_all()
+    {
+        SideLane::release_all();
+        std::lock_guard<std::mutex> lock(mu);
+        last.clear();
     }
 };
 Splitter& splitter()
 {
     static Splitter* s = new Splitter; // (never destroyed: streams outlive the statics' teardown)
     return *s;
+}
+SideLane& whole_lane()
+{
+    static SideLane* l = new SideLane;
+    return *l;
+}
+
+// The fork and join of the whole-track device calls, written once: `side_work(side stream)` beside `main_work()`
+// on the caller's stream `st`, both behind whatever `st` holds already, and `st` behind both when this returns.  Each returns a
+// SELA_HIP_ code, its error reported.  The lane's mutex is held from before the fork until the join is enqueued; the main work is
+// enqueued only behind side work that was enqueued whole; the join is enqueued on every path past the fork -- also after a failure
+// in between: a side stream that has joined a capture must leave it -- and the first failure is the one reported.  `name` opens
+// the texts; `ran_on`, if given, is told the device.
+template <typename SideWork, typename MainWork>
+int fork_join(SideLane& lane, hipStream_t st, const char* name, SideWork side_work, MainWork main_work, int* ran_on = nullptr)
+{
+    const std::string who = std::string(name) + ": ";
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+        return fail(SELA_HIP_ENODEV, who + "no current device");
+    std::lock_guard<std::mutex> lock(lane.mu);
+    if (!lane.ready(dev))
+        return fail(SELA_HIP_ENODEV, who + "no side stream");
+    const hipStream_t side = lane.side[dev];
+    // fork: the side stream follows whatever produced the call's input, and the workspace's previous user, on the caller's stream
+    hipError_t e = hipEventRecord(lane.forked[dev], st);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(side, lane.forked[dev], 0);
+    if (e != hipSuccess)
+        return fail_hip(e, (who + "fork").c_str());
+    int rc = side_work(side);
+    if (rc == SELA_HIP_OK && (e = hipEventRecord(lane.side_done[dev], side)) != hipSuccess)
+        rc = fail_hip(e, (who + "join").c_str());
+    if (rc == SELA_HIP_OK)
+        rc = main_work();
+    if ((e = hipStreamWaitEvent(st, lane.side_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
+        rc = fail_hip(e, (who + "join").c_str());
+    if (ran_on)
+        *ran_on = dev;
+    return rc;
 }
 std::atomic<int> g_encode_split{ 0 };    // debug (sela_hip_debug_encode_split): 0 never (the product), 1..999: every launch of teams of 16, that share to the first half
 std::atomic<int> g_launches_split{ 0 };
@@ -1215,7 +1268,7 @@ void sela_hip_shutdown(void)
     sela::generic_shutdown();
     flights().release_all();
     splitter().release_all();
-    sela::whole_shutdown();
+    whole_lane().release_all();
     pool().trim();
 }
 
@@ -1356,9 +1409,9 @@ int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channel
             void* const ws2 = halves.second;
             const int16_t* const pcm2 = d_pcm + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels;
             const hipStream_t side = sp.side[dev];
-            e = hipEventRecord(sp.begun[dev], st);
+            e = hipEventRecord(sp.forked[dev], st);
             if (e == hipSuccess)
-                e = hipStreamWaitEvent(side, sp.begun[dev], 0);
+                e = hipStreamWaitEvent(side, sp.forked[dev], 0);
             if (e == hipSuccess) // the first half's blocks, on the caller's stream
                 e = sela::launch_encode(d_pcm, first, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, nullptr, st, nullptr, nullptr, nullptr,
                     g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1, nullptr, false, lossless);
@@ -1366,12 +1419,12 @@ int encode_device_call(const int16_t* d_pcm, uint32_t n_frames, uint32_t channel
                 e = sela::launch_encode(pcm2, rest, channels, d_frames, frames_cap, d_frame_offsets + first, d_status, ws2, nullptr, side, nullptr, nullptr, nullptr,
                     g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 1, nullptr, false, lossless);
             if (e == hipSuccess)
-                e = hipEventRecord(sp.half_done[dev], side);
+                e = hipEventRecord(sp.side_done[dev], side);
             if (e == hipSuccess) // the first half's plan + assemble, under the second half's tail
                 e = sela::launch_encode(d_pcm, first, channels, d_frames, frames_cap, d_frame_offsets, d_status, d_workspace, nullptr, st, nullptr, nullptr, nullptr,
                     g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2, nullptr, false, lossless);
             if (e == hipSuccess)
-                e = hipStreamWaitEvent(st, sp.half_done[dev], 0);
+                e = hipStreamWaitEvent(st, sp.side_done[dev], 0);
             if (e == hipSuccess) // the second half's frames behind the first's
                 e = sela::launch_encode(pcm2, rest, channels, d_frames, frames_cap, d_frame_offsets + first, d_status, ws2, nullptr, st, nullptr, nullptr, nullptr,
                     g_force_plain_fir, g_self_blocks, 16, nullptr, priorities, 2, d_frame_offsets + first, true, lossless);
@@ -1727,14 +1780,26 @@ int levels_call(const Form& form, uint32_t channels, uint32_t stride, sela_hip_l
         });
 }
 
+// The shape checks of the int16 window calls, device and host pointers alike (5.17, 5.20): codes and texts in this order.
+// `more_channels` is the call that a caller with more than eight channels is sent to.
+int check_windows_shape(uint32_t channels, uint32_t n_windows, uint32_t window_samples, uint32_t format, const char* more_channels)
+{
+    if (channels == 0 || channels > 8)
+        return fail(SELA_HIP_EINVAL, std::string("channels must be in 1..8: the windows are cut from the on-chip decoder's second pass (more channels: ") + more_channels + ", then crop)");
+    if (window_samples == 0 || window_samples > (1u << 24))
+        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+    if (format != SELA_HIP_WINDOW_I16_INTERLEAVED && format != SELA_HIP_WINDOW_F32_PLANAR)
+        return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_I16_INTERLEAVED or SELA_HIP_WINDOW_F32_PLANAR");
+    if ((uint64_t)n_windows * sela::window_cover(window_samples) >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_windows * cover must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
+    return SELA_HIP_OK;
+}
 // sela_hip_decode_windows_device (5.17), in the frames form: the table is the form's, the windows are the call's.  Its workspace
 // is sized by the windows and not by the table, so its formula is sela_hip_decode_windows_workspace_bytes itself, closed over
 // the call's own arguments (the form asks it only after the check has passed them); the call has no stride.
 int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
     void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream, bool whole /* 5.20: the same checks, the long last frame's kernels behind */)
 {
-    const bool shaped = window_samples >= 1 && window_samples <= (1u << 24);
-    const uint64_t groups = shaped ? (uint64_t)n_windows * sela::window_cover(window_samples) : 0;
     const auto formula = [=](uint32_t /* the table's frames */, uint32_t, uint32_t) {
         return whole ? sela::window_whole_workspace_bytes(n_windows, window_samples, channels) : sela::window_workspace_bytes(n_windows, window_samples, channels);
     };
@@ -1742,21 +1807,15 @@ int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_windo
     return form(
         c,
         [&](uint32_t) {
-            if (channels == 0 || channels > 8)
-                return fail(SELA_HIP_EINVAL, "channels must be in 1..8: the windows are cut from the on-chip decoder's second pass (more channels: sela_hip_decode_device, then crop)");
-            if (window_samples == 0 || window_samples > (1u << 24))
-                return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
-            if (format != SELA_HIP_WINDOW_I16_INTERLEAVED && format != SELA_HIP_WINDOW_F32_PLANAR)
-                return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_I16_INTERLEAVED or SELA_HIP_WINDOW_F32_PLANAR");
-            if (groups >= (1ull << 31))
-                return fail(SELA_HIP_EINVAL, "n_windows * cover must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
-            int rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
+            int rc = check_windows_shape(channels, n_windows, window_samples, format, "sela_hip_decode_device");
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
             if (rc == SELA_HIP_OK && (((uintptr_t)d_windows & 7) || ((uintptr_t)d_out & (format == SELA_HIP_WINDOW_F32_PLANAR ? 3 : 1)) || ((uintptr_t)d_window_flags & 3) || ((uintptr_t)d_status & 3)))
                 rc = fail(SELA_HIP_EINVAL, "d_windows must be 8-byte aligned, d_out aligned to its element, d_window_flags and d_status 4-byte aligned");
             return rc;
         },
         [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames_total, const uint32_t*, void* d_ws) {
-            return launch_with_priorities((uint32_t)groups, stream, "decode_windows launch", [&](uint32_t synth_priorities) {
+            return launch_with_priorities(n_windows * sela::window_cover(window_samples), stream, "decode_windows launch", [&](uint32_t synth_priorities) {
                 const auto launch = whole ? sela::launch_window_whole : sela::launch_window_frames;
                 return launch(d_frames, d_frame_offsets, n_frames_total, channels, d_windows, n_windows,
                     window_samples, format, d_out, d_window_flags, d_status, d_ws, c.stream, g_recurrence_form, synth_priorities);
@@ -1764,15 +1823,26 @@ int windows_call(const FramesForm& form, uint32_t channels, const sela_hip_windo
         });
 }
 
-// sela_hip_decode_windows_i32_device (5.23): windows_call's checks in its order and with its codes -- the format's place holds the
-// wider formats and F32's sample_bits, the product counts the channels too (a wave per subframe) and is followed by a bound on
-// n_windows alone (the store's grid), d_out is a dword's.
-bool window32_format_ok(uint32_t format) { return format >= SELA_HIP_WINDOW_F32_PLANAR && format <= SELA_HIP_WINDOW_PCM32_INTERLEAVED; }
-constexpr const char* kWindow32Channels = "channels must be in 1..8: a frame's subframes are combined in one workgroup's table (more channels: sela_hip_decode_i32_device, then crop)";
-constexpr const char* kWindow32Format = "format must be SELA_HIP_WINDOW_F32_PLANAR, _I32_PLANAR, _PCM24_INTERLEAVED or _PCM32_INTERLEAVED (int16: sela_hip_decode_windows_device)";
-constexpr const char* kWindow32Bits = "sample_bits must be in 1..32 with SELA_HIP_WINDOW_F32_PLANAR";
-constexpr const char* kWindow32Product = "n_windows * cover * channels must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)";
-constexpr const char* kWindow32Windows = "n_windows must stay below 2^24 (a workgroup of 256 per window and covering frame: a launch holds fewer than 2^32 work-items per dimension)";
+// The shape checks of the 24- and 32-bit window calls, device and host pointers alike (5.23, 5.25): check_windows_shape's order
+// and codes -- the format's place holds the wider formats and F32's sample_bits, the product counts the channels too (a wave per
+// subframe) and is followed by a bound on n_windows alone (the store's grid).
+int check_windows_i32_shape(uint32_t channels, uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits)
+{
+    if (channels == 0 || channels > 8)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..8: a frame's subframes are combined in one workgroup's table (more channels: sela_hip_decode_i32_device, then crop)");
+    if (window_samples == 0 || window_samples > (1u << 24))
+        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
+    if (format < SELA_HIP_WINDOW_F32_PLANAR || format > SELA_HIP_WINDOW_PCM32_INTERLEAVED)
+        return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_F32_PLANAR, _I32_PLANAR, _PCM24_INTERLEAVED or _PCM32_INTERLEAVED (int16: sela_hip_decode_windows_device)");
+    if (format == SELA_HIP_WINDOW_F32_PLANAR && (sample_bits == 0 || sample_bits > 32))
+        return fail(SELA_HIP_EINVAL, "sample_bits must be in 1..32 with SELA_HIP_WINDOW_F32_PLANAR");
+    if ((uint64_t)n_windows * sela::window_cover(window_samples) * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_windows * cover * channels must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
+    if (n_windows >= (1u << 24))
+        return fail(SELA_HIP_EINVAL, "n_windows must stay below 2^24 (a workgroup of 256 per window and covering frame: a launch holds fewer than 2^32 work-items per dimension)");
+    return SELA_HIP_OK;
+}
+// sela_hip_decode_windows_i32_device (5.23): windows_call with the wider formats; d_out is a dword's.
 int windows_i32_call(const FramesForm& form, uint32_t channels, const sela_hip_window* d_windows, uint32_t n_windows, uint32_t window_samples, uint32_t format,
     uint32_t sample_bits, void* d_out, uint32_t* d_window_flags, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream,
     bool whole /* 5.25: the same checks, the long last frame's kernels behind */)
@@ -1784,19 +1854,9 @@ int windows_i32_call(const FramesForm& form, uint32_t channels, const sela_hip_w
     return form(
         c,
         [&](uint32_t) {
-            if (channels == 0 || channels > 8)
-                return fail(SELA_HIP_EINVAL, kWindow32Channels);
-            if (window_samples == 0 || window_samples > (1u << 24))
-                return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
-            if (!window32_format_ok(format))
-                return fail(SELA_HIP_EINVAL, kWindow32Format);
-            if (format == SELA_HIP_WINDOW_F32_PLANAR && (sample_bits == 0 || sample_bits > 32))
-                return fail(SELA_HIP_EINVAL, kWindow32Bits);
-            if ((uint64_t)n_windows * sela::window_cover(window_samples) * channels >= (1ull << 31))
-                return fail(SELA_HIP_EINVAL, kWindow32Product);
-            if (n_windows >= (1u << 24))
-                return fail(SELA_HIP_EINVAL, kWindow32Windows);
-            int rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
+            int rc = check_windows_i32_shape(channels, n_windows, window_samples, format, sample_bits);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && (!n_windows || (d_windows && d_out && d_workspace)));
             if (rc == SELA_HIP_OK && (((uintptr_t)d_windows & 7) || ((uintptr_t)d_out & 3) || ((uintptr_t)d_window_flags & 3) || ((uintptr_t)d_status & 3)))
                 rc = fail(SELA_HIP_EINVAL, "d_windows must be 8-byte aligned, d_out, d_window_flags and d_status 4-byte aligned");
             return rc;
@@ -2235,20 +2295,16 @@ int sela_hip_decode_windows_whole_device(const uint8_t* d_frames, const uint64_t
         d_workspace, workspace_bytes, stream, true);
 }
 
-// Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows (sela_capi_generic.hip) on the
-// any-length route's leased context and stream, past the coalescer; an open streaming job of the thread is left alone.
+// Host pointers, synchronous: the device call's shape checks (check_windows_shape), then generic_decode_windows
+// (sela_capi_generic.hip) on the any-length route's leased context and stream, past the coalescer; an open streaming job of the
+// thread is left alone.
 static int windows_host_call(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, void* out, uint32_t* window_flags, bool whole)
 {
     sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
-    if (channels == 0 || channels > 8)
-        return fail(SELA_HIP_EINVAL, "channels must be in 1..8: the windows are cut from the on-chip decoder's second pass (more channels: sela_hip_decode, then crop)");
-    if (window_samples == 0 || window_samples > (1u << 24))
-        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
-    if (format != SELA_HIP_WINDOW_I16_INTERLEAVED && format != SELA_HIP_WINDOW_F32_PLANAR)
-        return fail(SELA_HIP_EINVAL, "format must be SELA_HIP_WINDOW_I16_INTERLEAVED or SELA_HIP_WINDOW_F32_PLANAR");
-    if ((uint64_t)n_windows * sela::window_cover(window_samples) >= (1ull << 31))
-        return fail(SELA_HIP_EINVAL, "n_windows * cover must stay below 2^31 (cover = (window_samples + 2046) / 2048 + 1)");
+    const int rc = check_windows_shape(channels, n_windows, window_samples, format, "sela_hip_decode");
+    if (rc != SELA_HIP_OK)
+        return rc;
     if ((n_windows && (!windows || !out)) || !frame_offsets || (n_frames_total && !frames))
         return fail(SELA_HIP_EINVAL, "null pointer");
     if (n_windows == 0)
@@ -2298,24 +2354,15 @@ int sela_hip_decode_windows_i32_whole_device(const uint8_t* d_frames, const uint
         d_window_flags, d_status, d_workspace, workspace_bytes, stream, true);
 }
 
-// Host pointers, synchronous: the device call's checks in its order, then generic_decode_windows on the any-length route's leased
-// context and stream, as sela_hip_decode_windows runs.
+// Host pointers, synchronous: the device call's shape checks (check_windows_i32_shape), then generic_decode_windows on the
+// any-length route's leased context and stream, as sela_hip_decode_windows runs.
 static int windows_i32_host_call(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames_total, uint32_t channels, const sela_hip_window* windows,
     uint32_t n_windows, uint32_t window_samples, uint32_t format, uint32_t sample_bits, void* out, uint32_t* window_flags, bool whole)
 {
     sela::windows_staged_bytes_reset(); // a call that is refused, or has no windows, staged nothing
-    if (channels == 0 || channels > 8)
-        return fail(SELA_HIP_EINVAL, kWindow32Channels);
-    if (window_samples == 0 || window_samples > (1u << 24))
-        return fail(SELA_HIP_EINVAL, "window_samples must be in 1..2^24");
-    if (!window32_format_ok(format))
-        return fail(SELA_HIP_EINVAL, kWindow32Format);
-    if (format == SELA_HIP_WINDOW_F32_PLANAR && (sample_bits == 0 || sample_bits > 32))
-        return fail(SELA_HIP_EINVAL, kWindow32Bits);
-    if ((uint64_t)n_windows * sela::window_cover(window_samples) * channels >= (1ull << 31))
-        return fail(SELA_HIP_EINVAL, kWindow32Product);
-    if (n_windows >= (1u << 24))
-        return fail(SELA_HIP_EINVAL, kWindow32Windows);
+    const int rc = check_windows_i32_shape(channels, n_windows, window_samples, format, sample_bits);
+    if (rc != SELA_HIP_OK)
+        return rc;
     if ((n_windows && (!windows || !out)) || !frame_offsets || (n_frames_total && !frames))
         return fail(SELA_HIP_EINVAL, "null pointer");
     if (n_windows == 0)
@@ -2730,53 +2777,6 @@ int sela_hip_encode_opt(const int16_t* pcm, uint32_t n_frames, uint32_t channels
 
 // ---- a whole track with its tail (the rule, the workspace and the splice: sela_whole.hip) -------------------------
 namespace {
-// The last frame's chain beside the 2048-sample frames' launch: on a stream of the library's own per device, between two events --
-// forked from the caller's stream before the main launch, joined before the splice (the Splitter's plumbing; in a stream that is
-// being captured the side stream joins the capture at the fork and leaves it at the join).  One call at a time enqueues through
-// it; the calls' work still overlaps on the device.
-struct WholeFork {
-    std::mutex mu;
-    hipStream_t side[64] = {};
-    hipEvent_t forked[64] = {}, last_done[64] = {};
-    bool ready(int dev)
-    {
-        if (side[dev])
-            return true;
-        if (hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking) != hipSuccess) {
-            side[dev] = nullptr;
-            return false;
-        }
-        if (hipEventCreateWithFlags(&forked[dev], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&last_done[dev], hipEventDisableTiming) != hipSuccess) {
-            (void)hipStreamDestroy(side[dev]);
-            side[dev] = nullptr;
-            return false;
-        }
-        return true;
-    }
-    void release_all()
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        int before = -1;
-        (void)hipGetDevice(&before);
-        for (int dev = 0; dev < 64; dev++)
-            if (side[dev]) {
-                (void)hipSetDevice(dev);
-                (void)hipStreamSynchronize(side[dev]);
-                (void)hipEventDestroy(forked[dev]);
-                (void)hipEventDestroy(last_done[dev]);
-                (void)hipStreamDestroy(side[dev]);
-                side[dev] = nullptr;
-            }
-        if (before >= 0)
-            (void)hipSetDevice(before);
-    }
-};
-WholeFork& whole_fork()
-{
-    static WholeFork* f = new WholeFork; // (never destroyed: streams outlive the statics' teardown)
-    return *f;
-}
-
 int whole_arguments(uint64_t n_samples, uint32_t channels, const void* pcm, const void* frames, const void* frame_offsets)
 {
     if (channels == 0 || channels > 255)
@@ -2787,6 +2787,55 @@ int whole_arguments(uint64_t n_samples, uint32_t channels, const void* pcm, cons
         return fail(SELA_HIP_EINVAL, "null pointer");
     return SELA_HIP_OK;
 }
+
+// what both whole-track device encoders (this one and 5.25's, from packed PCM) ask behind their own argument checks
+int whole_device_arguments(const void* d_pcm, const void* d_frames, const void* d_status, const void* d_workspace, size_t workspace_bytes, size_t need, const char* sized_by)
+{
+    if (!d_status || !d_workspace)
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
+        return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
+    if (workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, std::string("workspace smaller than ") + sized_by + "()");
+    return SELA_HIP_OK;
+}
+
+// The cases of a whole track, for both device encoders.  `code(main_pieces, first, count, length, out, cap, offsets, status, on)`
+// codes frames [first, first + count) of `length` samples each, with the workspace's pieces for the 2048-sample frames or with the
+// last frame's, into these outputs on that stream.  A track with front frames and a long last frame takes the fork (fork_join):
+// the last frame coded into the workspace (`coded`) on the side stream, the front frames beside it, the splice behind the join.
+extern "C++" template <typename Code>
+int encode_whole_frames(const char* name, uint64_t n_samples, uint32_t channels, const sela::WholeLastWs& coded, uint8_t* d_frames, size_t frames_cap,
+    uint64_t* d_frame_offsets, uint32_t* d_status, hipStream_t st, Code code)
+{
+    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
+    if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
+        return code(false, 0u, 0u, 1u, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    if (tail == 0) // whole frames only: the plain call, its bytes and offsets
+        return code(true, 0u, frames, (uint32_t)SELA_HIP_SAMPLES_PER_FRAME, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
+    if (last == 0) // one frame, of up to 4095 samples: the any-length call as it stands
+        return code(false, 0u, 1u, last_samples, d_frames, frames_cap, d_frame_offsets, d_status, st);
+    const int rc = fork_join(
+        whole_lane(), st, name,
+        [&](hipStream_t side) { return code(false, last, 1u, last_samples, coded.frame, coded.cap, coded.offsets, coded.status, side); },
+        [&] { return code(true, 0u, last, (uint32_t)SELA_HIP_SAMPLES_PER_FRAME, d_frames, frames_cap, d_frame_offsets, d_status, st); });
+    if (rc != SELA_HIP_OK)
+        return rc;
+    return launched(sela::launch_whole_splice(coded, channels, d_frames, frames_cap, d_frame_offsets, last, d_status, st), (std::string(name) + " splice").c_str());
+}
+
+// The tail of both host-pointer encoders: `encode_last(out, cap, offsets)` codes the last frame, which starts behind `whole`
+// frames, as a stream of its own -- offsets {0, bytes} -- at frame_offsets_out[whole]; frame_offsets_out[whole + 1] is patched.
+extern "C++" template <typename EncodeLast>
+int encode_whole_last(uint32_t whole, uint8_t* frames_out, size_t frames_cap, uint64_t* frame_offsets_out, EncodeLast encode_last)
+{
+    const uint64_t before = frame_offsets_out[whole];
+    uint64_t last_offsets[2] = { 0, 0 };
+    const int rc = encode_last(frames_out + before, frames_cap - (size_t)before, last_offsets);
+    frame_offsets_out[whole + 1] = before + last_offsets[1];
+    return rc;
+}
 } // namespace
 
 int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint32_t channels, uint8_t* d_frames, size_t frames_cap, uint64_t* d_frame_offsets,
@@ -2796,62 +2845,21 @@ int sela_hip_encode_whole_device(const int16_t* d_pcm, uint64_t n_samples, uint3
     int rc = encode_options(options, &lossless);
     if (rc == SELA_HIP_OK)
         rc = whole_arguments(n_samples, channels, d_pcm, d_frames, d_frame_offsets);
+    if (rc == SELA_HIP_OK)
+        rc = whole_device_arguments(d_pcm, d_frames, d_status, d_workspace, workspace_bytes, sela::whole_workspace_bytes(n_samples, channels), "sela_hip_encode_whole_workspace_bytes");
     if (rc != SELA_HIP_OK)
         return rc;
-    if (!d_status || !d_workspace)
-        return fail(SELA_HIP_EINVAL, "null pointer");
-    if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
-        return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
-    if (workspace_bytes < sela::whole_workspace_bytes(n_samples, channels))
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_whole_workspace_bytes()");
     if (lossless && g_phase_cycles)
         return fail(SELA_HIP_EINVAL, "SELA_HIP_ENCODE_LOSSLESS while sela_hip_debug_phase_buffer is set: the phase counts are the plain kernels'");
-    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
     sela::Carve carve(d_workspace);
     const sela::WholeWs w = sela::carve_whole(carve, n_samples, channels);
-    if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
-        return encode_i32_device_call(d_pcm, true, 0, channels, 1, d_frames, frames_cap, d_frame_offsets, d_status, w.last_workspace, w.last_bytes, stream, lossless);
-    if (tail == 0) // whole frames only: the plain call, its bytes and offsets
-        return encode_device_call(d_pcm, frames, channels, d_frames, frames_cap, d_frame_offsets, d_status, w.main_workspace, w.main_bytes, nullptr, stream, lossless);
-    const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
-    const int16_t* const d_last_pcm = d_pcm + (size_t)last * SELA_HIP_SAMPLES_PER_FRAME * channels;
-    if (last == 0) // one frame, of up to 4095 samples: the any-length call as it stands
-        return encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_frames, frames_cap, d_frame_offsets, d_status, w.last_workspace, w.last_bytes, stream,
-            lossless);
-    uint8_t* const d_last_frame = w.last_frame;
-    uint64_t* const d_last_offsets = w.last_offsets;
-    uint32_t* const d_last_status = w.last_status;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-        return fail(SELA_HIP_ENODEV, "encode_whole: no current device");
-    WholeFork& wf = whole_fork();
-    std::lock_guard<std::mutex> lock(wf.mu);
-    if (!wf.ready(dev))
-        return fail(SELA_HIP_ENODEV, "encode_whole: no side stream");
-    const hipStream_t side = wf.side[dev];
-    // fork: the side stream follows whatever produced d_pcm, and the workspace's previous user, on the caller's stream
-    hipError_t e = hipEventRecord(wf.forked[dev], st);
-    if (e == hipSuccess)
-        e = hipStreamWaitEvent(side, wf.forked[dev], 0);
-    if (e != hipSuccess)
-        return fail_hip(e, "encode_whole: fork");
-    // the last frame, read in place and coded into the workspace, on the side stream ...
-    rc = encode_i32_device_call(d_last_pcm, true, 1, channels, last_samples, d_last_frame, w.last_cap, d_last_offsets, d_last_status, w.last_workspace, w.last_bytes,
-        side, lossless);
-    if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
-        rc = fail_hip(e, "encode_whole: join");
-    // ... beside it the 2048-sample frames, through the plain call's launches, on the caller's ...
-    if (rc == SELA_HIP_OK)
-        rc = encode_device_call(d_pcm, last, channels, d_frames, frames_cap, d_frame_offsets, d_status, w.main_workspace, w.main_bytes, nullptr, stream, lossless);
-    // ... the join (also after a failure in between: a side stream that has joined a capture must leave it) ...
-    if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
-        rc = fail_hip(e, "encode_whole: join");
-    if (rc != SELA_HIP_OK)
-        return rc;
-    // ... and the last frame behind them
-    return launched(sela::launch_whole_splice(d_last_frame, d_last_offsets, d_last_status, channels, d_frames, frames_cap, d_frame_offsets, last, d_status, st),
-        "encode_whole splice");
+    // the samples read in place: 2048-sample frames through the plain call's launches, every other length through the any-length call's
+    return encode_whole_frames("encode_whole", n_samples, channels, w.last, d_frames, frames_cap, d_frame_offsets, d_status, static_cast<hipStream_t>(stream),
+        [&](bool main_pieces, uint32_t first, uint32_t count, uint32_t length, uint8_t* out, size_t cap, uint64_t* offsets, uint32_t* status, hipStream_t on) {
+            const int16_t* const from = d_pcm + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels;
+            return main_pieces ? encode_device_call(from, count, channels, out, cap, offsets, status, w.main_workspace, w.main_bytes, nullptr, on, lossless)
+                               : encode_i32_device_call(from, true, count, channels, length, out, cap, offsets, status, w.last_workspace, w.last_bytes, on, lossless);
+        });
 }
 
 // Host pointers: the 2048-sample frames through sela_hip_encode_opt's route, the last frame through the any-length route -- which
@@ -2877,12 +2885,10 @@ int sela_hip_encode_whole(const int16_t* pcm, uint64_t n_samples, uint32_t chann
         if (rc != SELA_HIP_OK || !tail)
             return rc;
     }
-    const uint64_t before = frame_offsets_out[whole];
-    uint64_t last_offsets[2] = { 0, 0 };
-    rc = sela::generic_encode(pcm + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels, true, 1, channels, (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME),
-        frames_out + before, frames_cap - (size_t)before, last_offsets, lossless);
-    frame_offsets_out[whole + 1] = before + last_offsets[1];
-    return rc;
+    return encode_whole_last(whole, frames_out, frames_cap, frame_offsets_out, [&](uint8_t* out, size_t cap, uint64_t* last_offsets) {
+        return sela::generic_encode(pcm + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels, true, 1, channels,
+            (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME), out, cap, last_offsets, lossless);
+    });
 }
 
 // ---- the same track from packed 3- or 4-byte PCM (the workspace: sela_whole.hip) ------------------------------------
@@ -2907,70 +2913,31 @@ int whole_pcm_arguments(uint32_t bytes_per_sample, uint64_t n_samples, uint32_t 
 } // namespace
 
 // The launches: k_pcm_unpack and the any-length encoder's three on frames 0 .. F - 2, on `stream`; the last frame's own unpack and
-// three launches on WholeFork's side stream, forked before the main launches and joined behind them; the splice.  The last
-// frame's packed bytes start at byte (F - 1) * 2048 * channels * bytes_per_sample: a multiple of 4, as the unpack asks.
+// three launches on the side stream, forked before the main launches and joined behind them (encode_whole_frames); the splice.
+// The last frame's packed bytes start at byte (F - 1) * 2048 * channels * bytes_per_sample: a multiple of 4, as the unpack asks.
 int sela_hip_encode_whole_pcm_device(const void* d_pcm, uint32_t bytes_per_sample, uint64_t n_samples, uint32_t channels, uint32_t options, uint8_t* d_frames,
     size_t frames_cap, uint64_t* d_frame_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
 {
     bool lossless = false;
-    const int rc0 = whole_pcm_arguments(bytes_per_sample, n_samples, channels, options, &lossless, d_pcm, d_frames, d_frame_offsets);
-    if (rc0 != SELA_HIP_OK)
-        return rc0;
-    if (!d_status || !d_workspace)
-        return fail(SELA_HIP_EINVAL, "null pointer");
-    if (((uintptr_t)d_pcm & 3) || ((uintptr_t)d_frames & 3))
-        return fail(SELA_HIP_EINVAL, "d_pcm and d_frames must be 4-byte aligned");
-    if (workspace_bytes < sela::whole_pcm_workspace_bytes(n_samples, channels))
-        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_encode_whole_pcm_workspace_bytes()");
-    const uint32_t frames = (uint32_t)sela_hip_whole_frames(n_samples), tail = (uint32_t)(n_samples % SELA_HIP_SAMPLES_PER_FRAME);
-    sela::Carve carve(d_workspace);
-    const sela::WholePcmWs w = sela::carve_whole_pcm(carve, n_samples, channels);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    // frames [first, first + count) of `length` samples each, unpacked into `samples` and coded by the any-length encoder's launches
-    const auto encode = [&](uint32_t first, uint32_t count, uint32_t length, int32_t* samples, void* workspace, uint8_t* out, size_t cap, uint64_t* offsets,
-                            uint32_t* status, hipStream_t on) {
-        const uint8_t* const from = static_cast<const uint8_t*>(d_pcm) + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample;
-        hipError_t e = sela::launch_pcm_unpack(from, bytes_per_sample, count, channels, length, samples, on);
-        if (e == hipSuccess)
-            e = sela::launch_encode_i32_device(samples, false, count, channels, length, out, cap, offsets, status, workspace, on, lossless);
-        return launched(e, "encode_whole_pcm launch");
-    };
-    if (frames == 0) // nothing: offsets[0] = 0 and zero status words, as the any-length call leaves them
-        return encode(0, 0, 1, w.last_samples, w.last_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
-    if (tail == 0) // whole frames only: sela_hip_encode_pcm_device's stream
-        return encode(0, frames, SELA_HIP_SAMPLES_PER_FRAME, w.main_samples, w.main_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
-    const uint32_t last = frames - 1, last_samples = (uint32_t)(n_samples - (uint64_t)last * SELA_HIP_SAMPLES_PER_FRAME);
-    if (last == 0) // one frame, of up to 4095 samples
-        return encode(0, 1, last_samples, w.last_samples, w.last_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-        return fail(SELA_HIP_ENODEV, "encode_whole_pcm: no current device");
-    WholeFork& wf = whole_fork();
-    std::lock_guard<std::mutex> lock(wf.mu);
-    if (!wf.ready(dev))
-        return fail(SELA_HIP_ENODEV, "encode_whole_pcm: no side stream");
-    const hipStream_t side = wf.side[dev];
-    // fork: the side stream follows whatever produced d_pcm, and the workspace's previous user, on the caller's stream
-    hipError_t e = hipEventRecord(wf.forked[dev], st);
-    if (e == hipSuccess)
-        e = hipStreamWaitEvent(side, wf.forked[dev], 0);
-    if (e != hipSuccess)
-        return fail_hip(e, "encode_whole_pcm: fork");
-    // the last frame, coded into the workspace, on the side stream ...
-    int rc = encode(last, 1, last_samples, w.last_samples, w.last_workspace, w.last_frame, w.last_cap, w.last_offsets, w.last_status, side);
-    if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
-        rc = fail_hip(e, "encode_whole_pcm: join");
-    // ... beside it the 2048-sample frames on the caller's ...
+    int rc = whole_pcm_arguments(bytes_per_sample, n_samples, channels, options, &lossless, d_pcm, d_frames, d_frame_offsets);
     if (rc == SELA_HIP_OK)
-        rc = encode(0, last, SELA_HIP_SAMPLES_PER_FRAME, w.main_samples, w.main_workspace, d_frames, frames_cap, d_frame_offsets, d_status, st);
-    // ... the join (also after a failure in between: a side stream that has joined a capture must leave it) ...
-    if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
-        rc = fail_hip(e, "encode_whole_pcm: join");
+        rc = whole_device_arguments(d_pcm, d_frames, d_status, d_workspace, workspace_bytes, sela::whole_pcm_workspace_bytes(n_samples, channels),
+            "sela_hip_encode_whole_pcm_workspace_bytes");
     if (rc != SELA_HIP_OK)
         return rc;
-    // ... and the last frame behind them
-    return launched(sela::launch_whole_splice(w.last_frame, w.last_offsets, w.last_status, channels, d_frames, frames_cap, d_frame_offsets, last, d_status, st),
-        "encode_whole_pcm splice");
+    sela::Carve carve(d_workspace);
+    const sela::WholePcmWs w = sela::carve_whole_pcm(carve, n_samples, channels);
+    // the frames unpacked into the workspace's samples and coded by the any-length encoder's launches
+    return encode_whole_frames("encode_whole_pcm", n_samples, channels, w.last, d_frames, frames_cap, d_frame_offsets, d_status, static_cast<hipStream_t>(stream),
+        [&](bool main_pieces, uint32_t first, uint32_t count, uint32_t length, uint8_t* out, size_t cap, uint64_t* offsets, uint32_t* status, hipStream_t on) {
+            const uint8_t* const from = static_cast<const uint8_t*>(d_pcm) + (size_t)first * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample;
+            int32_t* const samples = main_pieces ? w.main_samples : w.last_samples;
+            hipError_t e = sela::launch_pcm_unpack(from, bytes_per_sample, count, channels, length, samples, on);
+            if (e == hipSuccess)
+                e = sela::launch_encode_i32_device(samples, false, count, channels, length, out, cap, offsets, status, main_pieces ? w.main_workspace : w.last_workspace, on,
+                    lossless);
+            return launched(e, "encode_whole_pcm launch");
+        });
 }
 
 // Host pointers: frames 0 .. F - 2 in sela_hip_encode_pcm's chunks, the last frame as one more chunk of its own length, on the
@@ -2993,12 +2960,10 @@ int sela_hip_encode_whole_pcm(const void* pcm, uint32_t bytes_per_sample, uint64
         if (rc != SELA_HIP_OK)
             return rc;
     }
-    const uint64_t before = frame_offsets_out[whole];
-    uint64_t last_offsets[2] = { 0, 0 };
-    rc = sela::generic_encode_pcm(bytes + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample, bytes_per_sample, 1, channels,
-        (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME), lossless, frames_out + before, frames_cap - (size_t)before, last_offsets);
-    frame_offsets_out[whole + 1] = before + last_offsets[1];
-    return rc;
+    return encode_whole_last(whole, frames_out, frames_cap, frame_offsets_out, [&](uint8_t* out, size_t cap, uint64_t* last_offsets) {
+        return sela::generic_encode_pcm(bytes + (size_t)whole * SELA_HIP_SAMPLES_PER_FRAME * channels * bytes_per_sample, bytes_per_sample, 1, channels,
+            (uint32_t)(n_samples - (uint64_t)whole * SELA_HIP_SAMPLES_PER_FRAME), lossless, out, cap, last_offsets);
+    });
 }
 
 namespace {
@@ -3058,8 +3023,8 @@ size_t sela_hip_decode_whole_workspace_bytes(uint32_t max_frames, uint32_t chann
 extern "C++" {
 namespace {
 // sela_hip_decode_whole_device / sela_hip_decode_whole_payload_device: the forms of the any-length calls (FramesForm, PayloadForm),
-// the window calls' channels.  The launch: the plan on `stream`; the last frame's two kernels on WholeFork's side stream, forked
-// behind the plan; the 2048-sample decoder on `stream` beside them, on the plan's count; the join.
+// the window calls' channels.  The launch: the plan on `stream`; the last frame's two kernels on the whole-track lane's side
+// stream, forked behind the plan; the 2048-sample decoder on `stream` beside them, on the plan's count; the join (fork_join).
 template <typename Form>
 int decode_whole_call(const Form& form, uint32_t channels, int16_t* d_pcm_out, uint64_t pcm_capacity, uint64_t* d_n_samples, uint32_t* d_status, void* d_workspace,
     size_t workspace_bytes, void* stream)
@@ -3084,31 +3049,18 @@ int decode_whole_call(const Form& form, uint32_t channels, int16_t* d_pcm_out, u
             if (rc != SELA_HIP_OK || max_frames == 0)
                 return rc;
             int dev = -1;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-                return fail(SELA_HIP_ENODEV, "decode_whole: no current device");
-            WholeFork& wf = whole_fork();
-            std::lock_guard<std::mutex> lock(wf.mu);
-            if (!wf.ready(dev))
-                return fail(SELA_HIP_ENODEV, "decode_whole: no side stream");
-            const hipStream_t side = wf.side[dev];
-            hipError_t e = hipEventRecord(wf.forked[dev], st);
-            if (e == hipSuccess)
-                e = hipStreamWaitEvent(side, wf.forked[dev], 0);
-            if (e != hipSuccess)
-                return fail_hip(e, "decode_whole: fork");
-            // the last frame on the side stream: memory disjoint from what the 2048-sample decoder writes ...
-            rc = launched(sela::launch_decode_whole_tail(d_frames, d_frame_offsets, channels, w, d_pcm_out, d_status, side), "decode_whole tail");
-            if (rc == SELA_HIP_OK && (e = hipEventRecord(wf.last_done[dev], side)) != hipSuccess)
-                rc = fail_hip(e, "decode_whole: join");
-            // ... beside it frames 0 .. n - 2 (or all n), on the plan's count; the status words are the plan's, so they are not zeroed
-            // (no priorities: the launch does not have the device to itself) ...
-            if (rc == SELA_HIP_OK)
-                rc = launched(sela::launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, w.fast_workspace, st, nullptr, nullptr, nullptr,
-                                  g_recurrence_form, 0, w.fast_frames, false),
-                    "decode_whole launch");
-            // ... and the join (also after a failure in between: a side stream that has joined a capture must leave it)
-            if ((e = hipStreamWaitEvent(st, wf.last_done[dev], 0)) != hipSuccess && rc == SELA_HIP_OK)
-                rc = fail_hip(e, "decode_whole: join");
+            rc = fork_join(
+                whole_lane(), st, "decode_whole",
+                // the last frame on the side stream: memory disjoint from what the 2048-sample decoder writes ...
+                [&](hipStream_t side) { return launched(sela::launch_decode_whole_tail(d_frames, d_frame_offsets, channels, w, d_pcm_out, d_status, side), "decode_whole tail"); },
+                // ... beside it frames 0 .. n - 2 (or all n), on the plan's count; the status words are the plan's, so they are not zeroed
+                // (no priorities: the launch does not have the device to itself)
+                [&] {
+                    return launched(sela::launch_decode(d_frames, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, w.fast_workspace, st, nullptr, nullptr, nullptr,
+                                        g_recurrence_form, 0, w.fast_frames, false),
+                        "decode_whole launch");
+                },
+                &dev);
             if (rc == SELA_HIP_OK && !stream_is_capturing(st))
                 flights().note(dev, st);
             return rc;
@@ -3610,7 +3562,3 @@ uint32_t sela_hip_index_frames(const uint8_t* frames, size_t frames_bytes, uint3
 }
 
 } // extern "C"
-
-namespace sela {
-void whole_shutdown() { whole_fork().release_all(); }
-} // namespace sela

@@ -105,14 +105,17 @@ hipError_t launch_decode_whole_tail(const uint8_t* d_frames, const uint64_t* d_f
     uint32_t* d_status, hipStream_t stream);
 
 // ---- sela_whole.hip: a whole track with its tail ---------------------------------------------------------------
+struct WholeLastWs { // the end of both whole-track encoders' workspaces: the last frame as coded, for the splice
+    uint8_t* frame;    // its bytes, and their room
+    size_t cap;
+    uint64_t* offsets; // its two offsets ...
+    uint32_t* status;  // ... and its four status words
+};
 struct WholeWs { // the workspace of sela_hip_encode_whole_device
     void* main_workspace;   // the 2048-sample frames' workspace (encode_workspace_bytes), and its bytes
     void* last_workspace;   // the last frame's any-length workspace (encode_i32_device_workspace_bytes), and its bytes
     size_t main_bytes, last_bytes;
-    uint8_t* last_frame;    // the last frame's bytes as coded, and their room
-    size_t last_cap;
-    uint64_t* last_offsets; // its two offsets ...
-    uint32_t* last_status;  // ... and its four status words
+    WholeLastWs last;
 };
 WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels); // (arguments that whole_workspace_bytes does not refuse)
 size_t whole_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at = nullptr); // SIZE_MAX for what the call refuses
@@ -121,21 +124,17 @@ struct WholePcmWs { // the workspace of sela_hip_encode_whole_pcm_device (DESIGN
     void* main_workspace;
     int32_t* last_samples;  // the last frame unpacked, and its any-length workspace
     void* last_workspace;
-    uint8_t* last_frame;    // the last frame's bytes as coded, and their room
-    size_t last_cap;
-    uint64_t* last_offsets; // its two offsets ...
-    uint32_t* last_status;  // ... and its four status words
+    WholeLastWs last;
 };
 WholePcmWs carve_whole_pcm(Carve& c, uint64_t max_samples, uint32_t channels); // (arguments that whole_pcm_workspace_bytes does not refuse)
 size_t whole_pcm_workspace_bytes(uint64_t max_samples, uint32_t channels, Carve* at = nullptr); // SIZE_MAX for what the call refuses
-hipError_t launch_whole_splice(const uint8_t* d_last_frame, const uint64_t* d_last_offsets, const uint32_t* d_last_status, uint32_t channels, uint8_t* d_frames,
-    uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last, uint32_t* d_status, hipStream_t stream);
+hipError_t launch_whole_splice(const WholeLastWs& coded, uint32_t channels, uint8_t* d_frames, uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last,
+    uint32_t* d_status, hipStream_t stream);
 
 // ---- sela_capi.hip: what the any-length route's host side shares with the boundary --------------------------------------------
 int report_error(int code, const std::string& what);   // sets the thread's last error, returns code
 int report_hip_error(hipError_t e, const char* where); // (ENOMEM for an allocation failure, ENODEV otherwise)
 int device_ready();                                    // SELA_HIP_OK, or ENODEV reported: there is no CPU fallback
-void whole_shutdown();                                 // sela_hip_encode_whole_device's side streams and events (sela_hip_shutdown)
 inline bool frame_offsets_ascend(const uint64_t* frame_offsets, uint32_t n_frames)
 {
     for (uint32_t f = 0; f < n_frames; f++)

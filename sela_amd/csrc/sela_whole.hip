@@ -20,8 +20,20 @@ constexpr uint64_t kFrame = SELA_HIP_SAMPLES_PER_FRAME;
 // the longest last frame of any track of at most max_samples samples per channel (0: no frame)
 static uint32_t longest_last_frame(uint64_t max_samples) { return (uint32_t)std::min<uint64_t>(max_samples, 2 * kFrame - 1); }
 
-// The 2048-sample frames' workspace | the last frame's any-length workspace | the last frame as coded | its head: two offsets
-// and four status words.  (Every shorter track is served from the same pieces: the sizes grow with the frames and with the length.)
+// What both workspaces end in: the last frame as coded, in room for `bound_bytes`, and its head -- two offsets, and the four
+// status words behind them.
+static WholeLastWs carve_whole_last(Carve& c, size_t bound_bytes)
+{
+    WholeLastWs w;
+    w.cap = (size_t)workspace_up(bound_bytes);
+    w.frame = c.take<uint8_t>(w.cap);
+    w.offsets = c.take<uint64_t>(2 + 2);
+    w.status = reinterpret_cast<uint32_t*>(w.offsets + 2);
+    return w;
+}
+
+// The 2048-sample frames' workspace | the last frame's any-length workspace | the last frame as coded | its head.  (Every
+// shorter track is served from the same pieces: the sizes grow with the frames and with the length.)
 WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels)
 {
     const uint32_t frames = (uint32_t)sela_hip_whole_frames(max_samples), last = std::max(longest_last_frame(max_samples), 1u);
@@ -35,10 +47,7 @@ WholeWs carve_whole(Carve& c, uint64_t max_samples, uint32_t channels)
         encode_workspace_bytes(frames, channels, &main_ws);
         encode_i32_device_workspace_bytes(1, channels, last, false, &last_ws);
     }
-    w.last_cap = (size_t)workspace_up(generic_encode_bound_bytes(1, channels, last));
-    w.last_frame = c.take<uint8_t>(w.last_cap);
-    w.last_offsets = c.take<uint64_t>(2 + 2); // (the head: the offsets, and the status words behind them)
-    w.last_status = reinterpret_cast<uint32_t*>(w.last_offsets + 2);
+    w.last = carve_whole_last(c, generic_encode_bound_bytes(1, channels, last));
     return w;
 }
 
@@ -67,10 +76,7 @@ WholePcmWs carve_whole_pcm(Carve& c, uint64_t max_samples, uint32_t channels)
     w.last_workspace = last_ws.base();
     if (c.listing())
         encode_i32_device_workspace_bytes(1, channels, last, false, &last_ws);
-    w.last_cap = (size_t)workspace_up(sela_hip_encode_pcm_bound_bytes(1, channels, last, 4));
-    w.last_frame = c.take<uint8_t>(w.last_cap);
-    w.last_offsets = c.take<uint64_t>(2 + 2); // (the head: the offsets, and the status words behind them)
-    w.last_status = reinterpret_cast<uint32_t*>(w.last_offsets + 2);
+    w.last = carve_whole_last(c, sela_hip_encode_pcm_bound_bytes(1, channels, last, 4));
     return w;
 }
 
@@ -106,13 +112,13 @@ __global__ __launch_bounds__(kSpliceThreads) void k_splice_tail(const uint32_t* 
         out[i] = last_frame[i];
 }
 
-hipError_t launch_whole_splice(const uint8_t* d_last_frame, const uint64_t* d_last_offsets, const uint32_t* d_last_status, uint32_t channels, uint8_t* d_frames,
-    uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last, uint32_t* d_status, hipStream_t stream)
+hipError_t launch_whole_splice(const WholeLastWs& coded, uint32_t channels, uint8_t* d_frames, uint64_t frames_cap, uint64_t* d_frame_offsets, uint32_t last,
+    uint32_t* d_status, hipStream_t stream)
 {
     // (a stereo frame of 4095 samples is some 12 KB: a dozen workgroups; wide frames of many channels stride)
     const uint32_t grid = std::min(channels * 6u, 240u);
-    hipLaunchKernelGGL(k_splice_tail, dim3(grid), dim3(kSpliceThreads), 0, stream, reinterpret_cast<const uint32_t*>(d_last_frame), d_last_offsets, d_last_status,
-        d_frames, frames_cap, d_frame_offsets, last, d_status);
+    hipLaunchKernelGGL(k_splice_tail, dim3(grid), dim3(kSpliceThreads), 0, stream, reinterpret_cast<const uint32_t*>(coded.frame), coded.offsets, coded.status, d_frames,
+        frames_cap, d_frame_offsets, last, d_status);
     return hipGetLastError();
 }
 

@@ -345,6 +345,53 @@ def test_a_captured_call_reads_the_stream_at_replay(gpu):  # noqa: F811
         assert np.array_equal(replayed, eager) and np.array_equal(replayed[:n], pcm_of(n, ch, k))
 
 
+def test_an_encode_and_a_decode_fork_in_one_capture(gpu):  # noqa: F811
+    """WholeEncoder.encode, then WholeDecoder.decode on the encoder's own buffers: two call families through the library's one
+    side stream back to back -- eager on one stream, then both in one capture, replayed once on a second track.  Two frames, the
+    last of 2048 + 777 samples: the smallest track with which both calls fork."""
+    torch, ch, n = gpu, 2, 2 * B + 777
+    tracks = [pcm_of(n, ch, 0), pcm_of(n, ch, 1)]
+    for lossless in (True, False):
+        enc, dec = codec.WholeEncoder(n, ch, lossless=lossless), codec.WholeDecoder(2, ch)
+        d_x = torch.zeros((n, ch), dtype=torch.int16, device="cuda")
+
+        def both():
+            frames, offsets, _ = enc.encode(d_x)
+            return dec.decode(frames, offsets, 2)
+
+        def poison():
+            enc.frames.fill_(0xA5), enc.offsets.fill_(-1), enc.status.fill_(-1)
+            dec.pcm.fill_(SENT16), dec.n_samples.fill_(-1), dec.status.fill_(-1)
+
+        def results(out, out_n):
+            return out[:n].cpu().numpy().copy(), int(out_n.item()), enc.status.cpu().numpy().copy(), dec.status.cpu().numpy().copy()
+
+        work, eager = torch.cuda.Stream(), []
+        for x in tracks:  # form 1: both calls uncaptured on one stream
+            d_x.copy_(torch.from_numpy(np.array(x, order="C")))
+            poison()
+            work.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(work):
+                out, out_n = both()
+            torch.cuda.current_stream().wait_stream(work)
+            torch.cuda.synchronize()
+            eager.append(results(out, out_n))
+            assert eager[-1][1] == n, lossless
+            assert not lossless or np.array_equal(eager[-1][0], x)
+        d_x.copy_(torch.from_numpy(np.array(tracks[0], order="C")))
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):  # form 2: both calls in one capture ...
+            out, out_n = both()
+        d_x.copy_(torch.from_numpy(np.array(tracks[1], order="C")))  # ... replayed once, on the second track
+        poison()
+        graph.replay()
+        torch.cuda.synchronize()
+        pcm, pcm_n, enc_status, dec_status = results(out, out_n)
+        assert pcm_n == n and np.array_equal(enc_status, eager[1][2]) and np.array_equal(dec_status, eager[1][3]), lossless
+        assert np.array_equal(pcm, tracks[1] if lossless else eager[1][0]), lossless
+
+
 # ---- the host call --------------------------------------------------------------------------------------------------------------------
 def host_equals_device(torch, n, ch, k):
     frames, offs = stream_of(n, ch, k)
