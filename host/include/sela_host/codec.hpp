@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "sela_host/files.hpp"
+#include "sela_host/digest.hpp"
 #include "sela_host/levels.hpp"
 
 namespace sela {
@@ -137,6 +138,13 @@ struct WideLevelReport {
 WideLevelReport measureWideFile(const std::string& selaPath);
 // formatLevelReport's lines, with the integers of the wide records; no GPU needed.
 std::string formatLevelReport(const WideLevelReport& report);
+
+// ---- digest: does this .sela still decode to that audio? -------------------------------------------------------
+// digestFile() reads the file the way verifyFile does (the frames it really holds; a --keep-tail file's long last frame as it
+// stands) and asks sela_hip_digest for the CRC-32 of the PCM it decodes to: computed on the GPU, nothing decoded into host
+// memory.  With a WAV named, the host's own CRC-32 of its data chunk is set beside it -- cut to the samples the .sela holds, as
+// verifyFile cuts it.  A 24- or 32-bit .sela is refused by name: the digest is that of 16-bit samples.
+DigestReport digestFile(const std::string& selaPath, const std::string& wavPath = std::string());
 
 // ---- many files, all GPUs of the node ------------------------------------------------------------------
 // BASELINE.json configs[3]: an album's tracks are one index space of frames, cut into contiguous balanced

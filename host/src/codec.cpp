@@ -1105,6 +1105,48 @@ std::string formatLevelReport(const LevelReport& r)
     return out;
 }
 
+// ---- digest ----------------------------------------------------------------------------------------------------------------
+DigestReport digestFile(const std::string& selaPath, const std::string& wavPath)
+{
+    const SelaInfo info = probeSela(selaPath);
+    if (info.header.bitsPerSample == 24 || info.header.bitsPerSample == 32)
+        throw data::Exception("Digest: " + selaPath + " holds " + std::to_string(info.header.bitsPerSample)
+            + "-bit samples: the digest is taken of 16-bit streams only");
+    const uint32_t channels = info.header.channels;
+    DigestReport r;
+    r.channels = channels;
+    // the frames the file really holds (as verifyFile finds them)
+    std::vector<uint8_t> payload(info.payload + 8);
+    if (info.payload)
+        sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
+    std::vector<uint64_t> offsets(info.announced + 1, 0);
+    const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
+    if (sela_hip_digest(payload.data(), offsets.data(), found, channels, nullptr, &r.crc32, &r.bytes) != SELA_HIP_OK)
+        gpuFailure("Digest");
+    r.frames = found;
+    if (wavPath.empty())
+        return r;
+    const WavInfo wav = probeWav(wavPath);
+    if (wav.channels != channels)
+        throw data::Exception("Digest: " + std::to_string(wav.channels) + " channels in the .wav, " + std::to_string(channels) + " in the .sela");
+    // the part of the data chunk the .sela can hold: whole samples, and no more of them than its frames have
+    const uint64_t sampleBytes = (uint64_t)channels * 2;
+    r.haveWav = true;
+    r.wavBytes = std::min<uint64_t>(wav.dataBytes / sampleBytes * sampleBytes, r.bytes);
+    r.wavTailBytes = wav.dataBytes - r.wavBytes;
+    Crc32 crc;
+    std::vector<uint8_t> piece((size_t)std::min<uint64_t>(r.wavBytes, (uint64_t)4 << 20) + 8);
+    const sela_host::PosixFile in = sela_host::PosixFile::openForRead(wavPath);
+    for (uint64_t at = 0; at < r.wavBytes;) {
+        const size_t n = (size_t)std::min<uint64_t>(r.wavBytes - at, (uint64_t)4 << 20);
+        in.readAt(piece.data(), n, wav.dataOffset + at);
+        crc.update(piece.data(), n);
+        at += n;
+    }
+    r.wavCrc32 = crc.value();
+    return r;
+}
+
 // ---- many files by path: every GPU worker reads, codes and writes its own pieces ----------------------------------
 namespace {
 

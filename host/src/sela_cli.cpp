@@ -28,6 +28,10 @@
 //   sela_mi355x -M in.sela             the same by the file's own header: a 16-bit file exactly as -m, a 24- or 32-bit file through
 //                                      sela_hip_levels_i32 -- the integers of its samples as they are (the sum of squares in 128
 //                                      bits, printed whole), dBFS against the file's own full scale; a --whole file as it stands
+//   sela_mi355x -c in.sela [in.wav]    digest: the CRC-32 (zlib's, `crc32`'s) of the PCM in.sela decodes to -- taken on the GPU, nothing
+//                                      decoded into memory -- its byte count and the frame count; with in.wav also the CRC-32 of its
+//                                      data chunk (cut to whole frames unless in.sela is a --keep-tail file, as -v cuts it), exit 0
+//                                      only if the two agree, else 3.  A 24- or 32-bit .sela is refused by name (exit 1)
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -71,6 +75,8 @@ int usage(const std::string& program)
               << program << " -m path/to/input.sela\n\n"
               << "Measuring a 16-, 24- or 32-bit file (as -m, by the file's own header; dBFS against the file's own full scale):\n"
               << program << " -M path/to/input.sela\n\n"
+              << "The CRC-32 of the audio a 16-bit file decodes to (with a .wav: held against the CRC-32 of its data chunk):\n"
+              << program << " -c path/to/input.sela [path/to/input.wav]\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -272,6 +278,14 @@ int run(int argc, char** argv)
         std::cout << "Measuring: " << argv[2] << std::endl;
         std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
         return 0;
+    }
+    if (verb == "-c") {
+        if (argc != 3 && argc != 4)
+            return usage(program);
+        std::cout << "Digest: " << argv[2] << std::endl;
+        const sela::DigestReport report = sela::digestFile(std::string(argv[2]), argc == 4 ? std::string(argv[3]) : std::string());
+        std::cout << sela::formatDigestReport(report) << std::flush;
+        return report.agree() ? 0 : 3;
     }
     if (verb == "-M") {
         if (argc != 3)

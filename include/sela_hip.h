@@ -1027,6 +1027,70 @@ int sela_hip_levels_samples_i32_device(const int32_t* d_samples /* [n_frames][ch
  * returns 0 and asks for no device. */
 int sela_hip_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level32* levels /* [n_frames][channels] */);
 
+/* ---- digest: the CRC-32 of the PCM a stream decodes to ------------------------------------------------------------
+ * "Does this stream still decode to that audio?", asked without holding the audio: the CRC-32 everybody computes (IEEE 802.3,
+ * reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF: zlib.crc32, `crc32`, `cksum -a crc32`) of the bytes
+ * sela_hip_decode_n_device writes, without writing them -- on the 2048-sample route (up to eight channels) in one kernel that
+ * stores no PCM at all.  Scope: the domain of sela_hip_decode_n_device (16-bit interleaved output, frames of 0 .. 65535 samples,
+ * 1 .. 255 channels, the long last frame of a whole-track stream included).
+ *   d_digests[f]   .crc32: the CRC-32 of exactly the samples * channels * 2 bytes sela_hip_decode_n_device writes for frame f with
+ *                  the same d_frames, d_frame_offsets, n_frames, channels and stride (little-endian int16, interleaved: its
+ *                  narrowing of wider samples, its combine of difference subframes, its route, its zeros for a channel that ends
+ *                  early); .samples: sample_offsets[f + 1] - sample_offsets[f].  A frame of 0 samples has crc32 0.  8-byte aligned.
+ *   d_track        uint64[2], 8-byte aligned, not NULL: [0] (its low 32 bits; the high ones 0) the CRC-32 of all frames' bytes in
+ *                  order, [1] their number.  For a stream of whole frames [0] is zlib.crc32 of the WAV data chunk a decode of the
+ *                  file writes; for a whole-track (keep-tail) file that of the whole original data chunk, where the file decodes
+ *                  losslessly.  Written on the device from the records: crc(A | B) = crc(A) * x^(8 |B|) ^ crc(B) in GF(2)[x] mod P.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_n_device leaves them for the same frames;
+ *                  [2] is 0.  sela_hip_decode_n_status_error() applies unchanged; where it gives non-zero, or SELA_HIP_FLAG_STRIDE
+ *                  is set, the records and d_track are not defined.  n_frames = 0 writes the status words, d_track = {0, 0} (and
+ *                  d_sample_offsets[0] = 0 where given) and nothing else.
+ * d_workspace: sela_hip_digest_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at a time may use it.  With up(b) = b rounded up to a
+ * multiple of 256 the size is
+ *     sela_hip_levels_workspace_bytes(max_frames, channels, stride)                        the levels call's two pieces, its alignment included
+ *   + up(4 * max(max_frames * ceil(2 * channels * stride / 32768), 1))                     a word per (frame, slice of 32 KiB of its PCM)
+ *   + up(4 * min(max(ceil(max_frames / 256), 1), 256))                                     the track fold's word per workgroup
+ * and SIZE_MAX where sela_hip_levels_workspace_bytes() is.
+ * Arguments, errors and their order are sela_hip_levels_device's (SELA_HIP_EINVAL: channels outside 1..255, stride 0, n_frames *
+ * channels at 2^31 or more, a null pointer -- d_sample_offsets may be NULL, d_digests only where there are frames, d_track never
+ * -- a d_digests or d_track that is not 8-byte aligned, a null or misaligned d_frames / d_payload; SELA_HIP_ECAPACITY: a smaller
+ * workspace), found before any device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no
+ * allocation, no host wait, no host read of device data, so a stream being captured into a HIP graph may take either call.
+ * Apart from d_digests[0 .. n_frames), d_track, d_sample_offsets, d_status and the workspace (the payload call: its two index
+ * outputs too) nothing is written.  The 24- and 32-bit family (sela_hip_decode_pcm_device's bytes) has no digest yet.
+ * (The record's struct tag and the host call share a name, so C++ code says `struct sela_hip_digest`; sela_hip_digest_record
+ * names the type in both languages.) */
+struct sela_hip_digest { /* 8 bytes */
+    uint32_t crc32;   /* CRC-32 of the frame's interleaved int16 bytes */
+    uint32_t samples; /* samples per channel of the frame */
+};
+typedef struct sela_hip_digest sela_hip_digest_record;
+size_t sela_hip_digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_digest_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    struct sela_hip_digest* d_digests /* [n_frames] */, uint64_t* d_track /* [2] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */,
+    uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written); d_track covers the frames found. */
+int sela_hip_digest_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames whose track words are folded on the host with sela_hip_crc32_combine(): returns
+ * what sela_hip_decode returns for the stream (0: the records and the two track figures are valid; digests, track_crc32 and
+ * track_bytes may each be NULL).  Runs where sela_hip_levels runs: the calling thread's any-length context and its own stream, past
+ * the coalescer; an open streaming job of the thread is left alone.  n_frames = 0 gives 0 / 0 and asks for no device. */
+int sela_hip_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests /* [n_frames] or NULL */,
+    uint32_t* track_crc32, uint64_t* track_bytes);
+/* crc32(A | B) from crc32(A), crc32(B) and the length of B in bytes, any length: zlib's crc32_combine.  Pure host arithmetic. */
+uint32_t sela_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* The same lanes, waves and folds on bytes that already lie in device memory -- a capture buffer, a WAV's data chunk, a decode's
+ * output: d_out[0] = the CRC-32 of d_bytes[0 .. n_bytes), d_out[1] = n_bytes; any length, any alignment of d_bytes (d_out: 8-byte).
+ * d_workspace: sela_hip_crc32_workspace_bytes(n_bytes) bytes (a word per slice of max(32 KiB, n_bytes / 4096), so at most 17 KiB).
+ * SELA_HIP_EINVAL: d_out or d_workspace NULL, d_bytes NULL with n_bytes != 0, a misaligned d_out; SELA_HIP_ECAPACITY: a smaller
+ * workspace.  Asynchronous on `stream`, two launches, capturable; only d_out and the workspace are written. */
+size_t sela_hip_crc32_workspace_bytes(uint64_t n_bytes);
+int sela_hip_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* d_out /* [2] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- a whole track from packed 3- or 4-byte PCM: the tail of a 24- or 32-bit file kept ----------------------------
  * sela_hip_encode_whole* ("a whole track", above) for the containers of sela_hip_encode_pcm*: d_pcm is little-endian interleaved
  * [N][channels] samples of bytes_per_sample = 3 or 4 bytes.  The layout rule is the one sela_hip_whole_frames / sela_hip_whole_frame

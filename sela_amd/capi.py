@@ -57,6 +57,8 @@ EXPORTS = [
     "sela_hip_levels_workspace_bytes", "sela_hip_levels_device", "sela_hip_levels_payload_device", "sela_hip_levels",
     "sela_hip_levels_i32_workspace_bytes", "sela_hip_levels_i32_device", "sela_hip_levels_payload_i32_device", "sela_hip_levels_samples_i32_workspace_bytes",
     "sela_hip_levels_samples_i32_device", "sela_hip_levels_i32",
+    "sela_hip_digest_workspace_bytes", "sela_hip_digest_device", "sela_hip_digest_payload_device", "sela_hip_digest", "sela_hip_crc32_combine",
+    "sela_hip_crc32_workspace_bytes", "sela_hip_crc32_device",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED, WINDOW_PCM32_INTERLEAVED = 2, 3, 4  # (sela_hip_decode_windows_i32*: these and F32_PLANAR)
@@ -70,7 +72,7 @@ DEBUG_EXPORTS = [
     "sela_hip_debug_reissued_feeds", "sela_hip_debug_contexts_created", "sela_hip_debug_decode_recurrence", "sela_hip_debug_coalesced", "sela_hip_debug_verify_lds_bytes",
     "sela_hip_debug_verify_i32_fallback_frames", "sela_hip_debug_window_lds_bytes", "sela_hip_debug_windows_staged_bytes",
     "sela_hip_debug_workspace_pieces", "sela_hip_debug_pcm_chunk_frames", "sela_hip_debug_verify_pcm_fallback_frames",
-    "sela_hip_debug_levels_lds_bytes", "sela_hip_debug_levels_i32_fallback_frames",
+    "sela_hip_debug_levels_lds_bytes", "sela_hip_debug_levels_i32_fallback_frames", "sela_hip_debug_digest_lds_bytes",
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
@@ -304,6 +306,21 @@ def lib() -> C.CDLL:
     L.sela_hip_debug_levels_i32_fallback_frames.restype = C.c_longlong
     L.sela_hip_debug_levels_lds_bytes.argtypes = [u32]
     L.sela_hip_debug_levels_lds_bytes.restype = sz
+    # digest
+    L.sela_hip_digest_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_digest_workspace_bytes.restype = sz
+    L.sela_hip_digest_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_digest_payload_device.argtypes = [vp, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_digest.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.sela_hip_crc32_device.argtypes = [vp, C.c_uint64, vp, vp, sz, vp]
+    for name in ("sela_hip_digest_device", "sela_hip_digest_payload_device", "sela_hip_digest", "sela_hip_crc32_device"):
+        getattr(L, name).restype = C.c_int
+    L.sela_hip_crc32_combine.argtypes = [u32, u32, C.c_uint64]
+    L.sela_hip_crc32_combine.restype = u32
+    L.sela_hip_crc32_workspace_bytes.argtypes = [C.c_uint64]
+    L.sela_hip_crc32_workspace_bytes.restype = sz
+    L.sela_hip_debug_digest_lds_bytes.argtypes = [u32]
+    L.sela_hip_debug_digest_lds_bytes.restype = sz
     L.sela_hip_debug_pcm_chunk_frames.argtypes = [u32]
     L.sela_hip_debug_pcm_chunk_frames.restype = None
     L.sela_hip_encode_status_error.argtypes = [vp]

@@ -436,6 +436,100 @@ def track_levels(levels: np.ndarray) -> np.ndarray:
     return out
 
 
+# struct sela_hip_digest (include/sela_hip.h): 8 bytes per frame
+DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("samples", "<u4")])
+
+
+class Digester(_DeviceCall):
+    """sela_hip_digest_device: the CRC-32 (zlib.crc32) of the int16 PCM DecoderN.decode would write, per frame and for the whole
+    track, on the device.  Owns its records, its two track words and its workspace on the current device (or
+    `device`); every call is asynchronous on the current stream, one serial chain, and overwrites them -- so it can be captured
+    into a graph.  No PCM is written: on the 2048-sample route of up to eight channels not even into the workspace."""
+
+    _call, _judge = "digest", staticmethod(decode_n_status_error)
+
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames]: crc32 | samples << 32; the track: [crc32, bytes]
+        self.digests = torch.zeros(self.max_frames, dtype=torch.int64, device=self.device)
+        self.track = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    route = _DeviceCall._route
+
+    def digest(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> (records int64 [n_frames],
+        track int64 [2]: the CRC-32 of all frames' bytes and their number), views of the digester's own buffers (records(): as
+        DIGEST_DTYPE)."""
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_digest_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.digests.data_ptr(), self.track.data_ptr(),
+            self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.digests[:n_frames], self.track
+
+    def digest_payload(self, payload, max_frames=None):
+        """Index and digest a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device.  -> (records [max_frames], track [2], count int32 [1]): records up to count[0] are the stream's, the
+        track covers those.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_digest_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.digests.data_ptr(), self.track.data_ptr(),
+            self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
+            self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.digests[:max_frames], self.track, self.count
+
+    @staticmethod
+    def records(digests) -> np.ndarray:
+        """Waits for the last call -> a host copy of records as DIGEST_DTYPE [n_frames]."""
+        host = np.ascontiguousarray(digests.cpu().numpy())
+        return host.view(DIGEST_DTYPE).reshape(host.shape)
+
+    def track_words(self):
+        """Waits for the last call -> (the track's CRC-32, its bytes)."""
+        t = self.track.cpu().numpy()
+        return int(t[0]) & 0xFFFFFFFF, int(t[1])
+
+
+def digest_host(frames: np.ndarray, offsets: np.ndarray, channels: int):
+    """sela_hip_digest on numpy arrays -> (records DIGEST_DTYPE [n_frames], the track's CRC-32, its bytes)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    out = np.zeros(n_frames, DIGEST_DTYPE)
+    crc, total = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    capi.check(lib.sela_hip_digest(fr.ctypes.data, offs.ctypes.data, n_frames, channels, out.ctypes.data, crc.ctypes.data, total.ctypes.data))
+    return out, int(crc[0]), int(total[0])
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """sela_hip_crc32_combine: crc32(A + B) from crc32(A), crc32(B) and len(B) -- pure host arithmetic."""
+    return int(capi.lib().sela_hip_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b))
+
+
+def crc32_device(data, n_bytes=None, offset: int = 0, workspace=None, out=None):
+    """sela_hip_crc32_device: the CRC-32 of n_bytes bytes of a contiguous cuda tensor from byte `offset` on (default: all of it)
+    -> int64 cuda tensor [2] (`out`, or a new one): the CRC-32 and the byte count; asynchronous on the current stream."""
+    import torch
+
+    assert data.is_cuda and data.is_contiguous()
+    total = data.numel() * data.element_size()
+    n_bytes = total - offset if n_bytes is None else n_bytes
+    assert 0 <= offset and offset + n_bytes <= total
+    lib = capi.lib()
+    need = int(lib.sela_hip_crc32_workspace_bytes(n_bytes))
+    with torch.cuda.device(data.device):
+        if out is None:
+            out = torch.zeros(2, dtype=torch.int64, device=data.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.numel() >= 2
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=data.device)
+        capi.check(lib.sela_hip_crc32_device(
+            data.data_ptr() + offset if n_bytes else None, n_bytes, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            torch.cuda.current_stream(data.device).cuda_stream))
+    return out
+
+
 # sela_hip_level32 (include/sela_hip.h): 32 bytes per (frame, channel); the energy is sum_squares_lo + (sum_squares_hi << 64)
 LEVEL32_DTYPE = np.dtype([("peak", "<u4"), ("samples", "<u4"), ("sum", "<i8"), ("sum_squares_lo", "<u8"), ("sum_squares_hi", "<u8")])
 

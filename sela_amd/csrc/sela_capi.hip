@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sela_coalescer.h"
+#include "sela_crc32.h"
 #include "sela_decode_whole_plan.h"
 #include "sela_host.h"
 #include "sela_lease.h"
@@ -1780,6 +1781,30 @@ int levels_call(const Form& form, uint32_t channels, uint32_t stride, sela_hip_l
         });
 }
 
+// sela_hip_digest_device / sela_hip_digest_payload_device (5.28): levels_call's checks in its order, with the track's two words
+template <typename Form>
+int digest_call(const Form& form, uint32_t channels, uint32_t stride, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "digest", sela::digest_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && d_track && (!n_frames || d_digests));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_digests & 7) || ((uintptr_t)d_track & 7)))
+                rc = fail(SELA_HIP_EINVAL, "d_digests and d_track must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launch_with_priorities(max_frames, stream, "digest launch", [&](uint32_t synth_priorities) {
+                return sela::launch_digest_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_digests, d_track, d_sample_offsets, d_status,
+                    d_ws, sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
 // The shape checks of the int16 window calls, device and host pointers alike (5.17, 5.20): codes and texts in this order.
 // `more_channels` is the call that a caller with more than eight channels is sent to.
 int check_windows_shape(uint32_t channels, uint32_t n_windows, uint32_t window_samples, uint32_t format, const char* more_channels)
@@ -2184,6 +2209,61 @@ int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32
 }
 
 // ---- levels of 24- and 32-bit streams ------------------------------------------------------------------------
+// ---- digest (5.28) ------------------------------------------------------------------------------------------------------------------
+size_t sela_hip_digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::digest_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_digest_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return digest_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, d_digests, d_track, d_sample_offsets, d_status, d_workspace, workspace_bytes,
+        stream);
+}
+
+int sela_hip_digest_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return digest_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, d_digests, d_track, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: where sela_hip_levels runs (generic_digest); no frames need no device.
+int sela_hip_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests, uint32_t* track_crc32,
+    uint64_t* track_bytes)
+{
+    if (track_crc32)
+        *track_crc32 = 0;
+    if (track_bytes)
+        *track_bytes = 0;
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!frame_offsets || (n_frames && !frames))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    return sela::generic_digest(frames, frame_offsets, n_frames, channels, digests, track_crc32, track_bytes, g_recurrence_form);
+}
+
+uint32_t sela_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return sela::crc_combine(crc_a, crc_b, len_b); }
+
+size_t sela_hip_crc32_workspace_bytes(uint64_t n_bytes) { return sela::crc32_workspace_bytes(n_bytes); }
+
+int sela_hip_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* d_out, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (!d_out || !d_workspace || (n_bytes && !d_bytes))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_out & 7)
+        return fail(SELA_HIP_EINVAL, "d_out must be 8-byte aligned");
+    if (workspace_bytes < sela::crc32_workspace_bytes(n_bytes))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_crc32_workspace_bytes()");
+    return launched(sela::launch_crc32_device(d_bytes, n_bytes, d_out, d_workspace, static_cast<hipStream_t>(stream)), "crc32 launch");
+}
+
 size_t sela_hip_levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return sela::levels_i32_workspace_bytes(max_frames, channels, stride);

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "sela_crc32.h"
 #include "sela_host.h"
 #include "sela_lease.h"
 #include "sela_pcm.h"
@@ -748,6 +749,73 @@ int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
         [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, sela_hip_level* d_levels, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
             return launch_levels_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
         });
+}
+
+// sela_hip_digest: generic_levels' walk and chunks.  Per chunk status (4 x u32) | the two track words | the
+// records come back, the records into the caller's where it wants them; the chunk's track word joins the call's by crc_combine.
+namespace {
+struct DigestOp {
+    size_t per_frame;
+    uint32_t channels, stride;
+    int recurrence_form;
+    struct sela_hip_digest* digests; // or null
+    uint32_t crc = 0;
+    uint64_t bytes = 0;
+    uint32_t* d_status = nullptr;
+    uint64_t* d_track = nullptr;
+    struct sela_hip_digest* d_digests = nullptr;
+    uint32_t status[4] = { 0, 0, 0, 0 };
+    uint64_t track[2] = { 0, 0 };
+    size_t workspace_bytes(uint32_t cf) const { return digest_workspace_bytes(cf, channels, stride); }
+    void pieces(Carve& c, uint32_t, uint32_t cf)
+    {
+        d_status = piece<uint32_t>(c, 4);
+        d_track = piece<uint64_t>(c, 2);
+        d_digests = piece<struct sela_hip_digest>(c, cf);
+    }
+    hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
+    {
+        hipError_t e = launch_digest_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_digests, d_track, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(track, d_track, sizeof(track), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && digests)
+            e = hipMemcpyAsync(digests + f0, d_digests, (size_t)cf * sizeof(struct sela_hip_digest), hipMemcpyDeviceToHost, st);
+        return e;
+    }
+    int finish(uint32_t, uint32_t)
+    {
+        const int rc = judge_n(status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        crc = crc_combine(crc, (uint32_t)track[0], track[1]);
+        bytes += track[1];
+        return SELA_HIP_OK;
+    }
+};
+} // namespace
+
+int generic_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests, uint32_t* track_crc32,
+    uint64_t* track_bytes, int recurrence_form)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    if (check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const uint32_t largest = generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (n_frames && largest == 0)
+        return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    const uint32_t stride = std::max(largest, 1u);
+    const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2) + (size_t)channels * sizeof(GenericSubInfo) + sizeof(struct sela_hip_digest) + 64;
+    DigestOp op{ per_frame, channels, stride, recurrence_form, digests };
+    const int rc = frame_chunks(call, "digest", frames, frame_offsets, n_frames, op);
+    if (rc == SELA_HIP_OK && track_crc32)
+        *track_crc32 = op.crc;
+    if (rc == SELA_HIP_OK && track_bytes)
+        *track_bytes = op.bytes;
+    return rc;
 }
 
 // The caller has walked the stream: the offsets never decrease, the largest samplesPerChannel fits the stride.

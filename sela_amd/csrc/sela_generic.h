@@ -89,6 +89,29 @@ inline size_t levels_workspace_bytes(uint32_t max_frames, uint32_t channels, uin
 hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, sela_hip_level* d_levels, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
     uint32_t synth_priorities, hipStream_t stream);
+// sela_hip_digest_device / sela_hip_digest_payload_device: launch_levels_n_device's shape with the reduction
+// turned into a CRC-32 of the bytes, and the track's two words folded from the records behind it.  Up to kVerifyFusedChannels
+// channels the 2048-sample route is one kernel (k_digest_frames, sela_digest.hip); every other route decodes into the workspace
+// and k_digest_pcm / k_digest_slices take it from there; k_digest_fold / k_digest_track write d_track.
+constexpr uint32_t kDigestSliceBytes = 32768;   // bytes of a frame's PCM one workgroup of k_digest_pcm takes
+uint32_t digest_slices(uint32_t channels, uint32_t stride);
+uint32_t digest_fold_blocks(uint32_t max_frames);
+hipError_t launch_digest_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* d_digests,
+    uint32_t* d_status, void* d_workspace, hipStream_t stream, int recurrence_form, uint32_t synth_priorities, const uint32_t* d_n_found);
+hipError_t launch_digest_pcm(const int16_t* d_decoded, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, uint32_t* d_parts /* [max_frames][digest_slices()] */, struct sela_hip_digest* d_digests,
+    hipStream_t stream);
+hipError_t launch_digest_fold(const struct sela_hip_digest* d_digests, const uint64_t* d_sample_offsets, uint32_t max_frames, const uint32_t* d_n_found,
+    uint32_t channels, uint32_t* d_fold /* [digest_fold_blocks()] */, uint64_t* d_track, hipStream_t stream);
+size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return digest_workspace_bytes(max_frames, channels, stride, nullptr); }
+hipError_t launch_digest_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode,
+    int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
+// sela_hip_crc32_device: k_digest_pcm / k_digest_slices on bytes that lie in device memory already
+size_t crc32_workspace_bytes(uint64_t n_bytes, Carve* at);
+inline size_t crc32_workspace_bytes(uint64_t n_bytes) { return crc32_workspace_bytes(n_bytes, nullptr); }
+hipError_t launch_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* d_out, void* d_workspace, hipStream_t stream);
 // sela_hip_verify_i32_device / sela_hip_verify_payload_i32_device: launch_decode_i32_device's shape with the
 // combine turned into a compare against d_samples ([frames][channels][stride] int32, d_lengths or null).  The kernels are
 // sela_verify32.hip's: frames of a direct layout are compared from the subframes as decoded, nothing stored; any other frame goes

@@ -1896,6 +1896,50 @@ hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_fra
         });
 }
 
+// ---- the digest on the device (sela_hip_digest_device) ----------------------------------------------------------
+// Workspace: the levels call's two pieces | a word per (frame, slice) of the routes that are not fused | the fold's word per
+// workgroup.
+struct DigestWs {
+    LevelsWs levels;
+    uint32_t *parts, *fold;
+};
+static DigestWs carve_digest(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    DigestWs w;
+    w.levels = carve_levels(c, max_frames, channels, stride);
+    w.parts = c.take<uint32_t>(std::max<uint64_t>((uint64_t)max_frames * digest_slices(channels, stride), 1));
+    w.fold = c.take<uint32_t>(digest_fold_blocks(max_frames));
+    return w;
+}
+
+size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (levels_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_digest(c, max_frames, channels, stride); });
+}
+
+// The digest plugs k_digest_frames, and k_digest_pcm / k_digest_slices, into launch_n_sequence (status[2] stays 0), and folds the
+// records into d_track behind it: with no frames only the fold runs, and writes {0, 0}.
+hipError_t launch_digest_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode,
+    int recurrence_form, uint32_t synth_priorities, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const DigestWs w = carve_digest(c, max_frames, channels, stride);
+    const hipError_t e = launch_n_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w.levels.n, w.levels.pcm,
+        d_sample_offsets, recurrence_form, synth_priorities,
+        [&](int32_t* dec, const uint32_t* n_fast) {
+            return launch_digest_frames(d_frames, d_frame_offsets, max_frames, channels, d_digests, d_status, dec, stream, recurrence_form, synth_priorities, n_fast);
+        },
+        [&](const uint64_t* d_so, const uint32_t* n_any, const uint32_t* n_fast) {
+            return launch_digest_pcm(w.levels.pcm, d_so, max_frames, channels, stride, n_any, n_fast, w.parts, d_digests, stream);
+        });
+    if (e != hipSuccess)
+        return e;
+    return launch_digest_fold(d_digests, d_sample_offsets ? d_sample_offsets : w.levels.n.offsets, max_frames, d_n_found, channels, w.fold, d_track, stream);
+}
+
 // ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
 // Workspace: launch_decode_i32_device's | the fallback's samples by channel, [frames][channels][stride] | its counts | a mark per
 // frame | k_verify32_direct's / _rest's words per (frame, slice) | the two control words.

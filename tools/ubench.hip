@@ -52,6 +52,11 @@ __global__ void k(uint32_t* out, long long* cyc, int iter)
         if (KIND == 18) asm volatile(REP4("v_mad_u32_u24 %0, %4, %5, %0\n v_mad_u32_u24 %1, %5, %6, %1\n v_mad_u32_u24 %2, %6, %7, %2\n v_mad_u32_u24 %3, %7, %4, %3\n") : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(a), "v"(b), "v"(c), "v"(d));
         if (KIND == 19) asm volatile(REP4("v_mul_hi_u32 %0, %4, %5\n v_mul_hi_u32 %1, %5, %6\n v_mul_hi_u32 %2, %6, %7\n v_mul_hi_u32 %3, %7, %4\n") : "=v"(a), "=v"(b), "=v"(c), "=v"(d) : "v"(a), "v"(b), "v"(c), "v"(d));
         if (KIND == 20) asm volatile(REP4("ds_bpermute_b32 %0, %4, %0\n ds_bpermute_b32 %1, %4, %1\n ds_bpermute_b32 %2, %4, %2\n ds_bpermute_b32 %3, %4, %3\n") "s_waitcnt lgkmcnt(0)\n" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(addr));
+        // CRC-32 over one more bit of a 32-bit word, two ways: the shift register, four dependent instructions a
+        // bit, and the multiply by a constant's columns, three a bit with only the XOR chained -- 16 bits each here
+        if (KIND == 21) asm volatile(REP16("v_bfe_i32 %1, %0, 0, 1\n v_lshrrev_b32 %0, 1, %0\n v_and_b32 %1, 0xedb88320, %1\n v_xor_b32 %0, %0, %1\n") : "+v"(a), "+v"(b));
+        if (KIND == 22) asm volatile(REP4("v_bfe_i32 %2, %0, 31, 1\n v_and_b32 %2, 0xedb88320, %2\n v_xor_b32 %1, %1, %2\n v_bfe_i32 %3, %0, 30, 1\n v_and_b32 %3, 0x76dc4190, %3\n v_xor_b32 %1, %1, %3\n"
+                                         "v_bfe_i32 %2, %0, 29, 1\n v_and_b32 %2, 0x3b6e20c8, %2\n v_xor_b32 %1, %1, %2\n v_bfe_i32 %3, %0, 28, 1\n v_and_b32 %3, 0x1db71064, %3\n v_xor_b32 %1, %1, %3\n") : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
     }
     const long long t1 = clock64();
     out[blockIdx.x * blockDim.x + threadIdx.x] = a + b + c + d + (uint32_t)(p + q + r + s) + (uint32_t)(x + y + z + w) + sg;
@@ -75,6 +80,7 @@ int main(int argc, char** argv)
         {"s_sub_u32 dependent", k<15>, 16}, {"IIR step candidate (12 instr/step)", k<16>, 4},
         {"v_add_co_u32 dependent", k<17>, 16}, {"v_mad_u32_u24", k<18>, 16}, {"v_mul_hi_u32", k<19>, 16},
         {"ds_bpermute_b32 (+wait per 16)", k<20>, 16},
+        {"CRC-32 bit, shift register (4 instr)", k<21>, 16}, {"CRC-32 bit, constant's columns (3 instr)", k<22>, 16},
     };
     printf("%-40s %12s %12s %12s   (cycles per instruction; waves on one SIMD share issue)\n", "instruction", "1 wave/SIMD", "2 waves/SIMD", "4 waves/SIMD");
     int idx = -1;
