@@ -1,5 +1,6 @@
 // digest.hpp -- the host's side of the digest (sela_hip_digest, include/sela_hip.h): a table-driven CRC-32 (IEEE
-// 802.3: zlib.crc32, `crc32`, `cksum -a crc32`) for the bytes of a WAV's data chunk, and the report sela::digestFile returns.  Pure
+// 802.3: zlib.crc32, `crc32`, `cksum -a crc32`) for the bytes of a WAV's data chunk, and the report sela::digestFile and
+// sela::digestWideFile (sela_hip_digest_pcm) return.  Pure
 // arithmetic: no GPU, no file, nothing but the standard library.
 #ifndef SELA_HOST_DIGEST_HPP_
 #define SELA_HOST_DIGEST_HPP_
@@ -53,6 +54,7 @@ struct DigestReport {
     uint32_t wavCrc32 = 0;
     uint64_t wavBytes = 0;      // the bytes of the data chunk the figure is taken over
     uint64_t wavTailBytes = 0;  // the bytes of the data chunk behind them
+    uint32_t wideSamples = 0;   // digestWideFile of a 24-bit file: samples beyond 24 bits (their low three bytes are digested)
     bool agree() const { return !haveWav || (wavCrc32 == crc32 && wavBytes == bytes); }
 };
 

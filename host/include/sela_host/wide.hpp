@@ -18,6 +18,7 @@
 
 #include "sela_host/codec.hpp"
 #include "sela_host/data.hpp"
+#include "sela_host/digest.hpp"
 
 namespace file {
 
@@ -60,6 +61,12 @@ size_t decodeWideFileRange(const std::string& in, const std::string& out, uint64
 // verifyExitCode apply unchanged): the frames that come back different, the WAV's tail, the samples the .sela holds beyond the WAV.
 // Throws data::Exception, naming both widths, where the two files' widths disagree.
 VerifyReport verifyWideFile(const std::string& wavPath, const std::string& selaPath);
+// digestFile for a 24- or 32-bit .sela: ONE call to sela_hip_digest_pcm gives the CRC-32 of the packed PCM the
+// file decodes to -- nothing is decoded into memory -- and, with a WAV of the same width and channel count, the host's Crc32 runs
+// over its data chunk cut to the samples the .sela holds, as verifyWideFile cuts it: all of it for a --whole file, its whole
+// 2048-sample frames for any other; wavTailBytes is the rest.  formatDigestReport applies unchanged.  Throws data::Exception,
+// naming both, where the WAV's width or channel count is not the file's.
+DigestReport digestWideFile(const std::string& selaPath, const std::string& wavPath = std::string());
 // what the .sela header at `path` says its samples' width is; 0 where there is no such header (the caller's path then reports it)
 uint16_t selaFileBits(const std::string& path);
 

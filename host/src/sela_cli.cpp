@@ -32,6 +32,10 @@
 //                                      decoded into memory -- its byte count and the frame count; with in.wav also the CRC-32 of its
 //                                      data chunk (cut to whole frames unless in.sela is a --keep-tail file, as -v cuts it), exit 0
 //                                      only if the two agree, else 3.  A 24- or 32-bit .sela is refused by name (exit 1)
+//   sela_mi355x -C in.sela [in.wav]    the same by the file's own header: a 16-bit file exactly as -c, a 24- or 32-bit file through
+//                                      sela_hip_digest_pcm -- the CRC-32 of the packed 3- or 4-byte samples as a WAV of that width
+//                                      holds them; one more line where samples of a 24-bit file lie beyond 24 bits; a --whole file
+//                                      as it stands; a .wav of another width is refused by name (exit 1)
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -77,6 +81,8 @@ int usage(const std::string& program)
               << program << " -M path/to/input.sela\n\n"
               << "The CRC-32 of the audio a 16-bit file decodes to (with a .wav: held against the CRC-32 of its data chunk):\n"
               << program << " -c path/to/input.sela [path/to/input.wav]\n\n"
+              << "The same for a 16-, 24- or 32-bit file (as -c, by the file's own header; the CRC-32 of the packed samples):\n"
+              << program << " -C path/to/input.sela [path/to/input.wav]\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -279,11 +285,23 @@ int run(int argc, char** argv)
         std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
         return 0;
     }
-    if (verb == "-c") {
+    if (verb == "-c" || verb == "-C") {
         if (argc != 3 && argc != 4)
             return usage(program);
+        // (-C goes by the .sela's header: a 24- or 32-bit file to sela_hip_digest_pcm; any other file, and -c, down -c's path)
+        const uint16_t bits = verb == "-C" ? sela::selaFileBits(argv[2]) : 0;
+        const std::string wav = argc == 4 ? std::string(argv[3]) : std::string();
+        if (bits == 24 || bits == 32) {
+            std::cout << "Digest (" << bits << "-bit): " << argv[2] << std::endl;
+            const sela::DigestReport report = sela::digestWideFile(std::string(argv[2]), wav);
+            std::cout << sela::formatDigestReport(report);
+            if (report.wideSamples)
+                std::cout << report.wideSamples << " samples beyond 24 bits (their low bytes digested)\n";
+            std::cout << std::flush;
+            return report.agree() ? 0 : 3;
+        }
         std::cout << "Digest: " << argv[2] << std::endl;
-        const sela::DigestReport report = sela::digestFile(std::string(argv[2]), argc == 4 ? std::string(argv[3]) : std::string());
+        const sela::DigestReport report = sela::digestFile(std::string(argv[2]), wav);
         std::cout << sela::formatDigestReport(report) << std::flush;
         return report.agree() ? 0 : 3;
     }

@@ -319,6 +319,45 @@ WideLevelReport measureWideFile(const std::string& selaPath)
     return r;
 }
 
+// ---- digest --------------------------------------------------------------------------------------------------
+DigestReport digestWideFile(const std::string& selaPath, const std::string& wavPath)
+{
+    WideSela s;
+    readWideSela(selaPath, "digestWideFile", s);
+    const uint32_t channels = s.channels, bytes = s.bits / 8u;
+    DigestReport r;
+    r.channels = channels;
+    if (sela_hip_digest_pcm(s.stream.data(), s.offsets.data(), s.found, channels, bytes, nullptr, &r.crc32, &r.bytes, &r.wideSamples) != SELA_HIP_OK)
+        failHip("Digest");
+    r.frames = s.found;
+    if (wavPath.empty())
+        return r;
+    const file::WavProbe wav = file::probeWav(wavPath);
+    if (wav.bitsPerSample != s.bits)
+        throw data::Exception("Digest: the .wav holds " + std::to_string(wav.bitsPerSample) + "-bit samples, the .sela " + std::to_string(s.bits)
+            + "-bit samples: files of different widths are not held against each other");
+    if (wav.channels != channels)
+        throw data::Exception("Digest: " + std::to_string(wav.channels) + " channels in the .wav, " + std::to_string(channels) + " in the .sela");
+    // the part of the data chunk the .sela can hold: whole samples, and no more of them than its frames have
+    const uint64_t sampleBytes = (uint64_t)channels * bytes;
+    r.haveWav = true;
+    r.wavBytes = std::min<uint64_t>(wav.dataBytes / sampleBytes * sampleBytes, r.bytes);
+    r.wavTailBytes = wav.dataBytes - r.wavBytes;
+    Crc32 crc;
+    std::vector<uint8_t> piece((size_t)std::min<uint64_t>(r.wavBytes, (uint64_t)4 << 20) + 8);
+    std::ifstream file(wavPath, std::ios::binary);
+    file.seekg((std::streamoff)wav.dataOffset, std::ios::beg);
+    for (uint64_t at = 0; at < r.wavBytes;) {
+        const size_t n = (size_t)std::min<uint64_t>(r.wavBytes - at, (uint64_t)4 << 20);
+        if (!readExact(file, piece.data(), n))
+            throw data::Exception("data subChunk is shorter than its header says");
+        crc.update(piece.data(), n);
+        at += n;
+    }
+    r.wavCrc32 = crc.value();
+    return r;
+}
+
 namespace {
 std::string wideLevelFigures(const ChannelLevelWide& l, double scale)
 {

@@ -1058,7 +1058,7 @@ int sela_hip_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, ui
  * workspace), found before any device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no
  * allocation, no host wait, no host read of device data, so a stream being captured into a HIP graph may take either call.
  * Apart from d_digests[0 .. n_frames), d_track, d_sample_offsets, d_status and the workspace (the payload call: its two index
- * outputs too) nothing is written.  The 24- and 32-bit family (sela_hip_decode_pcm_device's bytes) has no digest yet.
+ * outputs too) nothing is written.  The 24- and 32-bit family (sela_hip_decode_pcm_device's bytes): sela_hip_digest_pcm_device, below.
  * (The record's struct tag and the host call share a name, so C++ code says `struct sela_hip_digest`; sela_hip_digest_record
  * names the type in both languages.) */
 struct sela_hip_digest { /* 8 bytes */
@@ -1090,6 +1090,63 @@ uint32_t sela_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
  * workspace.  Asynchronous on `stream`, two launches, capturable; only d_out and the workspace are written. */
 size_t sela_hip_crc32_workspace_bytes(uint64_t n_bytes);
 int sela_hip_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* d_out /* [2] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- digest of 24- and 32-bit streams: the CRC-32 of the packed PCM they decode to ---------------------------------
+ * The digest above on the domain of sela_hip_decode_pcm_device: samples of up to 32 bits in a container of bytes_per_sample = 3 or
+ * 4 bytes, frames of any length, every subframe layout that call takes.  What sela_hip_decode_pcm_device does, with a CRC where it
+ * stores: frames of the layouts this project's encoders write are taken from the subframes as decoded, packed in LDS and digested
+ * there -- no decoded byte reaches memory; any other frame goes through the decode call's combine into the workspace first.
+ *   d_digests[f]   .crc32: the CRC-32 of exactly the samples * channels * bytes_per_sample bytes sela_hip_decode_pcm_device writes
+ *                  for frame f with the same d_frames, d_frame_offsets, n_frames, channels, stride and bytes_per_sample (little-
+ *                  endian, interleaved, each sample's low bytes_per_sample bytes, difference subframes combined mod 2^32);
+ *                  .samples: sample_offsets[f + 1] - sample_offsets[f].  A frame of 0 samples has crc32 0.  8-byte aligned; the
+ *                  record is the one above.
+ *   d_track        uint64[2], 8-byte aligned, not NULL: [0] (its low 32 bits; the high ones 0) the CRC-32 of all frames' bytes in
+ *                  order, [1] their number, sample_offsets[n_frames] * channels * bytes_per_sample.  For a lossless file that is
+ *                  zlib.crc32 of the WAV data chunk it was made from (cut to whole frames unless the tail was kept).
+ *   d_status uint32[4], written by the call: exactly what sela_hip_decode_pcm_device leaves for the same frames -- [0] and [1] with
+ *                  SELA_HIP_FLAG_STRIDE, SELA_HIP_FLAG_BAD_FRAME and the frames its pack refuses (channels that disagree about
+ *                  the frame's length) as there, [2] the largest samplesPerChannel, [3] the samples of digested frames outside
+ *                  [-2^23, 2^23) with a 3-byte container (their low three bytes are digested), 0 with 4 bytes.
+ *                  sela_hip_decode_pcm_status_error() applies unchanged; where it gives non-zero, or SELA_HIP_FLAG_STRIDE is set,
+ *                  the records and d_track are not defined.  n_frames = 0 writes the status words, d_track = {0, 0} (and
+ *                  d_sample_offsets[0] = 0 where given) and nothing else.
+ * d_workspace: sela_hip_digest_pcm_workspace_bytes(n_frames, channels, stride) bytes, no initialisation (the payload call:
+ * sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at a time may use it.  With up(b) = b rounded up to a
+ * multiple of 256 and tile = max((4096 / channels) & ~3, 4) samples it is
+ *     sela_hip_decode_i32_workspace_bytes(max_frames, channels, stride)      the subframes as decoded, their records, the index
+ *   + up(max_frames * channels * stride * 4)                                 the samples by channel, for frames of any other layout
+ *   + up(max_frames * channels * 4)                                          ... and their counts
+ *   + up(max(max_frames, 1) * 4)                                             a mark per frame: which way it went
+ *   + up(max(max_frames * ceil(stride / tile), 1) * 8)                       the raw CRC per (frame, tile): a word of the verify call's two
+ *   + 256                                                                    the two control words
+ *   + up((max_frames + 1) * 8)                                               the sample offsets of a caller that passes none
+ *   + up(4 * min(max(ceil(max_frames / 256), 1), 256))                       the track fold's word per workgroup
+ * -- sela_hip_verify_pcm_workspace_bytes() and the last line -- and SIZE_MAX where sela_hip_verify_pcm_workspace_bytes() is.
+ * Arguments, errors and their order are sela_hip_digest_device's (SELA_HIP_EINVAL: channels outside 1..255, stride 0, n_frames *
+ * channels at 2^31 or more, a null pointer -- d_sample_offsets may be NULL, d_digests only where there are frames, d_track never
+ * -- a d_digests or d_track that is not 8-byte aligned); then SELA_HIP_EINVAL for bytes_per_sample other than 3 or 4 and for a
+ * d_sample_offsets that is not 8-byte aligned, then for a null or misaligned d_frames / d_payload; SELA_HIP_ECAPACITY: a smaller
+ * workspace.  All are found before any device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain:
+ * no allocation, no host wait, no host read of device data, so a stream being captured into a HIP graph may take either call.
+ * Apart from d_digests[0 .. n_frames), d_track, d_sample_offsets, d_status and the workspace (the payload call: its two index
+ * outputs too) nothing is written. */
+size_t sela_hip_digest_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_digest_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, struct sela_hip_digest* d_digests /* [n_frames] */, uint64_t* d_track /* [2] */,
+    uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written); d_track covers the frames found. */
+int sela_hip_digest_payload_pcm_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames with the stream's largest samplesPerChannel for a stride; each chunk's track words
+ * and status[3] come back with its status and are folded on the host (sela_hip_crc32_combine): returns what sela_hip_decode_pcm
+ * returns for the stream (0: the records and the three figures are valid; digests, track_crc32, track_bytes and wide_samples may
+ * each be NULL).  Runs where sela_hip_levels_i32 runs: the calling thread's any-length context and its own stream, past the
+ * coalescer; an open streaming job of the thread is left alone.  n_frames = 0 gives 0 / 0 / 0 and asks for no device. */
+int sela_hip_digest_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample,
+    struct sela_hip_digest* digests /* [n_frames] or NULL */, uint32_t* track_crc32, uint64_t* track_bytes, uint32_t* wide_samples);
 
 /* ---- a whole track from packed 3- or 4-byte PCM: the tail of a 24- or 32-bit file kept ----------------------------
  * sela_hip_encode_whole* ("a whole track", above) for the containers of sela_hip_encode_pcm*: d_pcm is little-endian interleaved

@@ -1662,3 +1662,67 @@ def decode_pcm_host(frames: np.ndarray, offsets: np.ndarray, channels: int, byte
     capi.check(capi.lib().sela_hip_decode_pcm(frames.ctypes.data, offsets.ctypes.data, n_frames, channels, bytes_per_sample, pcm.ctypes.data,
                                               total * channels * bytes_per_sample, C.addressof(wide)))
     return pcm[: total * channels * bytes_per_sample], int(wide.value)
+
+
+class DigesterPcm(_DeviceCall):
+    """sela_hip_digest_pcm_device: the CRC-32 (zlib.crc32) of the packed 3- or 4-byte PCM DecoderPcm.decode would write, per frame
+    and for the whole track, on the device -- Digester for the 24- and 32-bit family.  Owns its records, its two
+    track words and its workspace on the current device (or `device`); every call is asynchronous on the current stream, one serial
+    chain, and overwrites them -- so it can be captured into a graph.  No PCM is written; the status words are DecoderPcm's."""
+
+    _call, _judge = "digest_pcm", staticmethod(decode_pcm_status_error)
+    _own_count = False  # status[2] stays the largest samplesPerChannel, as DecoderPcm leaves it
+    fallback_frames = _DeviceCall._fallback_frames
+
+    def __init__(self, max_frames: int, channels: int, stride: int, bytes_per_sample: int, device=None):
+        self.bytes_per_sample = bytes_per_sample
+        super().__init__(max_frames, channels, stride, device)
+
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames]: crc32 | samples << 32; the track: [crc32, bytes]
+        self.digests = torch.zeros(self.max_frames, dtype=torch.int64, device=self.device)
+        self.track = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def digest(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> (records int64 [n_frames],
+        track int64 [2]: the CRC-32 of all frames' bytes and their number), views of the digester's own buffers (records(): as
+        DIGEST_DTYPE)."""
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_digest_pcm_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.bytes_per_sample, self.digests.data_ptr(),
+            self.track.data_ptr(), self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.digests[:n_frames], self.track
+
+    def digest_payload(self, payload, max_frames=None):
+        """Index and digest a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device.  -> (records [max_frames], track [2], count int32 [1]): records up to count[0] are the stream's, the
+        track covers those.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_digest_payload_pcm_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.bytes_per_sample, self.digests.data_ptr(),
+            self.track.data_ptr(), self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
+            self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.digests[:max_frames], self.track, self.count
+
+    records = staticmethod(Digester.records)
+    track_words = Digester.track_words
+
+    def wide_samples(self) -> int:
+        """Waits for the last call -> how many samples of digested frames did not fit a 3-byte container (their low bytes were digested)."""
+        return int(self.status[3].item()) & 0xFFFFFFFF
+
+
+def digest_pcm_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bytes_per_sample: int):
+    """sela_hip_digest_pcm on numpy arrays -> (records DIGEST_DTYPE [n_frames], the track's CRC-32, its bytes, the samples beyond a
+    3-byte container)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    out = np.zeros(n_frames, DIGEST_DTYPE)
+    crc, total, wide = np.zeros(1, np.uint32), np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+    capi.check(lib.sela_hip_digest_pcm(fr.ctypes.data, offs.ctypes.data, n_frames, channels, bytes_per_sample, out.ctypes.data, crc.ctypes.data,
+                                       total.ctypes.data, wide.ctypes.data))
+    return out, int(crc[0]), int(total[0]), int(wide[0])

@@ -1805,6 +1805,34 @@ int digest_call(const Form& form, uint32_t channels, uint32_t stride, struct sel
         });
 }
 
+// sela_hip_digest_pcm_device / sela_hip_digest_payload_pcm_device (5.29): digest_call's checks in its order, then the container's, as
+// in verify_pcm_call; the decode_i32 call's launch shape
+template <typename Form>
+int digest_pcm_call(const Form& form, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track,
+    uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "digest_pcm", sela::digest_pcm_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && d_track && (!n_frames || d_digests));
+            if (rc == SELA_HIP_OK && (((uintptr_t)d_digests & 7) || ((uintptr_t)d_track & 7)))
+                rc = fail(SELA_HIP_EINVAL, "d_digests and d_track must be 8-byte aligned");
+            if (rc == SELA_HIP_OK && bytes_per_sample != 3 && bytes_per_sample != 4)
+                rc = fail(SELA_HIP_EINVAL, "bytes_per_sample must be 3 or 4 (16-bit samples: sela_hip_digest_device)");
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_sample_offsets & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_sample_offsets must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_digest_pcm_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, bytes_per_sample, d_digests, d_track,
+                                d_sample_offsets, d_status, d_ws, sela::generic_standard_first_mode(), c.stream),
+                "digest_pcm launch");
+        });
+}
+
 // The shape checks of the int16 window calls, device and host pointers alike (5.17, 5.20): codes and texts in this order.
 // `more_channels` is the call that a caller with more than eight channels is sent to.
 int check_windows_shape(uint32_t channels, uint32_t n_windows, uint32_t window_samples, uint32_t format, const char* more_channels)
@@ -2264,6 +2292,57 @@ int sela_hip_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* d_out
     return launched(sela::launch_crc32_device(d_bytes, n_bytes, d_out, d_workspace, static_cast<hipStream_t>(stream)), "crc32 launch");
 }
 
+// ---- digest of 24- and 32-bit streams (5.29) -----------------------------------------------------------------------------------------
+size_t sela_hip_digest_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::digest_pcm_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_digest_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return digest_pcm_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, bytes_per_sample, d_digests, d_track, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+int sela_hip_digest_payload_pcm_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return digest_pcm_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, bytes_per_sample, d_digests, d_track,
+        d_sample_offsets, d_status, d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: sela_hip_levels_i32's checks and walk, then chunks of frames where that call runs (generic_digest_pcm);
+// no frames need no device.
+int sela_hip_digest_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample,
+    struct sela_hip_digest* digests, uint32_t* track_crc32, uint64_t* track_bytes, uint32_t* wide_samples)
+{
+    if (track_crc32)
+        *track_crc32 = 0;
+    if (track_bytes)
+        *track_bytes = 0;
+    if (wide_samples)
+        *wide_samples = 0;
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!frame_offsets || (n_frames && !frames))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (bytes_per_sample != 3 && bytes_per_sample != 4)
+        return fail(SELA_HIP_EINVAL, "bytes_per_sample must be 3 or 4 (16-bit samples: sela_hip_digest)");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const uint32_t largest = sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (largest == 0)
+        return fail(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    return sela::generic_digest_pcm(frames, frame_offsets, n_frames, channels, largest, bytes_per_sample, digests, track_crc32, track_bytes, wide_samples);
+}
+
 size_t sela_hip_levels_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return sela::levels_i32_workspace_bytes(max_frames, channels, stride);
@@ -2557,6 +2636,11 @@ int sela_hip_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, ui
 long long sela_hip_debug_verify_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return fallback_frames(sela::verify_pcm_workspace_bytes, sela::verify_pcm_control_words, d_workspace, max_frames, channels, stride);
+}
+
+long long sela_hip_debug_digest_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return fallback_frames(sela::digest_pcm_workspace_bytes, sela::digest_pcm_control_words, d_workspace, max_frames, channels, stride);
 }
 
 // Test hook (include/sela_hip_debug.h): the pieces of a call's workspace, from the description its launch runs.  No device.

@@ -1160,6 +1160,71 @@ int generic_decode_pcm(const uint8_t* frames, const uint64_t* frame_offsets, con
     return frame_chunks(call, "decode_pcm", frames, frame_offsets, n_frames, op);
 }
 
+// sela_hip_digest_pcm: generic_levels_i32's chunks with DigestOp's outputs.  Per chunk status (4 x u32) | the two
+// track words | the records come back; the chunk's track word joins the call's by crc_combine, its status[3] the count of samples
+// beyond a 3-byte container.  The caller has walked the stream, as for generic_levels_i32.
+namespace {
+struct DigestPcmOp {
+    size_t per_frame;
+    uint32_t channels, stride, bytes_per_sample;
+    struct sela_hip_digest* digests; // or null
+    uint32_t crc = 0, wide = 0;
+    uint64_t bytes = 0;
+    uint32_t* d_status = nullptr;
+    uint64_t* d_track = nullptr;
+    struct sela_hip_digest* d_digests = nullptr;
+    uint32_t status[4] = { 0, 0, 0, 0 };
+    uint64_t track[2] = { 0, 0 };
+    size_t workspace_bytes(uint32_t cf) const { return digest_pcm_workspace_bytes(cf, channels, stride); }
+    void pieces(Carve& c, uint32_t, uint32_t cf)
+    {
+        d_status = piece<uint32_t>(c, 4);
+        d_track = piece<uint64_t>(c, 2);
+        d_digests = piece<struct sela_hip_digest>(c, cf);
+    }
+    hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
+    {
+        hipError_t e = launch_digest_pcm_device(d_frames, d_offsets, cf, nullptr, channels, stride, bytes_per_sample, d_digests, d_track, nullptr, d_status, d_ws, mode, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(track, d_track, sizeof(track), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && digests)
+            e = hipMemcpyAsync(digests + f0, d_digests, (size_t)cf * sizeof(struct sela_hip_digest), hipMemcpyDeviceToHost, st);
+        return e;
+    }
+    int finish(uint32_t, uint32_t)
+    {
+        const int rc = sela_hip_decode_pcm_status_error(status);
+        if (rc != SELA_HIP_OK)
+            return rc;
+        crc = crc_combine(crc, (uint32_t)track[0], track[1]);
+        bytes += track[1];
+        wide += status[3];
+        return SELA_HIP_OK;
+    }
+};
+} // namespace
+
+int generic_digest_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample,
+    struct sela_hip_digest* digests, uint32_t* track_crc32, uint64_t* track_bytes, uint32_t* wide_samples)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 8) + (size_t)verify_pcm_tiles(stride, channels) * 8
+        + sizeof(struct sela_hip_digest) + 64;
+    DigestPcmOp op{ per_frame, channels, stride, bytes_per_sample, digests };
+    const int rc = frame_chunks(call, "digest_pcm", frames, frame_offsets, n_frames, op);
+    if (rc == SELA_HIP_OK && track_crc32)
+        *track_crc32 = op.crc;
+    if (rc == SELA_HIP_OK && track_bytes)
+        *track_bytes = op.bytes;
+    if (rc == SELA_HIP_OK && wide_samples)
+        *wide_samples = op.wide;
+    return rc;
+}
+
 // sela_hip_verify_pcm: verify_chunks on the packed original.
 int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const uint8_t* pcm,
     uint64_t pcm_samples, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames)

@@ -12,13 +12,11 @@
 //   k_digest_fold, k_digest_track   the track: the XOR over f of crc_f * x^(8 * bytes behind frame f).
 //
 // A CRC is ordered, so the lanes, waves and slices are put together by the shift identity of sela_crc32.h: a piece's raw CRC
-// times x^(8 * bytes behind it), XORed.  A thread takes pieces of P bytes at the workgroup's stride T (piece t, t + T, ...): its
-// register times x^(8 P (T - 1)) before each further piece, each dword of the piece by (r ^ w) * x^32 -- the multiplier's 32
-// columns are literals.  The 64 lanes are joined on the DPP ladder of wave_sum_small with a multiply by x^(8 P 2^k) per rung, the
-// waves through one word each of LDS.  Everything is XOR, shift and AND on 32-bit integers: no float, no atomics, no table.
+// times x^(8 * bytes behind it), XORed -- the lanes' and waves' side of it is sela_crc32_lanes.h, which the digest of the 24- and
+// 32-bit family (sela_digest_pcm.hip, 5.29) shares; that call also runs the three folds here, with its own bytes per value.
 #include "sela_host.h"
 
-#include "sela_crc32.h"
+#include "sela_crc32_lanes.h"
 #include "sela_synth.h"
 
 namespace sela {
@@ -29,53 +27,6 @@ static_assert(kVerifyFusedChannels == (uint32_t)kDecMaxWaves, "the fused route t
 static_assert(sizeof(struct sela_hip_digest) == 8 && alignof(struct sela_hip_digest) == 4, "the record of include/sela_hip.h");
 static_assert(offsetof(struct sela_hip_digest, crc32) == 0 && offsetof(struct sela_hip_digest, samples) == 4, "a record leaves as one 8-byte word");
 
-// a * K for a constant K: the 32 columns K * x^i are literals
-template <uint32_t K>
-struct CrcColumns {
-    uint32_t c[32];
-    constexpr CrcColumns() : c{}
-    {
-        uint32_t b = K;
-        for (int i = 0; i < 32; i++) {
-            c[i] = b;
-            b = crc_times_x(b);
-        }
-    }
-};
-template <uint32_t K>
-__device__ __forceinline__ uint32_t crc_mul_const(uint32_t a)
-{
-    constexpr CrcColumns<K> cols;
-    uint32_t p = 0;
-#pragma unroll
-    for (int i = 0; i < 32; i++)
-        p ^= (uint32_t)((int32_t)(a << i) >> 31) & cols.c[i];
-    return p;
-}
-// the register after four more bytes (little-endian in w), after two (in the low half of v)
-__device__ __forceinline__ uint32_t crc_step32(uint32_t r, uint32_t w) { return crc_mul_const<kCrcX32>(r ^ w); }
-__device__ __forceinline__ uint32_t crc_step16(uint32_t r, uint32_t v) { return crc_mul_const<kCrcX16>(r ^ v); }
-
-// The constants of one (piece, workgroup) shape: P bytes a piece, T threads.
-struct DigestShape {
-    uint32_t stride;  // x^(8 P (T - 1)): a thread's register before its next piece
-    uint32_t lane[6]; // x^(8 P 2^k): the rungs of the lane ladder
-    uint32_t wave;    // x^(8 P 64): from one wave to the next
-    uint32_t finish;  // fused frames: crc = raw ^ finish (0xFFFFFFFF * x^(8 bytes) ^ 0xFFFFFFFF)
-    uint32_t steps, pad; // fused frames: pieces per thread, and the empty pieces ahead of the first (steps * T - pieces)
-};
-constexpr DigestShape digest_shape(uint32_t piece_bytes, uint32_t threads, uint32_t pieces)
-{
-    DigestShape s{};
-    s.stride = crc_xpow8((uint64_t)piece_bytes * (threads - 1));
-    for (int k = 0; k < 6; k++)
-        s.lane[k] = crc_xpow8((uint64_t)piece_bytes << k);
-    s.wave = crc_xpow8((uint64_t)piece_bytes * 64);
-    s.finish = crc_from_raw(0, (uint64_t)piece_bytes * pieces);
-    s.steps = (pieces + threads - 1) / threads;
-    s.pad = s.steps * threads - pieces;
-    return s;
-}
 // The fused kernel's shapes by channels: mono takes four samples a piece, stereo stereo_words' four of both channels, more
 // channels one sample of every channel.
 constexpr uint32_t fused_piece_samples(uint32_t channels) { return channels <= 2 ? 4u : 1u; }
@@ -87,40 +38,6 @@ constexpr DigestShape fused_shape(uint32_t channels)
 constexpr DigestShape kFusedShapes[kDecMaxWaves + 1] = { DigestShape{}, fused_shape(1), fused_shape(2), fused_shape(3), fused_shape(4), fused_shape(5), fused_shape(6),
     fused_shape(7), fused_shape(8) };
 static_assert(kFusedShapes[2].pad == 0 && kFusedShapes[2].steps == 4 && kFusedShapes[3].pad == 11 * 192 - 2048, "pieces and threads");
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118 /* row_shr:8 */, 0xf, 0xf, false);
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142 /* row_bcast:15 */, 0xa, 0xf, false);
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// The wave's raw CRC from its lanes' (lane l's pieces lie one piece ahead of lane l + 1's): wave_sum_small's ladder, what comes
-// from k lanes below times x^(8 P k) on its way.  A lane that receives nothing receives 0, and 0 times anything is 0.
-__device__ __forceinline__ uint32_t wave_crc(uint32_t v, const DigestShape& s)
-{
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, false), s.lane[0]);
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112 /* row_shr:2 */, 0xf, 0xf, false), s.lane[1]);
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114 /* row_shr:4 */, 0xf, 0xf, false), s.lane[2]);
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118 /* row_shr:8 */, 0xf, 0xf, false), s.lane[3]);
-    // lane 15 of every row now holds its row's; lanes 31 and 63 take the row below theirs, then lane 63 the lower half
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142 /* row_bcast:15 */, 0xa, 0xf, false), s.lane[4]);
-    v ^= crc_mul((uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143 /* row_bcast:31 */, 0xc, 0xf, false), s.lane[5]);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// The workgroup's raw CRC from its waves' (one word each in `part`), by one thread.
-__device__ __forceinline__ uint32_t waves_crc(const uint32_t* part, int part_stride, int n_waves, const DigestShape& s)
-{
-    uint32_t r = 0;
-    for (int w = 0; w < n_waves; w++)
-        r = crc_mul(r, s.wave) ^ part[w * part_stride];
-    return r;
-}
 
 __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_digest_frames(const uint8_t* __restrict__ frames,
     const uint64_t* __restrict__ frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* __restrict__ digests /* [n_frames] */,
@@ -218,12 +135,11 @@ __global__ __launch_bounds__(kDecMaxWaves * 64) __attribute__((amdgpu_waves_per_
 
 // ---- bytes in global memory -----------------------------------------------------------------------------------------------------
 // One workgroup per (range, slice of slice_bytes): a frame's range is what another kernel decoded into the workspace, at
-// sample_offsets[f] * channels * 2 (frames from *n_a + *n_b on are left alone: the device's count of the route that ran, the
-// other route's being 0); without sample offsets there is one range, [0, raw_bytes).  The slice's whole 16-byte lines are read as
+// sample_offsets[f] * channels * value_bytes (2: int16; sela_digest_pcm.hip's tiles: 3 or 4).  Frames from *n_a + *n_b on are left
+// alone: the device's count of the route that ran, the other route's being 0 (n_a null: every frame of the call); without sample
+// offsets there is one range, [0, raw_bytes).  The slice's whole 16-byte lines are read as
 // such, 256 threads at their stride; what lies ahead of the first line and behind the last (up to 15 bytes each) is taken byte by
 // byte by thread 0, which puts the three together.  parts[range * slices + slice]: the slice's raw CRC.
-constexpr uint32_t kDigestThreads = 256;
-constexpr DigestShape kPcmShape = digest_shape(16, kDigestThreads, 0);
 
 struct DigestRange {
     uint64_t start, bytes; // in `bytes`; bytes: what the decoder wrote
@@ -231,17 +147,17 @@ struct DigestRange {
     bool there;
 };
 __device__ __forceinline__ DigestRange digest_range(uint32_t f, const uint64_t* __restrict__ sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
-    const uint32_t* __restrict__ n_a, const uint32_t* __restrict__ n_b, uint64_t raw_bytes)
+    const uint32_t* __restrict__ n_a /* or null */, const uint32_t* __restrict__ n_b /* or null */, uint64_t raw_bytes, uint32_t value_bytes)
 {
     DigestRange g = { 0, raw_bytes, 0, true };
     if (!sample_offsets)
         return g;
-    const uint32_t n = *n_a + (n_b ? *n_b : 0u);
+    const uint32_t n = n_a ? *n_a + (n_b ? *n_b : 0u) : max_frames;
     g.there = f < min(n, max_frames);
     if (g.there) {
         const uint64_t so = sample_offsets[f], in_frame = sample_offsets[f + 1] - so;
-        g.start = so * channels * 2;
-        g.bytes = min(in_frame, (uint64_t)stride) * channels * 2; // (never more than the decoder wrote)
+        g.start = so * channels * value_bytes;
+        g.bytes = min(in_frame, (uint64_t)stride) * channels * value_bytes; // (never more than the decoder wrote)
         g.samples = (uint32_t)in_frame;
     }
     return g;
@@ -253,7 +169,7 @@ __global__ __launch_bounds__(kDigestThreads) void k_digest_pcm(const uint8_t* __
 {
     __shared__ uint32_t s_part[kDigestThreads / 64];
     const uint32_t f = blockIdx.x, s = blockIdx.y;
-    const DigestRange g = digest_range(f, sample_offsets, max_frames, channels, stride, n_a, n_b, raw_bytes);
+    const DigestRange g = digest_range(f, sample_offsets, max_frames, channels, stride, n_a, n_b, raw_bytes, 2);
     const uint64_t lo = (uint64_t)s * slice_bytes;
     if (!g.there || lo >= g.bytes)
         return;
@@ -289,42 +205,34 @@ __global__ __launch_bounds__(kDigestThreads) void k_digest_pcm(const uint8_t* __
     }
 }
 
-// XOR over the workgroup, in thread 0
-__device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t* s_part /* [kDigestThreads / 64] */)
-{
-    v = wave_xor(v);
-    if (threadIdx.x % 64 == 0)
-        s_part[threadIdx.x / 64] = v;
-    __syncthreads();
-    uint32_t all = 0;
-    if (threadIdx.x == 0)
-        for (uint32_t w = 0; w < kDigestThreads / 64; w++)
-            all ^= s_part[w];
-    return all;
-}
-
 // One workgroup per range: a thread takes a run of consecutive slices, moves its run's raw CRC over the bytes behind the run, and
 // the XOR of those is the range's; thread 0 turns it into the CRC and writes the record (a frame) or the two words (raw bytes).
 __global__ __launch_bounds__(kDigestThreads) void k_digest_slices(const uint32_t* __restrict__ parts, const uint64_t* __restrict__ sample_offsets /* or null */,
     uint32_t max_frames, uint32_t channels, uint32_t stride, const uint32_t* __restrict__ n_a, const uint32_t* __restrict__ n_b /* or null */, uint64_t raw_bytes,
-    uint64_t slice_bytes, uint32_t slices, struct sela_hip_digest* __restrict__ digests /* frames */, uint64_t* __restrict__ out /* raw bytes: [2] */)
+    uint64_t slice_bytes, uint32_t slices, uint32_t value_bytes, struct sela_hip_digest* __restrict__ digests /* frames */,
+    uint64_t* __restrict__ out /* raw bytes: [2] */)
 {
     __shared__ uint32_t s_part[kDigestThreads / 64];
     const uint32_t f = blockIdx.x;
-    const DigestRange g = digest_range(f, sample_offsets, max_frames, channels, stride, n_a, n_b, raw_bytes);
+    const DigestRange g = digest_range(f, sample_offsets, max_frames, channels, stride, n_a, n_b, raw_bytes, value_bytes);
     if (!g.there)
         return;
     const uint64_t used = (g.bytes + slice_bytes - 1) / slice_bytes; // (<= slices)
     const uint64_t run = (used + kDigestThreads - 1) / kDigestThreads;
     const uint64_t s0 = min(used, threadIdx.x * run), s1 = min(used, s0 + run);
-    const uint32_t whole = crc_xpow8(slice_bytes);
+    // (a run of one slice has nothing in front of it to move, and the last run nothing behind it: a frame of one slice -- every frame
+    // of a 2048-sample stream in sela_digest_pcm.hip's tiles -- costs no multiplier at all, and the threads without a run none either)
+    const uint32_t whole = run > 1 ? crc_xpow8(slice_bytes) : 0u;
     uint32_t r = 0;
     for (uint64_t s = s0; s < s1; s++) {
         const uint64_t in_slice = min(slice_bytes, g.bytes - s * slice_bytes);
-        r = crc_mul(r, in_slice == slice_bytes ? whole : crc_xpow8(in_slice)) ^ parts[(size_t)f * slices + s];
+        if (r)
+            r = crc_mul(r, in_slice == slice_bytes ? whole : crc_xpow8(in_slice));
+        r ^= parts[(size_t)f * slices + s];
     }
-    if (s1 > s0)
-        r = crc_mul(r, crc_xpow8(g.bytes - min(g.bytes, s1 * slice_bytes)));
+    const uint64_t behind = g.bytes - min(g.bytes, s1 * slice_bytes);
+    if (s1 > s0 && behind)
+        r = crc_mul(r, crc_xpow8(behind));
     const uint32_t raw = block_xor(r, s_part);
     if (threadIdx.x == 0) {
         const uint32_t crc = crc_from_raw(raw, g.bytes);
@@ -347,21 +255,22 @@ __device__ __forceinline__ uint32_t digest_frames_found(uint32_t max_frames, con
 }
 
 __global__ __launch_bounds__(kDigestThreads) void k_digest_fold(const struct sela_hip_digest* __restrict__ digests, const uint64_t* __restrict__ sample_offsets,
-    uint32_t max_frames, const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t channels, uint32_t* __restrict__ fold /* [gridDim.x] */)
+    uint32_t max_frames, const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t channels, uint32_t value_bytes,
+    uint32_t* __restrict__ fold /* [gridDim.x] */)
 {
     __shared__ uint32_t s_part[kDigestThreads / 64];
     const uint32_t n = digest_frames_found(max_frames, n_frames_found);
     const uint64_t end = n ? sample_offsets[n] : 0;
     uint32_t r = 0;
     for (uint64_t f = (uint64_t)blockIdx.x * kDigestThreads + threadIdx.x; f < n; f += (uint64_t)gridDim.x * kDigestThreads)
-        r ^= crc_mul(digests[f].crc32, crc_xpow8((end - sample_offsets[f + 1]) * channels * 2));
+        r ^= crc_mul(digests[f].crc32, crc_xpow8((end - sample_offsets[f + 1]) * channels * value_bytes));
     r = block_xor(r, s_part);
     if (threadIdx.x == 0)
         fold[blockIdx.x] = r;
 }
 
 __global__ __launch_bounds__(kDigestThreads) void k_digest_track(const uint32_t* __restrict__ fold, uint32_t fold_blocks, const uint64_t* __restrict__ sample_offsets,
-    uint32_t max_frames, const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t channels, uint64_t* __restrict__ track /* [2] */)
+    uint32_t max_frames, const uint32_t* __restrict__ n_frames_found /* or null */, uint32_t channels, uint32_t value_bytes, uint64_t* __restrict__ track /* [2] */)
 {
     __shared__ uint32_t s_part[kDigestThreads / 64];
     uint32_t r = 0;
@@ -371,7 +280,7 @@ __global__ __launch_bounds__(kDigestThreads) void k_digest_track(const uint32_t*
     if (threadIdx.x == 0) {
         const uint32_t n = digest_frames_found(max_frames, n_frames_found);
         track[0] = r;
-        track[1] = n ? sample_offsets[n] * channels * 2 : 0;
+        track[1] = n ? sample_offsets[n] * channels * value_bytes : 0;
     }
 }
 
@@ -421,17 +330,27 @@ hipError_t launch_digest_pcm(const int16_t* d_decoded, const uint64_t* d_sample_
     const uint32_t slices = digest_slices(channels, stride);
     hipLaunchKernelGGL(k_digest_pcm, dim3(max_frames, slices), dim3(kDigestThreads), 0, stream, reinterpret_cast<const uint8_t*>(d_decoded), d_sample_offsets, max_frames,
         channels, stride, d_n_a, d_n_b, (uint64_t)0, (uint64_t)kDigestSliceBytes, slices, d_parts, kPcmShape);
+    return launch_digest_slices(d_parts, d_sample_offsets, max_frames, channels, stride, d_n_a, d_n_b, kDigestSliceBytes, slices, 2, d_digests, stream);
+}
+
+// the records from the raw CRCs of a frame's slices -- k_digest_pcm's, or the tiles of sela_digest_pcm.hip (value_bytes 3 or 4)
+hipError_t launch_digest_slices(const uint32_t* d_parts, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const uint32_t* d_n_a, const uint32_t* d_n_b, uint64_t slice_bytes, uint32_t slices, uint32_t value_bytes, struct sela_hip_digest* d_digests, hipStream_t stream)
+{
+    if (max_frames == 0)
+        return hipSuccess;
     hipLaunchKernelGGL(k_digest_slices, dim3(max_frames), dim3(kDigestThreads), 0, stream, d_parts, d_sample_offsets, max_frames, channels, stride, d_n_a, d_n_b,
-        (uint64_t)0, (uint64_t)kDigestSliceBytes, slices, d_digests, static_cast<uint64_t*>(nullptr));
+        (uint64_t)0, slice_bytes, slices, value_bytes, d_digests, static_cast<uint64_t*>(nullptr));
     return hipGetLastError();
 }
 
 hipError_t launch_digest_fold(const struct sela_hip_digest* d_digests, const uint64_t* d_sample_offsets, uint32_t max_frames, const uint32_t* d_n_found,
-    uint32_t channels, uint32_t* d_fold, uint64_t* d_track, hipStream_t stream)
+    uint32_t channels, uint32_t value_bytes, uint32_t* d_fold, uint64_t* d_track, hipStream_t stream)
 {
     const uint32_t blocks = digest_fold_blocks(max_frames);
-    hipLaunchKernelGGL(k_digest_fold, dim3(blocks), dim3(kDigestThreads), 0, stream, d_digests, d_sample_offsets, max_frames, d_n_found, channels, d_fold);
-    hipLaunchKernelGGL(k_digest_track, dim3(1), dim3(kDigestThreads), 0, stream, d_fold, blocks, d_sample_offsets, max_frames, d_n_found, channels, d_track);
+    hipLaunchKernelGGL(k_digest_fold, dim3(blocks), dim3(kDigestThreads), 0, stream, d_digests, d_sample_offsets, max_frames, d_n_found, channels, value_bytes, d_fold);
+    hipLaunchKernelGGL(k_digest_track, dim3(1), dim3(kDigestThreads), 0, stream, d_fold, blocks, d_sample_offsets, max_frames, d_n_found, channels, value_bytes,
+        d_track);
     return hipGetLastError();
 }
 
@@ -461,7 +380,7 @@ hipError_t launch_crc32_device(const void* d_bytes, uint64_t n_bytes, uint64_t* 
         hipLaunchKernelGGL(k_digest_pcm, dim3(1, slices), dim3(kDigestThreads), 0, stream, static_cast<const uint8_t*>(d_bytes), static_cast<const uint64_t*>(nullptr), 1u,
             1u, 1u, static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), n_bytes, slice, slices, parts, kPcmShape);
     hipLaunchKernelGGL(k_digest_slices, dim3(1), dim3(kDigestThreads), 0, stream, parts, static_cast<const uint64_t*>(nullptr), 1u, 1u, 1u,
-        static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), n_bytes, slice, slices, static_cast<struct sela_hip_digest*>(nullptr), d_out);
+        static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), n_bytes, slice, slices, 1u, static_cast<struct sela_hip_digest*>(nullptr), d_out);
     return hipGetLastError();
 }
 

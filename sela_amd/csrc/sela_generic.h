@@ -101,8 +101,12 @@ hipError_t launch_digest_frames(const uint8_t* d_frames, const uint64_t* d_frame
 hipError_t launch_digest_pcm(const int16_t* d_decoded, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
     const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, uint32_t* d_parts /* [max_frames][digest_slices()] */, struct sela_hip_digest* d_digests,
     hipStream_t stream);
+// (the two folds take the bytes of a value: 2 here, 3 or 4 for the tiles of sela_digest_pcm.hip; d_n_a null: every frame of the call)
+hipError_t launch_digest_slices(const uint32_t* d_parts, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride,
+    const uint32_t* d_n_a /* or null */, const uint32_t* d_n_b /* or null */, uint64_t slice_bytes, uint32_t slices, uint32_t value_bytes,
+    struct sela_hip_digest* d_digests, hipStream_t stream);
 hipError_t launch_digest_fold(const struct sela_hip_digest* d_digests, const uint64_t* d_sample_offsets, uint32_t max_frames, const uint32_t* d_n_found,
-    uint32_t channels, uint32_t* d_fold /* [digest_fold_blocks()] */, uint64_t* d_track, hipStream_t stream);
+    uint32_t channels, uint32_t value_bytes, uint32_t* d_fold /* [digest_fold_blocks()] */, uint64_t* d_track, hipStream_t stream);
 size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
 inline size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return digest_workspace_bytes(max_frames, channels, stride, nullptr); }
 hipError_t launch_digest_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
@@ -172,6 +176,22 @@ const uint32_t* verify_pcm_control_words(const void* d_workspace, uint32_t max_f
 hipError_t launch_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, const void* d_pcm, uint32_t bytes_per_sample, uint64_t pcm_samples, uint32_t* d_diff_counts, uint32_t* d_first_diff, uint64_t* d_sample_offsets,
     uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_digest_pcm_device / sela_hip_digest_payload_pcm_device: launch_verify_pcm_device's shape with the
+// compare turned into the CRC-32 of the packed bytes sela_hip_decode_pcm_device would write -- sela_digest_pcm.hip's kernels on the
+// tiles of sela_pcm_layout.h, one raw CRC per (frame, tile) -- and sela_digest.hip's folds behind it.
+uint64_t digest_pcm_tile_bytes(uint32_t channels, uint32_t bytes_per_sample);
+hipError_t launch_digest32_begin(uint32_t* d_ctl /* [2] */, hipStream_t stream);
+hipError_t launch_digest32_direct(const int32_t* d_dec, const GenericSubInfo* d_info, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels, uint32_t stride,
+    uint32_t bytes_per_sample, const uint64_t* d_sample_offsets, uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks /* [max_frames] */,
+    uint32_t* d_parts /* [max_frames][verify_pcm_tiles()] */, hipStream_t stream);
+hipError_t launch_digest32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample,
+    const uint64_t* d_sample_offsets, uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks, uint32_t* d_parts, hipStream_t stream);
+size_t digest_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t digest_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return digest_pcm_workspace_bytes(max_frames, channels, stride, nullptr); }
+const uint32_t* digest_pcm_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
+hipError_t launch_digest_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, int mode, hipStream_t stream);
 // sela_hip_encode_i32_device / sela_hip_encode_n_device: k_generic_analyse, k_generic_plan<true> and
 // k_generic_write on `stream`, nothing waited for.  input as launch_generic_analyse; arguments checked by the caller.
 size_t encode_i32_device_workspace_bytes(uint32_t n_frames, uint32_t channels, uint32_t n, bool paired = false, Carve* at = nullptr);

@@ -1937,7 +1937,7 @@ hipError_t launch_digest_n_device(const uint8_t* d_frames, const uint64_t* d_fra
         });
     if (e != hipSuccess)
         return e;
-    return launch_digest_fold(d_digests, d_sample_offsets ? d_sample_offsets : w.levels.n.offsets, max_frames, d_n_found, channels, w.fold, d_track, stream);
+    return launch_digest_fold(d_digests, d_sample_offsets ? d_sample_offsets : w.levels.n.offsets, max_frames, d_n_found, channels, 2, w.fold, d_track, stream);
 }
 
 // ---- verification of 32-bit and ragged streams on the device (sela_hip_verify_i32_device) --------------------
@@ -2134,6 +2134,61 @@ hipError_t launch_verify_pcm_device(const uint8_t* d_frames, const uint64_t* d_f
                 return e;
             return launch_verify32_sum(w.parts, verify_pcm_tiles(stride, channels), max_frames, d_n_found, d_diff_counts, d_first_diff, d_status, stream);
         });
+}
+
+// ---- the digest of 24- and 32-bit streams on the device (sela_hip_digest_pcm_device) ---------------------------
+// Workspace: launch_verify_pcm_device's pieces (of its two words per (frame, tile) the tile's raw CRC takes the first max_frames *
+// tiles; its sample offsets for a caller that passes none) | the track fold's word per workgroup.
+struct DigestPcmWs {
+    VerifyPcmWs p;
+    uint32_t* fold;
+};
+static DigestPcmWs carve_digest_pcm(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    DigestPcmWs w;
+    w.p = carve_verify_pcm(c, max_frames, channels, stride);
+    w.fold = c.take<uint32_t>(digest_fold_blocks(max_frames));
+    return w;
+}
+
+size_t digest_pcm_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (verify_pcm_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_digest_pcm(c, max_frames, channels, stride); });
+}
+
+const uint32_t* digest_pcm_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    Carve c(d_workspace);
+    return carve_digest_pcm(c, max_frames, channels, stride).p.v.ctl;
+}
+
+// The digest plugs sela_digest_pcm.hip's kernels into launch_i32_sequence -- k_digest32_begin, k_digest32_tiles<., false>, and
+// k_digest32_tiles<., true> -- and runs sela_digest.hip's folds behind it with bytes_per_sample for the bytes of a value: the
+// tiles' words into the records, the records into d_track.  With no frames only the track fold runs, and writes {0, 0}.
+hipError_t launch_digest_pcm_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bytes_per_sample, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, int mode, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const DigestPcmWs dw = carve_digest_pcm(c, max_frames, channels, stride);
+    const VerifyI32Ws& w = dw.p.v;
+    uint64_t* const d_so = d_sample_offsets ? d_sample_offsets : dw.p.offsets;
+    uint32_t* const parts = reinterpret_cast<uint32_t*>(w.parts);
+    const uint32_t n_tiles = verify_pcm_tiles(stride, channels);
+    hipError_t e = launch_i32_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w, d_so,
+        [&] { return launch_digest32_begin(w.ctl, stream); },
+        [&] {
+            return launch_digest32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, bytes_per_sample, d_so, d_status, w.ctl, w.marks, parts, stream);
+        },
+        [&] { return launch_digest32_rest(w.all, w.counts, max_frames, channels, stride, bytes_per_sample, d_so, d_status, w.ctl, w.marks, parts, stream); });
+    if (e == hipSuccess)
+        e = launch_digest_slices(parts, d_so, max_frames, channels, stride, d_n_found, nullptr, digest_pcm_tile_bytes(channels, bytes_per_sample), n_tiles,
+            bytes_per_sample, d_digests, stream);
+    if (e != hipSuccess)
+        return e;
+    return launch_digest_fold(d_digests, d_so, max_frames, d_n_found, channels, bytes_per_sample, dw.fold, d_track, stream);
 }
 
 // Workspace of the device-pointer encode: signals | residues | q | meta records | word bases | choices | the plan's total.  No

@@ -188,6 +188,9 @@ int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
 int generic_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests, uint32_t* track_crc32,
     uint64_t* track_bytes, int recurrence_form);
 int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level32* levels);
+// sela_hip_digest_pcm: generic_levels_i32's chunks, the chunks' track words and wide-sample counts folded on the host (any output may be null)
+int generic_digest_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample,
+    struct sela_hip_digest* digests, uint32_t* track_crc32, uint64_t* track_bytes, uint32_t* wide_samples);
 // sela_hip_verify_pcm: the stride is the stream's largest samplesPerChannel (the host's walk); each chunk's packed bytes are staged
 // from the chunk's first frame, so the device's base is aligned and the chunk's own sample offsets start at 0.
 int generic_verify_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t bytes_per_sample, const uint8_t* pcm,
