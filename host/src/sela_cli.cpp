@@ -36,6 +36,11 @@
 //                                      sela_hip_digest_pcm -- the CRC-32 of the packed 3- or 4-byte samples as a WAV of that width
 //                                      holds them; one more line where samples of a 24-bit file lie beyond 24 bits; a --whole file
 //                                      as it stands; a .wav of another width is refused by name (exit 1)
+//   sela_mi355x -s in.sela out.sela   salvage: the frames of a damaged file found on the GPU past the positions where every other verb
+//                                      stops silently, and written back to back under a header that counts them.  Prints the announced
+//                                      and the found frame counts, a line per gap (file offset, bytes, index of the frame behind it)
+//                                      and the bytes behind the last frame; exit 0: nothing skipped, nothing trailing, found ==
+//                                      announced, 2: frames were written but something was lost, 1: no frame found, or not a .sela
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -57,6 +62,7 @@
 
 #include "sela_host/codec.hpp"
 #include "sela_host/player.hpp"
+#include "sela_host/salvage.hpp"
 #include "sela_host/wide.hpp"
 
 namespace {
@@ -83,6 +89,8 @@ int usage(const std::string& program)
               << program << " -c path/to/input.sela [path/to/input.wav]\n\n"
               << "The same for a 16-, 24- or 32-bit file (as -c, by the file's own header; the CRC-32 of the packed samples):\n"
               << program << " -C path/to/input.sela [path/to/input.wav]\n\n"
+              << "Salvaging a damaged file (the frames that can still be found, back to back; exit 2 where something was lost):\n"
+              << program << " -s path/to/input.sela path/to/output.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -304,6 +312,14 @@ int run(int argc, char** argv)
         const sela::DigestReport report = sela::digestFile(std::string(argv[2]), wav);
         std::cout << sela::formatDigestReport(report) << std::flush;
         return report.agree() ? 0 : 3;
+    }
+    if (verb == "-s") {
+        if (argc != 4)
+            return usage(program);
+        std::cout << "Salvaging: " << argv[2] << std::endl;
+        const sela::SalvageReport report = sela::salvageFile(std::string(argv[2]), std::string(argv[3]));
+        std::cout << sela::formatSalvageReport(report) << std::flush;
+        return sela::salvageExitCode(report);
     }
     if (verb == "-M") {
         if (argc != 3)

@@ -1229,6 +1229,80 @@ int sela_hip_decode_end(sela_hip_job* job, uint32_t* frames_final);
 uint32_t sela_hip_index_frames(const uint8_t* frames, size_t frames_bytes, uint32_t n_frames, uint32_t channels,
     uint64_t* frame_offsets);
 
+/* ---- salvage: the frames of a damaged payload ------------------------------------------------
+ * sela_hip_index_frames() and its device form stop silently at the first position that fails their test; every call that
+ * reads a payload decodes only what that walk found.  The salvage walk goes on past such a position.  For a payload of B
+ * bytes let W = B / 4 (integer division) and C = channels:
+ *   candidate   a word index w < W whose word is the sync word and whose C subframe headers, read with sela_format.h's
+ *               reader and bound B, all fit: sela_hip_index_frames()'s test of a position.  end(w) is the byte where that frame
+ *               would end, always a multiple of 4;
+ *   confirmed   a candidate with end(w) == 4 W, or with end(w) / 4 itself a candidate: a true frame followed by an intact
+ *               frame or by the end of the payload is one, a sync word met by chance in Rice data or in garbage almost never;
+ *   the walk    starts at p = 0 with no frame taken.  While fewer than max_frames frames are taken: if p / 4 is a candidate, it
+ *               is taken (the position is trusted: offset 0, or the end of a taken frame); otherwise the smallest confirmed
+ *               candidate q with 4 q >= p is taken with skipped_before = 4 q - p, and if there is none the walk ends.
+ *               Then p = end(taken).
+ * Per taken frame one record; totals[0] = frames taken, [1] = records with skipped_before > 0, [2] = sum of bytes,
+ * [3] = offset + bytes of the last record (0 without one): B - totals[3] bytes lie behind the last frame.
+ * What follows from the rule:
+ *   - where sela_hip_index_frames() finds n frames, the first n records are those frames with skipped_before == 0: on an
+ *     intact payload the salvage is the index;
+ *   - offsets strictly increase and frames never overlap;
+ *   - the taken frames written back to back form a payload on which sela_hip_index_frames() finds exactly those frames and
+ *     ends at its last byte; salvaging that payload again takes the same frames with no gap.
+ * Its limits, as they are:
+ *   - only word positions relative to the payload are looked at (as in sela_hip_index_frames_device): damage that inserts
+ *     or deletes a number of bytes that is not a multiple of 4 loses everything behind it;
+ *   - an intact frame whose predecessor was not taken AND whose successor's header is damaged is neither trusted nor
+ *     confirmed, and is not recovered;
+ *   - a trusted frame whose damaged length fields still pass the bounds sends the walk to the wrong place; it
+ *     resynchronises from there;
+ *   - a chance sync word whose headers fit and whose end lands on a candidate is confirmed, and is taken when the walk is
+ *     searching at or before it.
+ * Whether a taken frame's CONTENTS are sound is not judged here: that is the decoders' flags', sela_hip_verify*'s and
+ * sela_hip_digest*'s business. */
+typedef struct sela_hip_salvaged { /* 24 bytes, 8-byte aligned */
+    uint64_t offset;         /* of the frame in the payload, a multiple of 4 */
+    uint64_t skipped_before; /* bytes between the end of the frame before (or offset 0) and this one */
+    uint32_t bytes;          /* the frame's length, a multiple of 4 */
+    uint32_t reserved;       /* 0 */
+} sela_hip_salvaged;
+/* The walk on the host: pure CPU, no device needed, any alignment of `payload`.  records: [max_frames], entries
+ * [0 .. the count) are written (NULL: none); totals: uint64 [4] (or NULL).  channels outside 1..255: no frame.  Returns
+ * the number of frames taken. */
+uint32_t sela_hip_salvage_frames(const uint8_t* payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    sela_hip_salvaged* records, uint64_t* totals);
+/*
+ * The same walk on the device: d_records and d_totals receive exactly what sela_hip_salvage_frames() writes for the same
+ * bytes, for every input; entries beyond totals[0] are not written.  d_payload must be 4-byte aligned.  Asynchronous on
+ * `stream`, no allocation, no host synchronisation, no host read of device data; the launches are shaped by payload_bytes
+ * and max_frames alone (a stream being captured into a graph may take it): 8 + ceil(log2(max_frames)) kernel launches;
+ * one for a payload without a word or a max_frames of 0.
+ * d_workspace: sela_hip_salvage_workspace_bytes(payload_bytes, max_frames) bytes, no initialisation.  With W =
+ * payload_bytes / 4, K = ceil(W / 4096), F = min(max_frames, W) and up(b) = b rounded up to a multiple of 256 it is
+ *   9 up(4 W) + 2 up(4 (K + 1)) + 3 up(4 F) + 5 * 256 + 256
+ * bytes: the index's six arrays of one uint32 per payload word, three more, a word per 4096 candidates twice, three uint32
+ * per frame, five single words, and the base's alignment.
+ * SELA_HIP_EINVAL: channels outside 1..255, a null pointer, a misaligned d_payload, a payload of 16 GiB or more;
+ * SELA_HIP_ECAPACITY: a smaller workspace -- sela_hip_index_frames_device()'s cases and codes, found before anything is
+ * enqueued.
+ */
+size_t sela_hip_salvage_workspace_bytes(size_t payload_bytes, uint32_t max_frames);
+int sela_hip_salvage_frames_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    sela_hip_salvaged* d_records /* [max_frames] */, uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+/*
+ * The walk, then the taken frames copied back to back into d_out (one more launch): d_frame_offsets[0 .. totals[0]] are
+ * their offsets there, ready for every *_device call that takes frames with their offsets.  d_records may be NULL.
+ * A frame that ends beyond out_cap is counted and given its offsets but not written, and neither is any frame behind it:
+ * no byte of d_out at or behind the first such frame's offset is written.  The caller reads the room needed from
+ * d_frame_offsets[totals[0]] (== totals[2]), as with the encoders.  d_out is 4-byte aligned and does not overlap the
+ * payload (SELA_HIP_EINVAL).  Workspace, asynchrony and the other errors: as the call above.
+ */
+int sela_hip_salvage_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets /* [max_frames + 1] */, sela_hip_salvaged* d_records /* [max_frames] or NULL */,
+    uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the stages on their own -------------------------------------------------------------------------------
  * The reference's public L1 classes (src/include/lpc.hpp:73-117, src/include/rice.hpp:9-43; its tests call them directly:
  * test/lpctests.cpp:10-32, test/ricetests.cpp:7-25), batched, on HOST pointers.  Not the fast path -- a frame goes through

@@ -145,13 +145,13 @@ uint64_t sela_hip_debug_windows_staged_bytes(void);
  *   DECODE_I32, DECODE_N, VERIFY, VERIFY_I32: a = max_frames, b = channels, c = stride
  *   ENCODE_I32, ENCODE_PAIRED: a = n_frames, b = channels, c = samples_per_channel
  *   WINDOWS, WINDOWS_WHOLE: a = n_windows, b = window_samples, c = channels      ENCODE_WHOLE: a = max_samples, b = channels
- *   DECODE_WHOLE: a = max_frames, b = channels
+ *   DECODE_WHOLE: a = max_frames, b = channels            SALVAGE: a = payload_bytes, b = max_frames
  *   ENCODE_SPLIT (a launch that sela_hip_debug_encode_split cuts in two): a = n_frames, b = channels, c = frames of the first half */
 enum {
     SELA_HIP_WORKSPACE_ENCODE = 0, SELA_HIP_WORKSPACE_DECODE, SELA_HIP_WORKSPACE_INDEX, SELA_HIP_WORKSPACE_DECODE_I32, SELA_HIP_WORKSPACE_DECODE_N,
     SELA_HIP_WORKSPACE_VERIFY, SELA_HIP_WORKSPACE_VERIFY_I32, SELA_HIP_WORKSPACE_ENCODE_I32, SELA_HIP_WORKSPACE_ENCODE_PAIRED, SELA_HIP_WORKSPACE_WINDOWS,
     SELA_HIP_WORKSPACE_WINDOWS_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE, SELA_HIP_WORKSPACE_ENCODE_SPLIT, SELA_HIP_WORKSPACE_DECODE_WHOLE, SELA_HIP_WORKSPACE_WINDOWS_I32,
-    SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM
+    SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE, SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM, SELA_HIP_WORKSPACE_SALVAGE
 };
 int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c, uint64_t* offset_bytes_pairs, int capacity);
 /* Debug hook (tests; process-wide): the host-pointer calls that work in chunks of whole frames on one loop -- sela_hip_verify, sela_hip_verify_i32,

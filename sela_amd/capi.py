@@ -60,6 +60,7 @@ EXPORTS = [
     "sela_hip_digest_workspace_bytes", "sela_hip_digest_device", "sela_hip_digest_payload_device", "sela_hip_digest", "sela_hip_crc32_combine",
     "sela_hip_crc32_workspace_bytes", "sela_hip_crc32_device",
     "sela_hip_digest_pcm_workspace_bytes", "sela_hip_digest_pcm_device", "sela_hip_digest_payload_pcm_device", "sela_hip_digest_pcm",
+    "sela_hip_salvage_frames", "sela_hip_salvage_workspace_bytes", "sela_hip_salvage_frames_device", "sela_hip_salvage_payload_device",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED, WINDOW_PCM32_INTERLEAVED = 2, 3, 4  # (sela_hip_decode_windows_i32*: these and F32_PLANAR)
@@ -78,7 +79,7 @@ DEBUG_EXPORTS = [
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
-                   "encode_whole", "encode_split", "decode_whole", "windows_i32", "windows_i32_whole", "encode_whole_pcm")
+                   "encode_whole", "encode_split", "decode_whole", "windows_i32", "windows_i32_whole", "encode_whole_pcm", "salvage")
 
 
 class Trace(C.Structure):
@@ -145,6 +146,14 @@ def lib() -> C.CDLL:
     L.sela_hip_index_workspace_bytes.restype = sz
     L.sela_hip_index_frames_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, sz, vp]
     L.sela_hip_index_frames_device.restype = C.c_int
+    L.sela_hip_salvage_frames.argtypes = [vp, sz, u32, u32, vp, vp]
+    L.sela_hip_salvage_frames.restype = u32
+    L.sela_hip_salvage_workspace_bytes.argtypes = [sz, u32]
+    L.sela_hip_salvage_workspace_bytes.restype = sz
+    L.sela_hip_salvage_frames_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, sz, vp]
+    L.sela_hip_salvage_frames_device.restype = C.c_int
+    L.sela_hip_salvage_payload_device.argtypes = [vp, sz, u32, u32, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_salvage_payload_device.restype = C.c_int
     L.sela_hip_decode_payload_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, vp, vp, sz, vp]
     L.sela_hip_decode_payload_device.restype = C.c_int
     L.sela_hip_decode_i32_workspace_bytes.argtypes = [u32, u32, u32]

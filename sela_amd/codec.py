@@ -1328,6 +1328,89 @@ def index_workspace_bytes(payload_bytes: int, max_frames: int) -> int:
     return int(capi.lib().sela_hip_index_workspace_bytes(payload_bytes, max_frames))
 
 
+# struct sela_hip_salvaged (include/sela_hip.h): 24 bytes per taken frame
+SALVAGED_DTYPE = np.dtype([("offset", "<u8"), ("skipped_before", "<u8"), ("bytes", "<u4"), ("reserved", "<u4")])
+
+
+def salvage_frames(payload: np.ndarray, channels: int, max_frames=None):
+    """sela_hip_salvage_frames on a numpy array: the frames of a damaged payload, walked on the host (no device needed;
+    DESIGN.md 5.30) -> (records SALVAGED_DTYPE [frames taken], totals uint64 [4]: frames taken, records with a gap in front,
+    the sum of their bytes, the end of the last one).  max_frames: the cap (default: as many as the bytes could hold)."""
+    lib = capi.lib()
+    body = np.ascontiguousarray(payload, dtype=np.uint8)
+    if max_frames is None:
+        max_frames = body.nbytes // (4 + 12 * max(channels, 1))
+    records = np.zeros(max_frames, SALVAGED_DTYPE)
+    totals = np.zeros(4, np.uint64)
+    found = lib.sela_hip_salvage_frames(body.ctypes.data, body.nbytes, max_frames, channels, records.ctypes.data, totals.ctypes.data)
+    return records[:found], totals
+
+
+def salvage_workspace_bytes(payload_bytes: int, max_frames: int) -> int:
+    return int(capi.lib().sela_hip_salvage_workspace_bytes(payload_bytes, max_frames))
+
+
+class Salvager:
+    """sela_hip_salvage_frames_device / sela_hip_salvage_payload_device: the frames of a damaged .sela payload found on the
+    device, past positions where the index stops, and copied back to back.  Owns its records, totals, frame
+    offsets, compacted payload and workspace on the current device (or `device`), sized once for payloads of up to
+    max_payload_bytes; every call is asynchronous on the current stream and overwrites them -- so it can be captured into a
+    graph."""
+
+    def __init__(self, max_payload_bytes: int, max_frames: int, channels: int, device=None):
+        import torch
+
+        self.lib = capi.lib()
+        self.max_payload_bytes, self.max_frames, self.channels = int(max_payload_bytes), int(max_frames), int(channels)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # the records as int64 [max_frames, 3]: offset, skipped_before, bytes | reserved << 32; the totals as int64 [4]
+        self.salvaged = torch.zeros((self.max_frames, 3), dtype=torch.int64, device=self.device)
+        self.totals = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self.frame_offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
+        self.out = torch.zeros(self.max_payload_bytes // 4 * 4, dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty(salvage_workspace_bytes(self.max_payload_bytes, self.max_frames), dtype=torch.uint8, device=self.device)
+
+    def _payload_ok(self, payload) -> None:
+        import torch
+
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous() and payload.device == self.device
+        assert payload.numel() <= self.max_payload_bytes, "payload larger than the salvager was sized for"
+
+    def frames(self, payload):
+        """payload: uint8 cuda tensor (4-byte aligned) -> (records int64 [max_frames, 3], totals int64 [4]), views of the
+        salvager's own buffers: records up to totals[0] are the walk's (records(): as SALVAGED_DTYPE)."""
+        import torch
+
+        self._payload_ok(payload)
+        capi.check(self.lib.sela_hip_salvage_frames_device(
+            payload.data_ptr(), payload.numel(), self.max_frames, self.channels, self.salvaged.data_ptr(), self.totals.data_ptr(),
+            self.workspace.data_ptr(), self.workspace.numel(), torch.cuda.current_stream(self.device).cuda_stream))
+        return self.salvaged, self.totals
+
+    def payload(self, payload, out=None):
+        """The walk, then the taken frames copied back to back into `out` (uint8 cuda tensor, 4-byte aligned, apart from the
+        payload; default: the salvager's own, which holds any payload it was sized for) -> (out, frame offsets int64
+        [max_frames + 1], records, totals): out[: totals[2]] and offsets[: totals[0] + 1] are ready for every call that takes
+        frames with their offsets.  A frame that ends beyond out's size is counted but neither it nor any behind it is written."""
+        import torch
+
+        self._payload_ok(payload)
+        if out is None:
+            out = self.out
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+        capi.check(self.lib.sela_hip_salvage_payload_device(
+            payload.data_ptr(), payload.numel(), self.max_frames, self.channels, out.data_ptr(), out.numel(), self.frame_offsets.data_ptr(),
+            self.salvaged.data_ptr(), self.totals.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        return out, self.frame_offsets, self.salvaged, self.totals
+
+    def records(self) -> np.ndarray:
+        """Waits for the last call -> a host copy of the records it took, as SALVAGED_DTYPE [totals[0]]."""
+        found = int(self.totals.cpu()[0])
+        host = np.ascontiguousarray(self.salvaged[:found].cpu().numpy())
+        return host.view(SALVAGED_DTYPE).reshape(found)
+
+
 @dataclass
 class SelaPayload:
     """A .sela file's payload on the device, and what its 15-byte header says."""

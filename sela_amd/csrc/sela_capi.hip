@@ -27,6 +27,7 @@
 #include "sela_host.h"
 #include "sela_lease.h"
 #include "sela_pcm.h"
+#include "sela_salvage_walk.h"
 
 namespace {
 
@@ -1611,6 +1612,55 @@ int sela_hip_decode_payload_device(const uint8_t* d_payload, size_t payload_byte
     return decode_device_launch(d_payload, d_frame_offsets, max_frames, channels, d_pcm_out, d_status, ws.own, stream, d_n_frames);
 }
 
+// ---- salvage: the frames of a damaged payload (the walk: sela_salvage_walk.h, the device: sela_salvage.hip) ------
+uint32_t sela_hip_salvage_frames(const uint8_t* payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* records,
+    uint64_t* totals)
+{
+    return sela::salvage_walk(payload, payload_bytes, max_frames, channels, records, totals);
+}
+
+size_t sela_hip_salvage_workspace_bytes(size_t payload_bytes, uint32_t max_frames)
+{
+    return sela::salvage_workspace_bytes(payload_bytes, max_frames);
+}
+
+namespace {
+// both salvage calls' checks: the index's cases and codes; d_out null for the walk alone
+int salvage_call(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets,
+    sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream, bool copy)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (!d_totals || !d_workspace || (payload_bytes && !d_payload) || (!copy && max_frames && !d_records) || (copy && (!d_frame_offsets || (out_cap && !d_out))))
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if ((uintptr_t)d_payload & 3)
+        return fail(SELA_HIP_EINVAL, "d_payload must be 4-byte aligned");
+    if (copy && ((uintptr_t)d_out & 3))
+        return fail(SELA_HIP_EINVAL, "d_out must be 4-byte aligned");
+    if (payload_bytes / 4 >= 0xFFFFFFFFull)
+        return fail(SELA_HIP_EINVAL, "payloads of 16 GiB and more are not indexed on the device (32-bit word indices)");
+    if (copy && out_cap && payload_bytes && (uintptr_t)d_out < (uintptr_t)d_payload + payload_bytes && (uintptr_t)d_payload < (uintptr_t)d_out + out_cap)
+        return fail(SELA_HIP_EINVAL, "d_out must not overlap the payload");
+    if (workspace_bytes < sela::salvage_workspace_bytes(payload_bytes, max_frames))
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_salvage_workspace_bytes()");
+    return launched(sela::launch_salvage(d_payload, payload_bytes, max_frames, channels, d_records, d_totals, copy && out_cap ? d_out : nullptr, out_cap,
+                        d_frame_offsets, d_workspace, static_cast<hipStream_t>(stream)),
+        "salvage launch");
+}
+} // namespace
+
+int sela_hip_salvage_frames_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
+    uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return salvage_call(d_payload, payload_bytes, max_frames, channels, nullptr, 0, nullptr, d_records, d_totals, d_workspace, workspace_bytes, stream, false);
+}
+
+int sela_hip_salvage_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint8_t* d_out, size_t out_cap,
+    uint64_t* d_frame_offsets, sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return salvage_call(d_payload, payload_bytes, max_frames, channels, d_out, out_cap, d_frame_offsets, d_records, d_totals, d_workspace, workspace_bytes, stream, true);
+}
+
 // ---- the decode and verify calls of any length on device pointers, each in two forms ---------------
 // A call is its own check of its arguments, its workspace formula and its launch.  What it is given -- frames with their
 // offsets, or a payload that the device indexes first -- is a FORM, and the form runs the call:
@@ -2650,7 +2700,7 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
     sela::Carve at(&pieces);
     const uint32_t a32 = (uint32_t)a;
     size_t bytes = SIZE_MAX;
-    if (call != SELA_HIP_WORKSPACE_INDEX && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM && a > 0xFFFFFFFFull)
+    if (call != SELA_HIP_WORKSPACE_INDEX && call != SELA_HIP_WORKSPACE_SALVAGE && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE && call != SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM && a > 0xFFFFFFFFull)
         return -1;
     switch (call) {
     case SELA_HIP_WORKSPACE_ENCODE: bytes = sela::encode_workspace_bytes(a32, b, &at); break;
@@ -2674,6 +2724,7 @@ int sela_hip_debug_workspace_pieces(int call, uint64_t a, uint32_t b, uint32_t c
     case SELA_HIP_WORKSPACE_WINDOWS_I32: bytes = sela::window32_workspace_bytes(a32, b, c, &at); break;
     case SELA_HIP_WORKSPACE_WINDOWS_I32_WHOLE: bytes = sela::window32_whole_workspace_bytes(a32, b, c, &at); break;
     case SELA_HIP_WORKSPACE_ENCODE_WHOLE_PCM: bytes = sela::whole_pcm_workspace_bytes(a, b, &at); break;
+    case SELA_HIP_WORKSPACE_SALVAGE: bytes = sela::salvage_workspace_bytes(a, b, &at); break;
     default: return -1;
     }
     return bytes == SIZE_MAX ? -1 : pieces.count;

@@ -41,6 +41,48 @@ hipError_t launch_stage_rice_decode(const uint32_t* d_words, const uint64_t* d_w
 size_t index_workspace_bytes(uint64_t payload_bytes, Carve* at = nullptr);
 hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, uint64_t* d_frame_offsets,
     uint32_t* d_n_frames, void* d_workspace, hipStream_t stream);
+// What sela_salvage.hip shares with the index (sela_index.inc): its "none", the shape of its candidates kernel, its workspace,
+// and its first three launches.
+constexpr uint32_t kIndexNone = 0xFFFFFFFFu;
+constexpr int kIndexThreads = 256;
+constexpr int kIndexWordsPerThread = 16;
+constexpr uint32_t kIndexChunkWords = (uint32_t)kIndexThreads * kIndexWordsPerThread; // words one candidates workgroup covers
+struct IndexWs {
+    uint32_t* stage_pos;  // [words] per workgroup, then jump array A
+    uint32_t* stage_next; // [words] per workgroup, then jump array B
+    uint32_t* pos;        // [n_cand] word index of candidate i (increasing)
+    uint32_t* next;       // [n_cand] word index of the end of candidate i's frame (<= words)
+    uint32_t* rank;       // [n_cand] frame index of a reached candidate, kIndexNone otherwise
+    uint32_t* map;        // [words]  map[pos[i]] = i
+    uint32_t* counts;     // [blocks + 1] candidates per workgroup, then their exclusive scan
+    uint32_t* n_cand;     // [1]
+};
+// The workspace (sela_workspace.h), for a payload of `words` 32-bit words (every word may be a candidate): six arrays of one
+// uint32 per word, the scan's counts and the candidate count.
+inline IndexWs carve_index(Carve& c, uint64_t words)
+{
+    const uint64_t blocks = (words + kIndexChunkWords - 1) / kIndexChunkWords;
+    IndexWs ws;
+    ws.stage_pos = c.take<uint32_t>(words);
+    ws.stage_next = c.take<uint32_t>(words);
+    ws.pos = c.take<uint32_t>(words);
+    ws.next = c.take<uint32_t>(words);
+    ws.rank = c.take<uint32_t>(words);
+    ws.map = c.take<uint32_t>(words);
+    ws.counts = c.take<uint32_t>(blocks + 1);
+    ws.n_cand = c.take<uint32_t>(1);
+    return ws;
+}
+// k_index_candidates, k_index_scan and k_index_compact alone (words > 0): pos[], next[], map[] and *n_cand of `ws` filled.
+// k_index_scan also sets the outputs it is given to "no frame found": d_frame_offsets[0] = 0, *d_n_frames = 0.
+hipError_t launch_index_candidates(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t channels, const IndexWs& ws, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, hipStream_t stream);
+
+// ---- sela_salvage.hip: the frames of a damaged payload -----------------------------------------------------------
+size_t salvage_workspace_bytes(uint64_t payload_bytes, uint32_t max_frames, Carve* at = nullptr);
+// d_out null: the walk alone (d_frame_offsets may then be null too); d_records may be null.  The caller has checked the arguments.
+hipError_t launch_salvage(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
+    uint64_t* d_totals, uint8_t* d_out, uint64_t out_cap, uint64_t* d_frame_offsets, void* d_workspace, hipStream_t stream);
 
 // ---- sela_window.hip: sample windows of a stream ---------------------------------------------------------------
 uint32_t window_cover(uint32_t window_samples); // the most frames a window of that length touches: the grid's second extent

@@ -25,41 +25,11 @@
 //
 // links + rounds + scatter run in ONE workgroup, on LDS, when max_frames <= kIndexOneGroupFrames (a track; four launches in
 // all), and as 2 + ceil(log2(max_frames)) launches over the whole device otherwise.
-constexpr uint32_t kIndexNone = 0xFFFFFFFFu;
-constexpr int kIndexThreads = 256;
-constexpr int kIndexWordsPerThread = 16;
-constexpr uint32_t kIndexChunkWords = (uint32_t)kIndexThreads * kIndexWordsPerThread; // words one candidates workgroup covers
+// (kIndexNone, the candidates kernel's shape, IndexWs and carve_index: sela_host.h, for sela_salvage.hip's sake)
 constexpr int kIndexScanThreads = 1024;
 constexpr uint32_t kIndexOneGroupFrames = 4096;  // max_frames up to this: links, rounds and scatter in one workgroup
 constexpr uint32_t kIndexOneGroupNodes = 5120;   // ... on LDS while the candidates fit (12 bytes each: 60 KiB); beyond, in the workspace
 constexpr int kIndexLinkBlocks = 1024;           // grid of the device-wide link / round / scatter launches (grid-stride)
-
-struct IndexWs {
-    uint32_t* stage_pos;  // [words] per workgroup, then jump array A
-    uint32_t* stage_next; // [words] per workgroup, then jump array B
-    uint32_t* pos;        // [n_cand] word index of candidate i (increasing)
-    uint32_t* next;       // [n_cand] word index of the end of candidate i's frame (<= words)
-    uint32_t* rank;       // [n_cand] frame index of a reached candidate, kIndexNone otherwise
-    uint32_t* map;        // [words]  map[pos[i]] = i
-    uint32_t* counts;     // [blocks + 1] candidates per workgroup, then their exclusive scan
-    uint32_t* n_cand;     // [1]
-};
-// The workspace (sela_workspace.h), for a payload of `words` 32-bit words (every word may be a candidate): six arrays of one
-// uint32 per word, the scan's counts and the candidate count.
-inline IndexWs carve_index(Carve& c, uint64_t words)
-{
-    const uint64_t blocks = (words + kIndexChunkWords - 1) / kIndexChunkWords;
-    IndexWs ws;
-    ws.stage_pos = c.take<uint32_t>(words);
-    ws.stage_next = c.take<uint32_t>(words);
-    ws.pos = c.take<uint32_t>(words);
-    ws.next = c.take<uint32_t>(words);
-    ws.rank = c.take<uint32_t>(words);
-    ws.map = c.take<uint32_t>(words);
-    ws.counts = c.take<uint32_t>(blocks + 1);
-    ws.n_cand = c.take<uint32_t>(1);
-    return ws;
-}
 
 // The host walk's test of one position (sela_hip_index_frames): the frame's end in words, or kIndexNone.  `off` is a word
 // boundary that holds the sync word, so every subframe of the frame is one too: the word form of the header reader, whose
@@ -309,5 +279,16 @@ hipError_t launch_index(const uint8_t* d_payload, uint64_t payload_bytes, uint32
         std::swap(cur, nxt);
     }
     hipLaunchKernelGGL(k_index_scatter, dim3(grid), dim3(kIndexThreads), 0, stream, ws, max_frames, d_frame_offsets, d_n_frames);
+    return hipGetLastError();
+}
+
+// The first three launches alone, for sela_salvage.hip (sela_host.h): the candidates of a payload of words > 0 words, packed.
+hipError_t launch_index_candidates(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t channels, const IndexWs& ws, uint64_t* d_frame_offsets,
+    uint32_t* d_n_frames, hipStream_t stream)
+{
+    const uint32_t words = (uint32_t)(payload_bytes / 4), blocks = (uint32_t)(((uint64_t)words + kIndexChunkWords - 1) / kIndexChunkWords);
+    hipLaunchKernelGGL(k_index_candidates, dim3(blocks), dim3(kIndexThreads), 0, stream, d_payload, payload_bytes, words, channels, ws);
+    hipLaunchKernelGGL(k_index_scan, dim3(1), dim3(kIndexScanThreads), 0, stream, ws, blocks, d_frame_offsets, d_n_frames);
+    hipLaunchKernelGGL(k_index_compact, dim3(blocks), dim3(kIndexThreads), 0, stream, ws);
     return hipGetLastError();
 }
