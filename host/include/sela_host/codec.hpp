@@ -15,6 +15,7 @@
 
 #include "sela_host/files.hpp"
 #include "sela_host/digest.hpp"
+#include "sela_host/envelope.hpp"
 #include "sela_host/levels.hpp"
 
 namespace sela {
@@ -145,6 +146,15 @@ std::string formatLevelReport(const WideLevelReport& report);
 // memory.  With a WAV named, the host's own CRC-32 of its data chunk is set beside it -- cut to the samples the .sela holds, as
 // verifyFile cuts it.  A 24- or 32-bit .sela is refused by name: the digest is that of 16-bit samples.
 DigestReport digestFile(const std::string& selaPath, const std::string& wavPath = std::string());
+
+// ---- envelope: a waveform overview of this .sela ---------------------------------------------------------------
+// envelopeFile() reads the file the way measureFile does (the frames it really holds; a --keep-tail file's long last frame as it
+// stands) and asks sela_hip_envelope for every frame's records: min, max, sum and sum of squares per `bucket` samples and channel,
+// measured on the GPU, nothing decoded into host memory -- then compacts them onto the track's grid (envelope.hpp).  A bucket
+// outside {32, 64, ..., 2048} is refused with the set named, a 24- or 32-bit .sela by name: the records are those of 16-bit samples.
+EnvelopeReport envelopeFile(const std::string& selaPath, uint32_t bucket = kEnvelopeDefaultBucket);
+// envelopeFile(), then the .env file of envelope.hpp written to envPath.
+EnvelopeReport writeEnvelopeFile(const std::string& selaPath, const std::string& envPath, uint32_t bucket = kEnvelopeDefaultBucket);
 
 // ---- many files, all GPUs of the node ------------------------------------------------------------------
 // BASELINE.json configs[3]: an album's tracks are one index space of frames, cut into contiguous balanced

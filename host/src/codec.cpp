@@ -1105,6 +1105,52 @@ std::string formatLevelReport(const LevelReport& r)
     return out;
 }
 
+// ---- envelope --------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(EnvelopeRecord) == sizeof(struct sela_hip_envelope) && offsetof(EnvelopeRecord, max) == offsetof(struct sela_hip_envelope, max)
+        && offsetof(EnvelopeRecord, sum) == offsetof(struct sela_hip_envelope, sum) && offsetof(EnvelopeRecord, sumSquares) == offsetof(struct sela_hip_envelope, sum_squares),
+    "envelope.hpp restates the device's record");
+
+EnvelopeReport envelopeFile(const std::string& selaPath, uint32_t bucket)
+{
+    if (!envelopeBucketOk(bucket))
+        throw data::Exception(envelopeBucketRefusal(bucket));
+    const SelaInfo info = probeSela(selaPath);
+    if (info.header.bitsPerSample == 24 || info.header.bitsPerSample == 32)
+        throw data::Exception(envelopeBitsRefusal(selaPath, info.header.bitsPerSample));
+    const uint32_t channels = info.header.channels;
+    EnvelopeReport r;
+    r.channels = channels;
+    r.bucket = bucket;
+    r.sampleRate = info.header.sampleRate;
+    // the frames the file really holds (as verifyFile finds them)
+    std::vector<uint8_t> payload(info.payload + 8);
+    if (info.payload)
+        sela_host::PosixFile::openForRead(selaPath).readAt(payload.data(), info.payload, 15);
+    std::vector<uint64_t> offsets(info.announced + 1, 0);
+    const uint32_t found = sela_hip_index_frames(payload.data(), info.payload, (uint32_t)info.announced, channels, offsets.data());
+    std::vector<uint64_t> sampleOffsets((size_t)found + 1, 0);
+    const uint32_t stride = std::max(sela_hip_index_samples(payload.data(), offsets.data(), found, channels, sampleOffsets.data()), 1u);
+    const uint32_t slots = envelopeSlots(stride, bucket);
+    std::vector<EnvelopeRecord> records((size_t)found * slots * channels + 1);
+    if (sela_hip_envelope(payload.data(), offsets.data(), found, channels, stride, bucket, reinterpret_cast<struct sela_hip_envelope*>(records.data())) != SELA_HIP_OK)
+        gpuFailure("Envelope");
+    r.samplesPerChannel = sampleOffsets[found];
+    try {
+        r.records = compactEnvelope(records.data(), sampleOffsets.data(), found, slots, channels, bucket);
+    } catch (const std::invalid_argument& e) {
+        throw data::Exception(e.what());
+    }
+    return r;
+}
+
+EnvelopeReport writeEnvelopeFile(const std::string& selaPath, const std::string& envPath, uint32_t bucket)
+{
+    const EnvelopeReport r = envelopeFile(selaPath, bucket);
+    const std::vector<uint8_t> bytes = envelopeFileBytes(r);
+    sela_host::PosixFile::create(envPath).writeAt(bytes.data(), bytes.size(), 0);
+    return r;
+}
+
 // ---- digest ----------------------------------------------------------------------------------------------------------------
 DigestReport digestFile(const std::string& selaPath, const std::string& wavPath)
 {

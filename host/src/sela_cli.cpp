@@ -25,6 +25,12 @@
 //                                      int16 samples (reduced on the GPU, nothing decoded into memory), then dBFS peak, dBFS RMS and
 //                                      DC offset; a last line for the track.  A --keep-tail file is read as it stands; a 24- or
 //                                      32-bit .sela is refused by name (exit 1)
+//   sela_mi355x -w [--bucket B] in.sela out.env   waveform: per B samples (a power of two from 32 to 2048; 256 unless given) and channel
+//                                      the smallest and the largest sample, the sum and the sum of squares, on the track's own grid
+//                                      (reduced on the GPU, nothing decoded into memory) -> out.env: 32 bytes of header ("SELAENV1",
+//                                      uint32 channels, uint32 B, uint64 samples per channel, uint32 sample rate, uint32 16), then
+//                                      16-byte records [bucket][channel].  A --keep-tail file is read as it stands; a 24- or 32-bit
+//                                      .sela is refused by name, a bucket outside the set with the set named (exit 1, as -m)
 //   sela_mi355x -M in.sela             the same by the file's own header: a 16-bit file exactly as -m, a 24- or 32-bit file through
 //                                      sela_hip_levels_i32 -- the integers of its samples as they are (the sum of squares in 128
 //                                      bits, printed whole), dBFS against the file's own full scale; a --whole file as it stands
@@ -83,6 +89,8 @@ int usage(const std::string& program)
               << "Verifying a file against the .wav it was made from:\n" << program << " -v path/to/input.wav path/to/input.sela\n\n"
               << "Measuring a 16-bit file (per channel and for the track: peak, sum and sum of squares, then dBFS peak, dBFS RMS and DC):\n"
               << program << " -m path/to/input.sela\n\n"
+              << "The waveform envelope of a 16-bit file (min, max, sum and sum of squares per B samples and channel; B = 256 unless given):\n"
+              << program << " -w [--bucket B] path/to/input.sela path/to/output.env\n\n"
               << "Measuring a 16-, 24- or 32-bit file (as -m, by the file's own header; dBFS against the file's own full scale):\n"
               << program << " -M path/to/input.sela\n\n"
               << "The CRC-32 of the audio a 16-bit file decodes to (with a .wav: held against the CRC-32 of its data chunk):\n"
@@ -291,6 +299,23 @@ int run(int argc, char** argv)
             return usage(program);
         std::cout << "Measuring: " << argv[2] << std::endl;
         std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
+        return 0;
+    }
+    if (verb == "-w") {
+        long long bucket = sela::kEnvelopeDefaultBucket;
+        int at = 2;
+        if (argc > at + 1 && std::string(argv[at]) == "--bucket") {
+            bucket = std::atoll(argv[at + 1]);
+            at += 2;
+        }
+        if (argc != at + 2)
+            return usage(program);
+        if (bucket < 0 || bucket > 0xFFFFFFFFll || !sela::envelopeBucketOk((uint32_t)bucket))
+            throw data::Exception(sela::envelopeBucketRefusal(bucket));
+        std::cout << "Envelope: " << argv[at] << std::endl;
+        const sela::EnvelopeReport report = sela::writeEnvelopeFile(std::string(argv[at]), std::string(argv[at + 1]), (uint32_t)bucket);
+        std::cout << report.buckets() << " buckets of " << report.bucket << " samples, " << report.channels << " channels, " << report.samplesPerChannel
+                  << " samples per channel -> " << argv[at + 1] << std::endl;
         return 0;
     }
     if (verb == "-c" || verb == "-C") {

@@ -1303,6 +1303,56 @@ int sela_hip_salvage_payload_device(const uint8_t* d_payload, size_t payload_byt
     uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets /* [max_frames + 1] */, sela_hip_salvaged* d_records /* [max_frames] or NULL */,
     uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- envelope: min, max, sum and energy per bucket of samples ---------------------------------------------------
+ * The level record of 5.26 on a finer grid and with the signed extremes: what a waveform overview, the sample-accurate ends of
+ * silence, clip positions and onset candidates need, without decoding the track into memory.  `bucket` is a power of two from 32
+ * to 2048 samples; a frame has slots = sela_hip_envelope_slots(stride, bucket) = ceil(stride / bucket) records per channel.
+ * Record [f][b][c] is taken over exactly the int16 values v that sela_hip_decode_n_device writes for frame f, channel c, samples
+ * [b * bucket, min((b + 1) * bucket, n_f)) with the same d_frames, d_frame_offsets, n_frames, channels and stride (n_f: the
+ * frame's samples per channel): its narrowing of wider samples, its combine of difference subframes, its route, its zeros for a
+ * channel that ends early.  A last partial bucket is taken over the samples it has; a slot at or beyond n_f is the all-zero
+ * record.  Every record of every frame that ran is written exactly once: nothing is cleared first and nothing else is written.
+ * All fields are integers and exact, whatever the launch shape: |sum| <= 2048 * 32768 = 2^26, sum_squares <= 2048 * 2^30 = 2^41.
+ * Frames of 2048 samples, and the long last frame of a whole-track stream, start at a multiple of 2048, which every bucket
+ * divides: the frames' buckets are the track's absolute grid, and with stride = 2048 the array is [track bucket][channel].
+ * Scope: the domain of sela_hip_decode_n_device (16-bit output); samples of more than 16 bits are measured as that call narrows
+ * them, not as they are.
+ *   d_env          [n_frames][slots][channels], 8-byte aligned.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_n_device leaves them for the same frames;
+ *                  [2] is 0.  sela_hip_decode_n_status_error() applies unchanged; where it gives non-zero, or SELA_HIP_FLAG_STRIDE
+ *                  is set, d_env is not defined.  n_frames = 0 writes zero status words (and d_sample_offsets[0] = 0 where given)
+ *                  and nothing else.
+ * d_workspace: sela_hip_envelope_workspace_bytes(n_frames, channels, stride) bytes -- sela_hip_levels_workspace_bytes() of the
+ * same arguments, byte for byte, SIZE_MAX where that is -- no initialisation (the payload call: sela_hip_index_workspace_bytes
+ * (payload_bytes, max_frames) more); one call at a time may use it.
+ * Arguments, errors and their order are sela_hip_levels_device's, with two more: SELA_HIP_EINVAL for a bucket outside
+ * {32, 64, ..., 2048}, checked with the shape, and for a d_env that is not 8-byte aligned; SELA_HIP_ECAPACITY: a smaller
+ * workspace.  All found before any device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no
+ * allocation, no host wait, so a stream being captured into a HIP graph may take either call. */
+struct sela_hip_envelope { /* 16 bytes, 8-byte aligned */
+    int16_t min;          /* smallest v of the bucket (0 for an empty bucket) */
+    int16_t max;          /* largest v */
+    int32_t sum;          /* sum of v */
+    uint64_t sum_squares; /* sum of v * v */
+};
+typedef struct sela_hip_envelope sela_hip_envelope_record; /* (sela_hip_envelope itself names the host call below, as with the digest) */
+uint32_t sela_hip_envelope_slots(uint32_t stride, uint32_t bucket); /* ceil(stride / bucket); 0 for an invalid bucket or stride 0 */
+size_t sela_hip_envelope_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_envelope_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* d_env /* [n_frames][slots][channels] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written). */
+int sela_hip_envelope_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames: returns what sela_hip_decode returns for the stream (0: the records are
+ * valid; a frame longer than `stride` is SELA_HIP_ECAPACITY, as the status judge says it).  Runs where sela_hip_levels runs; an open
+ * streaming job of the thread is left alone.  n_frames = 0 returns 0 and asks for no device.  SELA_HIP_EINVAL: the level call's
+ * cases, stride 0, a bucket outside the set, and ceil(stride / bucket) * channels beyond 32 bits. */
+int sela_hip_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* env /* [n_frames][slots][channels] */);
+
 /* ---- the stages on their own -------------------------------------------------------------------------------
  * The reference's public L1 classes (src/include/lpc.hpp:73-117, src/include/rice.hpp:9-43; its tests call them directly:
  * test/lpctests.cpp:10-32, test/ricetests.cpp:7-25), batched, on HOST pointers.  Not the fast path -- a frame goes through

@@ -80,6 +80,8 @@ size_t sela_hip_debug_verify_lds_bytes(uint32_t channels);
 size_t sela_hip_debug_levels_lds_bytes(uint32_t channels);
 /* The same for k_digest_frames. */
 size_t sela_hip_debug_digest_lds_bytes(uint32_t channels);
+/* The same for k_envelope_frames. */
+size_t sela_hip_debug_envelope_lds_bytes(uint32_t channels);
 /* Debug hook (tests): how many frames of the LAST sela_hip_verify_i32_device call that used this workspace (same max_frames,
  * channels and stride as that call) were not of a direct layout and went through the fallback (k_generic_combine<false> and
  * k_verify32_rest) -- 0: k_verify32_direct compared every frame from the subframes as decoded.  For the payload

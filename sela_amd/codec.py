@@ -436,6 +436,116 @@ def track_levels(levels: np.ndarray) -> np.ndarray:
     return out
 
 
+# struct sela_hip_envelope (include/sela_hip.h): 16 bytes per (frame, bucket, channel)
+ENVELOPE_DTYPE = np.dtype([("min", "<i2"), ("max", "<i2"), ("sum", "<i4"), ("sum_squares", "<u8")])
+ENVELOPE_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)
+
+
+class Enveloper(_DeviceCall):
+    """sela_hip_envelope_device: the envelope of a stream on the device -- per frame, bucket of `bucket` samples (a power of two,
+    32 .. 2048) and channel the smallest and the largest value, the sum and the sum of squares of the int16 samples DecoderN.decode
+    would write (DESIGN.md 5.31).  All integers, so exact.  Owns its records and its workspace on the current device (or `device`);
+    every call is asynchronous on the current stream and overwrites them.  No PCM is written: on the 2048-sample route of up to
+    eight channels not even into the workspace."""
+
+    _call, _judge = "envelope", staticmethod(decode_n_status_error)
+
+    def __init__(self, max_frames: int, channels: int, stride: int, bucket: int, device=None):
+        self.bucket = bucket
+        self.slots = int(capi.lib().sela_hip_envelope_slots(stride, bucket))
+        if self.slots == 0:
+            raise ValueError(f"bucket must be one of {ENVELOPE_BUCKETS} and stride positive")
+        super().__init__(max_frames, channels, stride, device)
+
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames, slots, channels, 2]: word 0 min | max << 16 | sum << 32, word 1 sum_squares
+        self.envelope = torch.zeros((self.max_frames, self.slots, self.channels, 2), dtype=torch.int64, device=self.device)
+
+    route = _DeviceCall._route
+
+    def measure(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
+        n_frames frames, int64 cuda tensor [n_frames, slots, channels, 2], a view of the enveloper's own buffer (records(): as
+        ENVELOPE_DTYPE)."""
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_envelope_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.bucket, self.envelope.data_ptr(),
+            self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.envelope[:n_frames]
+
+    def measure_payload(self, payload, max_frames=None):
+        """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (records [max_frames, slots, channels, 2], count int32 [1]):
+        records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_envelope_payload_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.bucket, self.envelope.data_ptr(),
+            self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
+            self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.envelope[:max_frames], self.count
+
+    @staticmethod
+    def records(envelope) -> np.ndarray:
+        """Waits for the last call -> a host copy of records as ENVELOPE_DTYPE [n_frames, slots, channels]."""
+        host = np.ascontiguousarray(envelope.cpu().numpy())
+        return host.view(ENVELOPE_DTYPE).reshape(host.shape[:-1])
+
+
+def envelope_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bucket: int, stride=None) -> np.ndarray:
+    """sela_hip_envelope on numpy arrays -> the records, ENVELOPE_DTYPE [n_frames, slots, channels].  stride None: the stream's
+    largest samplesPerChannel (index_samples)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    if stride is None:
+        stride = max(index_samples(fr, offs, channels)[1], 1)
+    slots = int(lib.sela_hip_envelope_slots(stride, bucket))
+    out = np.zeros((n_frames, slots, channels), ENVELOPE_DTYPE)
+    capi.check(lib.sela_hip_envelope(fr.ctypes.data, offs.ctypes.data, n_frames, channels, stride, bucket, out.ctypes.data))
+    return out
+
+
+def track_envelope(records: np.ndarray, sample_offsets, bucket: int) -> np.ndarray:
+    """Records (ENVELOPE_DTYPE [n_frames, slots, channels]) on the track's grid: [ceil(total / bucket), channels], the empty slots
+    behind each frame's end dropped.  Every frame but the last must hold a multiple of `bucket` samples (ValueError): frames of
+    2048 samples and a whole-track stream's long last frame do."""
+    rec = np.asarray(records, dtype=ENVELOPE_DTYPE)
+    so = [int(s) for s in sample_offsets]
+    assert rec.ndim == 3 and len(so) == rec.shape[0] + 1
+    parts = []
+    for f in range(rec.shape[0]):
+        n = so[f + 1] - so[f]
+        if f + 1 < rec.shape[0] and n % bucket:
+            raise ValueError(f"frame {f} holds {n} samples, not a multiple of the bucket ({bucket}): its buckets are not the track's")
+        used = -(-n // bucket)
+        if used > rec.shape[1]:
+            raise ValueError(f"frame {f} holds {n} samples, more than its {rec.shape[1]} slots of {bucket}")
+        parts.append(rec[f, :used])
+    return np.concatenate(parts) if parts else np.zeros((0, rec.shape[2]), ENVELOPE_DTYPE)
+
+
+def fold_envelope(records: np.ndarray, factor: int) -> np.ndarray:
+    """Merges `factor` adjacent buckets along the slot axis (the last but one: [..., slots, channels] -> [..., ceil(slots / factor),
+    channels]): min of mins, max of maxes, the sums added in Python's integers -- a coarser zoom level of a waveform display
+    without another device call.  The records are taken as they are: an all-zero record of an empty slot counts as a 0 seen."""
+    rec = np.asarray(records, dtype=ENVELOPE_DTYPE)
+    assert rec.ndim >= 2 and factor >= 1
+    slots = rec.shape[-2]
+    groups = -(-slots // factor)
+    out = np.zeros(rec.shape[:-2] + (groups, rec.shape[-1]), ENVELOPE_DTYPE)
+    for g in range(groups):
+        part = rec[..., g * factor:(g + 1) * factor, :]
+        out["min"][..., g, :] = part["min"].min(axis=-2)
+        out["max"][..., g, :] = part["max"].max(axis=-2)
+        # (Python's integers: a sum that leaves its field's range raises OverflowError, as in track_levels)
+        out["sum"][..., g, :] = np.asarray(part["sum"].astype(object).sum(axis=-2), dtype=object)
+        out["sum_squares"][..., g, :] = np.asarray(part["sum_squares"].astype(object).sum(axis=-2), dtype=object)
+    return out
+
+
 # struct sela_hip_digest (include/sela_hip.h): 8 bytes per frame
 DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("samples", "<u4")])
 

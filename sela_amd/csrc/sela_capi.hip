@@ -1855,6 +1855,33 @@ int digest_call(const Form& form, uint32_t channels, uint32_t stride, struct sel
         });
 }
 
+// sela_hip_envelope_device / sela_hip_envelope_payload_device (5.31): levels_call's checks in its order, the bucket with the shape;
+// the workspace is the levels call's
+template <typename Form>
+int envelope_call(const Form& form, uint32_t channels, uint32_t stride, uint32_t bucket, struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint32_t* d_status,
+    void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "envelope", sela::levels_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK && !sela::envelope_bucket_ok(bucket))
+                rc = fail(SELA_HIP_EINVAL, "bucket must be one of 32, 64, 128, 256, 512, 1024, 2048");
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || d_env));
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_env & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_env must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launch_with_priorities(max_frames, stream, "envelope launch", [&](uint32_t synth_priorities) {
+                return sela::launch_envelope_n_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, bucket, d_env, d_sample_offsets, d_status, d_ws,
+                    sela::generic_standard_first_mode(), g_recurrence_form, synth_priorities, c.stream);
+            });
+        });
+}
+
 // sela_hip_digest_pcm_device / sela_hip_digest_payload_pcm_device (5.29): digest_call's checks in its order, then the container's, as
 // in verify_pcm_call; the decode_i32 call's launch shape
 template <typename Form>
@@ -2284,6 +2311,50 @@ int sela_hip_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32
     if (n_frames == 0)
         return SELA_HIP_OK;
     return sela::generic_levels(frames, frame_offsets, n_frames, channels, levels, g_recurrence_form);
+}
+
+// ---- envelope (5.31) ----------------------------------------------------------------------------------------------------------------
+uint32_t sela_hip_envelope_slots(uint32_t stride, uint32_t bucket) { return sela::envelope_slots(stride, bucket); }
+
+size_t sela_hip_envelope_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::levels_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_envelope_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return envelope_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, bucket, d_env, d_sample_offsets, d_status, d_workspace, workspace_bytes,
+        stream);
+}
+
+int sela_hip_envelope_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace, size_t workspace_bytes,
+    void* stream)
+{
+    return envelope_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, bucket, d_env, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+// Host pointers, synchronous: where sela_hip_levels runs (generic_envelope); no frames need no device.
+int sela_hip_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* env)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (stride == 0)
+        return fail(SELA_HIP_EINVAL, "stride must not be 0");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!sela::envelope_bucket_ok(bucket))
+        return fail(SELA_HIP_EINVAL, "bucket must be one of 32, 64, 128, 256, 512, 1024, 2048");
+    if ((uint64_t)sela::envelope_slots(stride, bucket) * channels > 0xFFFFFFFFull) // (the chunk loop counts a frame's records in 32 bits)
+        return fail(SELA_HIP_EINVAL, "ceil(stride / bucket) * channels must fit 32 bits");
+    if (!frame_offsets || (n_frames && (!frames || !env)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    return sela::generic_envelope(frames, frame_offsets, n_frames, channels, stride, bucket, env, g_recurrence_form);
 }
 
 // ---- levels of 24- and 32-bit streams ------------------------------------------------------------------------

@@ -672,14 +672,15 @@ int verify_chunks(const Call& call, const char* who, const uint8_t* frames, cons
     return rc;
 }
 
-// The two levels calls: no reference; status (4 x u32) | the chunk's records, read back in two pieces, the records straight into
-// the caller's.  `Launch`: the call's *_device launch on (d_frames, d_offsets, cf, d_levels, d_status, d_ws, mode, stream).
+// The two levels calls and the envelope: no reference; status (4 x u32) | the chunk's records (`records` of them a frame), read
+// back in two pieces, the records straight into the caller's.  `Launch`: the call's *_device launch on (d_frames, d_offsets, cf, d_levels, d_status, d_ws, mode, stream).
 template <typename Record, typename Launch>
 struct LevelsOp {
     size_t per_frame;
     size_t (*workspace)(uint32_t, uint32_t, uint32_t);
     int (*judge)(const uint32_t*);
     uint32_t channels, stride;
+    uint32_t records;
     Record* levels;
     Launch launch;
     uint32_t* d_status = nullptr;
@@ -689,7 +690,7 @@ struct LevelsOp {
     void pieces(Carve& c, uint32_t, uint32_t cf)
     {
         d_status = piece<uint32_t>(c, 4);
-        d_levels = piece<Record>(c, (uint64_t)cf * channels);
+        d_levels = piece<Record>(c, (uint64_t)cf * records);
     }
     hipError_t submit(const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t f0, uint32_t cf, void* d_ws, int mode, hipStream_t st)
     {
@@ -697,16 +698,16 @@ struct LevelsOp {
         if (e == hipSuccess)
             e = hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(levels + (size_t)f0 * channels, d_levels, (size_t)cf * channels * sizeof(Record), hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(levels + (size_t)f0 * records, d_levels, (size_t)cf * records * sizeof(Record), hipMemcpyDeviceToHost, st);
         return e;
     }
     int finish(uint32_t, uint32_t) const { return judge(status); }
 };
 template <typename Record, typename Launch>
 int levels_chunks(const Call& call, const char* who, const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride,
-    size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), int (*judge)(const uint32_t*), Record* levels, Launch launch)
+    uint32_t records, size_t per_frame, size_t (*workspace_bytes)(uint32_t, uint32_t, uint32_t), int (*judge)(const uint32_t*), Record* levels, Launch launch)
 {
-    LevelsOp<Record, Launch> op{ per_frame, workspace_bytes, judge, channels, stride, levels, launch };
+    LevelsOp<Record, Launch> op{ per_frame, workspace_bytes, judge, channels, stride, records, levels, launch };
     return frame_chunks(call, who, frames, frame_offsets, n_frames, op);
 }
 } // namespace
@@ -745,9 +746,30 @@ int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_
         return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
     const uint32_t stride = std::max(largest, 1u);
     const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2) + (size_t)channels * (sizeof(GenericSubInfo) + sizeof(sela_hip_level)) + 64;
-    return levels_chunks(call, "levels", frames, frame_offsets, n_frames, channels, stride, per_frame, levels_workspace_bytes, judge_n, levels,
+    return levels_chunks(call, "levels", frames, frame_offsets, n_frames, channels, stride, channels, per_frame, levels_workspace_bytes, judge_n, levels,
         [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, sela_hip_level* d_levels, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
             return launch_levels_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
+        });
+}
+
+// sela_hip_envelope: generic_levels' walk and chunks, at the caller's stride (a longer frame is the status
+// words' SELA_HIP_FLAG_STRIDE, judged like every other flag).
+int generic_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* env, int recurrence_form)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    if (check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    const uint32_t largest = generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr);
+    if (n_frames && largest == 0)
+        return report_error(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    const uint32_t records = envelope_slots(stride, bucket) * channels; // (fits 32 bits: sela_hip_envelope refuses a shape where it does not)
+    const size_t per_frame = (size_t)channels * stride * (4 + (channels > 8 ? 4 : 0) + 2) + (size_t)channels * sizeof(GenericSubInfo) + (size_t)records * sizeof(struct sela_hip_envelope) + 64;
+    return levels_chunks(call, "envelope", frames, frame_offsets, n_frames, channels, stride, records, per_frame, levels_workspace_bytes, judge_n, env,
+        [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, struct sela_hip_envelope* d_env, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
+            return launch_envelope_n_device(d_frames, d_offsets, cf, nullptr, channels, stride, bucket, d_env, nullptr, d_status, d_ws, mode, recurrence_form, 0, st);
         });
 }
 
@@ -837,7 +859,7 @@ int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
     if (call.rc != SELA_HIP_OK)
         return call.rc;
     const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 8 + sizeof(sela_hip_level32) * (1 + verify32_slices(stride))) + 64;
-    return levels_chunks(call, "levels_i32", frames, frame_offsets, n_frames, channels, stride, per_frame, levels_i32_workspace_bytes, judge_i32, levels,
+    return levels_chunks(call, "levels_i32", frames, frame_offsets, n_frames, channels, stride, channels, per_frame, levels_i32_workspace_bytes, judge_i32, levels,
         [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, sela_hip_level32* d_levels, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
             return launch_levels_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, d_levels, nullptr, d_status, d_ws, mode, st);
         });

@@ -455,7 +455,7 @@ __device__ __forceinline__ void step_up_from_q(uint32_t order, int32_t q_lo, int
 // resident_frames: the workgroups of `kernel` the current device holds at once (0: the runtime would not say), asked once per
 // (kernel slot, device, waves per workgroup) -- the occupancy query is per kernel, so every kernel has a slot of its own.
 // vec_shift_from_for: which workgroups of a launch run their recurrence in the lonely-wave form (k_decode_frames).
-constexpr int kResidencyDecode = 0, kResidencyVerify = 1, kResidencyWindows = 2, kResidencyLevels = 3, kResidencyDigest = 4, kResidencySlots = 5;
+constexpr int kResidencyDecode = 0, kResidencyVerify = 1, kResidencyWindows = 2, kResidencyLevels = 3, kResidencyDigest = 4, kResidencyEnvelope = 5, kResidencySlots = 6;
 uint32_t resident_frames(const void* kernel, int n_waves, size_t lds, int slot = kResidencyDecode);
 uint32_t vec_shift_from_for(uint32_t n_frames, int n_waves, uint32_t resident);
 int decode_waves(uint32_t channels);

@@ -112,6 +112,21 @@ inline size_t digest_workspace_bytes(uint32_t max_frames, uint32_t channels, uin
 hipError_t launch_digest_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
     uint32_t stride, struct sela_hip_digest* d_digests, uint64_t* d_track, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode,
     int recurrence_form, uint32_t synth_priorities, hipStream_t stream);
+// sela_hip_envelope_device / sela_hip_envelope_payload_device: launch_levels_n_device's shape and workspace with
+// the frame's total cut into buckets of 32 .. 2048 samples -- min, max, sum and sum of squares per (frame, bucket, channel).  Up to
+// kVerifyFusedChannels channels the 2048-sample route is one kernel (k_envelope_frames, sela_envelope.hip); every other route
+// decodes into the workspace and k_envelope_channels takes it from there.  status[2] stays 0.
+constexpr uint32_t kEnvelopeMinBucket = 32, kEnvelopeMaxBucket = 2048;
+inline bool envelope_bucket_ok(uint32_t bucket) { return bucket >= kEnvelopeMinBucket && bucket <= kEnvelopeMaxBucket && (bucket & (bucket - 1)) == 0; }
+// records per frame and channel: ceil(stride / bucket); 0 for an invalid bucket or stride 0
+inline uint32_t envelope_slots(uint32_t stride, uint32_t bucket) { return envelope_bucket_ok(bucket) ? (uint32_t)(((uint64_t)stride + bucket - 1) / bucket) : 0u; }
+hipError_t launch_envelope_frames(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* d_env, uint32_t* d_status, void* d_workspace, hipStream_t stream, int recurrence_form, uint32_t synth_priorities, const uint32_t* d_n_found);
+hipError_t launch_envelope_channels(const int16_t* d_decoded, const uint64_t* d_sample_offsets, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    const uint32_t* d_n_a, const uint32_t* d_n_b /* or null */, struct sela_hip_envelope* d_env, hipStream_t stream);
+hipError_t launch_envelope_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bucket, struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
+    uint32_t synth_priorities, hipStream_t stream);
 // sela_hip_crc32_device: k_digest_pcm / k_digest_slices on bytes that lie in device memory already
 size_t crc32_workspace_bytes(uint64_t n_bytes, Carve* at);
 inline size_t crc32_workspace_bytes(uint64_t n_bytes) { return crc32_workspace_bytes(n_bytes, nullptr); }

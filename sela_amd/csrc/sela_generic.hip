@@ -1896,6 +1896,26 @@ hipError_t launch_levels_n_device(const uint8_t* d_frames, const uint64_t* d_fra
         });
 }
 
+// ---- the envelope on the device (sela_hip_envelope_device) -------------------------------------------------------
+// The envelope plugs k_envelope_frames and k_envelope_channels into launch_n_sequence on the levels call's workspace
+// (carve_levels): status[2] stays 0.
+hipError_t launch_envelope_n_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bucket, struct sela_hip_envelope* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, int recurrence_form,
+    uint32_t synth_priorities, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const LevelsWs w = carve_levels(c, max_frames, channels, stride);
+    return launch_n_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w.n, w.pcm, d_sample_offsets, recurrence_form,
+        synth_priorities,
+        [&](int32_t* dec, const uint32_t* n_fast) {
+            return launch_envelope_frames(d_frames, d_frame_offsets, max_frames, channels, stride, bucket, d_env, d_status, dec, stream, recurrence_form, synth_priorities,
+                n_fast);
+        },
+        [&](const uint64_t* d_so, const uint32_t* n_any, const uint32_t* n_fast) {
+            return launch_envelope_channels(w.pcm, d_so, max_frames, channels, stride, bucket, n_any, n_fast, d_env, stream);
+        });
+}
+
 // ---- the digest on the device (sela_hip_digest_device) ----------------------------------------------------------
 // Workspace: the levels call's two pieces | a word per (frame, slice) of the routes that are not fused | the fold's word per
 // workgroup.

@@ -226,6 +226,9 @@ int generic_verify_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
     const uint32_t* lengths, uint32_t* diff_counts, uint32_t* first_diff, uint32_t* lossy_frames);
 // sela_hip_levels: generic_verify's walk and chunks, the records coming back where its two arrays do
 int generic_levels(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, sela_hip_level* levels, int recurrence_form);
+// sela_hip_envelope: generic_levels' walk and chunks at the caller's stride, ceil(stride / bucket) * channels records a frame
+int generic_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope* env, int recurrence_form);
 // sela_hip_digest: generic_levels' walk and chunks, the chunks' track words folded on the host (any of the three outputs may be null)
 int generic_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests, uint32_t* track_crc32,
     uint64_t* track_bytes, int recurrence_form);
