@@ -67,6 +67,13 @@ VerifyReport verifyWideFile(const std::string& wavPath, const std::string& selaP
 // 2048-sample frames for any other; wavTailBytes is the rest.  formatDigestReport applies unchanged.  Throws data::Exception,
 // naming both, where the WAV's width or channel count is not the file's.
 DigestReport digestWideFile(const std::string& selaPath, const std::string& wavPath = std::string());
+// envelopeFile for a 24- or 32-bit .sela: the frames the file really holds, a --whole file's long last frame as it
+// stands, through ONE call to sela_hip_envelope_i32 -- min, max, sum and the 128-bit sum of squares per `bucket` samples and
+// channel of the samples as they are, nothing decoded into host memory -- compacted onto the track's grid (envelope.hpp).  A bucket
+// outside {32, 64, ..., 2048} is refused with the set named.
+EnvelopeReport32 envelopeWideFile(const std::string& selaPath, uint32_t bucket = kEnvelopeDefaultBucket);
+// envelopeWideFile(), then the wide .env file of envelope.hpp written to envPath.
+EnvelopeReport32 writeEnvelopeWideFile(const std::string& selaPath, const std::string& envPath, uint32_t bucket = kEnvelopeDefaultBucket);
 // what the .sela header at `path` says its samples' width is; 0 where there is no such header (the caller's path then reports it)
 uint16_t selaFileBits(const std::string& path);
 

@@ -31,7 +31,11 @@
 //                                      uint32 channels, uint32 B, uint64 samples per channel, uint32 sample rate, uint32 16), then
 //                                      16-byte records [bucket][channel].  A --keep-tail file is read as it stands; a 24- or 32-bit
 //                                      .sela is refused by name, a bucket outside the set with the set named (exit 1, as -m)
-//   sela_mi355x -M in.sela             the same by the file's own header: a 16-bit file exactly as -m, a 24- or 32-bit file through
+//   sela_mi355x -W [--bucket B] in.sela out.env   the same by the file's own header: a 16-bit file exactly as -w, -w's bytes; a 24- or
+//                                      32-bit file (a --whole one as it stands) through sela_hip_envelope_i32 -- the samples as they are,
+//                                      the header's last word the file's bits (24 or 32), then 32-byte records [bucket][channel]: int32
+//                                      min, max, int64 sum, the sum of squares in 128 bits
+//   sela_mi355x -M in.sela             the same as -m by the file's own header: a 16-bit file exactly as -m, a 24- or 32-bit file through
 //                                      sela_hip_levels_i32 -- the integers of its samples as they are (the sum of squares in 128
 //                                      bits, printed whole), dBFS against the file's own full scale; a --whole file as it stands
 //   sela_mi355x -c in.sela [in.wav]    digest: the CRC-32 (zlib's, `crc32`'s) of the PCM in.sela decodes to -- taken on the GPU, nothing
@@ -91,6 +95,8 @@ int usage(const std::string& program)
               << program << " -m path/to/input.sela\n\n"
               << "The waveform envelope of a 16-bit file (min, max, sum and sum of squares per B samples and channel; B = 256 unless given):\n"
               << program << " -w [--bucket B] path/to/input.sela path/to/output.env\n\n"
+              << "The waveform envelope of a 16-, 24- or 32-bit file (as -w, by the file's own header; 32-byte records for 24 and 32 bits):\n"
+              << program << " -W [--bucket B] path/to/input.sela path/to/output.env\n\n"
               << "Measuring a 16-, 24- or 32-bit file (as -m, by the file's own header; dBFS against the file's own full scale):\n"
               << program << " -M path/to/input.sela\n\n"
               << "The CRC-32 of the audio a 16-bit file decodes to (with a .wav: held against the CRC-32 of its data chunk):\n"
@@ -301,7 +307,7 @@ int run(int argc, char** argv)
         std::cout << sela::formatLevelReport(sela::measureFile(std::string(argv[2]))) << std::flush;
         return 0;
     }
-    if (verb == "-w") {
+    if (verb == "-w" || verb == "-W") {
         long long bucket = sela::kEnvelopeDefaultBucket;
         int at = 2;
         if (argc > at + 1 && std::string(argv[at]) == "--bucket") {
@@ -312,6 +318,15 @@ int run(int argc, char** argv)
             return usage(program);
         if (bucket < 0 || bucket > 0xFFFFFFFFll || !sela::envelopeBucketOk((uint32_t)bucket))
             throw data::Exception(sela::envelopeBucketRefusal(bucket));
+        // (-W goes by the .sela's header: a 24- or 32-bit file to sela_hip_envelope_i32; any other file, and -w, down -w's path)
+        const uint16_t bits = verb == "-W" ? sela::selaFileBits(argv[at]) : 0;
+        if (bits == 24 || bits == 32) {
+            std::cout << "Envelope (" << bits << "-bit): " << argv[at] << std::endl;
+            const sela::EnvelopeReport32 report = sela::writeEnvelopeWideFile(std::string(argv[at]), std::string(argv[at + 1]), (uint32_t)bucket);
+            std::cout << report.buckets() << " buckets of " << report.bucket << " samples, " << report.channels << " channels, " << report.samplesPerChannel
+                      << " samples per channel -> " << argv[at + 1] << std::endl;
+            return 0;
+        }
         std::cout << "Envelope: " << argv[at] << std::endl;
         const sela::EnvelopeReport report = sela::writeEnvelopeFile(std::string(argv[at]), std::string(argv[at + 1]), (uint32_t)bucket);
         std::cout << report.buckets() << " buckets of " << report.bucket << " samples, " << report.channels << " channels, " << report.samplesPerChannel

@@ -319,6 +319,53 @@ WideLevelReport measureWideFile(const std::string& selaPath)
     return r;
 }
 
+// ---- envelope ------------------------------------------------------------------------------------------------
+static_assert(sizeof(EnvelopeRecord32) == sizeof(struct sela_hip_envelope32) && offsetof(EnvelopeRecord32, max) == offsetof(struct sela_hip_envelope32, max)
+        && offsetof(EnvelopeRecord32, sum) == offsetof(struct sela_hip_envelope32, sum)
+        && offsetof(EnvelopeRecord32, sumSquaresLo) == offsetof(struct sela_hip_envelope32, sum_squares_lo)
+        && offsetof(EnvelopeRecord32, sumSquaresHi) == offsetof(struct sela_hip_envelope32, sum_squares_hi),
+    "envelope.hpp restates the device's record");
+
+EnvelopeReport32 envelopeWideFile(const std::string& selaPath, uint32_t bucket)
+{
+    if (!envelopeBucketOk(bucket))
+        throw data::Exception(envelopeBucketRefusal(bucket));
+    WideSela s;
+    readWideSela(selaPath, "envelopeWideFile", s);
+    EnvelopeReport32 r;
+    r.channels = s.channels, r.bucket = bucket, r.sampleRate = s.rate, r.bitsPerSample = s.bits;
+    std::vector<uint64_t> sampleOffsets((size_t)s.found + 1, 0);
+    uint32_t largest = 0;
+    if (s.found && (largest = sela_hip_index_samples(s.stream.data(), s.offsets.data(), s.found, s.channels, sampleOffsets.data())) == 0)
+        throw data::Exception("Envelope: malformed frame stream");
+    const uint32_t stride = std::max(largest, 1u);
+    const uint32_t slots = envelopeSlots(stride, bucket);
+    std::vector<EnvelopeRecord32> records((size_t)s.found * slots * s.channels + 1);
+    if (sela_hip_envelope_i32(s.stream.data(), s.offsets.data(), s.found, s.channels, stride, bucket, reinterpret_cast<struct sela_hip_envelope32*>(records.data()))
+        != SELA_HIP_OK)
+        failHip("Envelope");
+    r.samplesPerChannel = sampleOffsets[s.found];
+    try {
+        r.records = compactEnvelope32(records.data(), sampleOffsets.data(), s.found, slots, s.channels, bucket);
+    } catch (const std::invalid_argument& e) {
+        throw data::Exception(e.what());
+    }
+    return r;
+}
+
+EnvelopeReport32 writeEnvelopeWideFile(const std::string& selaPath, const std::string& envPath, uint32_t bucket)
+{
+    const EnvelopeReport32 r = envelopeWideFile(selaPath, bucket);
+    const std::vector<uint8_t> bytes = envelopeFileBytes32(r);
+    std::ofstream o(envPath, std::ios::binary | std::ios::trunc);
+    if (!o)
+        throw data::Exception("cannot open " + envPath + " for writing");
+    o.write(reinterpret_cast<const char*>(bytes.data()), (std::streamsize)bytes.size());
+    if (!o)
+        throw data::Exception("cannot write " + envPath);
+    return r;
+}
+
 // ---- digest --------------------------------------------------------------------------------------------------
 DigestReport digestWideFile(const std::string& selaPath, const std::string& wavPath)
 {

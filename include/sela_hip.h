@@ -1353,6 +1353,61 @@ int sela_hip_envelope_payload_device(const uint8_t* d_payload, size_t payload_by
 int sela_hip_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
     struct sela_hip_envelope* env /* [n_frames][slots][channels] */);
 
+/* ---- envelope of 24- and 32-bit streams: wide records per bucket ------------------------------------------------
+ * The envelope above on the whole domain of sela_hip_decode_i32_device: samples of up to 32 bits as they are, channels of
+ * different lengths, every subframe layout.  `bucket` is the same set (a power of two from 32 to 2048), slots =
+ * sela_hip_envelope_slots(stride, bucket) the same function.  Record [f][b][c] is taken over exactly
+ * samples_out[f][c][b * bucket .. min((b + 1) * bucket, counts_out[f * channels + c])) as sela_hip_decode_i32_device writes them
+ * for the same d_frames, d_frame_offsets, n_frames, channels and stride: difference subframes combined mod 2^32, every channel
+ * ending at its own count, a channel no subframe names all zero records, a malformed frame measured with whatever counts that
+ * call gives it.  A last partial bucket is taken over the samples it has -- a sample that is not there is not a 0 --; a slot at
+ * or beyond the channel's count is the all-zero record.  Every record of every frame that ran is written exactly once: nothing is
+ * cleared first and nothing else is written.
+ * Bounds: a bucket holds at most 2048 samples, so |sum| <= 2048 * 2^31 = 2^42 and sum_squares <= 2048 * 2^62 = 2^73 -- four
+ * full-scale samples already reach 2^64, hence the two energy words.  All fields are integers and exact, whatever the launch
+ * shape.
+ *   d_env          [n_frames][slots][channels], 8-byte aligned.
+ *   d_status uint32[4], written by the call: [0], [1] and [3] exactly as sela_hip_decode_i32_device leaves them for the same
+ *                  frames; [2] is 0.  Where SELA_HIP_FLAG_STRIDE is set, d_env is not defined (nothing outside it is written).
+ * d_workspace: sela_hip_envelope_i32_workspace_bytes(n_frames, channels, stride) bytes -- sela_hip_verify_i32_workspace_bytes() of
+ * the same arguments, byte for byte, SIZE_MAX where that is: a slice of 4096 samples holds whole buckets, so no partial record
+ * lies in it -- no initialisation (the payload call: sela_hip_index_workspace_bytes(payload_bytes, max_frames) more); one call at
+ * a time may use it.
+ * Arguments, errors and their order are sela_hip_levels_i32_device's, with two more: SELA_HIP_EINVAL for a bucket outside
+ * {32, 64, ..., 2048}, checked with the shape, and for a d_env that is not 8-byte aligned; SELA_HIP_ECAPACITY: a smaller
+ * workspace.  All found before any device is asked for: nothing is enqueued then.  Asynchronous on `stream`, one serial chain: no
+ * allocation, no host wait, no host read, so a stream being captured into a HIP graph may take any of the three device calls. */
+struct sela_hip_envelope32 { /* 32 bytes, 8-byte aligned */
+    int32_t min, max;        /* smallest / largest v of the bucket (0, 0 for an empty bucket) */
+    int64_t sum;             /* sum of v */
+    uint64_t sum_squares_lo; /* sum of v * v, bits 0 .. 63 */
+    uint64_t sum_squares_hi; /* ... and bits 64 .. 127 */
+};
+typedef struct sela_hip_envelope32 sela_hip_envelope32_record;
+size_t sela_hip_envelope_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_envelope_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env /* [n_frames][slots][channels] */, uint64_t* d_sample_offsets /* [n_frames + 1] or NULL */, uint32_t* d_status /* [4] */,
+    void* d_workspace, size_t workspace_bytes, void* stream);
+/* sela_hip_index_frames_device() and then the call above on the frames it found, on one stream: the count stays on the device.
+ * Frames from *d_n_frames on are left alone (their records are not written). */
+int sela_hip_envelope_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* The same records from planar int32 samples that already lie in device memory (an unpack's output ahead of an encode, a
+ * decode's output), as sela_hip_levels_samples_i32_device: channel c of frame f holds min(d_counts[f * channels + c], stride)
+ * samples (d_counts NULL: stride).  d_samples and d_counts 4-byte aligned.  d_status: all four words zeroed.  d_workspace:
+ * sela_hip_envelope_samples_i32_workspace_bytes() bytes -- a token, nothing is kept in it. */
+size_t sela_hip_envelope_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride);
+int sela_hip_envelope_samples_i32_device(const int32_t* d_samples /* [n_frames][channels][stride] */, const uint32_t* d_counts /* [n_frames * channels] or NULL */,
+    uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket, struct sela_hip_envelope32* d_env, uint32_t* d_status /* [4] */, void* d_workspace,
+    size_t workspace_bytes, void* stream);
+/* Host pointers, synchronous, in chunks of frames: returns what sela_hip_decode_i32 returns for the stream (0: the records are
+ * valid; a frame longer than `stride` is SELA_HIP_ECAPACITY, as the status judge says it).  Runs where sela_hip_levels_i32 runs;
+ * an open streaming job of the thread is left alone.  n_frames = 0 returns 0 and asks for no device.  SELA_HIP_EINVAL: the level
+ * call's cases, stride 0, a bucket outside the set, and ceil(stride / bucket) * channels beyond 32 bits. */
+int sela_hip_envelope_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* env /* [n_frames][slots][channels] */);
+
 /* ---- the stages on their own -------------------------------------------------------------------------------
  * The reference's public L1 classes (src/include/lpc.hpp:73-117, src/include/rice.hpp:9-43; its tests call them directly:
  * test/lpctests.cpp:10-32, test/ricetests.cpp:7-25), batched, on HOST pointers.  Not the fast path -- a frame goes through

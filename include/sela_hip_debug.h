@@ -94,6 +94,9 @@ long long sela_hip_debug_verify_pcm_fallback_frames(const void* d_workspace, uin
 /* The same of the LAST sela_hip_levels_i32_device call that used this workspace: the frames that went through
  * k_generic_combine<false> and k_level32_rest -- 0: k_level32_direct reduced every frame from the subframes as decoded. */
 long long sela_hip_debug_levels_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);
+/* The same of the LAST sela_hip_envelope_i32_device call that used this workspace: the frames that went through
+ * k_generic_combine<false> and k_envelope32_rest -- 0: k_envelope32_direct reduced every frame from the subframes as decoded. */
+long long sela_hip_debug_envelope_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);
 /* The same of the LAST sela_hip_digest_pcm_device call that used this workspace: the frames that went through
  * k_generic_combine<false> and k_digest32_tiles' rest form -- 0: every frame was digested from the subframes as decoded. */
 long long sela_hip_debug_digest_pcm_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride);

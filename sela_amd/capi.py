@@ -62,6 +62,8 @@ EXPORTS = [
     "sela_hip_digest_pcm_workspace_bytes", "sela_hip_digest_pcm_device", "sela_hip_digest_payload_pcm_device", "sela_hip_digest_pcm",
     "sela_hip_salvage_frames", "sela_hip_salvage_workspace_bytes", "sela_hip_salvage_frames_device", "sela_hip_salvage_payload_device",
     "sela_hip_envelope_slots", "sela_hip_envelope_workspace_bytes", "sela_hip_envelope_device", "sela_hip_envelope_payload_device", "sela_hip_envelope",
+    "sela_hip_envelope_i32_workspace_bytes", "sela_hip_envelope_i32_device", "sela_hip_envelope_payload_i32_device",
+    "sela_hip_envelope_samples_i32_workspace_bytes", "sela_hip_envelope_samples_i32_device", "sela_hip_envelope_i32",
 ]
 WINDOW_I16_INTERLEAVED, WINDOW_F32_PLANAR = 0, 1  # SELA_HIP_WINDOW_*
 WINDOW_I32_PLANAR, WINDOW_PCM24_INTERLEAVED, WINDOW_PCM32_INTERLEAVED = 2, 3, 4  # (sela_hip_decode_windows_i32*: these and F32_PLANAR)
@@ -76,7 +78,7 @@ DEBUG_EXPORTS = [
     "sela_hip_debug_verify_i32_fallback_frames", "sela_hip_debug_window_lds_bytes", "sela_hip_debug_windows_staged_bytes",
     "sela_hip_debug_workspace_pieces", "sela_hip_debug_pcm_chunk_frames", "sela_hip_debug_verify_pcm_fallback_frames",
     "sela_hip_debug_levels_lds_bytes", "sela_hip_debug_levels_i32_fallback_frames", "sela_hip_debug_digest_lds_bytes",
-    "sela_hip_debug_digest_pcm_fallback_frames", "sela_hip_debug_envelope_lds_bytes",
+    "sela_hip_debug_digest_pcm_fallback_frames", "sela_hip_debug_envelope_lds_bytes", "sela_hip_debug_envelope_i32_fallback_frames",
 ]
 # `call` of sela_hip_debug_workspace_pieces, in the order of the enum in include/sela_hip_debug.h
 WORKSPACE_CALLS = ("encode", "decode", "index", "decode_i32", "decode_n", "verify", "verify_i32", "encode_i32", "encode_paired", "windows", "windows_whole",
@@ -330,6 +332,19 @@ def lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int
     L.sela_hip_debug_envelope_lds_bytes.argtypes = [u32]
     L.sela_hip_debug_envelope_lds_bytes.restype = sz
+    # envelope of 24- and 32-bit streams
+    L.sela_hip_envelope_i32_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_envelope_i32_workspace_bytes.restype = sz
+    L.sela_hip_envelope_samples_i32_workspace_bytes.argtypes = [u32, u32, u32]
+    L.sela_hip_envelope_samples_i32_workspace_bytes.restype = sz
+    L.sela_hip_envelope_i32_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_envelope_payload_i32_device.argtypes = [vp, sz, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_envelope_samples_i32_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, sz, vp]
+    L.sela_hip_envelope_i32.argtypes = [vp, vp, u32, u32, u32, u32, vp]
+    for name in ("sela_hip_envelope_i32_device", "sela_hip_envelope_payload_i32_device", "sela_hip_envelope_samples_i32_device", "sela_hip_envelope_i32"):
+        getattr(L, name).restype = C.c_int
+    L.sela_hip_debug_envelope_i32_fallback_frames.argtypes = [vp, u32, u32, u32]
+    L.sela_hip_debug_envelope_i32_fallback_frames.restype = C.c_longlong
     # digest
     L.sela_hip_digest_workspace_bytes.argtypes = [u32, u32, u32]
     L.sela_hip_digest_workspace_bytes.restype = sz

@@ -734,6 +734,139 @@ def track_levels32(levels: np.ndarray) -> list:
     return out
 
 
+# struct sela_hip_envelope32 (include/sela_hip.h): 32 bytes per (frame, bucket, channel); the energy is sum_squares_lo +
+# (sum_squares_hi << 64)
+ENVELOPE32_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("sum_squares_lo", "<u8"), ("sum_squares_hi", "<u8")])
+
+
+class Enveloper32(_DeviceCall):
+    """sela_hip_envelope_i32_device: Enveloper on the whole domain of sela_hip_decode_i32_device -- samples of up to 32 bits as
+    they are, channels of different lengths, every subframe layout.  Record [f][b][c] is taken over the samples
+    that call writes for channel c of frame f in bucket b, with a 128-bit sum of squares.  All integers, so exact.  Owns its
+    records and its workspace on the current device (or `device`); every call is asynchronous on the current stream and overwrites
+    them.  No decoded sample is stored for the layouts this project's encoders write."""
+
+    _call, _judge = "envelope_i32", staticmethod(decode_status_error)
+
+    def __init__(self, max_frames: int, channels: int, stride: int, bucket: int, device=None):
+        self.bucket = bucket
+        self.slots = int(capi.lib().sela_hip_envelope_slots(stride, bucket))
+        if self.slots == 0:
+            raise ValueError(f"bucket must be one of {ENVELOPE_BUCKETS} and stride positive")
+        super().__init__(max_frames, channels, stride, device)
+
+    def _allocate(self, torch) -> None:
+        # the records as int64 [max_frames, slots, channels, 4]: word 0 min | max << 32, word 1 sum, words 2 and 3 the energy
+        self.envelope = torch.zeros((self.max_frames, self.slots, self.channels, 4), dtype=torch.int64, device=self.device)
+
+    fallback_frames = _DeviceCall._fallback_frames
+
+    def measure(self, frames, offsets, n_frames: int):
+        """frames: uint8 cuda tensor (4-byte aligned), offsets: int64 cuda tensor [n_frames + 1] -> the records of the first
+        n_frames frames, int64 cuda tensor [n_frames, slots, channels, 4], a view of the enveloper's own buffer (records(): as
+        ENVELOPE32_DTYPE)."""
+        self._frames_ok(frames, offsets, n_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_envelope_i32_device(
+            frames.data_ptr(), offsets.data_ptr(), n_frames, self.channels, self.stride, self.bucket, self.envelope.data_ptr(),
+            self.sample_offsets.data_ptr(), self.status.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream))
+        return self.envelope[:n_frames]
+
+    def measure_payload(self, payload, max_frames=None):
+        """Index and measure a .sela payload (uint8 cuda tensor, 4-byte aligned) in one asynchronous call; the frame count never
+        leaves the device, so the call can be captured into a graph.  -> (records [max_frames, slots, channels, 4], count int32 [1]):
+        records up to count[0] are the stream's.  The workspace grows to the largest payload seen (make one call before capturing)."""
+        max_frames = self._payload_ok(payload, max_frames)
+        stream = self._stream()
+        capi.check(self.lib.sela_hip_envelope_payload_i32_device(
+            payload.data_ptr(), payload.numel(), max_frames, self.channels, self.stride, self.bucket, self.envelope.data_ptr(),
+            self.sample_offsets.data_ptr(), self.frame_offsets.data_ptr(), self.count.data_ptr(), self.status.data_ptr(),
+            self.payload_workspace.data_ptr(), self.payload_workspace.numel(), stream))
+        return self.envelope[:max_frames], self.count
+
+    @staticmethod
+    def records(envelope) -> np.ndarray:
+        """Waits for the last call -> a host copy of records as ENVELOPE32_DTYPE [n_frames, slots, channels]."""
+        host = np.ascontiguousarray(envelope.cpu().numpy())
+        return host.view(ENVELOPE32_DTYPE).reshape(host.shape[:-1])
+
+
+def envelope_i32_host(frames: np.ndarray, offsets: np.ndarray, channels: int, bucket: int, stride=None) -> np.ndarray:
+    """sela_hip_envelope_i32 on numpy arrays -> the records, ENVELOPE32_DTYPE [n_frames, slots, channels].  stride None: the
+    stream's largest samplesPerChannel (index_samples)."""
+    lib = capi.lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_frames = len(offs) - 1
+    if stride is None:
+        stride = max(index_samples(fr, offs, channels)[1], 1)
+    slots = int(lib.sela_hip_envelope_slots(stride, bucket))
+    out = np.zeros((n_frames, slots, channels), ENVELOPE32_DTYPE)
+    capi.check(lib.sela_hip_envelope_i32(fr.ctypes.data, offs.ctypes.data, n_frames, channels, stride, bucket, out.ctypes.data))
+    return out
+
+
+def envelope_samples_i32(samples, bucket: int, counts=None):
+    """sela_hip_envelope_samples_i32_device: samples int32 cuda tensor [n_frames, channels, stride] (contiguous), counts int32 cuda
+    tensor [n_frames * channels] or None (stride samples each) -> (records int64 cuda tensor [n_frames, slots, channels, 4], status
+    int32 cuda tensor [4]); asynchronous on the current stream.  Enveloper32.records() turns the records into ENVELOPE32_DTYPE."""
+    import torch
+
+    assert samples.dtype == torch.int32 and samples.is_cuda and samples.is_contiguous() and samples.dim() == 3
+    n_frames, channels, stride = samples.shape
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous() and counts.numel() == n_frames * channels)
+    lib = capi.lib()
+    slots = int(lib.sela_hip_envelope_slots(stride, bucket))
+    if slots == 0:
+        raise ValueError(f"bucket must be one of {ENVELOPE_BUCKETS} and stride positive")
+    envelope = torch.zeros((n_frames, slots, channels, 4), dtype=torch.int64, device=samples.device)
+    status = torch.zeros(4, dtype=torch.int32, device=samples.device)
+    workspace = torch.empty(int(lib.sela_hip_envelope_samples_i32_workspace_bytes(n_frames, channels, stride)), dtype=torch.uint8, device=samples.device)
+    capi.check(lib.sela_hip_envelope_samples_i32_device(
+        samples.data_ptr(), None if counts is None else counts.data_ptr(), n_frames, channels, stride, bucket, envelope.data_ptr(), status.data_ptr(),
+        workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(samples.device).cuda_stream))
+    return envelope, status
+
+
+def track_envelope32(records: np.ndarray, sample_offsets, bucket: int) -> np.ndarray:
+    """track_envelope for ENVELOPE32_DTYPE [n_frames, slots, channels]: the records on the track's grid, [ceil(total / bucket),
+    channels], the empty slots behind each frame's end dropped.  Every frame but the last must hold a multiple of `bucket` samples
+    (ValueError): frames of 2048 samples and a whole-track stream's long last frame do."""
+    rec = np.asarray(records, dtype=ENVELOPE32_DTYPE)
+    so = [int(s) for s in sample_offsets]
+    assert rec.ndim == 3 and len(so) == rec.shape[0] + 1
+    parts = []
+    for f in range(rec.shape[0]):
+        n = so[f + 1] - so[f]
+        if f + 1 < rec.shape[0] and n % bucket:
+            raise ValueError(f"frame {f} holds {n} samples, not a multiple of the bucket ({bucket}): its buckets are not the track's")
+        used = -(-n // bucket)
+        if used > rec.shape[1]:
+            raise ValueError(f"frame {f} holds {n} samples, more than its {rec.shape[1]} slots of {bucket}")
+        parts.append(rec[f, :used])
+    return np.concatenate(parts) if parts else np.zeros((0, rec.shape[2]), ENVELOPE32_DTYPE)
+
+
+def fold_envelope32(records: np.ndarray, factor: int) -> np.ndarray:
+    """fold_envelope for ENVELOPE32_DTYPE: merges `factor` adjacent buckets along the slot axis (the last but one), min of mins,
+    max of maxes, the sums and the 128-bit energies added in Python's integers.  The records are taken as they are: an all-zero
+    record of an empty slot counts as a 0 seen.  A sum that leaves its field's range raises OverflowError."""
+    rec = np.asarray(records, dtype=ENVELOPE32_DTYPE)
+    assert rec.ndim >= 2 and factor >= 1
+    slots = rec.shape[-2]
+    groups = -(-slots // factor)
+    out = np.zeros(rec.shape[:-2] + (groups, rec.shape[-1]), ENVELOPE32_DTYPE)
+    for g in range(groups):
+        part = rec[..., g * factor:(g + 1) * factor, :]
+        out["min"][..., g, :] = part["min"].min(axis=-2)
+        out["max"][..., g, :] = part["max"].max(axis=-2)
+        out["sum"][..., g, :] = np.asarray(part["sum"].astype(object).sum(axis=-2), dtype=object)
+        energy = np.asarray((part["sum_squares_lo"].astype(object) + part["sum_squares_hi"].astype(object) * (1 << 64)).sum(axis=-2), dtype=object)
+        out["sum_squares_lo"][..., g, :] = energy % (1 << 64)
+        out["sum_squares_hi"][..., g, :] = energy // (1 << 64)
+    return out
+
+
 class _WindowCall:
     """What WindowDecoder and WindowDecoder32 share: the buffers they own -- output, flags, status, and the workspace of
     sela_hip_<_entry>[_whole]_workspace_bytes -- the asserted decode(), flags, pack() and check().  A class names its entry, gives

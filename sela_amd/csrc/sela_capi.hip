@@ -2045,6 +2045,32 @@ int levels_i32_call(const Form& form, uint32_t channels, uint32_t stride, sela_h
         });
 }
 
+// sela_hip_envelope_i32_device / sela_hip_envelope_payload_i32_device (5.32): levels_i32_call's checks in its order, the bucket with
+// the shape as in envelope_call; the workspace is the verify_i32 call's
+template <typename Form>
+int envelope_i32_call(const Form& form, uint32_t channels, uint32_t stride, uint32_t bucket, struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets,
+    uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    const DeviceCall c = { "envelope_i32", sela::envelope_i32_workspace_bytes, channels, stride, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream) };
+    return form(
+        c,
+        [&](uint32_t n_frames) {
+            int rc = check_frames_shape(n_frames, channels, stride);
+            if (rc == SELA_HIP_OK && !sela::envelope_bucket_ok(bucket))
+                rc = fail(SELA_HIP_EINVAL, "bucket must be one of 32, 64, 128, 256, 512, 1024, 2048");
+            if (rc == SELA_HIP_OK)
+                rc = need_pointers(d_status && d_workspace && (!n_frames || d_env));
+            if (rc == SELA_HIP_OK && ((uintptr_t)d_env & 7))
+                rc = fail(SELA_HIP_EINVAL, "d_env must be 8-byte aligned");
+            return rc;
+        },
+        [&](const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, void* d_ws) {
+            return launched(sela::launch_envelope_i32_device(d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, bucket, d_env, d_sample_offsets, d_status,
+                                d_ws, sela::generic_standard_first_mode(), c.stream),
+                "envelope_i32 launch");
+        });
+}
+
 // sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device (5.24): the verify_i32 call's checks in its order, then the
 // container's and the original's alignment
 template <typename Form>
@@ -2546,6 +2572,87 @@ static long long fallback_frames(size_t (*workspace_bytes)(uint32_t, uint32_t, u
 long long sela_hip_debug_levels_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
 {
     return fallback_frames(sela::levels_i32_workspace_bytes, sela::levels_i32_control_words, d_workspace, max_frames, channels, stride);
+}
+
+// ---- envelope of 24- and 32-bit streams -----------------------------------------------------------------------
+size_t sela_hip_envelope_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::envelope_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+int sela_hip_envelope_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return envelope_i32_call(FramesForm{ d_frames, d_frame_offsets, n_frames }, channels, stride, bucket, d_env, d_sample_offsets, d_status, d_workspace, workspace_bytes,
+        stream);
+}
+
+int sela_hip_envelope_payload_i32_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets, uint64_t* d_frame_offsets, uint32_t* d_n_frames, uint32_t* d_status, void* d_workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return envelope_i32_call(PayloadForm{ d_payload, payload_bytes, max_frames, d_frame_offsets, d_n_frames }, channels, stride, bucket, d_env, d_sample_offsets, d_status,
+        d_workspace, workspace_bytes, stream);
+}
+
+size_t sela_hip_envelope_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return sela::envelope_samples_i32_workspace_bytes(max_frames, channels, stride);
+}
+
+// envelope_i32_call's checks in its order, with the samples where the frames are
+int sela_hip_envelope_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int rc = check_frames_shape(n_frames, channels, stride);
+    if (rc == SELA_HIP_OK && !sela::envelope_bucket_ok(bucket))
+        rc = fail(SELA_HIP_EINVAL, "bucket must be one of 32, 64, 128, 256, 512, 1024, 2048");
+    if (rc == SELA_HIP_OK)
+        rc = need_pointers(d_status && d_workspace && (!n_frames || d_env));
+    if (rc == SELA_HIP_OK && ((uintptr_t)d_env & 7))
+        rc = fail(SELA_HIP_EINVAL, "d_env must be 8-byte aligned");
+    if (rc != SELA_HIP_OK)
+        return rc;
+    if (n_frames && !d_samples)
+        return fail(SELA_HIP_EINVAL, "null device pointer");
+    if (((uintptr_t)d_samples & 3) || ((uintptr_t)d_counts & 3))
+        return fail(SELA_HIP_EINVAL, "d_samples and d_counts must be 4-byte aligned");
+    const size_t need = sela::envelope_samples_i32_workspace_bytes(n_frames, channels, stride);
+    if (need == SIZE_MAX || workspace_bytes < need)
+        return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_envelope_samples_i32_workspace_bytes()");
+    return launched(sela::launch_envelope_samples_i32_device(d_samples, d_counts, n_frames, channels, stride, bucket, d_env, d_status, static_cast<hipStream_t>(stream)),
+        "envelope_samples_i32 launch");
+}
+
+// Host pointers, synchronous: sela_hip_levels_i32's walk, then chunks of frames where that call runs (generic_envelope_i32), at the
+// caller's stride; no frames need no device.
+int sela_hip_envelope_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* env)
+{
+    if (channels == 0 || channels > 255)
+        return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
+    if (stride == 0)
+        return fail(SELA_HIP_EINVAL, "stride must not be 0");
+    if ((uint64_t)n_frames * channels >= (1ull << 31))
+        return fail(SELA_HIP_EINVAL, "n_frames * channels must stay below 2^31");
+    if (!sela::envelope_bucket_ok(bucket))
+        return fail(SELA_HIP_EINVAL, "bucket must be one of 32, 64, 128, 256, 512, 1024, 2048");
+    if ((uint64_t)sela::envelope_slots(stride, bucket) * channels > 0xFFFFFFFFull) // (the chunk loop counts a frame's records in 32 bits)
+        return fail(SELA_HIP_EINVAL, "ceil(stride / bucket) * channels must fit 32 bits");
+    if (!frame_offsets || (n_frames && (!frames || !env)))
+        return fail(SELA_HIP_EINVAL, "null pointer");
+    if (n_frames == 0)
+        return SELA_HIP_OK;
+    if (sela::check_frame_offsets(frame_offsets, n_frames) != SELA_HIP_OK)
+        return SELA_HIP_EFORMAT;
+    if (sela::generic_index_samples(frames, frame_offsets, n_frames, channels, nullptr, nullptr) == 0)
+        return fail(SELA_HIP_EFORMAT, "malformed frame stream (the header walk breaks, or no subframe says a length)");
+    return sela::generic_envelope_i32(frames, frame_offsets, n_frames, channels, stride, bucket, env);
+}
+
+long long sela_hip_debug_envelope_i32_fallback_frames(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return fallback_frames(sela::envelope_i32_workspace_bytes, sela::envelope_i32_control_words, d_workspace, max_frames, channels, stride);
 }
 
 size_t sela_hip_decode_windows_workspace_bytes(uint32_t n_windows, uint32_t window_samples, uint32_t channels)

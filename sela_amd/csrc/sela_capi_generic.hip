@@ -865,6 +865,24 @@ int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uin
         });
 }
 
+// sela_hip_envelope_i32: generic_levels_i32's chunks at the caller's stride, ceil(stride / bucket) * channels
+// records a frame (a longer frame is the status words' SELA_HIP_FLAG_STRIDE, judged like every other flag).  The caller has
+// walked the stream.
+int generic_envelope_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* env)
+{
+    const Call call;
+    if (call.rc != SELA_HIP_OK)
+        return call.rc;
+    const uint32_t records = envelope_slots(stride, bucket) * channels; // (fits 32 bits: sela_hip_envelope_i32 refuses a shape where it does not)
+    const size_t per_frame = (size_t)channels * stride * 8 + (size_t)channels * (sizeof(GenericSubInfo) + 8) + (size_t)records * sizeof(struct sela_hip_envelope32)
+        + 8 * (size_t)verify32_slices(stride) + 64;
+    return levels_chunks(call, "envelope_i32", frames, frame_offsets, n_frames, channels, stride, records, per_frame, envelope_i32_workspace_bytes, judge_i32, env,
+        [=](const uint8_t* d_frames, const uint64_t* d_offsets, uint32_t cf, struct sela_hip_envelope32* d_env, uint32_t* d_status, void* d_ws, int mode, hipStream_t st) {
+            return launch_envelope_i32_device(d_frames, d_offsets, cf, nullptr, channels, stride, bucket, d_env, nullptr, d_status, d_ws, mode, st);
+        });
+}
+
 // sela_hip_decode_windows: the *_device launch on chunks of WINDOWS, on the calling thread's context and stream.
 // Per chunk only the frames its windows touch go in (plan_windows: the distinct covering frames back to back, the descriptors
 // on that compacted table; runs of neighbouring frames are gathered with one memcpy each, the whole with one copy); status

@@ -175,6 +175,27 @@ size_t levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels
 inline size_t levels_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return levels_samples_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
 hipError_t launch_levels_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride,
     sela_hip_level32* d_levels, uint32_t* d_status, void* d_workspace, hipStream_t stream);
+// sela_hip_envelope_i32_device / sela_hip_envelope_payload_i32_device: launch_levels_i32_device's shape with the
+// frame's total cut into buckets of 32 .. 2048 samples -- min, max, sum and the 128-bit sum of squares per (frame, bucket, channel).
+// The kernels are sela_envelope32.hip's; a slice holds whole buckets, so they write the records themselves and the workspace is
+// launch_verify_i32_device's, byte for byte.  The begin step is launch_level32_begin; status[2] stays 0.
+hipError_t launch_envelope32_direct(const int32_t* d_dec, const GenericSubInfo* d_info, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bucket, const uint32_t* d_status, uint32_t* d_ctl, uint32_t* d_marks /* [max_frames] */,
+    struct sela_hip_envelope32* d_env /* [max_frames][envelope_slots()][channels] */, hipStream_t stream);
+// d_ctl and d_marks null: every frame of d_all (the caller's samples; d_counts or null: stride)
+hipError_t launch_envelope32_rest(const int32_t* d_all, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    const uint32_t* d_status, const uint32_t* d_ctl, const uint32_t* d_marks, struct sela_hip_envelope32* d_env, hipStream_t stream);
+size_t envelope_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t envelope_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return envelope_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
+const uint32_t* envelope_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride); // the call's two control words (device)
+hipError_t launch_envelope_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bucket, struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream);
+// sela_hip_envelope_samples_i32_device: the rest kernel on its own, over samples that already lie in device memory; the workspace
+// is a token (nothing lies between the kernels)
+size_t envelope_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at);
+inline size_t envelope_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride) { return envelope_samples_i32_workspace_bytes(max_frames, channels, stride, nullptr); }
+hipError_t launch_envelope_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint32_t* d_status, hipStream_t stream);
 // sela_hip_verify_pcm_device / sela_hip_verify_payload_pcm_device: launch_verify_i32_device's shape with the
 // original read as packed interleaved PCM of 3 or 4 bytes a sample, frame f at d_sample_offsets[f] (the caller's, or the
 // workspace's copy) -- sela_verify_pcm.hip's kernels on the tiles of sela_pcm_layout.h, no unpacked copy.

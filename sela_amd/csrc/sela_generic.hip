@@ -2102,6 +2102,56 @@ hipError_t launch_levels_samples_i32_device(const int32_t* d_samples, const uint
     return launch_level32_rest(d_samples, d_counts, max_frames, nullptr, channels, stride, d_status, nullptr, nullptr, parts, d_levels, stream);
 }
 
+// ---- the envelope of 32-bit and ragged streams on the device (sela_hip_envelope_i32_device) --------------------
+// Workspace: launch_verify_i32_device's pieces as that call carves them.  Its words per (frame, slice) lie unused: a slice holds
+// whole buckets, so the kernels write the records themselves.
+static VerifyI32Ws carve_envelope_i32(Carve& c, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    return carve_verify_i32(c, max_frames, channels, stride, verify32_slices(stride));
+}
+
+size_t envelope_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { carve_envelope_i32(c, max_frames, channels, stride); });
+}
+
+const uint32_t* envelope_i32_control_words(const void* d_workspace, uint32_t max_frames, uint32_t channels, uint32_t stride)
+{
+    Carve c(d_workspace);
+    return carve_envelope_i32(c, max_frames, channels, stride).ctl;
+}
+
+// The envelope plugs k_level32_begin, k_envelope32_direct and k_envelope32_rest into launch_i32_sequence: status[2] stays 0.
+hipError_t launch_envelope_i32_device(const uint8_t* d_frames, const uint64_t* d_frame_offsets, uint32_t max_frames, const uint32_t* d_n_found, uint32_t channels,
+    uint32_t stride, uint32_t bucket, struct sela_hip_envelope32* d_env, uint64_t* d_sample_offsets, uint32_t* d_status, void* d_workspace, int mode, hipStream_t stream)
+{
+    Carve c(d_workspace);
+    const VerifyI32Ws w = carve_envelope_i32(c, max_frames, channels, stride);
+    return launch_i32_sequence({d_frames, d_frame_offsets, max_frames, d_n_found, channels, stride, d_status, mode, stream}, w, d_sample_offsets,
+        [&] { return launch_level32_begin(d_status, w.ctl, false, stream); },
+        [&] { return launch_envelope32_direct(w.d.dec, w.d.info, max_frames, d_n_found, channels, stride, bucket, d_status, w.ctl, w.marks, d_env, stream); },
+        [&] { return launch_envelope32_rest(w.all, w.counts, max_frames, channels, stride, bucket, d_status, w.ctl, w.marks, d_env, stream); });
+}
+
+// A token: the one kernel leaves nothing between launches.
+size_t envelope_samples_i32_workspace_bytes(uint32_t max_frames, uint32_t channels, uint32_t stride, Carve* at)
+{
+    if (channels == 0 || verify_i32_workspace_bytes(max_frames, channels, stride) == SIZE_MAX)
+        return SIZE_MAX;
+    return measured(at, [&](Carve& c) { c.take<uint64_t>(1); });
+}
+
+hipError_t launch_envelope_samples_i32_device(const int32_t* d_samples, const uint32_t* d_counts, uint32_t max_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* d_env, uint32_t* d_status, hipStream_t stream)
+{
+    const hipError_t e = launch_level32_begin(d_status, nullptr, true, stream);
+    if (e != hipSuccess || max_frames * channels == 0)
+        return e;
+    return launch_envelope32_rest(d_samples, d_counts, max_frames, channels, stride, bucket, d_status, nullptr, nullptr, d_env, stream);
+}
+
 // ---- verification against packed PCM on the device (sela_hip_verify_pcm_device) -------------------------------
 // Workspace: launch_verify_i32_device's pieces, the words per (frame, slice) sized by the tiles of sela_pcm_layout.h | the sample
 // offsets of a caller that asks for none.

@@ -233,6 +233,9 @@ int generic_envelope(const uint8_t* frames, const uint64_t* frame_offsets, uint3
 int generic_digest(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, struct sela_hip_digest* digests, uint32_t* track_crc32,
     uint64_t* track_bytes, int recurrence_form);
 int generic_levels_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, sela_hip_level32* levels);
+// sela_hip_envelope_i32: generic_levels_i32's chunks at the caller's stride, ceil(stride / bucket) * channels records a frame
+int generic_envelope_i32(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bucket,
+    struct sela_hip_envelope32* env);
 // sela_hip_digest_pcm: generic_levels_i32's chunks, the chunks' track words and wide-sample counts folded on the host (any output may be null)
 int generic_digest_pcm(const uint8_t* frames, const uint64_t* frame_offsets, uint32_t n_frames, uint32_t channels, uint32_t stride, uint32_t bytes_per_sample,
     struct sela_hip_digest* digests, uint32_t* track_crc32, uint64_t* track_bytes, uint32_t* wide_samples);
