@@ -1,6 +1,8 @@
 // salvage.hpp -- the host's side of the salvage (sela_hip_salvage_payload_device, include/sela_hip.h): a .sela
 // file whose payload is damaged, read past the positions where every other verb stops, and written out again with the frames
-// that survived back to back and a header that counts them.  The report says what was lost and where.
+// that survived back to back and a header that counts them.  The report says what was lost and where.  With anyByte the frames
+// are looked for at every byte of the payload (sela_hip_salvage_payload_unaligned_device), so what lies behind
+// inserted or deleted bytes is found too.
 #ifndef SELA_HOST_SALVAGE_HPP_
 #define SELA_HOST_SALVAGE_HPP_
 
@@ -27,8 +29,9 @@ struct SalvageReport {
 
 // Reads inPath's 15-byte header (a file that is not 'SeLa' is refused, as everywhere), walks its payload on the GPU -- up to
 // as many frames as its bytes could hold, NOT the announced count -- and, where a frame was found, writes outPath: the header
-// with numFrames = found, then the frames taken.  Throws data::Exception; without a frame nothing is written.
-SalvageReport salvageFile(const std::string& inPath, const std::string& outPath);
+// with numFrames = found, then the frames taken.  Throws data::Exception; without a frame nothing is written.  anyByte: frames
+// at any byte offset of the payload, not only at multiples of 4 (payloads below 4 GiB).
+SalvageReport salvageFile(const std::string& inPath, const std::string& outPath, bool anyByte = false);
 
 // "announced A frames, found F" / one "gap: ..." line per gap / "trailing: T bytes"
 std::string formatSalvageReport(const SalvageReport& r);

@@ -1,5 +1,5 @@
-// salvage.cpp -- sela::salvageFile (see salvage.hpp): upload the payload, one sela_hip_salvage_payload_device, download what it
-// kept.  The one host source that talks to the HIP runtime itself: the call works on device pointers.
+// salvage.cpp -- sela::salvageFile (see salvage.hpp): upload the payload, one sela_hip_salvage_payload_device (or its _unaligned
+// form), download what it kept.  The one host source that talks to the HIP runtime itself: the call works on device pointers.
 #include "sela_host/salvage.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -40,7 +40,7 @@ void copy(void* dst, const void* src, size_t n, hipMemcpyKind kind)
 
 namespace sela {
 
-SalvageReport salvageFile(const std::string& inPath, const std::string& outPath)
+SalvageReport salvageFile(const std::string& inPath, const std::string& outPath, bool anyByte)
 {
     std::ifstream probe(inPath, std::ios::binary);
     if (!probe)
@@ -65,11 +65,12 @@ SalvageReport salvageFile(const std::string& inPath, const std::string& outPath)
     if (!sela_host::PosixFile::openForRead(inPath).readAt(payload.data(), payloadBytes, 15))
         throw data::Exception("File is too small, probably not a sela file.");
 
-    const size_t workspaceBytes = sela_hip_salvage_workspace_bytes(payloadBytes, cap), outCap = payloadBytes / 4 * 4;
+    const size_t workspaceBytes = anyByte ? sela_hip_salvage_unaligned_workspace_bytes(payloadBytes, cap) : sela_hip_salvage_workspace_bytes(payloadBytes, cap);
+    const size_t outCap = payloadBytes / 4 * 4;
     DeviceBytes dPayload(payloadBytes), dOut(outCap), dOffsets(((size_t)cap + 1) * 8), dRecords((size_t)cap * sizeof(sela_hip_salvaged)), dTotals(32),
         dWorkspace(workspaceBytes);
     copy(dPayload.p, payload.data(), payloadBytes, hipMemcpyHostToDevice);
-    if (sela_hip_salvage_payload_device(dPayload.as<uint8_t>(), payloadBytes, cap, channels, dOut.as<uint8_t>(), outCap, dOffsets.as<uint64_t>(),
+    if ((anyByte ? sela_hip_salvage_payload_unaligned_device : sela_hip_salvage_payload_device)(dPayload.as<uint8_t>(), payloadBytes, cap, channels, dOut.as<uint8_t>(), outCap, dOffsets.as<uint64_t>(),
             dRecords.as<sela_hip_salvaged>(), dTotals.as<uint64_t>(), dWorkspace.p, workspaceBytes, nullptr)
         != SELA_HIP_OK)
         gpuFailure(sela_hip_last_error());

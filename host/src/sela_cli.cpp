@@ -51,6 +51,9 @@
 //                                      and the found frame counts, a line per gap (file offset, bytes, index of the frame behind it)
 //                                      and the bytes behind the last frame; exit 0: nothing skipped, nothing trailing, found ==
 //                                      announced, 2: frames were written but something was lost, 1: no frame found, or not a .sela
+//   sela_mi355x -s --any-byte in.sela out.sela   the same with frames looked for at EVERY byte of the payload: what lies
+//                                      behind inserted or deleted bytes, or behind a second file's header, is found too.  The same lines
+//                                      (gaps in bytes at file offsets) and exit codes
 //   sela_mi355x -E out_dir [--gpus N | --devices a,b,..] a.wav b.wav ...    encode many files as one job -> out_dir/<name>.sela
 //   sela_mi355x -D out_dir [--gpus N | --devices a,b,..] a.sela b.sela ...  decode many files as one job -> out_dir/<name>.wav
 //   (-E / -D also take --io-threads N: threads that read and write files beside the GPU workers)
@@ -105,6 +108,8 @@ int usage(const std::string& program)
               << program << " -C path/to/input.sela [path/to/input.wav]\n\n"
               << "Salvaging a damaged file (the frames that can still be found, back to back; exit 2 where something was lost):\n"
               << program << " -s path/to/input.sela path/to/output.sela\n\n"
+              << "Salvaging a file that bytes were inserted into or deleted from (frames are looked for at every byte, not every 4th):\n"
+              << program << " -s --any-byte path/to/input.sela path/to/output.sela\n\n"
               << "Playing a file (raw interleaved int16 to a file, or to standard output):\n" << program << " -p path/to/input.sela [path/to/output.pcm]\n\n"
               << "Many files, all GPUs:\n" << program << " -E|-D path/to/output_dir [--gpus N | --devices 0,1,..] inputs...\n";
     return 2;
@@ -227,6 +232,11 @@ int run(int argc, char** argv)
         if (std::string(argv[i]) == "--lossless" && !(verb == "-e" && i == 2 && argc == 5) && !(pairedLossless && i == 3))
             return usage(program);
     }
+    // (--any-byte is -s's alone, right behind it: with any other verb and anywhere else it is refused, not ignored)
+    const bool anyByte = verb == "-s" && argc == 5 && std::string(argv[2]) == "--any-byte";
+    for (int i = 2; i < argc; i++)
+        if (std::string(argv[i]) == "--any-byte" && !(anyByte && i == 2))
+            return usage(program);
     // (--start / --count are -d's alone, together, in that place: anywhere else they are refused, not ignored)
     const bool ranged = verb == "-d" && argc == 8 && std::string(argv[2]) == "--start" && std::string(argv[4]) == "--count";
     for (int i = 2; i < argc; i++)
@@ -352,6 +362,12 @@ int run(int argc, char** argv)
         const sela::DigestReport report = sela::digestFile(std::string(argv[2]), wav);
         std::cout << sela::formatDigestReport(report) << std::flush;
         return report.agree() ? 0 : 3;
+    }
+    if (anyByte) {
+        std::cout << "Salvaging (any byte): " << argv[3] << std::endl;
+        const sela::SalvageReport report = sela::salvageFile(std::string(argv[3]), std::string(argv[4]), true);
+        std::cout << sela::formatSalvageReport(report) << std::flush;
+        return sela::salvageExitCode(report);
     }
     if (verb == "-s") {
         if (argc != 4)

@@ -1262,7 +1262,7 @@ uint32_t sela_hip_index_frames(const uint8_t* frames, size_t frames_bytes, uint3
  * Whether a taken frame's CONTENTS are sound is not judged here: that is the decoders' flags', sela_hip_verify*'s and
  * sela_hip_digest*'s business. */
 typedef struct sela_hip_salvaged { /* 24 bytes, 8-byte aligned */
-    uint64_t offset;         /* of the frame in the payload, a multiple of 4 */
+    uint64_t offset;         /* of the frame in the payload, a multiple of 4 (any byte from the *_unaligned calls) */
     uint64_t skipped_before; /* bytes between the end of the frame before (or offset 0) and this one */
     uint32_t bytes;          /* the frame's length, a multiple of 4 */
     uint32_t reserved;       /* 0 */
@@ -1300,6 +1300,56 @@ int sela_hip_salvage_frames_device(const uint8_t* d_payload, size_t payload_byte
  * payload (SELA_HIP_EINVAL).  Workspace, asynchrony and the other errors: as the call above.
  */
 int sela_hip_salvage_payload_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets /* [max_frames + 1] */, sela_hip_salvaged* d_records /* [max_frames] or NULL */,
+    uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- salvage at any byte: frames behind inserted or deleted bytes -------------------------------------------------
+ * The salvage above looks at word positions only.  These calls are its rule with "word" replaced by "byte": a frame is still a
+ * multiple of 4 bytes long, but it may start at any byte of the payload.  For a payload of B bytes and C = channels:
+ *   candidate   a byte offset b with b + 4 <= B whose four bytes are the sync word (little endian) and whose C subframe
+ *               headers, read with sela_format.h's byte reader and bound B, all fit.  end(b) is the byte where that frame would
+ *               end: b plus a multiple of 4;
+ *   confirmed   a candidate with B - end(b) < 4, or with end(b) itself a candidate.  (Where end(b) is a multiple of 4 the first
+ *               is the word rule's "end(w) == 4 W".);
+ *   the walk    starts at p = 0 with no frame taken.  While fewer than max_frames frames are taken: if p is a candidate, it is
+ *               taken as it stands (the position is trusted: offset 0, or the end of a taken frame; skipped_before = 0);
+ *               otherwise the smallest confirmed candidate b >= p is taken with skipped_before = b - p, and if there is none
+ *               the walk ends.  Then p = end(taken).
+ * Records and totals are the salvage's above; `offset` and `skipped_before` are any byte count, `bytes` a multiple of 4.
+ * What follows from the rule:
+ *   - where sela_hip_index_frames() finds n frames, the first n records are those frames with skipped_before == 0;
+ *   - offsets strictly increase and frames never overlap;
+ *   - the taken frames written back to back form a payload that sela_hip_index_frames() reads to its last byte, and that
+ *     both salvages take whole with no gap;
+ *   - on a payload of intact frames with garbage that holds no sync word, of any byte length, put between frames, every frame
+ *     is taken; the frames may sit at different phases.
+ * Its limits, as they are:
+ *   - a trusted frame whose length fields are wrong still sends the walk to the wrong place: where bytes were deleted INSIDE a
+ *     frame, that frame is taken with its neighbour's head in it, and the neighbour is lost;
+ *   - an intact frame whose predecessor was not taken AND whose successor's header is damaged is still missed;
+ *   - a chance sync word, at any byte now, whose headers fit and whose end lands on a candidate is confirmed, and is taken when
+ *     the walk is searching at or before it.
+ * The host walk: pure CPU, any alignment of `payload`; arguments and result as sela_hip_salvage_frames(). */
+uint32_t sela_hip_salvage_frames_unaligned(const uint8_t* payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    sela_hip_salvaged* records, uint64_t* totals);
+/*
+ * The same walk on the device, and the walk with the copy: arguments, outputs, out_cap, asynchrony, launch count, argument checks,
+ * their order and their codes are sela_hip_salvage_frames_device()'s and sela_hip_salvage_payload_device()'s, with two differences.
+ * Positions are uint32 BYTE offsets here, so a payload_bytes of 2^32 or more is SELA_HIP_EINVAL.  And no byte at or behind
+ * d_payload + payload_bytes is read although the last bytes of a payload whose length is no multiple of 4 matter (a frame may
+ * end there): they are read as bytes, never as a word that reaches past the end.  d_payload and d_out stay 4-byte aligned and
+ * apart; the compacted payload in d_out is made of whole frames, so every *_device call reads it as it stands.
+ * d_workspace: sela_hip_salvage_unaligned_workspace_bytes(payload_bytes, max_frames) bytes, no initialisation.  The sync word
+ * cannot overlap itself, so at most one candidate starts inside any aligned word and the workspace stays one entry per WORD: with
+ * W = payload_bytes / 4, K = ceil(W / 4096), F = min(max_frames, W) and up(b) = b rounded up to a multiple of 256 it is
+ *   9 up(4 W) + 2 up(4 (K + 1)) + 3 up(4 F) + 5 * 256 + 256
+ * bytes, sela_hip_salvage_workspace_bytes()'s formula.
+ */
+size_t sela_hip_salvage_unaligned_workspace_bytes(size_t payload_bytes, uint32_t max_frames);
+int sela_hip_salvage_frames_unaligned_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
+    sela_hip_salvaged* d_records /* [max_frames] */, uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes,
+    void* stream);
+int sela_hip_salvage_payload_unaligned_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels,
     uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets /* [max_frames + 1] */, sela_hip_salvaged* d_records /* [max_frames] or NULL */,
     uint64_t* d_totals /* [4] */, void* d_workspace, size_t workspace_bytes, void* stream);
 

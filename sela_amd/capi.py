@@ -61,6 +61,8 @@ EXPORTS = [
     "sela_hip_crc32_workspace_bytes", "sela_hip_crc32_device",
     "sela_hip_digest_pcm_workspace_bytes", "sela_hip_digest_pcm_device", "sela_hip_digest_payload_pcm_device", "sela_hip_digest_pcm",
     "sela_hip_salvage_frames", "sela_hip_salvage_workspace_bytes", "sela_hip_salvage_frames_device", "sela_hip_salvage_payload_device",
+    "sela_hip_salvage_frames_unaligned", "sela_hip_salvage_unaligned_workspace_bytes", "sela_hip_salvage_frames_unaligned_device",
+    "sela_hip_salvage_payload_unaligned_device",
     "sela_hip_envelope_slots", "sela_hip_envelope_workspace_bytes", "sela_hip_envelope_device", "sela_hip_envelope_payload_device", "sela_hip_envelope",
     "sela_hip_envelope_i32_workspace_bytes", "sela_hip_envelope_i32_device", "sela_hip_envelope_payload_i32_device",
     "sela_hip_envelope_samples_i32_workspace_bytes", "sela_hip_envelope_samples_i32_device", "sela_hip_envelope_i32",
@@ -157,6 +159,14 @@ def lib() -> C.CDLL:
     L.sela_hip_salvage_frames_device.restype = C.c_int
     L.sela_hip_salvage_payload_device.argtypes = [vp, sz, u32, u32, vp, sz, vp, vp, vp, vp, sz, vp]
     L.sela_hip_salvage_payload_device.restype = C.c_int
+    L.sela_hip_salvage_frames_unaligned.argtypes = [vp, sz, u32, u32, vp, vp]
+    L.sela_hip_salvage_frames_unaligned.restype = u32
+    L.sela_hip_salvage_unaligned_workspace_bytes.argtypes = [sz, u32]
+    L.sela_hip_salvage_unaligned_workspace_bytes.restype = sz
+    L.sela_hip_salvage_frames_unaligned_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, sz, vp]
+    L.sela_hip_salvage_frames_unaligned_device.restype = C.c_int
+    L.sela_hip_salvage_payload_unaligned_device.argtypes = [vp, sz, u32, u32, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.sela_hip_salvage_payload_unaligned_device.restype = C.c_int
     L.sela_hip_decode_payload_device.argtypes = [vp, sz, u32, u32, vp, vp, vp, vp, vp, sz, vp]
     L.sela_hip_decode_payload_device.restype = C.c_int
     L.sela_hip_decode_i32_workspace_bytes.argtypes = [u32, u32, u32]

@@ -1575,22 +1575,26 @@ def index_workspace_bytes(payload_bytes: int, max_frames: int) -> int:
 SALVAGED_DTYPE = np.dtype([("offset", "<u8"), ("skipped_before", "<u8"), ("bytes", "<u4"), ("reserved", "<u4")])
 
 
-def salvage_frames(payload: np.ndarray, channels: int, max_frames=None):
+def salvage_frames(payload: np.ndarray, channels: int, max_frames=None, unaligned: bool = False):
     """sela_hip_salvage_frames on a numpy array: the frames of a damaged payload, walked on the host (no device needed;
     DESIGN.md 5.30) -> (records SALVAGED_DTYPE [frames taken], totals uint64 [4]: frames taken, records with a gap in front,
-    the sum of their bytes, the end of the last one).  max_frames: the cap (default: as many as the bytes could hold)."""
+    the sum of their bytes, the end of the last one).  max_frames: the cap (default: as many as the bytes could hold).
+    unaligned: sela_hip_salvage_frames_unaligned, frames at any byte offset."""
     lib = capi.lib()
     body = np.ascontiguousarray(payload, dtype=np.uint8)
     if max_frames is None:
         max_frames = body.nbytes // (4 + 12 * max(channels, 1))
     records = np.zeros(max_frames, SALVAGED_DTYPE)
     totals = np.zeros(4, np.uint64)
-    found = lib.sela_hip_salvage_frames(body.ctypes.data, body.nbytes, max_frames, channels, records.ctypes.data, totals.ctypes.data)
+    walk = lib.sela_hip_salvage_frames_unaligned if unaligned else lib.sela_hip_salvage_frames
+    found = walk(body.ctypes.data, body.nbytes, max_frames, channels, records.ctypes.data, totals.ctypes.data)
     return records[:found], totals
 
 
-def salvage_workspace_bytes(payload_bytes: int, max_frames: int) -> int:
-    return int(capi.lib().sela_hip_salvage_workspace_bytes(payload_bytes, max_frames))
+def salvage_workspace_bytes(payload_bytes: int, max_frames: int, unaligned: bool = False) -> int:
+    lib = capi.lib()
+    sized = lib.sela_hip_salvage_unaligned_workspace_bytes if unaligned else lib.sela_hip_salvage_workspace_bytes
+    return int(sized(payload_bytes, max_frames))
 
 
 class Salvager:
@@ -1598,12 +1602,15 @@ class Salvager:
     device, past positions where the index stops, and copied back to back.  Owns its records, totals, frame
     offsets, compacted payload and workspace on the current device (or `device`), sized once for payloads of up to
     max_payload_bytes; every call is asynchronous on the current stream and overwrites them -- so it can be captured into a
-    graph."""
+    graph.  unaligned: the *_unaligned_device calls, frames at any byte offset."""
 
-    def __init__(self, max_payload_bytes: int, max_frames: int, channels: int, device=None):
+    def __init__(self, max_payload_bytes: int, max_frames: int, channels: int, device=None, unaligned: bool = False):
         import torch
 
         self.lib = capi.lib()
+        self.unaligned = bool(unaligned)
+        self._frames_call = self.lib.sela_hip_salvage_frames_unaligned_device if unaligned else self.lib.sela_hip_salvage_frames_device
+        self._payload_call = self.lib.sela_hip_salvage_payload_unaligned_device if unaligned else self.lib.sela_hip_salvage_payload_device
         self.max_payload_bytes, self.max_frames, self.channels = int(max_payload_bytes), int(max_frames), int(channels)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # the records as int64 [max_frames, 3]: offset, skipped_before, bytes | reserved << 32; the totals as int64 [4]
@@ -1611,7 +1618,7 @@ class Salvager:
         self.totals = torch.zeros(4, dtype=torch.int64, device=self.device)
         self.frame_offsets = torch.zeros(self.max_frames + 1, dtype=torch.int64, device=self.device)
         self.out = torch.zeros(self.max_payload_bytes // 4 * 4, dtype=torch.uint8, device=self.device)
-        self.workspace = torch.empty(salvage_workspace_bytes(self.max_payload_bytes, self.max_frames), dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty(salvage_workspace_bytes(self.max_payload_bytes, self.max_frames, self.unaligned), dtype=torch.uint8, device=self.device)
 
     def _payload_ok(self, payload) -> None:
         import torch
@@ -1625,7 +1632,7 @@ class Salvager:
         import torch
 
         self._payload_ok(payload)
-        capi.check(self.lib.sela_hip_salvage_frames_device(
+        capi.check(self._frames_call(
             payload.data_ptr(), payload.numel(), self.max_frames, self.channels, self.salvaged.data_ptr(), self.totals.data_ptr(),
             self.workspace.data_ptr(), self.workspace.numel(), torch.cuda.current_stream(self.device).cuda_stream))
         return self.salvaged, self.totals
@@ -1641,7 +1648,7 @@ class Salvager:
         if out is None:
             out = self.out
         assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
-        capi.check(self.lib.sela_hip_salvage_payload_device(
+        capi.check(self._payload_call(
             payload.data_ptr(), payload.numel(), self.max_frames, self.channels, out.data_ptr(), out.numel(), self.frame_offsets.data_ptr(),
             self.salvaged.data_ptr(), self.totals.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
             torch.cuda.current_stream(self.device).cuda_stream))

@@ -28,6 +28,7 @@
 #include "sela_lease.h"
 #include "sela_pcm.h"
 #include "sela_salvage_walk.h"
+#include "sela_salvage_walk_unaligned.h"
 
 namespace {
 
@@ -1627,7 +1628,7 @@ size_t sela_hip_salvage_workspace_bytes(size_t payload_bytes, uint32_t max_frame
 namespace {
 // both salvage calls' checks: the index's cases and codes; d_out null for the walk alone
 int salvage_call(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint8_t* d_out, size_t out_cap, uint64_t* d_frame_offsets,
-    sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream, bool copy)
+    sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream, bool copy, bool unaligned = false)
 {
     if (channels == 0 || channels > 255)
         return fail(SELA_HIP_EINVAL, "channels must be in 1..255");
@@ -1637,10 +1638,19 @@ int salvage_call(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_fr
         return fail(SELA_HIP_EINVAL, "d_payload must be 4-byte aligned");
     if (copy && ((uintptr_t)d_out & 3))
         return fail(SELA_HIP_EINVAL, "d_out must be 4-byte aligned");
+    if (unaligned && (uint64_t)payload_bytes >= (1ull << 32))
+        return fail(SELA_HIP_EINVAL, "payloads of 4 GiB and more are not salvaged at any byte on the device (32-bit byte offsets)");
     if (payload_bytes / 4 >= 0xFFFFFFFFull)
         return fail(SELA_HIP_EINVAL, "payloads of 16 GiB and more are not indexed on the device (32-bit word indices)");
     if (copy && out_cap && payload_bytes && (uintptr_t)d_out < (uintptr_t)d_payload + payload_bytes && (uintptr_t)d_payload < (uintptr_t)d_out + out_cap)
         return fail(SELA_HIP_EINVAL, "d_out must not overlap the payload");
+    if (unaligned) {
+        if (workspace_bytes < sela::salvage_unaligned_workspace_bytes(payload_bytes, max_frames))
+            return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_salvage_unaligned_workspace_bytes()");
+        return launched(sela::launch_salvage_unaligned(d_payload, payload_bytes, max_frames, channels, d_records, d_totals, copy && out_cap ? d_out : nullptr,
+                            out_cap, d_frame_offsets, d_workspace, static_cast<hipStream_t>(stream)),
+            "salvage launch");
+    }
     if (workspace_bytes < sela::salvage_workspace_bytes(payload_bytes, max_frames))
         return fail(SELA_HIP_ECAPACITY, "workspace smaller than sela_hip_salvage_workspace_bytes()");
     return launched(sela::launch_salvage(d_payload, payload_bytes, max_frames, channels, d_records, d_totals, copy && out_cap ? d_out : nullptr, out_cap,
@@ -1659,6 +1669,31 @@ int sela_hip_salvage_payload_device(const uint8_t* d_payload, size_t payload_byt
     uint64_t* d_frame_offsets, sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream)
 {
     return salvage_call(d_payload, payload_bytes, max_frames, channels, d_out, out_cap, d_frame_offsets, d_records, d_totals, d_workspace, workspace_bytes, stream, true);
+}
+
+// ---- salvage at any byte (the walk: sela_salvage_walk_unaligned.h, the device: sela_salvage_unaligned.hip) ----------
+uint32_t sela_hip_salvage_frames_unaligned(const uint8_t* payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* records,
+    uint64_t* totals)
+{
+    return sela::salvage_walk_unaligned(payload, payload_bytes, max_frames, channels, records, totals);
+}
+
+size_t sela_hip_salvage_unaligned_workspace_bytes(size_t payload_bytes, uint32_t max_frames)
+{
+    return sela::salvage_unaligned_workspace_bytes(payload_bytes, max_frames);
+}
+
+int sela_hip_salvage_frames_unaligned_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
+    uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return salvage_call(d_payload, payload_bytes, max_frames, channels, nullptr, 0, nullptr, d_records, d_totals, d_workspace, workspace_bytes, stream, false, true);
+}
+
+int sela_hip_salvage_payload_unaligned_device(const uint8_t* d_payload, size_t payload_bytes, uint32_t max_frames, uint32_t channels, uint8_t* d_out, size_t out_cap,
+    uint64_t* d_frame_offsets, sela_hip_salvaged* d_records, uint64_t* d_totals, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    return salvage_call(d_payload, payload_bytes, max_frames, channels, d_out, out_cap, d_frame_offsets, d_records, d_totals, d_workspace, workspace_bytes, stream, true,
+        true);
 }
 
 // ---- the decode and verify calls of any length on device pointers, each in two forms ---------------

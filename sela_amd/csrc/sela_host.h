@@ -77,11 +77,19 @@ inline IndexWs carve_index(Carve& c, uint64_t words)
 // k_index_scan also sets the outputs it is given to "no frame found": d_frame_offsets[0] = 0, *d_n_frames = 0.
 hipError_t launch_index_candidates(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t channels, const IndexWs& ws, uint64_t* d_frame_offsets,
     uint32_t* d_n_frames, hipStream_t stream);
+// k_index_scan alone: counts[0 .. blocks) of `ws` -> their exclusive scan, counts[blocks] = *n_cand = the total; the outputs as above.
+hipError_t launch_index_scan(const IndexWs& ws, uint32_t blocks, uint64_t* d_frame_offsets, uint32_t* d_n_frames, hipStream_t stream);
 
 // ---- sela_salvage.hip: the frames of a damaged payload -----------------------------------------------------------
 size_t salvage_workspace_bytes(uint64_t payload_bytes, uint32_t max_frames, Carve* at = nullptr);
 // d_out null: the walk alone (d_frame_offsets may then be null too); d_records may be null.  The caller has checked the arguments.
 hipError_t launch_salvage(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
+    uint64_t* d_totals, uint8_t* d_out, uint64_t out_cap, uint64_t* d_frame_offsets, void* d_workspace, hipStream_t stream);
+
+// ---- sela_salvage_unaligned.hip: the frames of a damaged payload at any byte ------------------------------------
+size_t salvage_unaligned_workspace_bytes(uint64_t payload_bytes, uint32_t max_frames, Carve* at = nullptr);
+// As launch_salvage; payload_bytes below 2^32.
+hipError_t launch_salvage_unaligned(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
     uint64_t* d_totals, uint8_t* d_out, uint64_t out_cap, uint64_t* d_frame_offsets, void* d_workspace, hipStream_t stream);
 
 // ---- sela_window.hip: sample windows of a stream ---------------------------------------------------------------

@@ -292,3 +292,10 @@ hipError_t launch_index_candidates(const uint8_t* d_payload, uint64_t payload_by
     hipLaunchKernelGGL(k_index_compact, dim3(blocks), dim3(kIndexThreads), 0, stream, ws);
     return hipGetLastError();
 }
+
+// k_index_scan alone, for sela_salvage_unaligned.hip (sela_host.h): the exclusive scan of counts[0 .. blocks), and *n_cand.
+hipError_t launch_index_scan(const IndexWs& ws, uint32_t blocks, uint64_t* d_frame_offsets, uint32_t* d_n_frames, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_index_scan, dim3(1), dim3(kIndexScanThreads), 0, stream, ws, blocks, d_frame_offsets, d_n_frames);
+    return hipGetLastError();
+}

@@ -34,79 +34,13 @@
 // one-workgroup form the index has for a track (links, rounds and scatter on LDS) was built and measured here too, and on the
 // bench track it was no faster -- 0.0744 ms against 0.0745 ms intact, 0.0845 ms against 0.0782 ms with 64 damaged headers
 //  -- so it was dropped, and with it a limit on max_frames and one on the candidates.
-#include <algorithm>
-
-#include "sela_host.h"
+//
+// The workspace, the workgroup's backward min-scan and the rank search live in sela_salvage_steps.h, and the block suffix, succ,
+// the rounds and the scatter are launched through launch_salvage_chain: sela_salvage_unaligned.hip runs them
+// as they are, on byte positions.
+#include "sela_salvage_steps.h"
 
 namespace sela {
-
-constexpr int kSalvageThreads = 256;
-constexpr int kSalvagePerThread = 16;
-constexpr uint32_t kSalvageChunk = (uint32_t)kSalvageThreads * kSalvagePerThread; // candidates one links workgroup covers; words one copy workgroup writes
-constexpr int kSalvageBlocks = 1024; // grid of the succ / round / scatter / records launches (grid-stride)
-
-struct SalvageWs {
-    IndexWs ix;             // the index's own, at the workspace's start as launch_index has it
-    uint64_t* scan_offsets; // [1] what k_index_scan initialises: nobody's output here
-    uint32_t* scan_count;   // [1]
-    uint32_t* nconf;        // [n_cand] the first confirmed candidate at or behind i within i's 4096, or none
-    uint32_t* gap_a;        // [n_cand] the gap, in words, of jump array A's links ...
-    uint32_t* gap_b;        // [n_cand] ... and of B's
-    uint32_t* bsuf;         // [blocks + 1] the first confirmed candidate in workgroup b's 4096 or behind
-    uint32_t* r_pos;        // [frames] by rank: the frame's word index,
-    uint32_t* r_end;        // [frames] its end,
-    uint32_t* r_dst;        // [frames] and its word index in the compacted payload
-    uint32_t* head;         // [1] the first frame taken, or none
-    uint32_t* copy_words;   // [1] the words of the compacted payload that fit out_cap in whole frames
-};
-// The workspace, for a payload of `words` 32-bit words: the index's, three more arrays of one uint32 per word, a word per 4096
-// candidates, three per frame (no more frames than words), and four single words.  (The chain's skip[] lives in ix.map, which
-// nothing reads after k_salvage_links.)
-inline SalvageWs carve_salvage(Carve& c, uint64_t words, uint32_t max_frames)
-{
-    const uint64_t blocks = (words + kSalvageChunk - 1) / kSalvageChunk, frames = std::min<uint64_t>(max_frames, words);
-    SalvageWs ws;
-    ws.ix = carve_index(c, words);
-    ws.scan_offsets = c.take<uint64_t>(1);
-    ws.scan_count = c.take<uint32_t>(1);
-    ws.nconf = c.take<uint32_t>(words);
-    ws.gap_a = c.take<uint32_t>(words);
-    ws.gap_b = c.take<uint32_t>(words);
-    ws.bsuf = c.take<uint32_t>(blocks + 1);
-    ws.r_pos = c.take<uint32_t>(frames);
-    ws.r_end = c.take<uint32_t>(frames);
-    ws.r_dst = c.take<uint32_t>(frames);
-    ws.head = c.take<uint32_t>(1);
-    ws.copy_words = c.take<uint32_t>(1);
-    return ws;
-}
-
-// Per thread: the minimum of v over the threads BEHIND it in the workgroup (kIndexNone, the largest value, where there is
-// none), and `total`, the minimum over all.  sh: a word per wave.
-__device__ __forceinline__ uint32_t block_suffix_min(uint32_t v, uint32_t* sh, uint32_t& total)
-{
-    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64, n_waves = blockDim.x / 64;
-    uint32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_down(incl, d); // (its own value where lane + d runs off the wave)
-        incl = min(incl, o);
-    }
-    uint32_t after = __shfl_down(incl, 1);
-    if (lane == 63)
-        after = kIndexNone;
-    if (lane == 0)
-        sh[wave] = incl;
-    __syncthreads();
-    total = kIndexNone;
-    for (int w = 0; w < n_waves; w++) {
-        const uint32_t t = sh[w];
-        total = min(total, t);
-        if (w > wave)
-            after = min(after, t);
-    }
-    __syncthreads();
-    return after;
-}
 
 __global__ __launch_bounds__(kSalvageThreads) void k_salvage_links(SalvageWs ws, uint32_t words)
 {
@@ -323,19 +257,6 @@ __global__ __launch_bounds__(kSalvageThreads) void k_salvage_records(SalvageWs w
         atomicAdd(reinterpret_cast<unsigned long long*>(totals + 1), (unsigned long long)mine);
 }
 
-// The rank whose frame holds word d of the compacted payload, between two ranks known to bracket it (r_dst[] increases).
-__device__ __forceinline__ uint32_t salvage_frame_of(const uint32_t* __restrict__ r_dst, uint32_t lo, uint32_t hi, uint32_t d)
-{
-    while (lo < hi) { // the last rank in [lo, hi] with r_dst <= d
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (r_dst[mid] <= d)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kSalvageThreads) void k_salvage_copy(const uint32_t* __restrict__ payload, uint32_t* __restrict__ out, SalvageWs ws,
     const uint64_t* __restrict__ totals)
 {
@@ -379,6 +300,27 @@ size_t salvage_workspace_bytes(uint64_t payload_bytes, uint32_t max_frames, Carv
     return measured(at, [&](Carve& c) { carve_salvage(c, payload_bytes / 4, max_frames); });
 }
 
+hipError_t launch_salvage_clear(uint64_t* d_totals, uint64_t* d_frame_offsets, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_salvage_clear, dim3(1), dim3(64), 0, stream, d_totals, d_frame_offsets);
+    return hipGetLastError();
+}
+
+hipError_t launch_salvage_chain(const SalvageWs& ws, uint32_t blocks, uint32_t limit, uint32_t grid_items, uint32_t max_frames, uint64_t* d_totals,
+    uint64_t* d_frame_offsets, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_salvage_block_suffix, dim3(1), dim3(1024), 0, stream, ws, blocks, d_totals, d_frame_offsets);
+    uint32_t rounds = 0;
+    while (rounds < 32 && (1ull << rounds) < max_frames)
+        rounds++;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(kSalvageBlocks, ((uint64_t)grid_items + kSalvageThreads - 1) / kSalvageThreads);
+    hipLaunchKernelGGL(k_salvage_succ, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, limit);
+    for (uint32_t r = 0; r < rounds; r++)
+        hipLaunchKernelGGL(k_salvage_round, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, r, max_frames, r & 1u, r + 1 < rounds ? 1u : 0u);
+    hipLaunchKernelGGL(k_salvage_scatter, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, max_frames, d_totals);
+    return hipGetLastError();
+}
+
 // Everything on `stream`, nothing waited for.  The caller has checked the arguments (payload and out 4-byte aligned and apart,
 // payload below 16 GiB, channels 1..255, workspace of salvage_workspace_bytes()).
 hipError_t launch_salvage(const uint8_t* d_payload, uint64_t payload_bytes, uint32_t max_frames, uint32_t channels, sela_hip_salvaged* d_records,
@@ -387,24 +329,17 @@ hipError_t launch_salvage(const uint8_t* d_payload, uint64_t payload_bytes, uint
     const uint32_t words = (uint32_t)(payload_bytes / 4), blocks = (uint32_t)(((uint64_t)words + kSalvageChunk - 1) / kSalvageChunk);
     Carve carve(d_workspace);
     const SalvageWs ws = carve_salvage(carve, words, max_frames);
-    if (blocks == 0 || max_frames == 0) {
-        hipLaunchKernelGGL(k_salvage_clear, dim3(1), dim3(64), 0, stream, d_totals, d_frame_offsets);
-        return hipGetLastError();
-    }
-    const hipError_t e = launch_index_candidates(d_payload, payload_bytes, channels, ws.ix, ws.scan_offsets, ws.scan_count, stream);
+    if (blocks == 0 || max_frames == 0)
+        return launch_salvage_clear(d_totals, d_frame_offsets, stream);
+    hipError_t e = launch_index_candidates(d_payload, payload_bytes, channels, ws.ix, ws.scan_offsets, ws.scan_count, stream);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_salvage_links, dim3(blocks), dim3(kSalvageThreads), 0, stream, ws, words);
-    hipLaunchKernelGGL(k_salvage_block_suffix, dim3(1), dim3(1024), 0, stream, ws, blocks, d_totals, d_frame_offsets);
+    e = launch_salvage_chain(ws, blocks, words, words, max_frames, d_totals, d_frame_offsets, stream);
+    if (e != hipSuccess)
+        return e;
     const uint32_t cap_words = d_out ? (uint32_t)std::min<uint64_t>(out_cap / 4, words) : 0u; // (the taken frames are no more than the payload)
-    uint32_t rounds = 0;
-    while (rounds < 32 && (1ull << rounds) < max_frames)
-        rounds++;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(kSalvageBlocks, ((uint64_t)words + kSalvageThreads - 1) / kSalvageThreads);
-    hipLaunchKernelGGL(k_salvage_succ, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, words);
-    for (uint32_t r = 0; r < rounds; r++)
-        hipLaunchKernelGGL(k_salvage_round, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, r, max_frames, r & 1u, r + 1 < rounds ? 1u : 0u);
-    hipLaunchKernelGGL(k_salvage_scatter, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, max_frames, d_totals);
     hipLaunchKernelGGL(k_salvage_records, dim3(grid), dim3(kSalvageThreads), 0, stream, ws, cap_words, d_records, d_totals, d_frame_offsets);
     if (cap_words)
         hipLaunchKernelGGL(k_salvage_copy, dim3((uint32_t)(((uint64_t)cap_words + kSalvageChunk - 1) / kSalvageChunk)), dim3(kSalvageThreads), 0, stream,
