@@ -515,7 +515,10 @@ int sela_hip_decode_windows(const uint8_t* frames, const uint64_t* frame_offsets
  * not longer than its order, channels that disagree about the length or a layout the combine refuses, a Rice stream that runs
  * dry, a coefficient outside the tables -- leaves its share zero and raises a flag in the window's word and in d_status[0]:
  * SELA_HIP_FLAG_RICE_OVERRUN, _Q_RANGE or _COEF_OVERFLOW where one was met, SELA_HIP_FLAG_BAD_FRAME otherwise.  Nothing outside
- * the frame's bytes is read.  Where n_L is 2048, 0 or above 4095 every word written (d_out, d_window_flags, d_status) is what
+ * the frame's bytes is read.  The combine writes L's independent subframes first, then its differences in subframe order, as the
+ * reference does: a difference under a difference that stands in front of it in the stream (a chain in stream order) is decoded,
+ * its parent being final by then; one whose parent is a difference behind it is a layout the combine refuses (BAD_FRAME).
+ * Where n_L is 2048, 0 or above 4095 every word written (d_out, d_window_flags, d_status) is what
  * sela_hip_decode_windows_device writes; so is everything for a frame in front of L that does not say 2048.
  * d_status[1] also counts the (window, L) decodes that raised SELA_HIP_FLAG_BAD_FRAME; d_status[2] counts each window with a
  * non-zero flag word once.  The device call is asynchronous and capturable as the one above: its launches are shaped by

@@ -1,7 +1,7 @@
 """sela_hip_envelope_device, sela_hip_envelope_payload_device and sela_hip_envelope: per frame, bucket of samples
 and channel the smallest and the largest value, the sum and the sum of squares of the int16 samples sela_hip_decode_n_device
 writes.  The expectation is always numpy on int16 PCM, bucketed by _expect below -- for encoder-made streams the CPU oracle's
-decode, for hand-built ones the decode call's output -- and every comparison is exact equality of all four fields.  status[0],
+decode, for hand-built frames the oracle's decode of them too -- and every comparison is exact equality of all four fields.  status[0],
 [1] and [3] are the decode call's; status[2] stays 0."""
 import ctypes as C
 import functools
@@ -189,6 +189,16 @@ def test_bucket_edges(gpu, bucket):  # noqa: F811
             assert (int(r["min"]), int(r["max"]), int(r["sum"]), int(r["sum_squares"])) == (min(value, 0), max(value, 0), value, value * value), (a, p, c, r)
 
 
+def _oracle_pcm(blobs, ch):
+    """the CPU oracle's decode of hand-built 2048-sample frames -> int16 [frames * 2048, ch]"""
+    out = []
+    for blob in blobs:
+        pcm, used = oracle().frame_decode(blob, ch)
+        assert used == len(blob)
+        out.append(pcm)
+    return np.concatenate(out)
+
+
 def test_a_frame_on_the_serial_parse_fallback(gpu, kats):  # noqa: F811
     """A Rice stream beyond the parser's plan (kStreamCap words): the serial parse into the workspace, then the same reduction."""
     rng = np.random.default_rng(77)
@@ -197,17 +207,17 @@ def test_a_frame_on_the_serial_parse_fallback(gpu, kats):  # noqa: F811
     small = _build_frame([(0, 0, 0, q_sine, rng.integers(-200, 200, 2048))])
     assert (len(big) - 16) // 4 + 2 > 1072 + 50, "the subframe's words (coefficients + 2 + residues) are meant to exceed kStreamCap"
     stream, offs = _stream([small, big, small])
-    back, so, st = _decode_n(gpu, stream, offs, 1, 2048)
-    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST
+    _, so, st = _decode_n(gpu, stream, offs, 1, 2048)
+    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST and int(so[-1]) == 3 * 2048
     for bucket in (32, 512):
-        _check(gpu, stream, offs, 1, 2048, bucket, back[: int(so[-1])].cpu().numpy(), FAST, "serial parse", st, so)
+        _check(gpu, stream, offs, 1, 2048, bucket, _oracle_pcm([small, big, small], 1), FAST, "serial parse", st, so)
     # ... and as one channel of a stereo frame beside a subframe that fits the plan (the whole frame takes the fallback)
     two = _build_frame([(0, 0, 0, q_sine, rng.integers(-120000, 120000, 2048)), (1, 0, 1, q_sine, rng.integers(-50, 50, 2048))])
     stream, offs = _stream([two, two])
-    back, so, st = _decode_n(gpu, stream, offs, 2, 2048)
-    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST
+    _, so, st = _decode_n(gpu, stream, offs, 2, 2048)
+    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST and int(so[-1]) == 2 * 2048
     for bucket in (64, 2048):
-        _check(gpu, stream, offs, 2, 2048, bucket, back[: int(so[-1])].cpu().numpy(), FAST, "serial parse, stereo", st, so)
+        _check(gpu, stream, offs, 2, 2048, bucket, _oracle_pcm([two, two], 2), FAST, "serial parse, stereo", st, so)
 
 
 # ---- 2. the cold route -------------------------------------------------------------------------------------------------------------

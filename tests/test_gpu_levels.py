@@ -1,6 +1,6 @@
 """sela_hip_levels_device, sela_hip_levels_payload_device and sela_hip_levels: per frame and channel the peak,
 the sample count, the sum and the sum of squares of the int16 samples sela_hip_decode_n_device writes.  The expectation is always
-numpy on int16 PCM -- for encoder-made streams the CPU oracle's decode, for hand-built ones the decode call's output -- and every
+numpy on int16 PCM -- the CPU oracle's decode, for encoder-made streams and for hand-built frames alike -- and every
 comparison is exact equality of all four fields.  status[0], [1] and [3] are the decode call's; status[2] counts the frames that
 are not digital silence."""
 import ctypes as C
@@ -128,6 +128,16 @@ def test_full_scale_constants(gpu):  # noqa: F811
     assert got[1].tolist() == got[0].tolist() and int(st[2]) == 2
 
 
+def _oracle_pcm(blobs, ch):
+    """the CPU oracle's decode of hand-built 2048-sample frames -> int16 [frames * 2048, ch]"""
+    out = []
+    for blob in blobs:
+        pcm, used = oracle().frame_decode(blob, ch)
+        assert used == len(blob)
+        out.append(pcm)
+    return np.concatenate(out)
+
+
 def test_a_frame_on_the_serial_parse_fallback(gpu, kats):  # noqa: F811
     """A Rice stream beyond the parser's plan (kStreamCap words): the serial parse into the workspace, then the same reduction."""
     rng = np.random.default_rng(77)
@@ -136,15 +146,15 @@ def test_a_frame_on_the_serial_parse_fallback(gpu, kats):  # noqa: F811
     small = _build_frame([(0, 0, 0, q_sine, rng.integers(-200, 200, 2048))])
     assert (len(big) - 16) // 4 + 2 > 1072 + 50, "the subframe's words (coefficients + 2 + residues) are meant to exceed kStreamCap"
     stream, offs = _stream([small, big, small])
-    back, so, st = _decode_n(gpu, stream, offs, 1, 2048)
-    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST
-    _check(gpu, stream, offs, 1, 2048, back[: int(so[-1])].cpu().numpy(), FAST, "serial parse")
+    _, so, st = _decode_n(gpu, stream, offs, 1, 2048)
+    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST and int(so[-1]) == 3 * 2048
+    _check(gpu, stream, offs, 1, 2048, _oracle_pcm([small, big, small], 1), FAST, "serial parse")
     # ... and as one channel of a stereo frame beside a subframe that fits the plan (the whole frame takes the fallback)
     two = _build_frame([(0, 0, 0, q_sine, rng.integers(-120000, 120000, 2048)), (1, 0, 1, q_sine, rng.integers(-50, 50, 2048))])
     stream, offs = _stream([two, two])
-    back, so, st = _decode_n(gpu, stream, offs, 2, 2048)
-    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST
-    _check(gpu, stream, offs, 2, 2048, back[: int(so[-1])].cpu().numpy(), FAST, "serial parse, stereo")
+    _, so, st = _decode_n(gpu, stream, offs, 2, 2048)
+    assert codec.decode_n_status_error(st) == 0 and int(st[3]) == FAST and int(so[-1]) == 2 * 2048
+    _check(gpu, stream, offs, 2, 2048, _oracle_pcm([two, two], 2), FAST, "serial parse, stereo")
 
 
 # ---- 2. the cold route -------------------------------------------------------------------------------------------------------------

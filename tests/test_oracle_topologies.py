@@ -13,16 +13,16 @@ ref = reference()
 needs_reference = pytest.mark.skipif(ref is None, reason="oracle/_ref/libsela_ref.so not built")
 
 
-def _same_both_ways(o, blob, ch, label):
-    pcm, used = o.frame_decode(blob, ch)
-    pcm_r, used_r = ref.frame_decode(blob, ch)
+def _same_both_ways(o, blob, ch, label, n=tc.N):
+    pcm, used = o.frame_decode(blob, ch, n=n)
+    pcm_r, used_r = ref.frame_decode(blob, ch, n=n)
     assert used == used_r == len(blob), label
-    assert pcm.tobytes() == pcm_r.tobytes(), label
+    assert pcm.shape == (n, ch) and pcm.tobytes() == pcm_r.tobytes(), label
     dec, used = o.frame_decode_i32(blob, ch)
     dec_r, used_r = ref.frame_decode_i32(blob, ch)
     assert used == used_r == len(blob), label
     for c in range(ch):
-        assert len(dec[c]) == len(dec_r[c]) == tc.N and dec[c].tobytes() == dec_r[c].tobytes(), (label, c)
+        assert len(dec[c]) == len(dec_r[c]) == n and dec[c].tobytes() == dec_r[c].tobytes(), (label, c)
     return pcm, dec
 
 
@@ -41,6 +41,54 @@ def test_the_modules_own_conditions_hold():
         cs, mask = tc.refused_stream(ch)[:2]
         assert len(cs) <= 20 and mask[0] and mask[-1] and not (~mask[1:] & ~mask[:-1]).any()  # (every refused frame between two accepted ones)
         assert int((~mask).sum()) == len(tc.refused(ch)) >= 7
+    # the long last frames: every label once, every subframe of the frame's own length, no layout an encoder writes; at +-12000
+    # _tailed() asserts a wrapped value in a dependent channel while it builds
+    labels = set()
+    for ch, n_last, scale, chain in _TAILS:
+        label, subs = tc.tail_subframes(ch, n_last, scale, chain)
+        labels.add(label)
+        layout = [s[:3] for s in subs]
+        assert len(subs) == ch and all(len(s[4]) == n_last and 1 <= len(s[3]) <= 29 for s in subs), label
+        assert sorted(s[0] for s in subs) == list(range(ch)) and tc.dependent_channels(subs), label
+        assert layout != [(0, tc.IND, 0), (1, tc.DEP, 0)] + [(c, tc.IND, c) for c in range(2, ch)], label
+        if chain:  # channel 2 under channel 1, itself a difference in front of it
+            assert layout[:3] == tc.CHAIN_IN_STREAM_ORDER and all(s[1] == tc.IND for s in subs[3:]), label
+        stream, offs, pcm = tc.tailed_stream(ch, n_last, scale, chain)
+        assert len(offs) == 4 and int(offs[3]) == len(stream) and pcm.shape == (2 * tc.N + n_last, ch) and pcm.dtype == np.int16
+        pcm32 = tc.tailed_stream_i32(ch, n_last, scale, chain)
+        assert np.array_equal(pcm, pcm32.astype(np.uint32).astype(np.uint16).view(np.int16)), label
+        if scale == tc.WRAPPING:
+            assert (pcm32[2 * tc.N:] != pcm[2 * tc.N:]).any(), label
+    assert len(labels) == len(_TAILS)
+
+
+# (channels, samples of the last frame, residue scale, a chain as the last frame): what test_gpu_tail_topologies.py decodes
+_TAILS = [(ch, n_last, scale, False) for ch in tc.TAIL_CHANNELS for n_last in tc.TAIL_LENGTHS for scale in (tc.ORDINARY, tc.WRAPPING)]
+_TAILS += [(ch, 2825, scale, True) for ch in tc.TAIL_CHANNELS if ch >= 3 for scale in (tc.ORDINARY, tc.WRAPPING)]
+
+
+@needs_reference
+@pytest.mark.parametrize("ch", tc.TAIL_CHANNELS)
+def test_long_last_frames_decode_as_the_reference_decodes_them(ch):
+    """Every last frame of tailed_stream, the chains among them, through frame::FrameDecoder and the oracle: the same PCM at the
+    frame's own length, the same int32 channels, the same bytes consumed; and the stream's PCM is those frames'."""
+    o = oracle()
+    mine = [t for t in _TAILS if t[0] == ch]
+    assert len(mine) == (6 if ch == 2 else 8)
+    for _, n_last, scale, chain in mine:
+        label, subs = tc.tail_subframes(ch, n_last, scale, chain)
+        blob = wc.frame_bytes(o, subs)
+        pcm, dec = _same_both_ways(o, blob, ch, label, n=n_last)
+        stream, offs, want = tc.tailed_stream(ch, n_last, scale, chain)
+        assert stream[int(offs[2]):].tobytes() == blob, label
+        assert np.array_equal(want[2 * tc.N:], pcm) and np.array_equal(tc.tailed_stream_i32(ch, n_last, scale, chain)[2 * tc.N:], np.stack(dec, axis=1)), label
+        for f in range(2):
+            front = stream[int(offs[f]): int(offs[f + 1])].tobytes()
+            assert np.array_equal(ref.frame_decode(front, ch)[0], want[f * tc.N: (f + 1) * tc.N]), (label, f)
+        if chain:  # resolved in stream order: channel 1 is final when channel 2 subtracts from it
+            raw = [o.lpc_synth(len(s[3]), s[3], s[4]) for s in subs[:3]]
+            with np.errstate(over="ignore"):
+                assert np.array_equal(dec[1], raw[0] - raw[1]) and np.array_equal(dec[2], raw[0] - raw[1] - raw[2]), label
 
 
 @needs_reference

@@ -1,6 +1,10 @@
-"""Subframe layouts of 2048-sample frames, shared by the oracle-versus-reference test (test_oracle_topologies.py) and the GPU
-tests of k_decode_frames, k_decode_frames_wide, k_verify_frames and k_verify_compare (test_gpu_decode_topologies.py).  Not a
-test file, and no GPU module is imported here.
+"""Subframe layouts, shared by the oracle-versus-reference test (test_oracle_topologies.py) and the GPU tests of every kernel
+that restates the reference's second pass.  Frames of 2048 samples: k_decode_frames, k_decode_frames_wide, k_verify_frames and
+k_verify_compare (test_gpu_decode_topologies.py); k_level_frames, k_digest_frames, k_envelope_frames, k_window_frames and the
+cold routes behind the wide kernel (test_gpu_fused_topologies.py); k_window32_decode / k_window32_store
+(test_gpu_tail_topologies.py); the first layouts per channel count also the 32-bit verify, levels, envelope and digest tests.
+Long last frames of whole-track streams (tailed_stream): the consumers of tail_store_list -- k_tailwin_store, k_whole_store,
+k_tail32_store (test_gpu_tail_topologies.py).  Not a test file, and no GPU module is imported here.
 
 frame::FrameDecoder::process (src/frame/frame_decoder.cpp:11-72) decodes the independent subframes first, wherever they stand in
 the stream and whatever channel they name, then turns every type-1 subframe into allSamples[parent] - difference.  The
@@ -122,14 +126,14 @@ def _seed(label):
     return _RESEED.get(label, zlib.crc32(label.encode()))
 
 
-def subframes(layout, scale, seed, scales=None):
-    """(channel, type, parent, q, residues) tuples of a layout: q 1 to 29 values in [-20, 20), residues in [-scale, scale)."""
+def subframes(layout, scale, seed, scales=None, n=N):
+    """(channel, type, parent, q, residues) tuples of a layout: q 1 to 29 values in [-20, 20), n residues in [-scale, scale)."""
     rng = np.random.default_rng(seed)
     out = []
     for pos, (channel, typ, parent) in enumerate(layout):
         q = rng.integers(-20, 20, size=int(rng.integers(1, 30))).astype(np.int32)
         s = (scales or {}).get(pos, scale)
-        out.append((channel, typ, parent, q, rng.integers(-s, s, size=N).astype(np.int32)))
+        out.append((channel, typ, parent, q, rng.integers(-s, s, size=n).astype(np.int32)))
     return out
 
 
@@ -253,3 +257,68 @@ def _stream(o, blobs, ch):
     for a in (stream, offs, pcm):
         a.setflags(write=False)
     return stream, offs, pcm
+
+
+# ---- whole-track streams: two frames of 2048 samples and a long last frame ----------------------------------------------------
+TAIL_CHANNELS = (2, 3, 5, 8)
+TAIL_LENGTHS = (2049, 2825, 4095)   # both ends of a last frame's range (2049 .. 4095) and one inside
+# the last frame's layout: none is channel order with 1 under 0, which is all an encoder writes
+TAIL_LAYOUTS = {
+    2: ("1 under 0, the difference first", [(1, DEP, 0), (0, IND, 0)]),
+    3: ACCEPTED_LAYOUTS[3][1],
+    5: ACCEPTED_LAYOUTS[5][0],
+    8: ACCEPTED_LAYOUTS[8][0],
+}
+
+
+def chain_layout(ch):
+    """CHAIN_IN_STREAM_ORDER and independent subframes in channel order behind it"""
+    return CHAIN_IN_STREAM_ORDER + [(c, IND, c) for c in range(3, ch)]
+
+
+def tail_subframes(ch, n_last, scale=ORDINARY, chain=False):
+    """-> (label, subframes) of the last frame of tailed_stream(ch, n_last, scale, chain)"""
+    name, layout = ("a chain in stream order", chain_layout(ch)) if chain else TAIL_LAYOUTS[ch]
+    label = f"{ch}ch last frame of {n_last}: {name} +-{scale}"
+    return label, subframes(layout, scale, _seed(label), n=n_last)
+
+
+@functools.lru_cache(maxsize=None)
+def _tailed(ch, n_last, scale, chain):
+    from oracle_lib import oracle
+
+    o = oracle()
+    assert ch in TAIL_CHANNELS and N < n_last < 2 * N and (ch >= 3 or not chain)
+    front = [c for c in accepted(ch) if f"+-{ORDINARY}" in c[0]][:2]
+    label, subs = tail_subframes(ch, n_last, scale, chain)
+    last = wc.frame_bytes(o, subs)
+    blobs = [wc.frame_bytes(o, c[2]) for c in front] + [last]
+    dec, used = o.frame_decode_i32(last, ch)
+    assert used == len(last) and all(len(d) == n_last for d in dec), label
+    if scale == WRAPPING:
+        assert any(((dec[c] < -32768) | (dec[c] > 32767)).any() for c in dependent_channels(subs)), label
+    stream = np.frombuffer(b"".join(blobs), np.uint8).copy()
+    offs = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
+    parts, wide = [], []
+    for b, n in zip(blobs, (N, N, n_last)):
+        pcm, used = o.frame_decode(b, ch, n=n)
+        assert used == len(b), label
+        parts.append(pcm)
+        wide.append(np.stack(o.frame_decode_i32(b, ch)[0], axis=1))
+    pcm, pcm32 = np.concatenate(parts), np.concatenate(wide)
+    assert pcm.shape == pcm32.shape == (2 * N + n_last, ch)
+    for a in (stream, offs, pcm, pcm32):
+        a.setflags(write=False)
+    return stream, offs, pcm, pcm32
+
+
+def tailed_stream(ch, n_last, scale=ORDINARY, chain=False):
+    """The first two +-300 frames of accepted(ch), then one last frame of n_last samples in TAIL_LAYOUTS[ch] (chain: in
+    chain_layout(ch)) -> (stream uint8, offsets uint64 [4], oracle PCM int16 [4096 + n_last, ch]).  At +-12000 a dependent channel
+    of the last frame leaves int16 (asserted from the oracle's int32 decode, as cases() does).  Cached and read-only."""
+    return _tailed(ch, n_last, scale, chain)[:3]
+
+
+def tailed_stream_i32(ch, n_last, scale=ORDINARY, chain=False):
+    """The oracle's int32 samples of the same stream, int32 [4096 + n_last, ch]: parent - difference kept, not wrapped."""
+    return _tailed(ch, n_last, scale, chain)[3]
